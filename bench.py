@@ -8,9 +8,13 @@ Slam::batch_optimization) of the BASELINE.json config-2 graph -- synthetic corri
 200 plane landmarks, 5 000 plane edges + 999 odometry edges + priors -- restarted from its initial
 (dead-reckoned) estimate, which is restored from a device-resident snapshot.  Graph, measurements
 and state are resident in HBM before the timed region starts.  value = LM iterations / second over
-all ranks (one independent graph per GPU, no collective: SURVEY.md section 8(e)).
+all ranks (one independent graph per GPU, no collective: SURVEY.md section 8(e)); ms_per_step = wall
+milliseconds of one timed step.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the --steps steps and prints the headline line.  --dump-outputs DIR
+also writes what the last timed step computed (per graph: the optimised poses n x 7 and planes n x 4,
+the final chi2 and the LM iteration count, float64) as DIR/<name>.npy.  Everything else is measured only
+with --full; the objects it adds to the JSON line include:
   roofline      K1 (Jacobian sweep) inside the timed solves: algorithmic bytes per launch (392 B per
                 plane edge, 840 B per odometry edge) / mean launch duration from HIP
                 event pairs recorded on the solver's stream.  The single C2 graph (2.8 MB) lives in
@@ -232,6 +236,17 @@ def aggregate(dist, elapsed, iters, device):
     return float(t.item()), float(it_t.item())
 
 
+def dump_outputs(path, graphs, seeds, last_iters):
+    """what the last timed step returned to its caller, per graph: the optimised estimate, chi2 and LM iterations; with several
+    graphs per rank (N > 1) every name carries its graph's seed"""
+    os.makedirs(path, exist_ok=True)
+    for gk, sd, it in zip(graphs, seeds, last_iters):
+        prefix = "" if len(graphs) == 1 else "seed%d_" % sd
+        arrays = {"poses": gk.get_poses(), "planes": gk.get_planes(), "final_chi2": [gk.chi2()], "lm_iterations": [it]}
+        for name, a in arrays.items():
+            np.save(os.path.join(path, prefix + name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def cpu_dry_run(args, rank, world):
     """No GPU: every rank builds and analyses ITS graph (host logic only) and feeds synthetic timings
     through the same aggregation the real run uses."""
@@ -299,6 +314,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mode", choices=["numeric", "analytic"], default="numeric",
                     help="Jacobian mode of the sweep (numeric = reference behaviour)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else: rooflines, the other Jacobian mode, pps_multi, concurrent "
+                         "handles, C3, C5 and the CPU baselines (the options below select among them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-c5", action="store_true", help="skip the config-5 frame loop (1000 frames, ~2 s)")
     ap.add_argument("--no-c3", action="store_true", help="skip the config-3 graph (10 000 poses)")
@@ -312,6 +331,8 @@ def main():
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return self_launch(args)
     rank = int(os.environ.get("RANK", "0"))
@@ -355,7 +376,6 @@ def main():
         spec_k.replay(gk)
         gk.save_state()
         graphs.append(gk)
-    spec = synth.corridor(seed=seeds[0])
     g = graphs[0]
 
     def barrier():
@@ -369,31 +389,60 @@ def main():
 
     def step():
         """N = 1: one LM solve of the C2 graph.  N > 1: this rank's eight C4 graphs solved once each, starting with graph
-        `rank` -- every rank does exactly the same work in every step, whatever K is."""
-        n = 0
+        `rank` -- every rank does exactly the same work in every step, whatever K is.  Returns the LM iterations per graph."""
+        its = []
         for gk in graphs:
             gk.restore_state()
-            n += gk.batch_optimize()
-        return n
+            its.append(gk.batch_optimize())
+        return its
 
     for i in range(args.warmup):
         step()
     barrier()
     t0 = time.perf_counter()
     iters = 0
-    k1_time, k1_launches = 0.0, 0
     for i in range(args.steps):
-        iters += step()
+        last = step()
+        iters += sum(last)
     barrier()
     elapsed = time.perf_counter() - t0
     solves = args.steps * len(graphs)
-    # outside the timed region: one more solve of this rank's first graph with an event pair around every K1 launch
-    g.restore_state(); g.set_profiling(1); g.batch_optimize(); g.set_profiling(0)
     chi2 = g.chi2()
     st = g.stats()
-    k1_time, k1_launches = st["t_linearize"], st["n_linearize"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, graphs, seeds, last)
 
     elapsed, total_iters = aggregate(dist, elapsed, iters, "cpu" if shared else "cuda")
+    out = {
+        "metric": "graph-solve iters/sec + final chi2, 1k-pose/5k-edge plane graph",
+        "value": total_iters / elapsed, "unit": "LM iters/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "C2 synthetic corridor: 1000 SE3 poses, 200 planes, 5000 plane edges, 999 odometry edges "
+                               "(BASELINE.json configs[1], seed 42)" + ("" if world == 1 else
+                               "; N > 1 = config 4: eight independently seeded C2 graphs per rank (timing seeds %s: the "
+                               "short, balanced LM runs; parity on SURVEY's seeds 100-107 is a test, not a bench line), one "
+                               "step = all eight solved once, rank r starting at graph r, no collective" % C4_SEEDS),
+                   "jacobian_mode": args.mode, "lm_solves_per_step": len(graphs), "lm_iterations_per_solve": iters / solves,
+                   "graphs_per_sec": world * solves / elapsed, "total_lm_iterations": total_iters, "total_lm_solves": world * solves},
+        "final_chi2": chi2, "chi2_initial": st["chi2_initial"],
+        "fronts": st["n_fronts"], "levels": st["n_levels"], "max_front": st["max_front"],
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return None
+
+    # --full: everything below runs after the headline's measurement and does not change it
+    spec = synth.corridor(seed=seeds[0])
+    # one more solve of this rank's first graph with an event pair around every K1 launch
+    g.restore_state(); g.set_profiling(1); g.batch_optimize(); g.set_profiling(0)
+    st = g.stats()
+    k1_time, k1_launches = st["t_linearize"], st["n_linearize"]
 
     # N > 1 (BASELINE config 4 / north_star: "graphs/sec and achieved-HBM-fraction at 1/2/4/8 GPUs"): every rank also runs the
     # many-graphs-per-launch form on ITS device -- G = 8 (config 4's size) and G = 128 (where one GPU saturates) -- and rank 0
@@ -478,26 +527,12 @@ def main():
             ent["replicas"], ent["n_plane_edges"], ent["n_odometry_edges"] = reps, npl, nod
             ent["traffic_source"] = pmc_src
             roofline_batched[mname] = ent
-        out = {
-            "metric": "graph-solve iters/sec + final chi2, 1k-pose/5k-edge plane graph",
-            "value": total_iters / elapsed, "unit": "LM iters/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "C2 synthetic corridor: 1000 SE3 poses, 200 planes, 5000 plane edges, 999 odometry edges "
-                                   "(BASELINE.json configs[1], seed 42)" + ("" if world == 1 else
-                                   "; N > 1 = config 4: eight independently seeded C2 graphs per rank (timing seeds %s: the "
-                                   "short, balanced LM runs; parity on SURVEY's seeds 100-107 is a test, not a bench line), one "
-                                   "step = all eight solved once, rank r starting at graph r, no collective" % C4_SEEDS),
-                       "jacobian_mode": args.mode, "lm_solves_per_step": len(graphs), "lm_iterations_per_solve": iters / solves,
-                       "graphs_per_sec": world * solves / elapsed, "total_lm_iterations": total_iters, "total_lm_solves": world * solves},
-            "final_chi2": chi2, "chi2_initial": st["chi2_initial"],
-            "fronts": st["n_fronts"], "levels": st["n_levels"], "max_front": st["max_front"],
+        out.update({
             # kernel launches of one LM solve (pps_stats.n_launches): the dual loop issues both damping values of a
             # linearisation in the same launches on one stream (round 1: 21 launches per accepted + rejected pair on two streams)
             "launches_per_lm_iteration": st["n_launches"] / max(1, st["lm_iterations"]), "launches_per_solve": st["n_launches"],
             "roofline": roofline, "roofline_batched": roofline_batched,
-        }
+        })
         if multi_ranks is not None:
             # whole-job figures of the many-graphs-per-launch form: graphs/s added up over the ranks (every rank ran the same G
             # graphs on its own device between the same two barriers), roofline fractions as the range over the ranks

@@ -170,7 +170,7 @@ def test_two_bench_ranks_on_one_gpu(built):
     rank runs pps_multi on its device and rank 0 aggregates graphs/s and the roofline fractions (multi_graph_per_gpu)."""
     import json, os, socket, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-c5", "--no-c3"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-c5", "--no-c3"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(PPS_BENCH_SHARED_GPU="1", OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0", PPS_BENCH_MULTI_G="8,16")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
@@ -202,3 +202,31 @@ def test_two_bench_ranks_on_one_gpu(built):
         for key in ("roofline_k1", "roofline_k3_hbm"):
             assert 0 < ent[key]["frac_min"] <= ent[key]["frac_max"] < 1 and len(ent[key]["achieved_per_rank"]) == 2
     assert "multi_graph_per_gpu['128'].graphs_per_sec" in cfg["scale_line"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(built, tmp_path):
+    """`python bench.py --gpus 1` without --full: the headline line only, with ms_per_step; --dump-outputs writes the C2 graph's estimate,
+    chi2 and LM iterations of the last timed step, the same as a solve of the C2 graph in this process"""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    js = json.loads(lines[0])
+    assert js["steps"] == 3 and js["config"]["total_lm_solves"] == 3 and js["unit"] == "LM iters/s" and js["dtype"] == "f64"
+    assert js["ms_per_step"] > 0 and abs(js["value"] * js["ms_per_step"] / 1e3 - js["config"]["lm_iterations_per_solve"]) <= 1e-9 * js["value"]
+    assert not {"roofline", "roofline_batched", "cpu_baseline", "multi_graph_one_gpu", "c3", "c5_frame_loop"} & set(js)
+    g = P.Graph(); synth.corridor(seed=42).replay(g)
+    it = g.batch_optimize()
+    dumped = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in ("poses", "planes", "final_chi2", "lm_iterations")}
+    assert all(a.dtype == np.float64 for a in dumped.values())
+    assert dumped["poses"].shape == (1000, 7) and dumped["planes"].shape == (200, 4)
+    assert dumped["lm_iterations"][0] == it == js["config"]["lm_iterations_per_solve"]
+    assert dumped["final_chi2"][0] == js["final_chi2"] and abs(js["final_chi2"] - g.chi2()) <= 1e-12 * g.chi2()
+    np.testing.assert_allclose(dumped["poses"], g.get_poses(), rtol=0, atol=1e-9)
+    np.testing.assert_allclose(dumped["planes"], g.get_planes(), rtol=0, atol=1e-9)
+    g.close()

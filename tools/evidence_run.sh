@@ -16,7 +16,7 @@ summary() {   # summary NAME -- cmd...: rocprofv3 kernel trace of the command, s
   sed -i "1i # workload: $*" $out/kernel_stats_$name.txt
 }
 # 1. the bench line
-( cd $ROOT && timeout 900 python bench.py > $out/bench.json 2> $out/bench.err ); echo "bench rc $?"
+( cd $ROOT && timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err ); echo "bench rc $?"
 # 2. one kernel summary per workload
 summary c2 -- python $ROOT/tools/timeline_c2.py run                 # two LM solves of the C2 graph: nothing else
 python - $out $raw <<'PY'
