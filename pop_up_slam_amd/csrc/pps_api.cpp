@@ -41,6 +41,77 @@ Switches read_switches() {
 }
 }  // namespace pps
 
+namespace pps_impl {
+// PPS_TRACE: the cycle counters every front left in its eight trace slots during the last solve, as per-level tables on stderr
+// (level 1: the phases of the factorisation; level 2: of the back-substitution).  Called once, at the end of lm_solve.
+void report_front_trace(pps_graph* g) {
+  const Analysis& A = g->an;
+  std::vector<long long> tr((size_t)A.n_fronts * 8);
+  (void)hipMemcpy(tr.data(), g->dev.trace, tr.size() * 8, hipMemcpyDeviceToHost);
+  if (g->dev.trace_solve) {
+    // PPS_TRACE=2: the slots hold the back-substitution of the last solve (parents before children)
+    for (int l = A.n_levels - 1; l >= 0; l--) {
+      double ph[5] = {0, 0, 0, 0, 0}, gap = 0; int n = 0, ng = 0;
+      for (int s2 = 0; s2 < A.n_fronts; s2++) {
+        if (A.f_level[s2] != l) continue;
+        n++;
+        for (int k = 0; k < 5; k++) ph[k] += (double)(tr[(size_t)s2 * 8 + k + 1] - tr[(size_t)s2 * 8 + k]);
+        const int par = A.f_parent[s2];
+        if (par >= 0) { gap += (double)(tr[(size_t)s2 * 8] - tr[(size_t)par * 8 + 5]); ng++; }
+      }
+      if (!n) continue;
+      fprintf(stderr, "  solve level %d (%d fronts): panel load %.0f boundary values %.0f y - L_B^T x_b %.0f back-substitution %.0f store %.0f | start after parent's end %.0f\n",
+              l, n, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[4] / n, ng ? gap / ng : 0.0);
+    }
+  } else {                        // (PPS_TRACE=1)
+    double acc[5] = {0, 0, 0, 0, 0};
+    std::vector<double> lvl_tot(A.n_levels, 0.0); std::vector<int> lvl_n(A.n_levels, 0);
+    for (int s2 = 0; s2 < A.n_fronts; s2++) {
+      for (int k = 0; k < 5; k++) acc[k] += (double)(tr[(size_t)s2 * 8 + k + 1] - tr[(size_t)s2 * 8 + k]);
+      lvl_tot[A.f_level[s2]] += (double)(tr[(size_t)s2 * 8 + 5] - tr[(size_t)s2 * 8]); lvl_n[A.f_level[s2]]++;
+    }
+    { double pn = 0, tr2 = 0; for (int s2 = 0; s2 < A.n_fronts; s2++) { pn += (double)tr[(size_t)s2 * 8 + 6]; tr2 += (double)tr[(size_t)s2 * 8 + 7]; }
+      fprintf(stderr, "PPS_TRACE elimination split: panel %.0f trailing %.0f cycles per front\n", pn / A.n_fronts, tr2 / A.n_fronts); }
+    fprintf(stderr, "PPS_TRACE mean cycles per front: zero %.0f gather %.0f extend-add %.0f eliminate %.0f store %.0f\n",
+            acc[0] / A.n_fronts, acc[1] / A.n_fronts, acc[2] / A.n_fronts, acc[3] / A.n_fronts, acc[4] / A.n_fronts);
+    for (int l = 0; l < A.n_levels; l++) fprintf(stderr, "  level %d: %d fronts, mean total %.0f cycles\n", l, lvl_n[l], lvl_tot[l] / std::max(1, lvl_n[l]));
+    {
+      // per level: the phases, and how long a front's start lies behind the end of its last child (barrier, launch boundary,
+      // record load) -- the part of a tree level that no phase accounts for
+      std::vector<long long> last_child_end(A.n_fronts, 0);
+      for (int s2 = 0; s2 < A.n_fronts; s2++) if (A.f_parent[s2] >= 0) last_child_end[A.f_parent[s2]] = std::max(last_child_end[A.f_parent[s2]], tr[(size_t)s2 * 8 + 5]);
+      for (int l = 0; l < A.n_levels; l++) {
+        double ph[7] = {0, 0, 0, 0, 0, 0, 0}, gap = 0; int n = 0, ng = 0;
+        for (int s2 = 0; s2 < A.n_fronts; s2++) {
+          if (A.f_level[s2] != l) continue;
+          n++;
+          for (int k = 0; k < 5; k++) ph[k] += (double)(tr[(size_t)s2 * 8 + k + 1] - tr[(size_t)s2 * 8 + k]);
+          ph[5] += (double)tr[(size_t)s2 * 8 + 6]; ph[6] += (double)tr[(size_t)s2 * 8 + 7];
+          if (last_child_end[s2] > 0) { gap += (double)(tr[(size_t)s2 * 8] - last_child_end[s2]); ng++; }
+        }
+        if (!n) continue;
+        fprintf(stderr, "  level %d: zero %.0f gather %.0f extend-add %.0f eliminate %.0f (panel %.0f trailing %.0f) store %.0f | start after last child's end %.0f\n", l,
+                ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[5] / n, ph[6] / n, ph[4] / n, ng ? gap / ng : 0.0);
+      }
+    }
+    {
+      double w[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int nw2 = 0;
+      for (int s2 = 0; s2 < A.n_fronts; s2++) {
+        if (A.f_p[s2] + A.f_b[s2] + 1 <= 64) continue;
+        nw2++;
+        for (int k = 0; k < 5; k++) w[k] += (double)(tr[(size_t)s2 * 8 + k + 1] - tr[(size_t)s2 * 8 + k]);
+        w[5] += (double)tr[(size_t)s2 * 8 + 6]; w[6] += (double)tr[(size_t)s2 * 8 + 7];
+      }
+      if (nw2) fprintf(stderr, "  fronts beyond 64 rows (%d): zero %.0f gather %.0f extend-add %.0f eliminate %.0f (panel %.0f trailing %.0f) store %.0f cycles\n", nw2,
+                       w[0] / nw2, w[1] / nw2, w[2] / nw2, w[3] / nw2, w[5] / nw2, w[6] / nw2, w[4] / nw2);
+    }
+    long long tmin = tr[0], tmax = tr[5];
+    for (int s2 = 0; s2 < A.n_fronts; s2++) { tmin = std::min(tmin, tr[(size_t)s2 * 8]); tmax = std::max(tmax, tr[(size_t)s2 * 8 + 5]); }
+    fprintf(stderr, "  first start -> last end: %lld cycles\n", tmax - tmin);
+  }
+}
+}  // namespace pps_impl
+
 extern "C" {
 
 void pps_default_props(pps_props* p) {

@@ -4,6 +4,7 @@
 //   pps_upload.cpp   compaction + symbolic analysis, device arenas, difference upload, state / measurement transfers
 //   pps_solve.cpp    pps_update (Optimizer::relinearize), pps_batch_optimize (Optimizer::levenberg_marquardt), chi2
 //   pps_multi.cpp    pps_multi: G graphs per launch, lockstep LM rounds
+//   pps_lm.h         the LM rule the loops of pps_solve.cpp and pps_multi.cpp share (accept / reject / stop, lambda schedule, trace, counters): host only, no HIP
 //   pps_frames.cpp   registered frames (measurement refresh on the device), data association, point re-projection
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
 #pragma once
@@ -25,6 +26,7 @@
 #include "../../include/pps.h"
 #include "pps_device.h"
 #include "pps_geom.h"
+#include "pps_lm.h"
 #include "pps_popup_dev.h"
 #include "pps_symbolic.h"
 
@@ -240,8 +242,11 @@ int upload_all(pps_graph* g);
 int prepare_solve(pps_graph* g);
 // ---- pps_solve.cpp ----
 int read_result(pps_graph* g, bool at_estimate, double* chi2, double* dnorm, bool* notpd);
-void reset_solve_stats(pps_graph* g);
+void begin_solve(pps_graph* g);                // an LM solve starts: the last one's stats and trace go
 void abandon_device_copy(pps_graph* g);
+inline LmSink lm_sink(pps_graph* g, bool verbose) { return LmSink{&g->props, &g->tr_lambda, &g->tr_chi2, &g->tr_acc, &g->stats, verbose}; }
+// ---- pps_api.cpp ----
+void report_front_trace(pps_graph* g);         // PPS_TRACE: the per-front cycle counters of the last solve -> stderr
 
 template <class T>
 int arena_alloc(pps_graph* g, pps_graph::Arena& a, T** out, size_t count) {

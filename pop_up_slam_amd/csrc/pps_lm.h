@@ -1,0 +1,81 @@
+// pps_lm.h -- the Levenberg-Marquardt rule of Optimizer::levenberg_marquardt (Thirdparty/isam/isamlib/Optimizer.cpp:371-467), once.
+// Host only, no HIP: the three host loops (lm_solve, lm_solve_dual: pps_solve.cpp; the rounds of pps_multi.cpp) decide WHEN a trial's
+// chi2 is on the host and what to launch next; what a chi2 means -- accept / reject / stop, the lambda schedule, the trace, the trial
+// counters, the not-PD report -- is here, and tests/test_host_lm.py replays recorded trajectories through it without a device.
+#pragma once
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+#include "../../include/pps.h"
+
+namespace pps_impl {
+
+// what the rule writes besides its own state (a handle's properties, LM trace and stats record), gathered once per solve
+struct LmSink {
+  const pps_props* prop;
+  std::vector<double>*tr_lambda, *tr_chi2;
+  std::vector<int>* tr_acc;
+  pps_stats* stats;
+  bool verbose;                  // the "LM Iteration" line per trial (the batched rounds print none)
+};
+
+enum class LmVerdict { Rejected, Accepted, Converged };
+
+constexpr const char* kLmNotPdMessage = "normal equations not positive definite at the last LM trial";
+
+struct LmControl {
+  double lambda, error = 0.0, dnorm = 0.0;      // error: chi2 at the linearisation point; dnorm: |delta| of the trial judged next
+  int num_iter = 0;
+  // Not-PD is a property of ONE factorisation (one lambda): every result record carries the flag of the solve that produced
+  // its step, and the chi2 kernel clears it.  CHOLMOD is silent here and LM simply rejects such a step and raises lambda
+  // (Optimizer.cpp:448-455), so only a solve whose LAST trial was still not PD reports PPS_ENOTPD.
+  bool last_notpd = false;
+  int n_notpd = 0;
+
+  explicit LmControl(const pps_props& p) : lambda(p.lm_lambda0) {}
+
+  // the loop condition (:398)
+  bool running(const pps_props& p) const { return (p.max_iterations <= 0 || num_iter < p.max_iterations) && dnorm > p.epsilon2 && error > p.epsilon_abs; }
+
+  // a trial's result record (chi2, |delta|^2, status word) is on the host: the step it stands for is the one judged next
+  void take_step(const double* rec) {
+    dnorm = std::sqrt(rec[1]);
+    last_notpd = rec[2] != 0.0;
+    n_notpd += last_notpd ? 1 : 0;
+  }
+
+  // one pass of the loop body (:400-456) for the trial whose chi2 is error_new.  Forced inline: with its three push_backs the compiler
+  // otherwise emits it out of line, a call per trial between a record's arrival and the next launch that the loops did not have before
+  __attribute__((always_inline)) LmVerdict judge(const LmSink& s, double error_new) {
+    const pps_props& p = *s.prop;
+    num_iter++;
+    const double error_diff = error - error_new;
+    const bool accepted = error_diff > 0.;
+    s.tr_lambda->push_back(lambda); s.tr_chi2->push_back(error_new); s.tr_acc->push_back(accepted ? 1 : 0);
+    if (s.verbose) fprintf(stderr, "LM Iteration %d: (lambda=%g) %s %.12g\n", num_iter, lambda, accepted ? "residual:" : "rejected", error_new);
+    if (!accepted) {
+      s.stats->lm_trials_rejected++;
+      lambda *= p.lm_lambda_factor;                              // (:452)
+      return LmVerdict::Rejected;
+    }
+    s.stats->lm_trials_accepted++;
+    const bool converged = error_diff < p.epsilon_rel * error;   // (:431-434) against the chi2 the step started from
+    error = error_new;
+    if (converged) return LmVerdict::Converged;
+    lambda /= p.lm_lambda_factor;                                // (:438)
+    return LmVerdict::Accepted;
+  }
+
+  // the solve is over: its figures -> stats; PPS_ENOTPD (the caller sets kLmNotPdMessage on its handle) when the last trial was not PD
+  int finish(const LmSink& s, int* iterations) const {
+    pps_stats& st = *s.stats;
+    st.lm_iterations = num_iter;
+    st.chi2_final = error; st.lambda_final = lambda; st.last_delta_norm = dnorm;
+    st.lm_trials_notpd = n_notpd;
+    if (iterations) *iterations = num_iter;
+    return last_notpd ? PPS_ENOTPD : PPS_OK;
+  }
+};
+
+}  // namespace pps_impl

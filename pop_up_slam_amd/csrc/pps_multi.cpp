@@ -166,16 +166,13 @@ int pps_multi_optimize(pps_multi* m, int* iterations, int* status) {
   return rc;
 }
 
-static int multi_optimize(pps_multi* m, int* iterations, int* status) {
-  const double t0 = now_s();
+// ---- 1. every graph analysed, uploaded and idle; all of them must take the wave-per-front path ----
+static int check_graphs(pps_multi* m, int* mode_out, int* max_stages_out) {
   const int G = (int)m->gs.size();
-  if (hipSetDevice(m->device) != hipSuccess) return mfail(m, PPS_EHIP, "hipSetDevice failed (no HIP device: there is no CPU fallback)");
-  // ---- every graph analysed, uploaded and idle; all of them must take the wave-per-front path ----
   int mode = m->gs[0]->props.jacobian_mode, max_stages = 0;
   for (int i = 0; i < G; i++) {
     pps_graph* g = m->gs[i];
-    reset_solve_stats(g);
-    g->tr_lambda.clear(); g->tr_chi2.clear(); g->tr_acc.clear();
+    begin_solve(g);
     int rc = prepare_solve(g);
     if (rc != PPS_OK) return mfail(m, rc, "graph " + std::to_string(i) + ": " + g->err);
     if (!g->use_band) return mfail(m, PPS_ESTATE, "graph " + std::to_string(i) + " has fronts beyond the wave-per-front kernels (loop closures): solve it through its own handle");
@@ -188,13 +185,19 @@ static int multi_optimize(pps_multi* m, int* iterations, int* status) {
     g->status_clean = false;
     max_stages = std::max(max_stages, g->an.n_stages);
   }
-  const double t_s1 = now_s() - t0;
   // both damping values of a linearisation in the same launches (lm_solve_dual's scheme): every uploaded handle has its second
   // factor / state set
   for (int i = 0; i < G; i++)
     if (!(m->gs[i]->spec_L && m->gs[i]->spec_U && m->gs[i]->spec_delta && m->gs[i]->spec_pose && m->gs[i]->spec_result))
       return mfail(m, PPS_ESTATE, "graph " + std::to_string(i) + " has no second factor set (not uploaded)");
-  const bool dual = true;
+  *mode_out = mode; *max_stages_out = max_stages;
+  return PPS_OK;
+}
+
+// ---- 2. streams, pinned result records, device tables: the graphs' records, their band schedules, and (ha, kept for the epilogue) the second
+// factorisation + the three state copies per graph ----
+static int upload_tables(pps_multi* m, int max_stages, std::vector<BatchAlt>& ha) {
+  const int G = (int)m->gs.size();
   if (!m->stream) MHIP(m, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
   if (!m->stream2) MHIP(m, hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking));
   if (!m->stream3) MHIP(m, hipStreamCreateWithFlags(&m->stream3, hipStreamNonBlocking));
@@ -205,22 +208,36 @@ static int multi_optimize(pps_multi* m, int* iterations, int* status) {
     m->cap_results = G;
   }
   memset(m->results, 0, sizeof(double) * 12 * (size_t)G);
-  // ---- device tables: the graphs' records and their band schedules ----
   std::vector<DevGraph> hg(G);
   std::vector<BatchStage> hs((size_t)std::max(1, max_stages) * G, BatchStage{0, 0});
+  ha.resize(G);
   for (int i = 0; i < G; i++) {
-    hg[i] = m->gs[i]->dev;
-    const Analysis& A = m->gs[i]->an;
+    const pps_graph* g = m->gs[i];
+    hg[i] = g->dev;
+    const Analysis& A = g->an;
     for (int stg = 0; stg < A.n_stages; stg++) hs[(size_t)stg * G + i] = BatchStage{A.stage_grp_off[stg], A.stage_grp_off[stg + 1] - A.stage_grp_off[stg]};
+    ha[i] = BatchAlt{g->spec_L, g->spec_U, g->spec_delta, g->spec_result, g->spec_chi2_partials, g->spec_dn_partials, g->spec_ticket,
+                     {g->dev.pose_est, g->dev.pose_lin, g->spec_pose}, {g->dev.plane_est, g->dev.plane_lin, g->spec_plane}};
   }
   if (m->cap_gs < (size_t)G) { if (m->d_gs) (void)hipFree(m->d_gs); m->d_gs = nullptr; MHIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_gs), sizeof(DevGraph) * (size_t)G)); m->cap_gs = G; }
   if (m->cap_stage < hs.size()) { if (m->d_stage) (void)hipFree(m->d_stage); m->d_stage = nullptr; MHIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_stage), sizeof(BatchStage) * hs.size())); m->cap_stage = hs.size(); }
+  if (m->cap_alt < (size_t)G) { if (m->d_alt) (void)hipFree(m->d_alt); m->d_alt = nullptr; MHIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_alt), sizeof(BatchAlt) * (size_t)G)); m->cap_alt = G; }
   MHIP(m, hipMemcpy(m->d_gs, hg.data(), sizeof(DevGraph) * (size_t)G, hipMemcpyHostToDevice));
   MHIP(m, hipMemcpy(m->d_stage, hs.data(), sizeof(BatchStage) * hs.size(), hipMemcpyHostToDevice));
-  const double t_s2 = now_s() - t0;
-  // ---- launch geometry per chunk of kBatchMax graphs ----
-  int n_cu = 256;
-  { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, m->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount; }
+  MHIP(m, hipMemcpy(m->d_alt, ha.data(), sizeof(BatchAlt) * (size_t)G, hipMemcpyHostToDevice));
+  return PPS_OK;
+}
+
+// ---- 3. launch geometry per chunk of at most kBatchMax graphs: a function of host data only (the graphs' analyses, device counts and per-stage
+// wave counts, the number of CUs, the switches) ----
+struct ChunkPlan {
+  int n_split = 1, CH = kBatchMax, n_chunks = 0;      // streams the chunks are dealt to | graphs per chunk | chunks: graphs [c CH, min(G, (c + 1) CH))
+  std::vector<BatchGeom> geom;
+};
+
+// false: a band group of the batch does not fit the LDS
+static bool plan_chunks(const std::vector<pps_graph*>& gs, int max_stages, int n_cu, const Switches& sw, bool profiling, ChunkPlan* plan) {
+  const int G = (int)gs.size();
   // Large batches are split into two or three chunks of equal size that advance on their own streams: the launches of a chunk's upper tree
   // levels hold a few hundred wavefronts each and leave most of the device to the other chunks' kernels.  A chunk keeps at least 120 000
   // factors -- below that its kernels would be the latency forms.  Round 6 (with the throughput forms from 120 000 factors per chunk on, same
@@ -228,23 +245,24 @@ static int multi_optimize(pps_multi* m, int* iterations, int* status) {
   // G = 80 2 220 / 2 199; G = 96 2 234 / 2 269; G = 128 2 314 / 2 346 -- two chunks from 240 000 factors, three from 560 000.  (Event-timed
   // profiling keeps one stream and whole chunks: the phases must not overlap.)
   long long total_factors = 0;
-  for (int i = 0; i < G; i++) total_factors += m->gs[i]->n_live_factors;
-  const int n_split = m->sw.multi_split > 0 ? std::min(3, m->sw.multi_split)      // (PPS_MULTI_SPLIT: the multi-chunk scheduler on a small batch -- tests)
-                                            : (total_factors >= 560000 ? 3 : (total_factors >= 240000 ? 2 : 1));
-  const bool two_streams = n_split > 1 && !m->profiling;
+  for (int i = 0; i < G; i++) total_factors += gs[i]->n_live_factors;
+  const int n_split = sw.multi_split > 0 ? std::min(3, sw.multi_split)      // (PPS_MULTI_SPLIT: the multi-chunk scheduler on a small batch -- tests)
+                                         : (total_factors >= 560000 ? 3 : (total_factors >= 240000 ? 2 : 1));
+  const bool two_streams = n_split > 1 && !profiling;
   const int CH = two_streams ? std::min(kBatchMax, (G + n_split - 1) / n_split) : kBatchMax;
   const int n_chunks = (G + CH - 1) / CH;
-  std::vector<BatchGeom> geom(n_chunks);
+  plan->n_split = n_split; plan->CH = CH; plan->n_chunks = n_chunks;
+  plan->geom.assign(n_chunks, BatchGeom{});
   const size_t lds_budget = 150 * 1024;
   for (int c = 0; c < n_chunks; c++) {
-    BatchGeom& q = geom[c];
+    BatchGeom& q = plan->geom[c];
     q.n_stages = max_stages;
     int max_panel[32] = {0};
     for (int stg = 0; stg < 32; stg++) q.stage_reg_only[stg] = true;
     bool level_ok = true;
     bool lvl_direct_bad[64] = {false};
     for (int i = c * CH; i < std::min(G, (c + 1) * CH); i++) {
-      const pps_graph* g = m->gs[i];
+      const pps_graph* g = gs[i];
       const DevGraph& d = g->dev;
       const Analysis& A = g->an;
       q.lin_blocks = std::max(q.lin_blocks, (d.n_obs_fixed + 11) / 12 + (d.n_odo + 7) / 8 + (d.n_pp + 7) / 8 + (d.n_lp + 7) / 8);   // (lane form: 12 plane observations / 8 other factors per block)
@@ -288,34 +306,34 @@ static int multi_optimize(pps_multi* m, int* iterations, int* status) {
     for (int l = 0; l < 64; l++) if (lvl_direct_bad[l]) q.lvl_direct_pp[l] = 0;
     // the lane-parallel central differences (32 lanes per factor, 13 of them idle) are the low-latency form; from a few
     // hundred thousand factors per launch the thread-per-factor form has the higher throughput
-    const long long thr = m->sw.multi_thread_factors;          // 120 000 (PPS_MULTI_THREAD_FACTORS lowers it for the tests)
-    q.lin_thread_form = q.n_factors_total > thr || m->sw.multi_thread_form;      // (PPS_MULTI_THREAD_FORM / PPS_MULTI_LEVELS: forced onto small batches by the parity test)
+    const long long thr = sw.multi_thread_factors;          // 120 000 (PPS_MULTI_THREAD_FACTORS lowers it for the tests)
+    q.lin_thread_form = q.n_factors_total > thr || sw.multi_thread_form;      // (PPS_MULTI_THREAD_FORM / PPS_MULTI_LEVELS: forced onto small batches by the parity test)
     // throughput over latency from the same size on: a launch per tree level and size class instead of a launch per band
-    q.level_form = level_ok && (q.n_factors_total > thr || m->sw.multi_levels);
+    q.level_form = level_ok && (q.n_factors_total > thr || sw.multi_levels);
     { int mp = 1; for (int stg = 0; stg < max_stages; stg++) mp = std::max(mp, max_panel[stg]); q.solve_per_wave_all = (int)(band_solve_lds_bytes(mp) / sizeof(double)); }
     for (int stg = 0; stg < max_stages; stg++) {
       q.stage_per_wave_factor[stg] = (int)(band_lds_bytes(q.stage_per_wave_factor[stg], q.stage_reg_only[stg]) / sizeof(double));
       q.stage_per_wave_solve[stg] = (int)(band_solve_lds_bytes(max_panel[stg]) / sizeof(double));
-      const size_t fw = (size_t)q.stage_per_wave_factor[stg] * sizeof(double), sw = (size_t)q.stage_per_wave_solve[stg] * sizeof(double);
+      const size_t fw = (size_t)q.stage_per_wave_factor[stg] * sizeof(double), sv = (size_t)q.stage_per_wave_solve[stg] * sizeof(double);
       const size_t xbytes = (size_t)q.stage_grp_fronts[stg] * band_max_rows() * sizeof(double);
-      if (fw > lds_budget || xbytes + sw > lds_budget) return mfail(m, PPS_ESTATE, "a band group of this batch does not fit the LDS: solve the graphs through their own handles");
+      if (fw > lds_budget || xbytes + sv > lds_budget) return false;
       q.stage_nw_factor[stg] = (int)std::max<size_t>(1, std::min<size_t>(q.stage_nw_factor[stg], lds_budget / fw));
-      q.stage_nw_solve[stg] = (int)std::max<size_t>(1, std::min<size_t>(q.stage_nw_solve[stg], (lds_budget - xbytes) / sw));
+      q.stage_nw_solve[stg] = (int)std::max<size_t>(1, std::min<size_t>(q.stage_nw_solve[stg], (lds_budget - xbytes) / sv));
       // Throughput, not latency, is what a batch is for.  A band group is a sub-tree (8 + 4 + 2 + 1 fronts on C2): walked
       // by 8 waves, half of the wave-slots -- and the LDS they hold -- idle on its upper levels.  When the chunk has more
       // groups than the device has wave-slots, fewer waves per group keep every slot on a front (2 waves: 94 % instead of
       // 47 %); the groups of the upper stages stay wide, there the tree depth is the cost.
-      long long total_groups = 0;
+      long long total_groups = 0;                  // (two per group of a graph: both damping values are factored)
       for (int i = c * CH; i < std::min(G, (c + 1) * CH); i++) {
-        const Analysis& A = m->gs[i]->an;
-        if (stg < A.n_stages) total_groups += (dual ? 2 : 1) * (A.stage_grp_off[stg + 1] - A.stage_grp_off[stg]);
+        const Analysis& A = gs[i]->an;
+        if (stg < A.n_stages) total_groups += 2 * (A.stage_grp_off[stg + 1] - A.stage_grp_off[stg]);
       }
       if (total_groups > 0) {
         // (wave-slots of a CU: what its LDS holds, and no more than the registers allow -- 2 waves per SIMD for the factor kernels, 3 for the
         // back-substitution: G = 8 is 512 groups of stage 0, and with eight waves each only 256 of them were resident at a time)
         // (counted by the LDS alone, up to round 4: G = 8 786 graphs/s against 865, G = 16 1 138 against 1 176, G = 24 1 222 against 1 259)
         const long long slots_f = (long long)n_cu * std::min<size_t>(8, std::max<size_t>(1, lds_budget / fw));
-        const long long slots_s = (long long)n_cu * std::min<size_t>(12, std::max<size_t>(1, (lds_budget - std::min(lds_budget / 2, xbytes)) / sw));
+        const long long slots_s = (long long)n_cu * std::min<size_t>(12, std::max<size_t>(1, (lds_budget - std::min(lds_budget / 2, xbytes)) / sv));
         q.stage_nw_factor[stg] = (int)std::max<long long>(1, std::min<long long>(q.stage_nw_factor[stg], (slots_f + total_groups - 1) / total_groups));
         q.stage_nw_solve[stg] = (int)std::max<long long>(1, std::min<long long>(q.stage_nw_solve[stg], (slots_s + total_groups - 1) / total_groups));
       }
@@ -323,12 +341,12 @@ static int multi_optimize(pps_multi* m, int* iterations, int* status) {
   }
   // the pre-assembling walk (k_band_factor_pre) and the data-flow back-substitution (k_band_solve_flow) of the band kernels, per chunk
   for (int c = 0; c < n_chunks; c++) {
-    BatchGeom& q = geom[c];
+    BatchGeom& q = plan->geom[c];
     for (int stg = 0; stg < q.n_stages && stg < 32; stg++) {
-      bool pre = q.stage_reg_only[stg] && !m->sw.no_preassemble;
+      bool pre = q.stage_reg_only[stg] && !sw.no_preassemble;
       const int nw = q.stage_nw_factor[stg];
       for (int i = c * CH; pre && i < std::min(G, (c + 1) * CH); i++) {
-        const Analysis& A = m->gs[i]->an;
+        const Analysis& A = gs[i]->an;
         if (stg >= A.n_stages) continue;
         for (int gi = A.stage_grp_off[stg]; pre && gi < A.stage_grp_off[stg + 1]; gi++) {
           const int l0 = A.grp_lvl_off[gi], nl = A.grp_lvl_off[gi + 1] - l0;
@@ -346,10 +364,9 @@ static int multi_optimize(pps_multi* m, int* iterations, int* status) {
       // narrowed to fill the device with groups (throughput: G = 32 and up) keeps the barrier form -- waves that spin on a flag hold
       // wave slots other groups could use (G = 32: 3.9 against 3.7 ms of back-substitution per batch solve)
       q.stage_nw_flow[stg] = 0;
-      if (!m->sw.no_solve_flow && q.stage_grp_fronts[stg] > 1 && q.stage_nw_solve[stg] >= std::min(8, q.stage_grp_fronts[stg])) {
+      if (!sw.no_solve_flow && q.stage_grp_fronts[stg] > 1 && q.stage_nw_solve[stg] >= std::min(8, q.stage_grp_fronts[stg])) {
         const size_t per_wave = (size_t)q.stage_per_wave_solve[stg] * sizeof(double);
         const size_t fixed = ((size_t)q.stage_grp_fronts[stg] * band_max_rows() + (size_t)(q.stage_grp_fronts[stg] + 1) / 2) * sizeof(double);
-        const size_t lds_budget = 150 * 1024;
         if (fixed + per_wave <= lds_budget) {
           const int room = (int)((lds_budget - fixed) / per_wave);
           int nwf = std::min(std::min(12, q.stage_grp_fronts[stg]), room);
@@ -358,227 +375,234 @@ static int multi_optimize(pps_multi* m, int* iterations, int* status) {
       }
     }
   }
-  // ---- dual-lambda form: every graph walks lm_solve_dual's scheme, in lockstep rounds of one linearisation each ----
-  const double t_setup = now_s() - t0;
-  const bool timing_rounds = m->sw.multi_timing > 1;
-  m->n_chunks_last = n_chunks; m->forms_last = 0;
-  for (int c = 0; c < n_chunks; c++) m->forms_last |= (geom[c].lin_thread_form ? 1 : 0) | (geom[c].level_form ? 2 : 0);
+  return true;
+}
 
-  {
-    std::vector<BatchAlt> ha(G);
-    for (int i = 0; i < G; i++) {
-      pps_graph* g = m->gs[i];
-      ha[i] = BatchAlt{g->spec_L, g->spec_U, g->spec_delta, g->spec_result, g->spec_chi2_partials, g->spec_dn_partials, g->spec_ticket,
-                       {g->dev.pose_est, g->dev.pose_lin, g->spec_pose}, {g->dev.plane_est, g->dev.plane_lin, g->spec_plane}};
+// ---- 4. the rounds: every graph walks lm_solve_dual's scheme, in lockstep rounds of one linearisation each ----
+// a graph's place in that scheme: the LM rule's state and what it writes, and which of its records / state copies the next verdict is about
+struct GraphRun {
+  LmControl lm;
+  LmSink sink;                     // (no "LM Iteration" lines from a batch)
+  int cur = 0, xsel = 0;
+  bool done = false, have_next = true, relin = true, active = true, trial_taken = false;
+};
+
+// the part of lm_solve_dual's loop that needs no launch: consume the verdicts that are on the host (rec: the graph's 12 result doubles).
+// Returns with the graph done, or active (and possibly relin) for the next round.
+static void advance(GraphRun& q, pps_graph* g, const double* rec) {
+  q.active = false; q.relin = false;
+  for (;;) {
+    if (!q.lm.running(g->props)) { q.done = true; return; }
+    const LmVerdict v = q.lm.judge(q.sink, rec[4 * (1 + q.cur)]);
+    if (v == LmVerdict::Converged) { q.trial_taken = true; q.done = true; return; }
+    if (v == LmVerdict::Accepted) {
+      q.xsel = (q.xsel + 1 + q.cur) % 3;                           // the accepted copy is the linearisation point now
+      q.relin = true; q.active = true; q.cur = 0; q.have_next = true;
+      g->stats.n_linearize++; g->stats.n_factorize += 2;
+      return;
     }
-    if (m->cap_alt < (size_t)G) { if (m->d_alt) (void)hipFree(m->d_alt); m->d_alt = nullptr; MHIP(m, hipMalloc(reinterpret_cast<void**>(&m->d_alt), sizeof(BatchAlt) * (size_t)G)); m->cap_alt = G; }
-    MHIP(m, hipMemcpy(m->d_alt, ha.data(), sizeof(BatchAlt) * (size_t)G, hipMemcpyHostToDevice));
-    struct LMD { double lambda, error, dnorm; int num_iter, cur, xsel; bool done, have_next, relin, active, last_notpd, trial_taken; int n_notpd; };
-    std::vector<LMD> lm(G);
-    for (int i = 0; i < G; i++) lm[i] = LMD{m->gs[i]->props.lm_lambda0, 0.0, 0.0, 0, 0, 0, false, true, true, true, false, false, 0};
-    auto make_args = [&](int c, double seq) {
-      BatchArgs a{};
-      a.gs = m->d_gs; a.stage_tab = m->d_stage; a.results = m->results; a.n_total = G; a.b0 = c * CH;
-      a.n = std::min(G, (c + 1) * CH) - a.b0; a.seq = seq;
-      a.alt = m->d_alt; a.rstride = 12;
-      a.no_products = geom[c].lin_thread_form ? 1 : 0;
-      for (int k = 0; k < a.n; k++) {
-        const LMD& q = lm[a.b0 + k];
-        a.lambda[k] = q.lambda; a.lambda2[k] = q.lambda * m->gs[a.b0 + k]->props.lm_lambda_factor;
-        a.xsel[k] = (unsigned char)q.xsel;
-        a.flags[k] = (unsigned char)((q.active ? BF_ACTIVE : 0) | (q.relin ? BF_RELIN : 0));
-      }
-      return a;
-    };
-    m->ev_used = 0; m->n_relin = 0; m->n_solves = 0;
-    for (double& t : m->t_phase) t = 0;
-    auto mark = [&]() {
-      if (!m->profiling) return;
-      if (m->ev_used == m->evs.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; m->evs.push_back(e); }
-      (void)hipEventRecord(m->evs[m->ev_used++], m->stream);
-    };
-    auto next_event = [&]() -> hipEvent_t {
-      if (!m->profiling) return nullptr;
-      if (m->ev_used == m->evs.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return nullptr; m->evs.push_back(e); }
-      return m->evs[m->ev_used++];
-    };
-    // one round of one chunk: e0 | K1 | e1 | K2 (+ chi2 at x) | e2 | factor x 2 | e3 | solve x 2 | e4 | both trials | e5
-    auto run_round = [&](const BatchArgs& a, const BatchGeom& q, bool first, bool any_relin, hipStream_t st) -> int {
-      if (first) MHIP(m, launch_batch_begin_dual(a, q, st));
-      mark();
-      if (any_relin) MHIP(m, launch_batch_linearize(a, q, q.lin_thread_form ? mode | 2 : mode, st));
-      mark();
-      if (any_relin) MHIP(m, launch_batch_hblocks(a, q, st, !q.lin_thread_form));
-      if (first) MHIP(m, launch_batch_chi2(a, q, 0, st));
-      mark();
-      hipEvent_t ef = next_event();
-      MHIP(m, launch_batch_solve(a, q, st, ef));
-      mark();
-      MHIP(m, launch_batch_trial_dual(a, q, st));
-      mark();
-      return PPS_OK;
-    };
-    // the part of lm_solve_dual's loop that needs no launch: consume the verdicts that are on the host.  Returns with the
-    // graph done, or active (and possibly relin) for the next round.
-    auto advance = [&](int i) {
-      LMD& q = lm[i];
-      pps_graph* g = m->gs[i];
-      const pps_props& prop = g->props;
-      q.active = false; q.relin = false;
-      for (;;) {
-        if (!((prop.max_iterations <= 0 || q.num_iter < prop.max_iterations) && q.dnorm > prop.epsilon2 && q.error > prop.epsilon_abs)) { q.done = true; return; }
-        q.num_iter++;
-        const double* rec = m->results + 12 * (size_t)i + 4 * (1 + q.cur);
-        const double error_new = rec[0];
-        const double error_diff = q.error - error_new;
-        const bool accepted = error_diff > 0.;
-        g->tr_lambda.push_back(q.lambda); g->tr_chi2.push_back(error_new); g->tr_acc.push_back(accepted ? 1 : 0);
-        if (accepted) {
-          g->stats.lm_trials_accepted++;
-          if (error_diff < prop.epsilon_rel * q.error) { q.error = error_new; q.trial_taken = true; q.done = true; return; }   // (:431-434)
-          q.lambda /= prop.lm_lambda_factor;
-          q.error = error_new;
-          q.xsel = (q.xsel + 1 + q.cur) % 3;                           // the accepted copy is the linearisation point now
-          q.relin = true; q.active = true; q.cur = 0; q.have_next = true;
-          g->stats.n_linearize++; g->stats.n_factorize += 2;
-          return;
-        }
-        g->stats.lm_trials_rejected++;
-        q.lambda *= prop.lm_lambda_factor;
-        if (q.have_next) {                                             // the step for this lambda was computed alongside
-          q.cur = 1; q.have_next = false;
-          const double* rb = m->results + 12 * (size_t)i + 8;
-          q.dnorm = std::sqrt(rb[1]); q.last_notpd = rb[2] != 0.0; q.n_notpd += q.last_notpd ? 1 : 0;
-          continue;
-        }
-        q.active = true; q.cur = 0; q.have_next = true;               // both rejected: same J and H, two more damping values
-        g->stats.n_factorize += 2;
-        return;
-      }
-    };
-    // The chunks advance on their own: a chunk's next round is launched as soon as ITS graphs have delivered their records, while the
-    // other chunk's kernels keep the device busy -- no barrier over the whole batch between rounds (the device would idle for the
-    // host's bookkeeping 42 times per solve), and the chunks drift apart, so that one's narrow tree levels meet the other's wide ones.
-    struct ChunkRun { double seq = 0.0; bool in_flight = false, first = true; int rounds = 0; };
-    std::vector<ChunkRun> cr(n_chunks);
-    hipStream_t const streams[3] = {m->stream, m->stream2, m->stream3};
-    auto stream_of = [&](int c) { return n_chunks > 1 && !m->profiling ? streams[c % n_split] : m->stream; };
-    auto chunk_done = [&](int c) -> bool {                     // (non-blocking) both records of every active graph of the chunk are this round's
-      for (int i = c * CH; i < std::min(G, (c + 1) * CH); i++) {
-        if (!lm[i].active) continue;
-        const volatile double* r = m->results + 12 * (size_t)i;
-        if (r[4 + 3] != cr[c].seq || r[8 + 3] != cr[c].seq) return false;
-      }
-      return true;
-    };
-    m->rounds = 0;
-    for (int c = 0; c < n_chunks; c++) {
-      m->seq += 1.0; cr[c].seq = m->seq; cr[c].in_flight = true;
-      const BatchArgs a = make_args(c, cr[c].seq);
-      int rc = run_round(a, geom[c], true, true, stream_of(c)); if (rc != PPS_OK) return rc;
+    if (q.have_next) {                                             // the step for this lambda was computed alongside
+      q.cur = 1; q.have_next = false;
+      q.lm.take_step(rec + 8);
+      continue;
     }
-    m->n_relin += G; m->n_solves += 2 * (long long)G;
-    int n_flight = n_chunks;
-    double t_progress = now_s();
-    // a HIP failure inside the loop: whatever the other chunks still have in flight is drained before the caller sees the error
-    auto drain = [&]() { for (hipStream_t s3 : streams) if (s3) (void)hipStreamSynchronize(s3); };
-    double t_launch = 0.0, t_book = 0.0;                       // host seconds inside run_round / between a chunk's records and its next launch
-    int n_launch_rounds = 0;
-    while (n_flight > 0) {
-      bool progressed = false;
-      for (int c = 0; c < n_chunks; c++) {
-        if (!cr[c].in_flight || !chunk_done(c)) continue;
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        const double tb0 = m->sw.multi_timing ? now_s() : 0.0;
-        progressed = true;
-        cr[c].rounds++;
-        const int i0 = c * CH, i1 = std::min(G, (c + 1) * CH);
-        int n_active = 0;
-        for (int i = i0; i < i1; i++) {
-          pps_graph* g = m->gs[i];
-          if (cr[c].first) {
-            const double* r0 = m->results + 12 * (size_t)i;
-            lm[i].error = r0[0]; g->stats.chi2_initial = r0[0];
-            lm[i].dnorm = std::sqrt(r0[5]); lm[i].last_notpd = r0[6] != 0.0; lm[i].n_notpd = lm[i].last_notpd ? 1 : 0;
-            g->stats.n_linearize = 1; g->stats.n_factorize = 2;
-          } else if (lm[i].active) {
-            const double* r1 = m->results + 12 * (size_t)i + 4;
-            lm[i].dnorm = std::sqrt(r1[1]);
-            lm[i].last_notpd = r1[2] != 0.0;
-            lm[i].n_notpd += lm[i].last_notpd ? 1 : 0;
-          }
-          if (lm[i].active || cr[c].first) {                      // status words of this round's records (see wait_result, pps_solve.cpp)
-            const double* rr = m->results + 12 * (size_t)i;
-            if (rr[4 + 2] >= kStatusInternal || rr[8 + 2] >= kStatusInternal) {
-              drain();
-              return mfail(m, PPS_EHIP, "graph " + std::to_string(i) + ": internal error: a hand-over flag between the waves or workgroups of a K3 launch never arrived");
-            }
-          }
-          if (!lm[i].done) advance(i); else { lm[i].active = false; lm[i].relin = false; }
-          n_active += lm[i].active ? 1 : 0;
-        }
-        if (timing_rounds) fprintf(stderr, "  chunk %d round %d at %.3f ms: %d active next\n", c, cr[c].rounds, 1e3 * (now_s() - t0), n_active);
-        cr[c].first = false;
-        if (n_active == 0) { cr[c].in_flight = false; n_flight--; continue; }
-        m->seq += 1.0; cr[c].seq = m->seq;
-        const BatchArgs a = make_args(c, cr[c].seq);
-        bool any_relin = false;
-        for (int k = 0; k < a.n; k++) { any_relin = any_relin || (a.flags[k] & BF_RELIN); m->n_solves += (a.flags[k] & BF_ACTIVE) ? 2 : 0; m->n_relin += (a.flags[k] & BF_RELIN) ? 1 : 0; }
-        const double tb1 = m->sw.multi_timing ? now_s() : 0.0;
-        int rc = run_round(a, geom[c], false, any_relin, stream_of(c)); if (rc != PPS_OK) { drain(); return rc; }
-        if (m->sw.multi_timing) { t_book += tb1 - tb0; t_launch += now_s() - tb1; n_launch_rounds++; }
-      }
-      if (progressed) { t_progress = now_s(); continue; }
-      if (now_s() - t_progress > 2.0) {                        // (nothing for two seconds: let the streams drain, look once more)
-        MHIP(m, hipStreamSynchronize(m->stream));
-        MHIP(m, hipStreamSynchronize(m->stream2));
-        MHIP(m, hipStreamSynchronize(m->stream3));
-        bool any_done = false;
-        for (int c = 0; c < n_chunks; c++) any_done = any_done || (cr[c].in_flight && chunk_done(c));
-        if (!any_done) return mfail(m, PPS_EHIP, "result records of a round did not arrive");     // (all three streams are idle here)
-      }
-    }
-    for (int c = 0; c < n_chunks; c++) m->rounds = std::max(m->rounds, cr[c].rounds);
-    MHIP(m, hipStreamSynchronize(m->stream));
-    MHIP(m, hipStreamSynchronize(m->stream2));
-    MHIP(m, hipStreamSynchronize(m->stream3));
-    for (size_t k = 0; k + 6 <= m->ev_used; k += 6) {
-      const hipEvent_t* e = &m->evs[k];
-      for (int ph = 0; ph < 5; ph++) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, e[ph], e[ph + 1]) == hipSuccess) m->t_phase[ph] += 1e-3 * ms;
-      }
-    }
-    int first_bad = PPS_OK;
-    m->t_total = now_s() - t0;
-    if (m->sw.multi_timing)
-      fprintf(stderr, "pps_multi: G %d total %.3f ms, of which setup %.3f (per-graph checks %.3f, tables %.3f, geometry %.3f); %d rounds\n", G,
-              1e3 * m->t_total, 1e3 * t_setup, 1e3 * t_s1, 1e3 * (t_s2 - t_s1), 1e3 * (t_setup - t_s2), m->rounds);
-    if (m->sw.multi_timing && n_launch_rounds > 0)
-      fprintf(stderr, "pps_multi: host side of %d chunk rounds: launches %.3f ms (%.1f us per round), verdicts + arguments %.3f ms (%.1f us per round)\n",
-              n_launch_rounds, 1e3 * t_launch, 1e6 * t_launch / n_launch_rounds, 1e3 * t_book, 1e6 * t_book / n_launch_rounds);
-    for (int i = 0; i < G; i++) {
-      pps_graph* g = m->gs[i];
-      const LMD& q = lm[i];
-      // linpoint_to_estimate (:466): the accepted, converged trial -- or the linearisation point when the pending step is dropped
-      const int fin = q.trial_taken ? (q.xsel + 1 + q.cur) % 3 : q.xsel;
-      double* const sp[3] = {ha[i].pose[0], ha[i].pose[1], ha[i].pose[2]};
-      double* const sl[3] = {ha[i].plane[0], ha[i].plane[1], ha[i].plane[2]};
-      g->dev.pose_est = sp[fin]; g->dev.plane_est = sl[fin];
-      g->dev.pose_lin = sp[(fin + 1) % 3]; g->dev.plane_lin = sl[(fin + 1) % 3];
-      g->spec_pose = sp[(fin + 2) % 3]; g->spec_plane = sl[(fin + 2) % 3];
-      g->dev_values_newer = true; g->pin_holds_est = false;
-      g->stats.lm_iterations = q.num_iter; g->stats.chi2_final = q.error; g->stats.lambda_final = q.lambda; g->stats.last_delta_norm = q.dnorm;
-      g->stats.lm_trials_notpd = q.n_notpd; g->stats.t_total = m->t_total;
-      if (iterations) iterations[i] = q.num_iter;
-      const int st_i = q.last_notpd ? PPS_ENOTPD : PPS_OK;
-      if (st_i != PPS_OK) g->err = "normal equations not positive definite at the last LM trial";
-      if (status) status[i] = st_i;
-      if (st_i != PPS_OK && first_bad == PPS_OK) first_bad = st_i;
-    }
-    if (first_bad != PPS_OK) return mfail(m, first_bad, "at least one graph ended on a factorisation that was not positive definite (see status[])");
-    return PPS_OK;
+    q.active = true; q.cur = 0; q.have_next = true;               // both rejected: same J and H, two more damping values
+    g->stats.n_factorize += 2;
+    return;
   }
+}
+
+struct RoundsHostTime { double launch = 0.0, book = 0.0; int n = 0; };   // host seconds inside run_round / between a chunk's records and its next launch
+
+static int run_rounds(pps_multi* m, const ChunkPlan& plan, int mode, std::vector<GraphRun>& lm, double t0, RoundsHostTime* ht) {
+  const int G = (int)m->gs.size(), CH = plan.CH, n_chunks = plan.n_chunks;
+  const std::vector<BatchGeom>& geom = plan.geom;
+  const bool timing_rounds = m->sw.multi_timing > 1;
+  auto make_args = [&](int c, double seq) {
+    BatchArgs a{};
+    a.gs = m->d_gs; a.stage_tab = m->d_stage; a.results = m->results; a.n_total = G; a.b0 = c * CH;
+    a.n = std::min(G, (c + 1) * CH) - a.b0; a.seq = seq;
+    a.alt = m->d_alt; a.rstride = 12;
+    a.no_products = geom[c].lin_thread_form ? 1 : 0;
+    for (int k = 0; k < a.n; k++) {
+      const GraphRun& q = lm[a.b0 + k];
+      a.lambda[k] = q.lm.lambda; a.lambda2[k] = q.lm.lambda * m->gs[a.b0 + k]->props.lm_lambda_factor;
+      a.xsel[k] = (unsigned char)q.xsel;
+      a.flags[k] = (unsigned char)((q.active ? BF_ACTIVE : 0) | (q.relin ? BF_RELIN : 0));
+    }
+    return a;
+  };
+  m->ev_used = 0; m->n_relin = 0; m->n_solves = 0;
+  for (double& t : m->t_phase) t = 0;
+  auto mark = [&]() {
+    if (!m->profiling) return;
+    if (m->ev_used == m->evs.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; m->evs.push_back(e); }
+    (void)hipEventRecord(m->evs[m->ev_used++], m->stream);
+  };
+  auto next_event = [&]() -> hipEvent_t {
+    if (!m->profiling) return nullptr;
+    if (m->ev_used == m->evs.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return nullptr; m->evs.push_back(e); }
+    return m->evs[m->ev_used++];
+  };
+  // one round of one chunk: e0 | K1 | e1 | K2 (+ chi2 at x) | e2 | factor x 2 | e3 | solve x 2 | e4 | both trials | e5
+  auto run_round = [&](const BatchArgs& a, const BatchGeom& q, bool first, bool any_relin, hipStream_t st) -> int {
+    if (first) MHIP(m, launch_batch_begin_dual(a, q, st));
+    mark();
+    if (any_relin) MHIP(m, launch_batch_linearize(a, q, q.lin_thread_form ? mode | 2 : mode, st));
+    mark();
+    if (any_relin) MHIP(m, launch_batch_hblocks(a, q, st, !q.lin_thread_form));
+    if (first) MHIP(m, launch_batch_chi2(a, q, 0, st));
+    mark();
+    hipEvent_t ef = next_event();
+    MHIP(m, launch_batch_solve(a, q, st, ef));
+    mark();
+    MHIP(m, launch_batch_trial_dual(a, q, st));
+    mark();
+    return PPS_OK;
+  };
+  // The chunks advance on their own: a chunk's next round is launched as soon as ITS graphs have delivered their records, while the
+  // other chunk's kernels keep the device busy -- no barrier over the whole batch between rounds (the device would idle for the
+  // host's bookkeeping 42 times per solve), and the chunks drift apart, so that one's narrow tree levels meet the other's wide ones.
+  struct ChunkRun { double seq = 0.0; bool in_flight = false, first = true; int rounds = 0; };
+  std::vector<ChunkRun> cr(n_chunks);
+  hipStream_t const streams[3] = {m->stream, m->stream2, m->stream3};
+  auto stream_of = [&](int c) { return n_chunks > 1 && !m->profiling ? streams[c % plan.n_split] : m->stream; };
+  auto chunk_done = [&](int c) -> bool {                     // (non-blocking) both records of every active graph of the chunk are this round's
+    for (int i = c * CH; i < std::min(G, (c + 1) * CH); i++) {
+      if (!lm[i].active) continue;
+      const volatile double* r = m->results + 12 * (size_t)i;
+      if (r[4 + 3] != cr[c].seq || r[8 + 3] != cr[c].seq) return false;
+    }
+    return true;
+  };
+  m->rounds = 0;
+  for (int c = 0; c < n_chunks; c++) {
+    m->seq += 1.0; cr[c].seq = m->seq; cr[c].in_flight = true;
+    const BatchArgs a = make_args(c, cr[c].seq);
+    int rc = run_round(a, geom[c], true, true, stream_of(c)); if (rc != PPS_OK) return rc;
+  }
+  m->n_relin += G; m->n_solves += 2 * (long long)G;
+  int n_flight = n_chunks;
+  double t_progress = now_s();
+  // a HIP failure inside the loop: whatever the other chunks still have in flight is drained before the caller sees the error
+  auto drain = [&]() { for (hipStream_t s3 : streams) if (s3) (void)hipStreamSynchronize(s3); };
+  while (n_flight > 0) {
+    bool progressed = false;
+    for (int c = 0; c < n_chunks; c++) {
+      if (!cr[c].in_flight || !chunk_done(c)) continue;
+      __atomic_thread_fence(__ATOMIC_ACQUIRE);
+      const double tb0 = m->sw.multi_timing ? now_s() : 0.0;
+      progressed = true;
+      cr[c].rounds++;
+      const int i0 = c * CH, i1 = std::min(G, (c + 1) * CH);
+      int n_active = 0;
+      for (int i = i0; i < i1; i++) {
+        pps_graph* g = m->gs[i];
+        const double* rr = m->results + 12 * (size_t)i;       // chi2 at x | trial 0 | trial 1: (chi2, |delta|^2, status word, seq) each
+        if (cr[c].first) {
+          lm[i].lm.error = rr[0]; g->stats.chi2_initial = rr[0];
+          lm[i].lm.take_step(rr + 4);
+          g->stats.n_linearize = 1; g->stats.n_factorize = 2;
+        } else if (lm[i].active) lm[i].lm.take_step(rr + 4);
+        if (lm[i].active || cr[c].first) {                      // status words of this round's records (see wait_result, pps_solve.cpp)
+          if (rr[4 + 2] >= kStatusInternal || rr[8 + 2] >= kStatusInternal) {
+            drain();
+            return mfail(m, PPS_EHIP, "graph " + std::to_string(i) + ": internal error: a hand-over flag between the waves or workgroups of a K3 launch never arrived");
+          }
+        }
+        if (!lm[i].done) advance(lm[i], g, rr); else { lm[i].active = false; lm[i].relin = false; }
+        n_active += lm[i].active ? 1 : 0;
+      }
+      if (timing_rounds) fprintf(stderr, "  chunk %d round %d at %.3f ms: %d active next\n", c, cr[c].rounds, 1e3 * (now_s() - t0), n_active);
+      cr[c].first = false;
+      if (n_active == 0) { cr[c].in_flight = false; n_flight--; continue; }
+      m->seq += 1.0; cr[c].seq = m->seq;
+      const BatchArgs a = make_args(c, cr[c].seq);
+      bool any_relin = false;
+      for (int k = 0; k < a.n; k++) { any_relin = any_relin || (a.flags[k] & BF_RELIN); m->n_solves += (a.flags[k] & BF_ACTIVE) ? 2 : 0; m->n_relin += (a.flags[k] & BF_RELIN) ? 1 : 0; }
+      const double tb1 = m->sw.multi_timing ? now_s() : 0.0;
+      int rc = run_round(a, geom[c], false, any_relin, stream_of(c)); if (rc != PPS_OK) { drain(); return rc; }
+      if (m->sw.multi_timing) { ht->book += tb1 - tb0; ht->launch += now_s() - tb1; ht->n++; }
+    }
+    if (progressed) { t_progress = now_s(); continue; }
+    if (now_s() - t_progress > 2.0) {                        // (nothing for two seconds: let the streams drain, look once more)
+      MHIP(m, hipStreamSynchronize(m->stream));
+      MHIP(m, hipStreamSynchronize(m->stream2));
+      MHIP(m, hipStreamSynchronize(m->stream3));
+      bool any_done = false;
+      for (int c = 0; c < n_chunks; c++) any_done = any_done || (cr[c].in_flight && chunk_done(c));
+      if (!any_done) return mfail(m, PPS_EHIP, "result records of a round did not arrive");     // (all three streams are idle here)
+    }
+  }
+  for (int c = 0; c < n_chunks; c++) m->rounds = std::max(m->rounds, cr[c].rounds);
+  MHIP(m, hipStreamSynchronize(m->stream));
+  MHIP(m, hipStreamSynchronize(m->stream2));
+  MHIP(m, hipStreamSynchronize(m->stream3));
+  for (size_t k = 0; k + 6 <= m->ev_used; k += 6) {
+    const hipEvent_t* e = &m->evs[k];
+    for (int ph = 0; ph < 5; ph++) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, e[ph], e[ph + 1]) == hipSuccess) m->t_phase[ph] += 1e-3 * ms;
+    }
+  }
+  return PPS_OK;
+}
+
+// ---- 5. per graph: linpoint_to_estimate by rotating the three state copies, the controller's figures -> stats, status[] ----
+static int finish_graphs(pps_multi* m, const std::vector<BatchAlt>& ha, const std::vector<GraphRun>& lm, int* iterations, int* status) {
+  int first_bad = PPS_OK;
+  for (size_t i = 0; i < m->gs.size(); i++) {
+    pps_graph* g = m->gs[i];
+    const GraphRun& q = lm[i];
+    // linpoint_to_estimate (:466): the accepted, converged trial -- or the linearisation point when the pending step is dropped
+    const int fin = q.trial_taken ? (q.xsel + 1 + q.cur) % 3 : q.xsel;
+    double* const sp[3] = {ha[i].pose[0], ha[i].pose[1], ha[i].pose[2]};
+    double* const sl[3] = {ha[i].plane[0], ha[i].plane[1], ha[i].plane[2]};
+    g->dev.pose_est = sp[fin]; g->dev.plane_est = sl[fin];
+    g->dev.pose_lin = sp[(fin + 1) % 3]; g->dev.plane_lin = sl[(fin + 1) % 3];
+    g->spec_pose = sp[(fin + 2) % 3]; g->spec_plane = sl[(fin + 2) % 3];
+    g->dev_values_newer = true; g->pin_holds_est = false;
+    g->stats.t_total = m->t_total;
+    const int st_i = q.lm.finish(q.sink, iterations ? &iterations[i] : nullptr);
+    if (st_i != PPS_OK) g->err = kLmNotPdMessage;
+    if (status) status[i] = st_i;
+    if (st_i != PPS_OK && first_bad == PPS_OK) first_bad = st_i;
+  }
+  if (first_bad != PPS_OK) return mfail(m, first_bad, "at least one graph ended on a factorisation that was not positive definite (see status[])");
+  return PPS_OK;
+}
+
+static int multi_optimize(pps_multi* m, int* iterations, int* status) {
+  const double t0 = now_s();
+  const int G = (int)m->gs.size();
+  if (hipSetDevice(m->device) != hipSuccess) return mfail(m, PPS_EHIP, "hipSetDevice failed (no HIP device: there is no CPU fallback)");
+  int mode = 0, max_stages = 0;
+  int rc = check_graphs(m, &mode, &max_stages); if (rc != PPS_OK) return rc;
+  const double t_s1 = now_s() - t0;
+  std::vector<BatchAlt> ha;
+  rc = upload_tables(m, max_stages, ha); if (rc != PPS_OK) return rc;
+  const double t_s2 = now_s() - t0;
+  int n_cu = 256;
+  { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, m->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount; }
+  ChunkPlan plan;
+  if (!plan_chunks(m->gs, max_stages, n_cu, m->sw, m->profiling != 0, &plan))
+    return mfail(m, PPS_ESTATE, "a band group of this batch does not fit the LDS: solve the graphs through their own handles");
+  const double t_setup = now_s() - t0;
+  m->n_chunks_last = plan.n_chunks; m->forms_last = 0;
+  for (const BatchGeom& q : plan.geom) m->forms_last |= (q.lin_thread_form ? 1 : 0) | (q.level_form ? 2 : 0);
+  std::vector<GraphRun> lm;
+  lm.reserve(G);
+  for (int i = 0; i < G; i++) lm.push_back(GraphRun{LmControl(m->gs[i]->props), lm_sink(m->gs[i], false)});
+  RoundsHostTime ht;
+  rc = run_rounds(m, plan, mode, lm, t0, &ht); if (rc != PPS_OK) return rc;
+  m->t_total = now_s() - t0;
+  if (m->sw.multi_timing)
+    fprintf(stderr, "pps_multi: G %d total %.3f ms, of which setup %.3f (per-graph checks %.3f, tables %.3f, geometry %.3f); %d rounds\n", G,
+            1e3 * m->t_total, 1e3 * t_setup, 1e3 * t_s1, 1e3 * (t_s2 - t_s1), 1e3 * (t_setup - t_s2), m->rounds);
+  if (m->sw.multi_timing && ht.n > 0)
+    fprintf(stderr, "pps_multi: host side of %d chunk rounds: launches %.3f ms (%.1f us per round), verdicts + arguments %.3f ms (%.1f us per round)\n",
+            ht.n, 1e3 * ht.launch, 1e6 * ht.launch / ht.n, 1e3 * ht.book, 1e6 * ht.book / ht.n);
+  return finish_graphs(m, ha, lm, iterations, status);
 }
 
 int pps_multi_set_profiling(pps_multi* m, int level) { if (!m) return PPS_EINVAL; m->profiling = level > 0 ? 1 : 0; return PPS_OK; }

@@ -212,7 +212,7 @@ void resolve_k1_events(pps_graph* g) {
   g->fk_used = 0;
 }
 
-void reset_solve_stats(pps_graph* g) {
+static void reset_solve_stats(pps_graph* g) {
   pps_stats& s = g->stats;
   s.t_linearize = s.t_assemble = s.t_factor = s.t_backsolve = s.t_retract_chi2 = 0;
   s.n_linearize = s.n_factorize = 0;
@@ -220,6 +220,11 @@ void reset_solve_stats(pps_graph* g) {
   s.t_analysis = s.t_upload = 0;
   s.n_launches = 0;
   g->launches0 = launch_count();
+}
+
+void begin_solve(pps_graph* g) {
+  reset_solve_stats(g);
+  g->tr_lambda.clear(); g->tr_chi2.clear(); g->tr_acc.clear();
 }
 
 // the device copy of a handle is given up after a failed solve: streams drained, nothing on the device is trusted any more --
@@ -302,14 +307,28 @@ static int lm_solve(pps_graph* g, int* iterations);
 int pps_batch_optimize(pps_graph* g, int* iterations) {
   if (!g) return PPS_EINVAL;
   if (g->n_live_nodes > 0 && g->n_live_factors == 0) {          // nothing to optimise: chi2 = 0 ends LM before its first trial
-    reset_solve_stats(g);
-    g->tr_lambda.clear(); g->tr_chi2.clear(); g->tr_acc.clear();
+    begin_solve(g);
     if (iterations) *iterations = 0;
     return PPS_OK;
   }
   const int rc = lm_solve(g, iterations);
   if (rc != PPS_OK && rc != PPS_ENOTPD) abandon_device_copy(g);
   return rc;
+}
+
+// The common end of the two single-graph loops, entered with est / lin in their final places: the state comes down, the stream
+// drains, and the controller's figures go into the stats.
+static int end_lm_solve(pps_graph* g, const LmControl& lm, const LmSink& sink, int* iterations, double t0) {
+  { const int rc2 = enqueue_state_download(g); if (rc2 != PPS_OK) return rc2; }
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  g->dev_values_newer = true;
+  state_download_arrived(g);
+  g->status_clean = true;                // every solve was followed by its chi2 kernel (the dual loop: by both)
+  resolve_k1_events(g);
+  g->stats.t_total = now_s() - t0; g->stats.n_launches = (int)(launch_count() - g->launches0);
+  if (g->dev.trace) report_front_trace(g);
+  if (lm.finish(sink, iterations) != PPS_OK) return fail(g, PPS_ENOTPD, kLmNotPdMessage);
+  return PPS_OK;
 }
 
 // Optimizer::levenberg_marquardt (Optimizer.cpp:371-467) with both candidate steps of a linearisation in the same launches.
@@ -327,8 +346,8 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
     HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
   }
   g->status_clean = false;
-  int num_iter = 0;
-  double lambda = prop.lm_lambda0;
+  LmControl lm(prop);
+  const LmSink sink = lm_sink(g, prop.verbose != 0);
   double* slot0 = g->host_result;                                   // chi2 at the linearisation point
   double* slot[2] = {g->host_result + 4, g->host_result + 8};       // trial for lambda / for lambda * factor
   DevGraph& d = g->dev;
@@ -352,8 +371,7 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
   int fused_pair = -1;                   // K1 event pair of the last fused launch (profiling level 1)
   int pred = 0, pred_launched = 0;       // the trial predicted to be accepted: the one that was accepted last | the one the last launch linearised
   // trials + the predicted linearisation + its H blocks: what ends every launch set in this mode
-  bool error_known = false;              // `error` holds chi2 at the linearisation point (not yet while the first launch set is queued)
-  double error = 0.0;
+  bool error_known = false;              // lm.error holds chi2 at the linearisation point (not yet while the first launch set is queued)
   auto enqueue_trial_lin = [&](const DualAlt& alt, double s0, double s1) -> int {
     pred_launched = use_alt ? pred : 0;
     const SpecLin sl{g->spec_J, g->spec_P, g->spec_H, g->spec_Hf, pred_launched};
@@ -368,7 +386,7 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
     }
     HIP_TRY(g, launch_trial_lin(d, alt, sl, d.pose_lin, d.plane_lin, t_pose[0], t_plane[0], t_pose[1], t_plane[1], slot[0], s0, slot[1], s1, g->stream, e0, e1));
     // (K2 of that linearisation leaves at once where the records say the prediction failed: 2 us instead of 7 in front of the plain sweep)
-    const LinGuard gd{{d.result_dev, g->spec_result}, {nullptr, nullptr}, {nullptr, nullptr}, error, error_known ? 1 : 0, use_alt ? 0 : 1, pred_launched};
+    const LinGuard gd{{d.result_dev, g->spec_result}, {nullptr, nullptr}, {nullptr, nullptr}, lm.error, error_known ? 1 : 0, use_alt ? 0 : 1, pred_launched};
     HIP_TRY(g, launch_hblocks_spec(d, sl, g->stream, &gd));
     return PPS_OK;
   };
@@ -376,26 +394,17 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
     DualAlt alt{g->spec_L, g->spec_U, g->spec_delta, g->spec_result, g->spec_chi2_partials, g->spec_dn_partials, g->spec_ticket,
                 lam * prop.lm_lambda_factor};
     have_next = use_alt;
-    if (!use_alt) {
-      // one damping value: the single-lambda launches, and the trial kernel with ONE trial (round 6: it used to walk both copies, the second
-      // one with a stale delta that nothing read -- twice the retraction and chi2 work of a launch that C3 pays 22 us for; have_next is false,
-      // the second record is never waited for)
-      { const int rc2 = enqueue_factor_solve(g, d, nullptr, lam, g->stream, g->profiling == 1); if (rc2 != PPS_OK) return rc2; }
-      g->stats.n_factorize += 1;
-      g->seq += 1.0; seqs[0] = g->seq;
-      g->seq2 += 1.0; seqs[1] = g->seq2;
-      if (fuse_lin) return enqueue_trial_lin(alt, seqs[0], seqs[1]);
-      HIP_TRY(g, launch_trial_dual(d, alt, d.pose_lin, d.plane_lin, t_pose[0], t_plane[0], t_pose[1], t_plane[1], slot[0], seqs[0], slot[1], seqs[1],
-                                   g->stream, 1));
-      return PPS_OK;
-    }
-    { const int rc2 = enqueue_factor_solve(g, d, &alt, lam, g->stream, g->profiling == 1); if (rc2 != PPS_OK) return rc2; }
-    g->stats.n_factorize += 2;
+    // one damping value (!use_alt): the single-lambda launches, and the trial kernel with ONE trial (round 6: it used to walk both copies, the
+    // second one with a stale delta that nothing read -- twice the retraction and chi2 work of a launch that C3 pays 22 us for; have_next is
+    // false, the second record is never waited for)
+    const int n_trials = use_alt ? 2 : 1;
+    { const int rc2 = enqueue_factor_solve(g, d, use_alt ? &alt : nullptr, lam, g->stream, g->profiling == 1); if (rc2 != PPS_OK) return rc2; }
+    g->stats.n_factorize += n_trials;
     g->seq += 1.0; seqs[0] = g->seq;
     g->seq2 += 1.0; seqs[1] = g->seq2;
     if (fuse_lin) return enqueue_trial_lin(alt, seqs[0], seqs[1]);
     HIP_TRY(g, launch_trial_dual(d, alt, d.pose_lin, d.plane_lin, t_pose[0], t_plane[0], t_pose[1], t_plane[1], slot[0], seqs[0], slot[1], seqs[1],
-                                 g->stream));
+                                 g->stream, n_trials));
     return PPS_OK;
   };
   rc = do_linearize(g); if (rc != PPS_OK) return rc;               // jacobian() (:379)
@@ -416,29 +425,19 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
     return do_linearize(g, &gd);
   };
   auto drop_spec_lin = [&]() { if (spec_pair >= 0 && (size_t)spec_pair < g->k1_skip.size()) g->k1_skip[spec_pair] = 1; spec_pair = -1; };
-  rc = enqueue_dual(lambda); if (rc != PPS_OK) return rc;
+  rc = enqueue_dual(lm.lambda); if (rc != PPS_OK) return rc;
   rc = wait_result(g, slot0, seq0); if (rc != PPS_OK) return rc;
-  error = slot0[0]; error_known = true;
-  g->stats.chi2_initial = error;
-  rc = enqueue_spec_lin(error); if (rc != PPS_OK) return rc;
+  lm.error = slot0[0]; error_known = true;
+  g->stats.chi2_initial = lm.error;
+  rc = enqueue_spec_lin(lm.error); if (rc != PPS_OK) return rc;
   rc = wait_result(g, slot[0], seqs[0]); if (rc != PPS_OK) return rc;
   int cur = 0;                           // which of the two trials the loop is looking at
-  double dnorm = std::sqrt(slot[0][1]);
-  bool last_notpd = slot[0][2] != 0.0;
-  int n_notpd = last_notpd ? 1 : 0;
+  lm.take_step(slot[0]);
   bool trial_taken = false;              // the loop ended on an accepted, converged step: the estimate is that trial
-  while ((prop.max_iterations <= 0 || num_iter < prop.max_iterations) && dnorm > prop.epsilon2 && error > prop.epsilon_abs) {
-    num_iter++;
-    const double error_new = slot[cur][0];
-    const double error_diff = error - error_new;
-    const bool accepted = error_diff > 0.;
-    g->tr_lambda.push_back(lambda); g->tr_chi2.push_back(error_new); g->tr_acc.push_back(accepted ? 1 : 0);
-    if (prop.verbose) fprintf(stderr, "LM Iteration %d: (lambda=%g) %s %.12g\n", num_iter, lambda, accepted ? "residual:" : "rejected", error_new);
-    if (accepted) {
-      g->stats.lm_trials_accepted++;
-      if (error_diff < prop.epsilon_rel * error) { error = error_new; trial_taken = true; break; }   // (:431-434)
-      lambda /= prop.lm_lambda_factor;
-      error = error_new;
+  while (lm.running(prop)) {
+    const LmVerdict v = lm.judge(sink, slot[cur][0]);
+    if (v == LmVerdict::Converged) { trial_taken = true; break; }
+    if (v == LmVerdict::Accepted) {
       if (adaptive) use_alt = cur != 0;                           // (accepted at once: no speculation next time; after a rejection: keep it)
       pred = cur;
       // the accepted copy becomes the linearisation point; the old one is the spare now
@@ -451,28 +450,24 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
       else if (fuse_lin) { rc = do_linearize(g); if (rc != PPS_OK) return rc; }      // (the other trial was accepted: the plain way)
       else if (spec_lin) { g->stats.n_linearize++; spec_pair = -1; }    // ... queued already, at this very copy
       else { rc = do_linearize(g); if (rc != PPS_OK) return rc; }
-      rc = enqueue_dual(lambda); if (rc != PPS_OK) return rc;      // (:458)
-      rc = enqueue_spec_lin(error); if (rc != PPS_OK) return rc;
+      rc = enqueue_dual(lm.lambda); if (rc != PPS_OK) return rc;   // (:458)
+      rc = enqueue_spec_lin(lm.error); if (rc != PPS_OK) return rc;
       cur = 0;
       rc = wait_result(g, slot[0], seqs[0]); if (rc != PPS_OK) return rc;
-    } else {
-      g->stats.lm_trials_rejected++;
-      lambda *= prop.lm_lambda_factor;                             // estimate_to_linpoint (:454): x was never overwritten
+    } else {                                                       // estimate_to_linpoint (:454): x was never overwritten
       if (have_next) {                                             // computed alongside: nothing to launch
         cur = 1; have_next = false;
         rc = wait_result(g, slot[1], seqs[1]); if (rc != PPS_OK) return rc;
       } else {
         drop_spec_lin();                                           // both trials rejected: its kernels left J and H alone
         if (adaptive) use_alt = true;                              // LM is zig-zagging: the next rejection should be free again
-        rc = enqueue_dual(lambda); if (rc != PPS_OK) return rc;    // (:458), same J and H
-        rc = enqueue_spec_lin(error); if (rc != PPS_OK) return rc;
+        rc = enqueue_dual(lm.lambda); if (rc != PPS_OK) return rc; // (:458), same J and H
+        rc = enqueue_spec_lin(lm.error); if (rc != PPS_OK) return rc;
         cur = 0;
         rc = wait_result(g, slot[0], seqs[0]); if (rc != PPS_OK) return rc;
       }
     }
-    dnorm = std::sqrt(slot[cur][1]);
-    last_notpd = slot[cur][2] != 0.0;
-    n_notpd += last_notpd ? 1 : 0;
+    lm.take_step(slot[cur]);
   }
   // linpoint_to_estimate (:466): the estimate is the accepted trial, or the linearisation point when the pending step is dropped
   drop_spec_lin();                       // (a linearisation queued behind the last trials is not one the solve asked for)
@@ -480,33 +475,20 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
   d.pose_est = d.pose_lin; d.plane_est = d.plane_lin;
   d.pose_lin = t_pose[0]; d.plane_lin = t_plane[0];
   g->spec_pose = t_pose[1]; g->spec_plane = t_plane[1];
-  { const int rc2 = enqueue_state_download(g); if (rc2 != PPS_OK) return rc2; }
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  g->dev_values_newer = true;
-  state_download_arrived(g);
-  g->status_clean = true;                // every dual solve was followed by both chi2 kernels
-  resolve_k1_events(g);
-  g->stats.lm_iterations = num_iter;
-  g->stats.chi2_final = error; g->stats.lambda_final = lambda; g->stats.last_delta_norm = dnorm;
-  g->stats.lm_trials_notpd = n_notpd;
-  g->stats.t_total = now_s() - t0; g->stats.n_launches = (int)(launch_count() - g->launches0);
-  if (iterations) *iterations = num_iter;
-  if (last_notpd) return fail(g, PPS_ENOTPD, "normal equations not positive definite at the last LM trial");
-  return PPS_OK;
+  return end_lm_solve(g, lm, sink, iterations, t0);
 }
 
 static int lm_solve(pps_graph* g, int* iterations) {
   const double t0 = now_s();
-  reset_solve_stats(g);
-  g->tr_lambda.clear(); g->tr_chi2.clear(); g->tr_acc.clear();
+  begin_solve(g);
   int rc = prepare_solve(g);
   if (rc != PPS_OK) return rc;
   if (g->use_band && g->profiling < 2 && !g->dev.trace && !g->sw.no_dual) return lm_solve_dual(g, iterations, t0);      // (PPS_NO_DUAL: the loop-forms parity test)
   const pps_props& prop = g->props;
   if (!g->status_clean) HIP_TRY(g, launch_clear_status(g->dev, g->stream));
   g->status_clean = false;
-  int num_iter = 0;
-  double lambda = prop.lm_lambda0;
+  LmControl lm(prop);
+  const LmSink sink = lm_sink(g, prop.verbose != 0);
   double* slot0 = g->host_result;       // chi2 at the linearisation point
   double* slot1 = g->host_result + 4;   // the trial: |delta|^2 of the step and chi2 after it
   // One stream, one result record per LM trial.  After every solve the trial step is applied at once (est <- lin,
@@ -528,123 +510,25 @@ static int lm_solve(pps_graph* g, int* iterations) {
   g->seq += 1.0;
   const double seq0 = g->seq;
   HIP_TRY(g, launch_chi2(g->dev, false, slot0, seq0, g->stream)); // r = weighted_errors(LINPOINT); error = |r|^2 (:382-385)
-  rc = enqueue_trial(lambda); if (rc != PPS_OK) return rc;
+  rc = enqueue_trial(lm.lambda); if (rc != PPS_OK) return rc;
   rc = wait_result(g, slot0, seq0); if (rc != PPS_OK) return rc;
   rc = wait_result(g, slot1, g->seq); if (rc != PPS_OK) return rc;
-  double error = slot0[0];
-  g->stats.chi2_initial = error;
-  double dnorm = std::sqrt(slot1[1]);
-  // Not-PD is a property of ONE factorisation (one lambda): every result record carries the flag of the solve that produced
-  // its step, and the chi2 kernel clears it.  CHOLMOD is silent here and LM simply rejects such a step and raises lambda
-  // (Optimizer.cpp:448-455), so only a solve whose LAST trial was still not PD reports PPS_ENOTPD.
-  bool last_notpd = slot1[2] != 0.0;
-  int n_notpd = last_notpd ? 1 : 0;
+  lm.error = slot0[0];
+  g->stats.chi2_initial = lm.error;
+  lm.take_step(slot1);
   bool trial_pending = true;
-  while ((prop.max_iterations <= 0 || num_iter < prop.max_iterations) && dnorm > prop.epsilon2 && error > prop.epsilon_abs) {
-    num_iter++;
-    const double error_new = slot1[0];
-    const double error_diff = error - error_new;
-    const bool accepted = error_diff > 0.;
-    g->tr_lambda.push_back(lambda); g->tr_chi2.push_back(error_new); g->tr_acc.push_back(accepted ? 1 : 0);
-    if (prop.verbose) fprintf(stderr, "LM Iteration %d: (lambda=%g) %s %.12g\n", num_iter, lambda, accepted ? "residual:" : "rejected", error_new);
-    if (accepted) {
-      g->stats.lm_trials_accepted++;
-      if (error_diff < prop.epsilon_rel * error) { error = error_new; trial_pending = false; break; }   // (:431-434)
-      lambda /= prop.lm_lambda_factor;
-      error = error_new;
-      rc = do_linearize(g); if (rc != PPS_OK) return rc;          // relinearise around the accepted point (:444)
-    } else {
-      g->stats.lm_trials_rejected++;
-      lambda *= prop.lm_lambda_factor;
-      swap_state(g);                                              // estimate_to_linpoint: restore (:454)
-    }
-    rc = enqueue_trial(lambda); if (rc != PPS_OK) return rc;      // (:458)
+  while (lm.running(prop)) {
+    const LmVerdict v = lm.judge(sink, slot1[0]);
+    if (v == LmVerdict::Converged) { trial_pending = false; break; }
+    if (v == LmVerdict::Accepted) { rc = do_linearize(g); if (rc != PPS_OK) return rc; }   // relinearise around the accepted point (:444)
+    else swap_state(g);                                           // estimate_to_linpoint: restore (:454)
+    rc = enqueue_trial(lm.lambda); if (rc != PPS_OK) return rc;   // (:458)
     rc = wait_result(g, slot1, g->seq); if (rc != PPS_OK) return rc;
-    dnorm = std::sqrt(slot1[1]);
-    last_notpd = slot1[2] != 0.0;
-    n_notpd += last_notpd ? 1 : 0;
+    lm.take_step(slot1);
   }
   if (trial_pending) swap_state(g);                               // undo the pending step
   swap_state(g);                                                  // linpoint_to_estimate (:466)
-  { const int rc2 = enqueue_state_download(g); if (rc2 != PPS_OK) return rc2; }
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  g->dev_values_newer = true;
-  state_download_arrived(g);
-  g->status_clean = true;                                         // every solve was followed by its chi2 kernel
-  resolve_k1_events(g);
-  g->stats.lm_iterations = num_iter;
-  g->stats.chi2_final = error; g->stats.lambda_final = lambda; g->stats.last_delta_norm = dnorm;
-  g->stats.t_total = now_s() - t0; g->stats.n_launches = (int)(launch_count() - g->launches0);
-  if (g->dev.trace) {
-    const Analysis& A = g->an;
-    std::vector<long long> tr((size_t)A.n_fronts * 8);
-    (void)hipMemcpy(tr.data(), g->dev.trace, tr.size() * 8, hipMemcpyDeviceToHost);
-    if (g->dev.trace_solve) {
-      // PPS_TRACE=2: the slots hold the back-substitution of the last solve (parents before children)
-      for (int l = A.n_levels - 1; l >= 0; l--) {
-        double ph[5] = {0, 0, 0, 0, 0}, gap = 0; int n = 0, ng = 0;
-        for (int s2 = 0; s2 < A.n_fronts; s2++) {
-          if (A.f_level[s2] != l) continue;
-          n++;
-          for (int k = 0; k < 5; k++) ph[k] += (double)(tr[(size_t)s2 * 8 + k + 1] - tr[(size_t)s2 * 8 + k]);
-          const int par = A.f_parent[s2];
-          if (par >= 0) { gap += (double)(tr[(size_t)s2 * 8] - tr[(size_t)par * 8 + 5]); ng++; }
-        }
-        if (!n) continue;
-        fprintf(stderr, "  solve level %d (%d fronts): panel load %.0f boundary values %.0f y - L_B^T x_b %.0f back-substitution %.0f store %.0f | start after parent's end %.0f\n",
-                l, n, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[4] / n, ng ? gap / ng : 0.0);
-      }
-    } else {                        // (PPS_TRACE=1; either way the common epilogue below reports iterations and the not-PD status)
-    double acc[5] = {0, 0, 0, 0, 0};
-    std::vector<double> lvl_tot(A.n_levels, 0.0); std::vector<int> lvl_n(A.n_levels, 0);
-    for (int s2 = 0; s2 < A.n_fronts; s2++) {
-      for (int k = 0; k < 5; k++) acc[k] += (double)(tr[(size_t)s2 * 8 + k + 1] - tr[(size_t)s2 * 8 + k]);
-      lvl_tot[A.f_level[s2]] += (double)(tr[(size_t)s2 * 8 + 5] - tr[(size_t)s2 * 8]); lvl_n[A.f_level[s2]]++;
-    }
-    { double pn = 0, tr2 = 0; for (int s2 = 0; s2 < A.n_fronts; s2++) { pn += (double)tr[(size_t)s2 * 8 + 6]; tr2 += (double)tr[(size_t)s2 * 8 + 7]; }
-      fprintf(stderr, "PPS_TRACE elimination split: panel %.0f trailing %.0f cycles per front\n", pn / A.n_fronts, tr2 / A.n_fronts); }
-    fprintf(stderr, "PPS_TRACE mean cycles per front: zero %.0f gather %.0f extend-add %.0f eliminate %.0f store %.0f\n",
-            acc[0] / A.n_fronts, acc[1] / A.n_fronts, acc[2] / A.n_fronts, acc[3] / A.n_fronts, acc[4] / A.n_fronts);
-    for (int l = 0; l < A.n_levels; l++) fprintf(stderr, "  level %d: %d fronts, mean total %.0f cycles\n", l, lvl_n[l], lvl_tot[l] / std::max(1, lvl_n[l]));
-    {
-      // per level: the phases, and how long a front's start lies behind the end of its last child (barrier, launch boundary,
-      // record load) -- the part of a tree level that no phase accounts for
-      std::vector<long long> last_child_end(A.n_fronts, 0);
-      for (int s2 = 0; s2 < A.n_fronts; s2++) if (A.f_parent[s2] >= 0) last_child_end[A.f_parent[s2]] = std::max(last_child_end[A.f_parent[s2]], tr[(size_t)s2 * 8 + 5]);
-      for (int l = 0; l < A.n_levels; l++) {
-        double ph[7] = {0, 0, 0, 0, 0, 0, 0}, gap = 0; int n = 0, ng = 0;
-        for (int s2 = 0; s2 < A.n_fronts; s2++) {
-          if (A.f_level[s2] != l) continue;
-          n++;
-          for (int k = 0; k < 5; k++) ph[k] += (double)(tr[(size_t)s2 * 8 + k + 1] - tr[(size_t)s2 * 8 + k]);
-          ph[5] += (double)tr[(size_t)s2 * 8 + 6]; ph[6] += (double)tr[(size_t)s2 * 8 + 7];
-          if (last_child_end[s2] > 0) { gap += (double)(tr[(size_t)s2 * 8] - last_child_end[s2]); ng++; }
-        }
-        if (!n) continue;
-        fprintf(stderr, "  level %d: zero %.0f gather %.0f extend-add %.0f eliminate %.0f (panel %.0f trailing %.0f) store %.0f | start after last child's end %.0f\n", l,
-                ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[5] / n, ph[6] / n, ph[4] / n, ng ? gap / ng : 0.0);
-      }
-    }
-    {
-      double w[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int nw2 = 0;
-      for (int s2 = 0; s2 < A.n_fronts; s2++) {
-        if (A.f_p[s2] + A.f_b[s2] + 1 <= 64) continue;
-        nw2++;
-        for (int k = 0; k < 5; k++) w[k] += (double)(tr[(size_t)s2 * 8 + k + 1] - tr[(size_t)s2 * 8 + k]);
-        w[5] += (double)tr[(size_t)s2 * 8 + 6]; w[6] += (double)tr[(size_t)s2 * 8 + 7];
-      }
-      if (nw2) fprintf(stderr, "  fronts beyond 64 rows (%d): zero %.0f gather %.0f extend-add %.0f eliminate %.0f (panel %.0f trailing %.0f) store %.0f cycles\n", nw2,
-                       w[0] / nw2, w[1] / nw2, w[2] / nw2, w[3] / nw2, w[5] / nw2, w[6] / nw2, w[4] / nw2);
-    }
-    long long tmin = tr[0], tmax = tr[5];
-    for (int s2 = 0; s2 < A.n_fronts; s2++) { tmin = std::min(tmin, tr[(size_t)s2 * 8]); tmax = std::max(tmax, tr[(size_t)s2 * 8 + 5]); }
-    fprintf(stderr, "  first start -> last end: %lld cycles\n", tmax - tmin);
-    }
-  }
-  if (iterations) *iterations = num_iter;
-  g->stats.lm_trials_notpd = n_notpd;
-  if (last_notpd) return fail(g, PPS_ENOTPD, "normal equations not positive definite at the last LM trial");
-  return PPS_OK;
+  return end_lm_solve(g, lm, sink, iterations, t0);
 }
 
 int pps_chi2(pps_graph* g, double* chi2) {
