@@ -123,6 +123,41 @@ int pps_batch_optimize(pps_graph* g, int* iterations);
 /* Slam::chi2(ESTIMATE) (Slam.cpp:266-268) */
 int pps_chi2(pps_graph* g, double* chi2);
 
+/* ---- marginal covariances: Slam::covariances() -> isam::Covariances (Covariances.h:42-110, isamlib/covariance.cpp) ----------
+ * Sigma = (J'J)^-1 at the ESTIMATE, in tangent coordinates: a pose block is 6 x 6 over (dx, dy, dz, rotx, roty, rotz), a plane block 3 x 3
+ * over the 3-vector of Plane3d::exmap_3dof -- the column order of pps_eval_factor.  The factor never leaves the device; the entries
+ * of Sigma inside its sparsity pattern are recovered from it front by front, root -> leaves (selected inverse), without a dense inverse.
+ * That pattern holds the diagonal block of EVERY node and the cross block of every pair of nodes that share a front of the
+ * elimination tree: every pair joined by a factor (pose - plane observations, consecutive poses) and the fill between them.
+ *
+ * pps_cov_recover: relinearise at the estimate in the handle's jacobian_mode, factor H = J'J with lambda = 0 (the system of pps_update,
+ * without applying a step), then the recursion.  The estimate, the linearisation point, the LM trace and the stats of the last solve stay
+ * as they were; a pps_batch_optimize after it gives the trace it would have given without it.  Results stay on the device until read.
+ *   PPS_ENOTPD  H is not positive definite: a pivot of the factor was not positive, or smaller than 1e-7 of the largest pivot of its
+ *               front (H singular to working precision, e.g. a graph without any prior: its "covariance" would be rounding noise)
+ *   PPS_ESTATE  the graph has fronts beyond the wave-per-front kernels (loop-closure graphs in the dense-front form: sphere2500, graphs
+ *               after a landmark merge across the map -- what pps_multi_create refuses, too).  Not supported; the handle stays usable.
+ * Validity: a recovery ends with every call that changes the estimate, the measurements or the topology -- any pps_add_*, pps_remove_*,
+ * pps_set_* (pps_set_props: when it changes jacobian_mode), pps_update, pps_batch_optimize, pps_restore_state, pps_refresh_measurements,
+ * membership in a pps_multi_optimize / pps_multi_restore_state.  The read calls then return PPS_ESTATE ("no valid recovery"): never stale
+ * numbers, never a silent recomputation.  Ids are checked first (PPS_EINVAL), on the host, before anything is launched.
+ * Pairs OUTSIDE the pattern (e.g. the newest pose against a plane it has not observed) are not available: they need column solves with
+ * a forward substitution this library does not have (its right-hand side rides in the factorisation).
+ * PPS_VERSION stays 304: a caller detects these entry points by symbol lookup (dlsym "pps_cov_recover"). */
+int pps_cov_recover(pps_graph* g);
+/* diagonal blocks: ids[n] node ids (NULL = all live nodes in insertion order, n = their number); out = concatenated row-major blocks,
+ * 36 doubles per pose, 9 per plane; offsets[n + 1] (may be NULL) = start of each block in out.  Every block is exactly symmetric. */
+int pps_cov_marginals(pps_graph* g, int n, const int* ids, double* out, int64_t* offsets);
+/* cross blocks Sigma(rows[i], cols[i]), row-major dim(rows[i]) x dim(cols[i]), block i at out + offsets[i] (blocks are laid out back to
+ * back whether written or not; offsets[n + 1] may be NULL); in_pattern[i] = 1 if the pair lies in the factor's pattern (the block is
+ * written), 0 otherwise (the block is left untouched, the call still returns PPS_OK) */
+int pps_cov_access(pps_graph* g, int n, const int* rows, const int* cols, double* out, int64_t* offsets, int* in_pattern);
+/* joint marginal over a list of distinct nodes (Covariances::marginal(list)): (sum of dims)^2 doubles, row-major, nodes in list order;
+ * PPS_ESTATE, naming the first pair, when two of them lie outside the pattern */
+int pps_cov_joint(pps_graph* g, int n, const int* ids, double* out);
+/* device seconds (HIP events) of the last pps_cov_recover: sec[0] the whole call's launches, sec[1] the root -> leaves pass alone */
+int pps_cov_last_times(const pps_graph* g, double sec[2]);
+
 /* ---- many graphs side by side (BASELINE config 4 on one device; north_star reports graphs/sec) ----------------
  * One C2-size LM solve is a dependency chain that occupies a few dozen of the 256 CUs.  pps_multi runs
  * Optimizer::levenberg_marquardt (Optimizer.cpp:371-467) on n independent graphs in rounds: every kernel of an LM

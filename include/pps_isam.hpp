@@ -9,6 +9,7 @@
 //   isam::Pose3d_Factor, Pose3d_Pose3d_Factor                  slam3d.h:58-193
 //   isam::Pose3d_Plane3d_Factor, Plane3d_Factor                src/isam_plane3d.h:221-308,428-474
 //   isam::Properties, isam::Slam                               Properties.h:37-110, Slam.h:66-277
+//   isam::Covariances (Slam::covariances())                    Covariances.h:42-110, isamlib/covariance.cpp
 // Same raw-pointer, non-owning semantics as the reference ("the node itself is not deallocated",
 // Slam.h:122-134).  The image has no Eigen, so small fixed-size std::array types stand in for
 // Eigen::Vector/Matrix; a maintainer maps them with Eigen::Map.
@@ -20,6 +21,7 @@
 
 #include <array>
 #include <cmath>
+#include <list>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -206,6 +208,20 @@ public:
 
 class Slam;
 
+// a dense row-major matrix: what stands in for Eigen::MatrixXd in the results of Covariances
+struct MatrixXd {
+  int _rows = 0, _cols = 0;
+  std::vector<double> _d;
+  MatrixXd() {}
+  MatrixXd(int r, int c) : _rows(r), _cols(c), _d((size_t)r * c, 0.0) {}
+  int rows() const { return _rows; }
+  int cols() const { return _cols; }
+  double operator()(int r, int c) const { return _d[(size_t)r * _cols + c]; }
+  double& operator()(int r, int c) { return _d[(size_t)r * _cols + c]; }
+  const double* data() const { return _d.data(); }
+  double* data() { return _d.data(); }
+};
+
 // ---- nodes ------------------------------------------------------------------------------------
 class Node {
 protected:
@@ -350,6 +366,67 @@ protected:
   }
 };
 
+// ---- Covariances (Covariances.h:42-110) ---------------------------------------------------------
+// Slam::covariances(): marginal covariances recovered on the device from the factor of the last linearisation (pps_cov_*, pps.h).
+// Like the reference's object it "always refers to the latest state of slam": a call recovers again when the handle holds no valid
+// recovery (after any update, optimisation or edit).  Two limits of the backend, reported as exceptions with the library's text:
+// graphs whose fronts exceed the wave-per-front kernels (loop closures in the dense-front form), and pairs / lists of nodes that do
+// not share a front of the elimination tree (entries outside the pattern of the factor).  clone() -- a stand-alone copy for another
+// thread -- is not offered: the factor lives in the handle's device buffers.
+class Covariances {
+  Slam* _slam;
+  int _probe_id = 0;
+  pps_graph* handle() const;
+  void ensure() const;      // a valid recovery on the handle
+  static std::vector<int> ids_of(const std::list<Node*>& nodes) {
+    std::vector<int> ids;
+    for (Node* n : nodes) { if (!n || n->backend_id() < 0) throw std::runtime_error("Covariances: node is not part of the graph"); ids.push_back(n->backend_id()); }
+    return ids;
+  }
+public:
+  typedef std::list<std::list<Node*> > node_lists_t;
+  typedef std::list<std::pair<Node*, Node*> > node_pair_list_t;
+  explicit Covariances(Slam* slam) : _slam(slam) {}
+  // marginal covariance over a list of nodes (a single node: its 6 x 6 / 3 x 3 block)
+  MatrixXd marginal(const std::list<Node*>& nodes) const {
+    ensure();
+    const std::vector<int> ids = ids_of(nodes);
+    int N = 0;
+    for (Node* n : nodes) N += n->dim();
+    MatrixXd M(N, N);
+    detail::check(pps_cov_joint(handle(), (int)ids.size(), ids.data(), M.data()), handle(), "pps_cov_joint");
+    return M;
+  }
+  std::list<MatrixXd> marginal(const node_lists_t& node_lists) const {
+    std::list<MatrixXd> out;
+    for (const std::list<Node*>& l : node_lists) out.push_back(marginal(l));
+    return out;
+  }
+  // blocks Sigma(first, second) of the pairs, one launch and one copy for the whole list
+  std::list<MatrixXd> access(const node_pair_list_t& pairs) const {
+    ensure();
+    std::vector<int> rows, cols; std::vector<int64_t> off(pairs.size() + 1, 0);
+    size_t total = 0;
+    for (const std::pair<Node*, Node*>& pr : pairs) {
+      if (!pr.first || !pr.second || pr.first->backend_id() < 0 || pr.second->backend_id() < 0) throw std::runtime_error("Covariances: node is not part of the graph");
+      rows.push_back(pr.first->backend_id()); cols.push_back(pr.second->backend_id());
+      total += (size_t)pr.first->dim() * pr.second->dim();
+    }
+    std::vector<double> buf(total + 1, 0.0); std::vector<int> in(pairs.size() + 1, 0);
+    detail::check(pps_cov_access(handle(), (int)rows.size(), rows.data(), cols.data(), buf.data(), off.data(), in.data()), handle(), "pps_cov_access");
+    std::list<MatrixXd> out;
+    size_t k = 0;
+    for (const std::pair<Node*, Node*>& pr : pairs) {
+      if (!in[k]) throw std::runtime_error("Covariances::access: nodes " + std::to_string(rows[k]) + " and " + std::to_string(cols[k]) +
+                                           " share no front (the entry lies outside the pattern of the factor)");
+      MatrixXd M(pr.first->dim(), pr.second->dim());
+      for (size_t e = 0; e < M._d.size(); e++) M._d[e] = buf[(size_t)off[k] + e];
+      out.push_back(M); k++;
+    }
+    return out;
+  }
+};
+
 // ---- Properties / Slam ------------------------------------------------------------------------
 enum Method { GAUSS_NEWTON, LEVENBERG_MARQUARDT, DOG_LEG };
 
@@ -383,6 +460,7 @@ public:
   Slam(const Slam&) = delete;
   Slam& operator=(const Slam&) = delete;
   pps_graph* handle() { return _g; }
+  Covariances covariances() { return Covariances(this); }      // Slam::covariances(), Slam.h:208-210
   const Properties& properties() const { return _prop; }
   void set_properties(const Properties& p) {
     if (p.method != LEVENBERG_MARQUARDT) throw std::runtime_error("pps backend implements the mapper's configuration: method = LEVENBERG_MARQUARDT (Mapping.cpp:33)");
@@ -434,6 +512,13 @@ inline void Plane3d_Node::push() {
 inline Plane3d Plane3d_Node::value() const {
   if (_slam && _id >= 0) { Vector4d v; detail::check(pps_get_plane(_slam->handle(), _id, v.data()), _slam->handle(), "pps_get_plane"); return Plane3d(v); }
   return _v;
+}
+inline pps_graph* Covariances::handle() const { return _slam->handle(); }
+inline void Covariances::ensure() const {
+  // (a read with no node asks nothing but "is there a valid recovery": PPS_ESTATE when there is none)
+  double none = 0.0;
+  if (pps_cov_marginals(handle(), 0, &_probe_id, &none, nullptr) == PPS_OK) return;
+  detail::check(pps_cov_recover(handle()), handle(), "pps_cov_recover");
 }
 inline void Pose3d_Plane3d_Factor::set_measurement(const Plane3d& m) {
   _measure = m;

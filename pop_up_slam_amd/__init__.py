@@ -109,6 +109,7 @@ SYMBOLS = [
     "pps_edges_download_label", "pps_edges_contour", "pps_edges_last_kernel_time", "pps_edges_host_contour",
     "pps_edges_host_select", "pps_popup_fill_depth", "pps_popup_plane_info", "pps_popup_mask_host",
     "pps_multi_create", "pps_multi_destroy", "pps_multi_last_error", "pps_multi_optimize", "pps_multi_rounds", "pps_multi_save_state", "pps_multi_restore_state", "pps_multi_set_profiling", "pps_multi_phase_times", "pps_popup_polygons_simple", "pps_analysis_reuse", "pps_analysis_kept",
+    "pps_cov_recover", "pps_cov_marginals", "pps_cov_access", "pps_cov_joint", "pps_cov_last_times",
 ]
 
 
@@ -221,6 +222,12 @@ def lib():
         L.pps_graph_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.pps_graph_load.argtypes = [C.c_char_p, C.POINTER(PpsProps), C.POINTER(C.c_void_p)]
         L.pps_find_closest_planes.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _ip, _fp, _fp, C.POINTER(PpsAssocParams), _ip, _dp]
+        _i64p = C.POINTER(C.c_int64)
+        L.pps_cov_recover.argtypes = [C.c_void_p]
+        L.pps_cov_marginals.argtypes = [C.c_void_p, C.c_int, _ip, _dp, _i64p]
+        L.pps_cov_access.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _dp, _i64p, _ip]
+        L.pps_cov_joint.argtypes = [C.c_void_p, C.c_int, _ip, _dp]
+        L.pps_cov_last_times.argtypes = [C.c_void_p, _dp]
         _LIB = L
     return _LIB
 
@@ -343,6 +350,65 @@ class Graph:
 
     def chi2(self):
         v = C.c_double(); self._ck(self.L.pps_chi2(self.h, C.byref(v))); return v.value
+
+    # ---- marginal covariances (Slam::covariances() -> isam::Covariances) ----
+    def _node_dims(self, ids):
+        # 6 for a pose, 3 for a plane; an unknown id raises PPS_EINVAL through the bulk getters' id check
+        dims = []
+        for i in ids:
+            try:
+                self.get_pose(int(i)); dims.append(6)
+            except PpsError:
+                self.get_plane(int(i)); dims.append(3)
+        return dims
+
+    def cov_recover(self):
+        """Relinearise at the estimate, factor H = J'J (lambda = 0) and recover the selected inverse on the device; valid until the
+        estimate, the measurements or the topology change."""
+        self._ck(self.L.pps_cov_recover(self.h))
+
+    def cov_marginals(self, ids=None):
+        """Diagonal blocks of Sigma (6 x 6 per pose, 3 x 3 per plane) as a list of arrays; ids None = every live node in insertion order."""
+        if ids is None:
+            n = self.num_nodes(); ptr = None
+        else:
+            i = np.ascontiguousarray(ids, dtype=np.int32); n = len(i); ptr = i.ctypes.data_as(_ip)
+        out = np.zeros(36 * max(n, 1)); off = np.zeros(n + 1, dtype=np.int64)
+        self._ck(self.L.pps_cov_marginals(self.h, n, ptr, out.ctypes.data_as(_dp), off.ctypes.data_as(C.POINTER(C.c_int64))))
+        blocks = []
+        for k in range(n):
+            d = int(round(np.sqrt(off[k + 1] - off[k])))
+            blocks.append(out[off[k]:off[k + 1]].reshape(d, d).copy())
+        return blocks
+
+    def cov_access(self, pairs):
+        """Cross blocks Sigma(row, col) for (row, col) node-id pairs: a list with one array per pair, None where the pair lies outside
+        the pattern of the factor."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2); n = len(pr)
+        rows = np.ascontiguousarray(pr[:, 0]); cols = np.ascontiguousarray(pr[:, 1])
+        out = np.full(36 * max(n, 1), np.nan); off = np.zeros(n + 1, dtype=np.int64); inp = np.zeros(max(n, 1), dtype=np.int32)
+        self._ck(self.L.pps_cov_access(self.h, n, rows.ctypes.data_as(_ip), cols.ctypes.data_as(_ip), out.ctypes.data_as(_dp),
+                                       off.ctypes.data_as(C.POINTER(C.c_int64)), inp.ctypes.data_as(_ip)))
+        res = []
+        for k in range(n):
+            if not inp[k]:
+                res.append(None); continue
+            size = int(off[k + 1] - off[k])
+            dr = 6 if size == 36 else 3 if size == 9 else self._node_dims([pr[k, 0]])[0]       # (18 values: 6 x 3 or 3 x 6)
+            res.append(out[off[k]:off[k + 1]].reshape(dr, size // dr).copy())
+        return res
+
+    def cov_joint(self, ids):
+        """Joint marginal over a list of distinct nodes (Covariances::marginal(list)), nodes in list order."""
+        i = np.ascontiguousarray(ids, dtype=np.int32); n = len(i)
+        N = sum(self._node_dims(i))
+        out = np.zeros((N, N))
+        self._ck(self.L.pps_cov_joint(self.h, n, i.ctypes.data_as(_ip), out.ctypes.data_as(_dp)))
+        return out
+
+    def cov_last_times(self):
+        """device seconds of the last cov_recover: (whole call, root -> leaves pass alone)"""
+        s = (C.c_double * 2)(); self._ck(self.L.pps_cov_last_times(self.h, s)); return float(s[0]), float(s[1])
 
     # ---- state ----
     def num_nodes(self):

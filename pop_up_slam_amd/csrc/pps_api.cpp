@@ -166,6 +166,7 @@ int pps_graph_destroy(pps_graph* g) {
     if (g->d_results) (void)hipHostFree(g->d_results);
     if (g->d_lm_planes) (void)hipFree(g->d_lm_planes);
     if (g->rp_pin) (void)hipHostFree(g->rp_pin);
+    cov_release(g);
     (void)hipStreamDestroy(g->stream);
   }
   delete g;
@@ -180,6 +181,7 @@ int pps_get_props(const pps_graph* g, pps_props* out) {
 int pps_set_props(pps_graph* g, const pps_props* p) {
   if (!g || !p) return PPS_EINVAL;
   if (g->dev_ready && p->device != g->props.device) return fail(g, PPS_ESTATE, "device cannot change after the first solve");
+  if (p->jacobian_mode != g->props.jacobian_mode) cov_invalidate(g);      // (a recovery belongs to the mode it was linearised in)
   g->props = *p;
   return PPS_OK;
 }
@@ -188,6 +190,7 @@ static int add_node(pps_graph* g, int type, const double* v, int nv, int* id) {
   if (!g || !v) return PPS_EINVAL;
   for (int k = 0; k < nv; k++) if (!std::isfinite(v[k])) return fail(g, PPS_EINVAL, "non-finite node value");
   if (g->dev_values_newer) { int rc = download_state(g); if (rc != PPS_OK) return rc; }
+  cov_invalidate(g);
   HostNode n{};
   n.type = type;
   for (int k = 0; k < nv; k++) n.v[k] = v[k];
@@ -208,6 +211,7 @@ static int add_factor(pps_graph* g, int type, int a, int b, const double* meas, 
   if (!g || !meas || !ut) return PPS_EINVAL;
   for (int k = 0; k < nm; k++) if (!std::isfinite(meas[k])) return fail(g, PPS_EINVAL, "non-finite measurement");
   for (int k = 0; k < nw; k++) if (!std::isfinite(ut[k])) return fail(g, PPS_EINVAL, "non-finite sqrtinf");
+  cov_invalidate(g);
   HostFactor f{};
   f.type = type; f.a = a; f.b = b; f.deleted = false; f.slot = -1;
   for (int k = 0; k < nm; k++) f.meas[k] = meas[k];
@@ -273,6 +277,7 @@ int pps_set_measurement(pps_graph* g, int fid, const double meas4[4]) { return p
 
 int pps_set_measurements(pps_graph* g, int n, const int* fids, const double* meas4) {
   if (!g || !fids || !meas4 || n < 0) return PPS_EINVAL;
+  cov_invalidate(g);
   if (g->dev_meas_newer) { int rc = download_measurements(g); if (rc != PPS_OK) return rc; }
   for (int i = 0; i < n; i++) {
     const int fid = fids[i];
@@ -292,6 +297,7 @@ int pps_set_measurements(pps_graph* g, int n, const int* fids, const double* mea
 int pps_remove_factor(pps_graph* g, int fid) {
   if (!g) return PPS_EINVAL;
   if (fid < 0 || fid >= (int)g->factors.size() || g->factors[fid].deleted) return fail(g, PPS_EINVAL, "remove_factor: unknown id");
+  cov_invalidate(g);
   g->factors[fid].deleted = true;
   g->n_removals++;
   g->grown_only = false; g->grown_only_upload = false;
@@ -311,6 +317,7 @@ int pps_remove_node(pps_graph* g, int nid) {
     HostFactor& f = g->factors[i];
     if (!f.deleted && (f.a == nid || f.b == nid)) pps_remove_factor(g, (int)i);
   }
+  cov_invalidate(g);
   g->nodes[nid].deleted = true;
   g->n_removals++;
   g->grown_only = false; g->grown_only_upload = false;
@@ -342,7 +349,7 @@ int pps_set_pose(pps_graph* g, int id, const double tq[7]) {
   if (!live_node(g, id, NODE_POSE)) return fail(g, PPS_EINVAL, "set_pose: unknown id");
   int rc = download_state(g); if (rc != PPS_OK) return rc;
   memcpy(g->nodes[id].v, tq, 7 * sizeof(double));
-  g->host_values_newer = true;
+  g->host_values_newer = true; cov_invalidate(g);
   return PPS_OK;
 }
 int pps_set_plane(pps_graph* g, int id, const double abcd[4]) {
@@ -351,7 +358,7 @@ int pps_set_plane(pps_graph* g, int id, const double abcd[4]) {
   int rc = download_state(g); if (rc != PPS_OK) return rc;
   memcpy(g->nodes[id].v, abcd, 4 * sizeof(double));
   normalize4(g->nodes[id].v);
-  g->host_values_newer = true;
+  g->host_values_newer = true; cov_invalidate(g);
   return PPS_OK;
 }
 
@@ -395,7 +402,7 @@ int pps_restore_state(pps_graph* g) {
   if (g->host_values_newer) return fail(g, PPS_ESTATE, "host values were modified after the snapshot");
   const DevGraph& d = g->dev;
   HIP_TRY(g, hipMemcpyAsync(d.pose_est, g->snap_pose, ((size_t)7 * d.pose_ld + (size_t)4 * d.plane_ld) * 8, hipMemcpyDeviceToDevice, g->stream));
-  g->dev_values_newer = true; g->pin_holds_est = false;
+  g->dev_values_newer = true; g->pin_holds_est = false; cov_invalidate(g);
   return PPS_OK;
 }
 

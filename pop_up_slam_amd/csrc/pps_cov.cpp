@@ -1,0 +1,316 @@
+// pps_cov.cpp -- isam::Covariances on the handle (Thirdparty/isam/include/isam/Covariances.h:42-110, isamlib/covariance.cpp): marginal
+// covariances recovered from the multifrontal factor without a dense inverse.
+//
+//   pps_cov_recover    relinearise at the estimate, H = J'J factored with lambda = 0 (the launches of pps_update's factorisation, one per band
+//                      stage), then the selected inverse root -> leaves (pps_cov.hip), one launch per tree level
+//   pps_cov_marginals / _access / _joint   look the requested blocks up in the fronts (host tables built at recovery time), collect them with
+//                      one gather launch and one copy
+// Every entry of Sigma inside the pattern of L is available: the diagonal block of every node and the cross block of every pair of nodes
+// that share a front (in particular every pair joined by a factor).  A recovery stays valid until the estimate, the measurements or the
+// topology change (cov_invalidate, pps_graph.h); the read calls then answer PPS_ESTATE.
+#include "pps_cov.h"
+#include "pps_graph.h"
+
+using namespace pps;
+using namespace pps_impl;
+
+namespace pps_impl {
+
+void cov_release(pps_graph* g) {
+  if (g->cov_S) (void)hipFree(g->cov_S);
+  if (g->cov_parent) (void)hipFree(g->cov_parent);
+  if (g->cov_req) (void)hipFree(g->cov_req);
+  if (g->cov_out) (void)hipFree(g->cov_out);
+  for (hipEvent_t& e : g->cov_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  g->cov_S = nullptr; g->cov_parent = nullptr; g->cov_req = nullptr; g->cov_out = nullptr;
+  g->cov_S_cap = g->cov_parent_cap = g->cov_req_cap = g->cov_out_cap = 0;
+  g->cov_valid = false;
+}
+
+template <class T>
+static int cov_reserve(pps_graph* g, T** buf, size_t* cap, size_t count) {
+  if (count <= *cap && *buf) return PPS_OK;
+  HIP_TRY(g, hipStreamSynchronize(g->stream));          // (nothing in flight reads the old buffer)
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr; *cap = 0;
+  const size_t want = std::max<size_t>(64, count + count / 4);
+  HIP_TRY(g, hipMalloc(reinterpret_cast<void**>(buf), want * sizeof(T)));
+  *cap = want;
+  return PPS_OK;
+}
+
+static bool cov_current(const pps_graph* g) {
+  return g->cov_valid && g->dev_ready && !g->topo_dirty && !g->analysis_stale && !g->host_values_newer && !g->meas_dirty &&
+         g->cov_version == g->upload_version;
+}
+
+static const char* kNoRecovery = "no valid covariance recovery: call pps_cov_recover (a recovery ends with every change of the estimate, the measurements or the topology)";
+
+// where a node's scalars sit in the elimination order: its front and the local index of its first pivot
+struct CovNode { int front, local, dim, epos, voff; };
+
+static int cov_node(pps_graph* g, int id, CovNode* out) {
+  if (id < 0 || id >= (int)g->nodes.size() || g->nodes[id].deleted) return fail(g, PPS_EINVAL, "covariance: unknown node id " + std::to_string(id));
+  out->dim = g->nodes[id].type == NODE_POSE ? 6 : 3;
+  out->front = -1; out->local = out->epos = out->voff = 0;
+  return PPS_OK;
+}
+
+// (only with a current recovery: the analysis is the one the tables were built from)
+static int cov_locate(pps_graph* g, int id, CovNode* n) {
+  const Analysis& A = g->an;
+  const int c = g->nodes[id].compact;
+  if (c < 0 || c >= A.n_nodes) return fail(g, PPS_ESTATE, "covariance: node " + std::to_string(id) + " is not part of the analysed graph");
+  n->voff = A.node_voff[c];
+  n->epos = g->cov_epos[n->voff];
+  n->front = g->cov_front_of[n->epos];
+  n->local = n->epos - A.f_poff[n->front];
+  return PPS_OK;
+}
+
+// the block Sigma(rows, cols) as a gather request; false: the pair is outside the pattern of L
+static bool cov_request(const pps_graph* g, const CovNode& r, const CovNode& c, long long dst, CovReq* q) {
+  const Analysis& A = g->an;
+  const bool r_first = r.epos <= c.epos;               // the earlier-eliminated node owns the columns of the panel
+  const CovNode& e = r_first ? r : c;
+  const CovNode& o = r_first ? c : r;
+  const int s = e.front, p = A.f_p[s];
+  int lo = -1;
+  if (o.front == s) lo = o.local;
+  else {
+    const int b0 = A.f_bidx_off[s], b1 = A.f_bidx_off[s + 1];
+    const int* it = std::find(A.bidx.data() + b0, A.bidx.data() + b1, o.voff);
+    if (it != A.bidx.data() + b1 && (it - (A.bidx.data() + b0)) + o.dim <= b1 - b0) lo = p + (int)(it - (A.bidx.data() + b0));
+  }
+  if (lo < 0) return false;
+  q->src = (long long)A.f_Loff[s] + (long long)lo * p + e.local;
+  q->dst = dst; q->ld = p;
+  q->dr = r.dim; q->dc = c.dim;
+  q->tr = r_first ? 1 : 0;                              // rows = the earlier node: the stored block is its transpose
+  if (r.epos == c.epos) q->tr = 0;
+  return true;
+}
+
+// requests -> device, one gather launch, one copy back into `host` (n_out doubles)
+static int cov_fetch(pps_graph* g, const std::vector<CovReq>& req, size_t n_out, double* host) {
+  if (req.empty() || n_out == 0) return PPS_OK;
+  HIP_TRY(g, hipSetDevice(g->props.device));
+  int rc = cov_reserve(g, &g->cov_req, &g->cov_req_cap, req.size() * sizeof(CovReq)); if (rc != PPS_OK) return rc;
+  rc = cov_reserve(g, &g->cov_out, &g->cov_out_cap, n_out); if (rc != PPS_OK) return rc;
+  HIP_TRY(g, hipMemcpyAsync(g->cov_req, req.data(), req.size() * sizeof(CovReq), hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(g, launch_cov_gather(g->cov_S, reinterpret_cast<const CovReq*>(g->cov_req), (int)req.size(), g->cov_out, g->stream));
+  HIP_TRY(g, hipMemcpyAsync(host, g->cov_out, n_out * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  return PPS_OK;
+}
+
+// node -> front tables of the current analysis; checks what the gather relies on: a node's scalars are consecutive pivots of ONE front
+static int cov_build_tables(pps_graph* g) {
+  const Analysis& A = g->an;
+  g->cov_epos.assign((size_t)std::max(1, A.n_scalars), -1);
+  g->cov_front_of.assign((size_t)std::max(1, A.n_scalars), -1);
+  for (int s = 0; s < A.n_fronts; s++)
+    for (int k = 0; k < A.f_p[s]; k++) {
+      const int e = A.f_poff[s] + k;
+      if (e < 0 || e >= A.n_scalars || A.pidx[e] < 0 || A.pidx[e] >= A.n_scalars) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (pivot index)");
+      g->cov_epos[A.pidx[e]] = e; g->cov_front_of[e] = s;
+    }
+  for (int c = 0; c < A.n_nodes; c++) {
+    const int v = A.node_voff[c], dim = g->sym_nodes[c].dim;
+    for (int k = 0; k < dim; k++)
+      if (v + k >= A.n_scalars || g->cov_epos[v + k] != g->cov_epos[v] + k || g->cov_front_of[g->cov_epos[v + k]] != g->cov_front_of[g->cov_epos[v]])
+        return fail(g, PPS_ESTATE, "covariance: a node's scalars are not consecutive pivots of one front");
+  }
+  return PPS_OK;
+}
+
+static int cov_recover_impl(pps_graph* g) {
+  int rc;
+  if (!g->analyzed || g->analysis_stale) { rc = pps_analyze(g); if (rc != PPS_OK) return rc; }
+  if (!g->use_band)
+    return fail(g, PPS_ESTATE, "covariance recovery is limited to graphs whose fronts all fit the wave-per-front kernels (max front " +
+                               std::to_string(g->an.max_front) + " scalars here: loop-closure graphs in the dense-front form are not supported)");
+  rc = prepare_solve(g); if (rc != PPS_OK) return rc;
+  const Analysis& A = g->an;
+  const DevGraph& d = g->dev;
+  for (hipEvent_t& e : g->cov_ev) if (!e) HIP_TRY(g, hipEventCreate(&e));
+  rc = cov_reserve(g, &g->cov_S, &g->cov_S_cap, (size_t)std::max<int64_t>(1, A.L_size)); if (rc != PPS_OK) return rc;
+  if (g->cov_parent_version != g->upload_version) {
+    rc = cov_build_tables(g); if (rc != PPS_OK) return rc;
+    for (int s = 0; s < A.n_fronts; s++) {             // what k_cov_level indexes with: checked here, before anything is launched
+      const int q = A.f_parent[s];
+      if (A.f_b[s] > 0 && (q < 0 || q >= A.n_fronts || A.f_level[q] <= A.f_level[s] || A.f_cmap_off[s + 1] - A.f_cmap_off[s] < A.f_b[s]))
+        return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (parent / child map)");
+      for (int k = 0; k < A.f_b[s]; k++) {
+        const int r = A.cmap[A.f_cmap_off[s] + k];
+        if (r < 0 || r >= A.f_p[q] + A.f_b[q]) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (child map entry)");
+      }
+      if (A.f_p[s] < 1 || A.f_p[s] > 64 || cov_level_lds_bytes(A.f_p[s], A.f_b[s]) > (size_t)159 * 1024)
+        return fail(g, PPS_ESTATE, "covariance: front outside the supported shapes");
+    }
+    rc = cov_reserve(g, &g->cov_parent, &g->cov_parent_cap, (size_t)std::max(1, A.n_fronts)); if (rc != PPS_OK) return rc;
+    HIP_TRY(g, hipMemcpyAsync(g->cov_parent, A.f_parent.data(), (size_t)A.n_fronts * sizeof(int), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));         // (f_parent may be reallocated by the next analysis)
+    g->cov_parent_version = g->upload_version;
+  }
+  if (!g->status_clean) {
+    HIP_TRY(g, launch_clear_status(d, g->stream));
+    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
+  }
+  g->status_clean = false;
+  HIP_TRY(g, hipEventRecord(g->cov_ev[0], g->stream));
+  // jacobian() at the ESTIMATE (the linearisation point stays what it is), H blocks, factorisation with lambda = 0: one launch per band
+  // stage, the form whose panels all pass through d.L.  The update matrices in d.U are dead once their parents are assembled.
+  HIP_TRY(g, launch_linearize(d, g->props.jacobian_mode, true, g->stream));
+  HIP_TRY(g, launch_hblocks(d, g->stream, nullptr, k1_products(d, g->props.jacobian_mode)));
+  for (int st = 0; st < A.n_stages; st++)
+    HIP_TRY(g, launch_band_factor(d, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_factor[st], A.stage_max_front[st], 0.0, g->stream));
+  HIP_TRY(g, hipEventRecord(g->cov_ev[1], g->stream));
+  for (int l = A.n_levels - 1; l >= 0; l--) {
+    size_t lds = 0;
+    for (int k = A.level_off[l]; k < A.level_off[l + 1]; k++) lds = std::max(lds, cov_level_lds_bytes(A.f_p[A.level_fronts[k]], A.f_b[A.level_fronts[k]]));
+    HIP_TRY(g, launch_cov_level(d, g->cov_S, g->cov_parent, A.level_off[l], A.level_off[l + 1] - A.level_off[l], lds, g->stream));
+  }
+  HIP_TRY(g, hipEventRecord(g->cov_ev[2], g->stream));
+  double status[4] = {0, 0, 0, 0};
+  HIP_TRY(g, hipMemcpyAsync(status, d.result_dev, sizeof status, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, g->cov_ev[0], g->cov_ev[2]) == hipSuccess) g->cov_sec[0] = 1e-3 * ms;
+  if (hipEventElapsedTime(&ms, g->cov_ev[1], g->cov_ev[2]) == hipSuccess) g->cov_sec[1] = 1e-3 * ms;
+  if (status[2] != 0.0) {
+    HIP_TRY(g, launch_clear_status(d, g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+  }
+  g->status_clean = true;
+  if (status[2] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: the covariance recovery met an index outside its front");
+  if (status[2] != 0.0)
+    return fail(g, PPS_ENOTPD, "normal equations not positive definite at lambda = 0 (a pivot was not positive, or below 1e-7 of the largest pivot of its front): no covariance");
+  g->cov_version = g->upload_version;
+  g->cov_valid = true;
+  return PPS_OK;
+}
+
+}  // namespace pps_impl
+
+extern "C" {
+
+int pps_cov_recover(pps_graph* g) {
+  if (!g) return PPS_EINVAL;
+  cov_invalidate(g);
+  if (g->n_live_nodes == 0) return fail(g, PPS_ESTATE, "empty graph");
+  if (g->n_live_factors == 0) return fail(g, PPS_ENOTPD, "normal equations not positive definite: the graph has no factor");
+  // the figures of the last solve stay what they were: this call is no solve (the fields that describe the analysis follow the analysis)
+  const pps_stats saved = g->stats;
+  const int profiling = g->profiling;
+  g->profiling = 0;
+  const unsigned long long launches0 = g->launches0;
+  const int rc = cov_recover_impl(g);
+  g->profiling = profiling;
+  g->launches0 = launches0;
+  { pps_stats s = saved;
+    s.n_fronts = g->stats.n_fronts; s.n_levels = g->stats.n_levels; s.max_front = g->stats.max_front; s.nnz_L = g->stats.nnz_L;
+    g->stats = s; }
+  if (rc == PPS_EHIP) abandon_device_copy(g);
+  return rc;
+}
+
+int pps_cov_last_times(const pps_graph* g, double sec[2]) {
+  if (!g || !sec) return PPS_EINVAL;
+  sec[0] = g->cov_sec[0]; sec[1] = g->cov_sec[1];
+  return PPS_OK;
+}
+
+int pps_cov_marginals(pps_graph* g, int n, const int* ids, double* out, int64_t* offsets) {
+  if (!g || !out || n < 0) return PPS_EINVAL;
+  std::vector<int> all;
+  if (!ids) {
+    for (size_t i = 0; i < g->nodes.size(); i++) if (!g->nodes[i].deleted) all.push_back((int)i);
+    if ((int)all.size() != n) return fail(g, PPS_EINVAL, "covariance marginals: count mismatch (ids == NULL asks for all " + std::to_string(all.size()) + " nodes)");
+    ids = all.data();
+  }
+  std::vector<CovNode> nd((size_t)n);
+  for (int i = 0; i < n; i++) { const int rc = cov_node(g, ids[i], &nd[i]); if (rc != PPS_OK) return rc; }
+  if (!cov_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
+  std::vector<CovReq> req((size_t)n);
+  long long o = 0;
+  for (int i = 0; i < n; i++) {
+    const int rc = cov_locate(g, ids[i], &nd[i]); if (rc != PPS_OK) return rc;
+    if (!cov_request(g, nd[i], nd[i], o, &req[i])) return fail(g, PPS_ESTATE, "covariance: diagonal block not found");
+    if (offsets) offsets[i] = o;
+    o += (long long)nd[i].dim * nd[i].dim;
+  }
+  if (offsets) offsets[n] = o;
+  return cov_fetch(g, req, (size_t)o, out);
+}
+
+int pps_cov_access(pps_graph* g, int n, const int* rows, const int* cols, double* out, int64_t* offsets, int* in_pattern) {
+  if (!g || !rows || !cols || !out || !in_pattern || n < 0) return PPS_EINVAL;
+  std::vector<CovNode> nr((size_t)n), nc((size_t)n);
+  for (int i = 0; i < n; i++) {
+    int rc = cov_node(g, rows[i], &nr[i]); if (rc != PPS_OK) return rc;
+    rc = cov_node(g, cols[i], &nc[i]); if (rc != PPS_OK) return rc;
+  }
+  if (!cov_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
+  // the blocks are collected densely on the device and copied to their places in `out`, so that a block outside the pattern is left untouched
+  std::vector<CovReq> req;
+  std::vector<long long> place;
+  long long o = 0, packed = 0;
+  for (int i = 0; i < n; i++) {
+    int rc = cov_locate(g, rows[i], &nr[i]); if (rc != PPS_OK) return rc;
+    rc = cov_locate(g, cols[i], &nc[i]); if (rc != PPS_OK) return rc;
+    CovReq q;
+    in_pattern[i] = cov_request(g, nr[i], nc[i], packed, &q) ? 1 : 0;
+    if (in_pattern[i]) { req.push_back(q); place.push_back(o); packed += (long long)q.dr * q.dc; }
+    if (offsets) offsets[i] = o;
+    o += (long long)nr[i].dim * nc[i].dim;
+  }
+  if (offsets) offsets[n] = o;
+  std::vector<double> tmp((size_t)packed);
+  const int rc = cov_fetch(g, req, (size_t)packed, tmp.data());
+  if (rc != PPS_OK) return rc;
+  for (size_t k = 0; k < req.size(); k++) memcpy(out + place[k], tmp.data() + req[k].dst, sizeof(double) * (size_t)req[k].dr * req[k].dc);
+  return PPS_OK;
+}
+
+int pps_cov_joint(pps_graph* g, int n, const int* ids, double* out) {
+  if (!g || !ids || !out || n < 0) return PPS_EINVAL;
+  std::vector<CovNode> nd((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const int rc = cov_node(g, ids[i], &nd[i]); if (rc != PPS_OK) return rc;
+    for (int j = 0; j < i; j++) if (ids[j] == ids[i]) return fail(g, PPS_EINVAL, "covariance joint: node " + std::to_string(ids[i]) + " is listed twice");
+  }
+  if (!cov_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
+  std::vector<int> off((size_t)n + 1, 0);
+  for (int i = 0; i < n; i++) {
+    const int rc = cov_locate(g, ids[i], &nd[i]); if (rc != PPS_OK) return rc;
+    off[i + 1] = off[i] + nd[i].dim;
+  }
+  const int N = off[n];
+  std::vector<CovReq> req;
+  std::vector<std::pair<int, int>> who;
+  long long packed = 0;
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j <= i; j++) {
+      CovReq q;
+      if (!cov_request(g, nd[i], nd[j], packed, &q))
+        return fail(g, PPS_ESTATE, "covariance joint: nodes " + std::to_string(ids[j]) + " and " + std::to_string(ids[i]) +
+                                   " share no front (the pair is outside the pattern of the factor: not recoverable without column solves)");
+      req.push_back(q); who.emplace_back(i, j); packed += (long long)q.dr * q.dc;
+    }
+  std::vector<double> tmp((size_t)packed);
+  const int rc = cov_fetch(g, req, (size_t)packed, tmp.data());
+  if (rc != PPS_OK) return rc;
+  for (size_t k = 0; k < req.size(); k++) {
+    const int i = who[k].first, j = who[k].second;
+    const double* blk = tmp.data() + req[k].dst;
+    for (int a = 0; a < nd[i].dim; a++)
+      for (int c = 0; c < nd[j].dim; c++) {
+        out[(size_t)(off[i] + a) * N + off[j] + c] = blk[a * nd[j].dim + c];
+        out[(size_t)(off[j] + c) * N + off[i] + a] = blk[a * nd[j].dim + c];
+      }
+  }
+  return PPS_OK;
+}
+
+}  // extern "C"

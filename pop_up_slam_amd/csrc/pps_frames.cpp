@@ -35,6 +35,7 @@ int pps_frames_add(pps_graph* g, int pose_id, int n_seg, const float* seg2d, con
 
 int pps_refresh_measurements(pps_graph* g) {
   if (!g) return PPS_EINVAL;
+  cov_invalidate(g);
   int rc = prepare_solve(g);
   if (rc != PPS_OK) return rc;
   if (g->fr_item_frame.empty()) return PPS_OK;

@@ -7,6 +7,7 @@
 //   pps_lm.h         the LM rule the loops of pps_solve.cpp and pps_multi.cpp share (accept / reject / stop, lambda schedule, trace, counters): host only, no HIP
 //   pps_frames.cpp   registered frames (measurement refresh on the device), data association, point re-projection
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
+//   pps_cov.cpp      marginal covariances from the factor (isam::Covariances); kernels in pps_cov.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -192,6 +193,18 @@ struct pps_graph {
   pps::AssocQuery* d_queries = nullptr; pps::AssocResult* d_results = nullptr; size_t d_q_cap = 0;   // PINNED host memory: k_assoc reads the queries and writes the results over the bus
   double* d_lm_planes = nullptr; size_t d_lm_planes_cap = 0;   // [4][n] landmark planes when the solver state is not current
   char* rp_pin = nullptr; size_t rp_cap = 0;                  // pinned block of pps_reproject_points: [slots | points in | points out], read and written by the kernel
+  // marginal covariances (pps_cov.cpp): the selected inverse of the last pps_cov_recover, in the panel layout of L ([Sigma_AA; Sigma_BA] per
+  // front at f_Loff; a front's Sigma_BB sits in its -- then dead -- update matrix in dev.U).  Buffers of their own, allocated on the first
+  // recovery; cov_valid falls with every call that moves the estimate, the measurements or the topology (cov_invalidate)
+  bool cov_valid = false;
+  int cov_version = -1;              // upload_version the recovery (and cov_parent) belongs to
+  double* cov_S = nullptr; size_t cov_S_cap = 0;
+  int* cov_parent = nullptr; size_t cov_parent_cap = 0; int cov_parent_version = -1;
+  char* cov_req = nullptr; size_t cov_req_cap = 0;       // gather requests of a read call (device)
+  double* cov_out = nullptr; size_t cov_out_cap = 0;     // ... and the blocks they collect
+  std::vector<int> cov_epos, cov_front_of;               // delta index -> elimination-ordered scalar; that scalar -> front
+  hipEvent_t cov_ev[3] = {nullptr, nullptr, nullptr};
+  double cov_sec[2] = {0, 0};        // device seconds of the last recovery: whole call | root -> leaves pass alone
   // stats / trace
   pps_stats stats{};
   std::vector<double> tr_lambda, tr_chi2;
@@ -245,8 +258,11 @@ int read_result(pps_graph* g, bool at_estimate, double* chi2, double* dnorm, boo
 void begin_solve(pps_graph* g);                // an LM solve starts: the last one's stats and trace go
 void abandon_device_copy(pps_graph* g);
 inline LmSink lm_sink(pps_graph* g, bool verbose) { return LmSink{&g->props, &g->tr_lambda, &g->tr_chi2, &g->tr_acc, &g->stats, verbose}; }
+// ---- pps_cov.cpp ----
+inline void cov_invalidate(pps_graph* g) { g->cov_valid = false; }   // estimate, measurements or topology are about to change
+void cov_release(pps_graph* g);                // pps_graph_destroy: the recovery's own device buffers
 // ---- pps_api.cpp ----
-void report_front_trace(pps_graph* g);         // PPS_TRACE: the per-front cycle counters of the last solve -> stderr
+void report_front_trace(pps_graph* g);        // PPS_TRACE: the per-front cycle counters of the last solve -> stderr
 
 template <class T>
 int arena_alloc(pps_graph* g, pps_graph::Arena& a, T** out, size_t count) {

@@ -95,6 +95,7 @@ int pps_multi_restore_state(pps_multi* m) {
   if (!m) return PPS_EINVAL;
   m->err.clear();
   const int G = (int)m->gs.size();
+  for (pps_graph* g : m->gs) cov_invalidate(g);
   if (hipSetDevice(m->device) != hipSuccess) return mfail(m, PPS_EHIP, "hipSetDevice failed (no HIP device: there is no CPU fallback)");
   for (int i = 0; i < G; i++) {
     const pps_graph* g = m->gs[i];
@@ -156,6 +157,7 @@ static int ensure_k2t_lists(pps_graph* g) {
 
 int pps_multi_optimize(pps_multi* m, int* iterations, int* status) {
   if (!m) return PPS_EINVAL;
+  for (pps_graph* g : m->gs) cov_invalidate(g);
   const int rc = multi_optimize(m, iterations, status);
   if (rc != PPS_OK && rc != PPS_ENOTPD && rc != PPS_EINVAL && rc != PPS_ESTATE) {       // a HIP failure in the middle of the rounds: as a failed single solve
     // every stream a chunk may still be running on is drained BEFORE the handles are marked abandoned: the next upload_all frees or

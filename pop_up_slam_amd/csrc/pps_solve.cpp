@@ -250,6 +250,7 @@ static int update_impl(pps_graph* g);
 // dead data -- like the LM drivers, a failed update abandons the device copy, and the next call uploads from the host's values.
 int pps_update(pps_graph* g) {
   if (!g) return PPS_EINVAL;
+  cov_invalidate(g);
   const int rc = update_impl(g);
   if (rc != PPS_OK && rc != PPS_ENOTPD) abandon_device_copy(g);
   return rc;
@@ -306,6 +307,7 @@ static int lm_solve(pps_graph* g, int* iterations);
 
 int pps_batch_optimize(pps_graph* g, int* iterations) {
   if (!g) return PPS_EINVAL;
+  cov_invalidate(g);
   if (g->n_live_nodes > 0 && g->n_live_factors == 0) {          // nothing to optimise: chi2 = 0 ends LM before its first trial
     begin_solve(g);
     if (iterations) *iterations = 0;
