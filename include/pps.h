@@ -141,8 +141,8 @@ int pps_chi2(pps_graph* g, double* chi2);
  * pps_set_* (pps_set_props: when it changes jacobian_mode), pps_update, pps_batch_optimize, pps_restore_state, pps_refresh_measurements,
  * membership in a pps_multi_optimize / pps_multi_restore_state.  The read calls then return PPS_ESTATE ("no valid recovery"): never stale
  * numbers, never a silent recomputation.  Ids are checked first (PPS_EINVAL), on the host, before anything is launched.
- * Pairs OUTSIDE the pattern (e.g. the newest pose against a plane it has not observed) are not available: they need column solves with
- * a forward substitution this library does not have (its right-hand side rides in the factorisation).
+ * Pairs OUTSIDE the pattern (e.g. the newest pose against a plane it has not observed) are not available from these three read calls,
+ * which report them; pps_cov_block below answers for any nodes, by column solves on the same factor.
  * PPS_VERSION stays 304: a caller detects these entry points by symbol lookup (dlsym "pps_cov_recover"). */
 int pps_cov_recover(pps_graph* g);
 /* diagonal blocks: ids[n] node ids (NULL = all live nodes in insertion order, n = their number); out = concatenated row-major blocks,
@@ -157,6 +157,21 @@ int pps_cov_access(pps_graph* g, int n, const int* rows, const int* cols, double
 int pps_cov_joint(pps_graph* g, int n, const int* ids, double* out);
 /* device seconds (HIP events) of the last pps_cov_recover: sec[0] the whole call's launches, sec[1] the root -> leaves pass alone */
 int pps_cov_last_times(const pps_graph* g, double sec[2]);
+/* Sigma(rows, cols) for ANY nodes, inside the pattern of the factor or not (the reference's marginal(node_list) / access(pairs) without
+ * the limit above): out is (sum dim(rows)) x (sum dim(cols)), row-major, nodes in the order given.  cols == NULL (nc ignored): cols =
+ * rows, the joint marginal, exactly symmetric.  A node may appear in both lists, not twice in one.
+ * With H = L L' and E_S the unit columns of a node set S, Sigma(R, C) = (L^-1 E_R)' (L^-1 E_C): each distinct node costs one forward
+ * solve along its path from its front to the root of the elimination tree (its columns of L^-1 are zero elsewhere), the block one
+ * product over the pivots of common ancestors.  Cost: about (pivots on the path) x (front rows) x dim(node) multiply-adds per node, all
+ * nodes side by side; one upload, two launches and one copy per call, whatever nr, nc and the depth of the tree.  Nothing is factored
+ * again: the call reads the factor of the last pps_cov_recover and falls under the same validity rules.
+ *   PPS_EINVAL  NULL handle, rows or out; a negative count; an unknown or removed node id; a node twice in rows or twice in cols
+ *   PPS_ESTATE  no valid recovery (also: a dense-front graph, for which pps_cov_recover has none to give)
+ *   PPS_OK      with out untouched for nr == 0 or nc == 0
+ * pps_cov_marginals / _access / _joint keep their in-pattern contract and their refusals.  Found by symbol lookup, like the calls above. */
+int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols, double* out);
+/* the last pps_cov_block: device seconds (HIP events) around its two kernels, and the number of kernel launches it made (either may be NULL) */
+int pps_cov_block_last(const pps_graph* g, double* kernel_sec, int* launches);
 
 /* ---- many graphs side by side (BASELINE config 4 on one device; north_star reports graphs/sec) ----------------
  * One C2-size LM solve is a dependency chain that occupies a few dozen of the 256 CUs.  pps_multi runs

@@ -373,6 +373,9 @@ protected:
 // graphs whose fronts exceed the wave-per-front kernels (loop closures in the dense-front form), and pairs / lists of nodes that do
 // not share a front of the elimination tree (entries outside the pattern of the factor).  clone() -- a stand-alone copy for another
 // thread -- is not offered: the factor lives in the handle's device buffers.
+// marginal() and access() keep that strict in-pattern contract (they read the selected inverse and throw for anything outside it).
+// block() and marginal_any() are the unrestricted forms: any nodes, by root-path solves on the same factor (pps_cov_block) -- what the
+// reference's marginal(node_list) / access(pairs) answer for nodes that share no front, e.g. the current pose against an old landmark.
 class Covariances {
   Slam* _slam;
   int _probe_id = 0;
@@ -395,6 +398,27 @@ public:
     for (Node* n : nodes) N += n->dim();
     MatrixXd M(N, N);
     detail::check(pps_cov_joint(handle(), (int)ids.size(), ids.data(), M.data()), handle(), "pps_cov_joint");
+    return M;
+  }
+  // Sigma(rows, cols) for any nodes, in list order; a node may be in both lists, not twice in one
+  MatrixXd block(const std::list<Node*>& rows, const std::list<Node*>& cols) const {
+    ensure();
+    const std::vector<int> r = ids_of(rows), c = ids_of(cols);
+    int R = 0, Cn = 0;
+    for (Node* n : rows) R += n->dim();
+    for (Node* n : cols) Cn += n->dim();
+    MatrixXd M(R, Cn);
+    detail::check(pps_cov_block(handle(), (int)r.size(), r.data(), (int)c.size(), c.data(), M.data()), handle(), "pps_cov_block");
+    return M;
+  }
+  // the joint marginal over any list of distinct nodes (exactly symmetric), whether they share a front or not
+  MatrixXd marginal_any(const std::list<Node*>& nodes) const {
+    ensure();
+    const std::vector<int> ids = ids_of(nodes);
+    int N = 0;
+    for (Node* n : nodes) N += n->dim();
+    MatrixXd M(N, N);
+    detail::check(pps_cov_block(handle(), (int)ids.size(), ids.data(), 0, nullptr, M.data()), handle(), "pps_cov_block");
     return M;
   }
   std::list<MatrixXd> marginal(const node_lists_t& node_lists) const {

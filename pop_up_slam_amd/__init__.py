@@ -110,6 +110,7 @@ SYMBOLS = [
     "pps_edges_host_select", "pps_popup_fill_depth", "pps_popup_plane_info", "pps_popup_mask_host",
     "pps_multi_create", "pps_multi_destroy", "pps_multi_last_error", "pps_multi_optimize", "pps_multi_rounds", "pps_multi_save_state", "pps_multi_restore_state", "pps_multi_set_profiling", "pps_multi_phase_times", "pps_popup_polygons_simple", "pps_analysis_reuse", "pps_analysis_kept",
     "pps_cov_recover", "pps_cov_marginals", "pps_cov_access", "pps_cov_joint", "pps_cov_last_times",
+    "pps_cov_block", "pps_cov_block_last",
 ]
 
 
@@ -228,6 +229,8 @@ def lib():
         L.pps_cov_access.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _dp, _i64p, _ip]
         L.pps_cov_joint.argtypes = [C.c_void_p, C.c_int, _ip, _dp]
         L.pps_cov_last_times.argtypes = [C.c_void_p, _dp]
+        L.pps_cov_block.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int, _ip, _dp]
+        L.pps_cov_block_last.argtypes = [C.c_void_p, _dp, _ip]
         _LIB = L
     return _LIB
 
@@ -405,6 +408,23 @@ class Graph:
         out = np.zeros((N, N))
         self._ck(self.L.pps_cov_joint(self.h, n, i.ctypes.data_as(_ip), out.ctypes.data_as(_dp)))
         return out
+
+    def cov_block(self, rows, cols=None):
+        """Sigma(rows, cols) for ANY node ids, inside the pattern of the factor or not: a (sum dim(rows)) x (sum dim(cols)) array, nodes in
+        the order given.  cols None: the joint marginal of rows (exactly symmetric).  One root-path solve per distinct node on the factor
+        of the last cov_recover."""
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        c = r if cols is None else np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        # (sized for poses: the ids are checked by the library, before and not after a size is derived from them)
+        out = np.full(36 * max(len(r), 1) * max(len(c), 1), np.nan)
+        self._ck(self.L.pps_cov_block(self.h, len(r), r.ctypes.data_as(_ip), len(c), None if cols is None else c.ctypes.data_as(_ip),
+                                      out.ctypes.data_as(_dp)))
+        nr, nc = sum(self._node_dims(r)), sum(self._node_dims(c))
+        return out[:nr * nc].reshape(nr, nc).copy()
+
+    def cov_block_last(self):
+        """(device seconds around the two kernels, kernel launches) of the last cov_block"""
+        s = C.c_double(); n = C.c_int(); self._ck(self.L.pps_cov_block_last(self.h, C.byref(s), C.byref(n))); return s.value, n.value
 
     def cov_last_times(self):
         """device seconds of the last cov_recover: (whole call, root -> leaves pass alone)"""

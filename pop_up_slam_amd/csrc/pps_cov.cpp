@@ -8,6 +8,13 @@
 // Every entry of Sigma inside the pattern of L is available: the diagonal block of every node and the cross block of every pair of nodes
 // that share a front (in particular every pair joined by a factor).  A recovery stays valid until the estimate, the measurements or the
 // topology change (cov_invalidate, pps_graph.h); the read calls then answer PPS_ESTATE.
+//   pps_cov_block      Sigma(rows, cols) for ANY nodes: (L^-1 E_rows)' (L^-1 E_cols) by one walk up the elimination tree per distinct node
+//                      and one Gram product over common ancestors (pps_cov.hip) -- one upload, two launches, one copy, whatever the query
+// pps_cov_block reads the lambda = 0 factor the recovery leaves in dev.L.  dev.L is written by the factorisations alone (pps_solve.cpp:
+// enqueue_factor_solve and do_solve, reached from pps_update and pps_batch_optimize; the pps_multi launches), and each of those callers
+// ends the recovery.  What keeps it -- pps_chi2 (K4 reads the states), the getters and pps_save_state (state copies), pps_eval_factor and
+// pps_time_linearize (K1: J and the linearisation point), pps_get_stats / pps_get_trace (host fields), pps_analysis_dump, the
+// association and reprojection calls -- launches nothing that writes dev.L, so no invalidation had to be added for it.
 #include "pps_cov.h"
 #include "pps_graph.h"
 
@@ -21,9 +28,15 @@ void cov_release(pps_graph* g) {
   if (g->cov_parent) (void)hipFree(g->cov_parent);
   if (g->cov_req) (void)hipFree(g->cov_req);
   if (g->cov_out) (void)hipFree(g->cov_out);
+  if (g->cov_breq) (void)hipFree(g->cov_breq);
+  if (g->cov_strip) (void)hipFree(g->cov_strip);
+  if (g->cov_bout) (void)hipFree(g->cov_bout);
   for (hipEvent_t& e : g->cov_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  for (hipEvent_t& e : g->cov_bev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   g->cov_S = nullptr; g->cov_parent = nullptr; g->cov_req = nullptr; g->cov_out = nullptr;
+  g->cov_breq = nullptr; g->cov_strip = nullptr; g->cov_bout = nullptr;
   g->cov_S_cap = g->cov_parent_cap = g->cov_req_cap = g->cov_out_cap = 0;
+  g->cov_breq_cap = g->cov_strip_cap = g->cov_bout_cap = 0; g->cov_bout_clean = false;
   g->cov_valid = false;
 }
 
@@ -120,6 +133,20 @@ static int cov_build_tables(pps_graph* g) {
     for (int k = 0; k < dim; k++)
       if (v + k >= A.n_scalars || g->cov_epos[v + k] != g->cov_epos[v] + k || g->cov_front_of[g->cov_epos[v + k]] != g->cov_front_of[g->cov_epos[v]])
         return fail(g, PPS_ESTATE, "covariance: a node's scalars are not consecutive pivots of one front");
+  }
+  // pps_cov_block: the length of every front's path to the root in pivots (where the front's pivots sit in a strip, counted from its end)
+  g->cov_rootlen.assign((size_t)std::max(1, A.n_fronts), 0);
+  g->cov_max_p = g->cov_max_rows = 1;
+  for (int s = 0; s < A.n_fronts; s++) {
+    long long len = 0;
+    int hops = 0;
+    for (int t = s; t >= 0; t = A.f_parent[t]) {
+      if (t >= A.n_fronts || ++hops > A.n_fronts) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (the parents form no tree)");
+      len += A.f_p[t];
+    }
+    if (len > A.n_scalars) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (path longer than the system)");
+    g->cov_rootlen[s] = (int)len;
+    g->cov_max_p = std::max(g->cov_max_p, A.f_p[s]); g->cov_max_rows = std::max(g->cov_max_rows, A.f_p[s] + A.f_b[s]);
   }
   return PPS_OK;
 }
@@ -221,6 +248,13 @@ int pps_cov_last_times(const pps_graph* g, double sec[2]) {
   return PPS_OK;
 }
 
+int pps_cov_block_last(const pps_graph* g, double* kernel_sec, int* launches) {
+  if (!g) return PPS_EINVAL;
+  if (kernel_sec) *kernel_sec = g->cov_block_sec;
+  if (launches) *launches = g->cov_block_launches;
+  return PPS_OK;
+}
+
 int pps_cov_marginals(pps_graph* g, int n, const int* ids, double* out, int64_t* offsets) {
   if (!g || !out || n < 0) return PPS_EINVAL;
   std::vector<int> all;
@@ -310,6 +344,104 @@ int pps_cov_joint(pps_graph* g, int n, const int* ids, double* out) {
         out[(size_t)(off[j] + c) * N + off[i] + a] = blk[a * nd[j].dim + c];
       }
   }
+  return PPS_OK;
+}
+
+int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols, double* out) {
+  if (!g || !rows || !out || nr < 0 || (cols && nc < 0)) return PPS_EINVAL;
+  const bool joint = cols == nullptr;
+  if (joint) { cols = rows; nc = nr; }
+  // distinct nodes of the query: every one is walked once, however often it is asked for
+  std::vector<int> walk_of(g->nodes.size(), -1), ids, ri((size_t)nr), ci((size_t)nc);
+  std::vector<CovNode> nd;
+  for (int pass = 0; pass < (joint ? 1 : 2); pass++) {
+    const int n = pass ? nc : nr;
+    const int* list = pass ? cols : rows;
+    std::vector<char> seen(g->nodes.size(), 0);
+    for (int i = 0; i < n; i++) {
+      CovNode c;
+      const int rc = cov_node(g, list[i], &c); if (rc != PPS_OK) return rc;
+      if (seen[list[i]]) return fail(g, PPS_EINVAL, "covariance block: node " + std::to_string(list[i]) + " is listed twice among the " + (pass ? "columns" : "rows"));
+      seen[list[i]] = 1;
+      if (walk_of[list[i]] < 0) { walk_of[list[i]] = (int)ids.size(); ids.push_back(list[i]); nd.push_back(c); }
+      (pass ? ci : ri)[i] = walk_of[list[i]];
+    }
+  }
+  if (joint) ci = ri;
+  if (!cov_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
+  if (nr == 0 || nc == 0) return PPS_OK;
+  const Analysis& A = g->an;
+  const int nw = (int)ids.size();
+  // paths (leaf -> root) and strips; K = the longest path of the query in pivots
+  int K = 0;
+  for (int w = 0; w < nw; w++) {
+    const int rc = cov_locate(g, ids[w], &nd[w]); if (rc != PPS_OK) return rc;
+    K = std::max(K, g->cov_rootlen[nd[w].front]);
+  }
+  std::vector<CovWalk> walks((size_t)nw);
+  std::vector<CovStep> steps;
+  std::vector<int> step_end((size_t)nw);
+  long long n_strip = 0;
+  for (int w = 0; w < nw; w++) {
+    walks[w] = CovWalk{n_strip, (int)steps.size(), 0, nd[w].local, nd[w].dim};
+    for (int s = nd[w].front; s >= 0; s = A.f_parent[s]) steps.push_back(CovStep{s, K - g->cov_rootlen[s]});
+    walks[w].n_steps = (int)steps.size() - walks[w].step0;
+    step_end[w] = (int)steps.size();
+    n_strip += (long long)K * nd[w].dim;
+  }
+  // blocks: the pivots two paths have in common are a suffix of both
+  auto common = [&](int a, int b) {
+    int len = 0;
+    for (int i = step_end[a] - 1, j = step_end[b] - 1; i >= walks[a].step0 && j >= walks[b].step0 && steps[i].front == steps[j].front; i--, j--) len += A.f_p[steps[i].front];
+    return len;
+  };
+  std::vector<int> roff((size_t)nr + 1, 0), coff((size_t)nc + 1, 0);
+  for (int i = 0; i < nr; i++) roff[i + 1] = roff[i] + nd[ri[i]].dim;
+  for (int j = 0; j < nc; j++) coff[j + 1] = coff[j] + nd[ci[j]].dim;
+  const int ld = coff[nc];
+  const long long n_out = (long long)roff[nr] * ld;
+  std::vector<CovPair> pairs;
+  pairs.reserve(joint ? (size_t)nr * (nr + 1) / 2 : (size_t)nr * nc);
+  for (int i = 0; i < nr; i++)
+    for (int j = 0; j < (joint ? i + 1 : nc); j++) {
+      const int a = ri[i], b = ci[j], len = common(a, b);
+      CovPair q;
+      q.yi = walks[a].strip + (long long)(K - len) * nd[a].dim; q.yj = walks[b].strip + (long long)(K - len) * nd[b].dim;
+      q.dst = (long long)roff[i] * ld + coff[j];
+      q.dst_t = joint ? (long long)roff[j] * ld + coff[i] : -1;          // (cols = rows: the lower triangle, mirrored)
+      q.di = nd[a].dim; q.dj = nd[b].dim; q.len = len; q.ld = ld;
+      pairs.push_back(q);
+    }
+  // one request: [walks | steps | pairs]
+  const size_t o_steps = walks.size() * sizeof(CovWalk), o_pairs = (o_steps + steps.size() * sizeof(CovStep) + 15) & ~(size_t)15;
+  std::vector<char> req(o_pairs + pairs.size() * sizeof(CovPair));
+  memcpy(req.data(), walks.data(), walks.size() * sizeof(CovWalk));
+  memcpy(req.data() + o_steps, steps.data(), steps.size() * sizeof(CovStep));
+  memcpy(req.data() + o_pairs, pairs.data(), pairs.size() * sizeof(CovPair));
+  HIP_TRY(g, hipSetDevice(g->props.device));
+  for (hipEvent_t& e : g->cov_bev) if (!e) HIP_TRY(g, hipEventCreate(&e));
+  int rc = cov_reserve(g, &g->cov_breq, &g->cov_breq_cap, req.size()); if (rc != PPS_OK) return rc;
+  rc = cov_reserve(g, &g->cov_strip, &g->cov_strip_cap, (size_t)n_strip); if (rc != PPS_OK) return rc;
+  if ((size_t)n_out + 1 > g->cov_bout_cap || !g->cov_bout) g->cov_bout_clean = false;
+  rc = cov_reserve(g, &g->cov_bout, &g->cov_bout_cap, (size_t)n_out + 1); if (rc != PPS_OK) return rc;
+  if (!g->cov_bout_clean) HIP_TRY(g, hipMemsetAsync(g->cov_bout, 0, sizeof(double), g->stream));      // (a new buffer, or a query that failed)
+  g->cov_bout_clean = false;
+  const unsigned long long launches0 = launch_count();
+  HIP_TRY(g, hipMemcpyAsync(g->cov_breq, req.data(), req.size(), hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(g, hipEventRecord(g->cov_bev[0], g->stream));
+  HIP_TRY(g, launch_cov_path(g->dev, reinterpret_cast<const CovWalk*>(g->cov_breq), nw, reinterpret_cast<const CovStep*>(g->cov_breq + o_steps), (int)steps.size(), K,
+                             g->cov_max_p, g->cov_max_rows, g->cov_strip, n_strip, g->cov_bout, g->stream));
+  HIP_TRY(g, launch_cov_gram(reinterpret_cast<const CovPair*>(g->cov_breq + o_pairs), (int)pairs.size(), g->cov_strip, n_strip, g->cov_bout, n_out, g->stream));
+  HIP_TRY(g, hipEventRecord(g->cov_bev[1], g->stream));
+  std::vector<double> host((size_t)n_out + 1);
+  HIP_TRY(g, hipMemcpyAsync(host.data(), g->cov_bout, host.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  g->cov_block_launches = (int)(launch_count() - launches0);
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, g->cov_bev[0], g->cov_bev[1]) == hipSuccess) g->cov_block_sec = 1e-3 * ms;
+  if (host[0] != 0.0) return fail(g, PPS_EHIP, "internal error: a covariance path solve met an index outside its front or its strip");
+  g->cov_bout_clean = true;
+  memcpy(out, host.data() + 1, (size_t)n_out * sizeof(double));
   return PPS_OK;
 }
 

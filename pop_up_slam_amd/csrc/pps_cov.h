@@ -6,6 +6,12 @@
 // Sigma_BB gathered from the parent's full block through cmap.  Results: S, in the panel layout of L (rows 0 .. p-1 of a front =
 // Sigma_AA, full and exactly symmetric; rows p .. p+b-1 = Sigma_BA), and each front's Sigma_BB (b x b, row-major) in its update
 // matrix slot of d.U, which nothing reads between a factorisation and the next one.
+//
+// Blocks OUTSIDE the pattern (pps_cov_block) come from column solves on the same factor: with E_S the unit columns of a node set S,
+//   Sigma(R, C) = E_R' H^-1 E_C = (L^-1 E_R)' (L^-1 E_C),
+// and the columns of L^-1 E that belong to one node are non-zero only on the pivots of the fronts between the node's front and the
+// root.  k_cov_path walks that path once per node (forward substitution per front, the remainder carried up through cmap) and stores
+// the node's strip Y = L^-1 E_node; k_cov_gram multiplies two strips over the pivots of their common ancestors.
 #pragma once
 #include "pps_device.h"
 
@@ -20,5 +26,24 @@ size_t cov_level_lds_bytes(int p, int b);      // dynamic LDS one front of this 
 // largest pivot of its front raises d.result_dev[2] to 1 (not positive definite), like the factorisation.
 hipError_t launch_cov_level(const DevGraph& d, double* S, const int* parent, int level_begin, int level_count, size_t lds_bytes, hipStream_t st);
 hipError_t launch_cov_gather(const double* S, const CovReq* req, int n, double* out, hipStream_t st);
+
+// ---- pps_cov_block: root-path solves ----
+// A strip holds K rows of dim doubles (row k, column a at strip + k * dim + a), K = the longest requested path in pivots, and is filled
+// from its END: the pivots of front s sit at rows K - rootlen(s) .. + p, rootlen(s) = the pivots of s and of all its ancestors.  A front
+// that two nodes have in common therefore starts at the same row in both strips, and their common ancestors are a common suffix.
+struct CovStep { int front, row; };             // one front of a path and the strip row of its first pivot
+// one requested node: its dim unit columns start at pivot `local` of the first front of its path (steps[step0 .. + n_steps), leaf -> root)
+struct CovWalk { long long strip; int step0, n_steps, local, dim; };
+// one block of the result: out[dst + a * ld + c] = sum over k < len of Yi[k * di + a] * Yj[k * dj + c], Yi / Yj = the two strips from
+// the first row of their common suffix.  dst_t >= 0: the transposed block is written as well (at dst_t + c * ld + a); dst_t == dst is
+// the diagonal block of a joint marginal, computed on and below its diagonal and mirrored.
+struct CovPair { long long yi, yj, dst, dst_t; int di, dj, len, ld; };
+
+size_t cov_path_lds_bytes(int max_p, int max_front);   // dynamic LDS of k_cov_path for fronts of at most max_p pivots and max_front rows
+// one workgroup per walk; status (one double, raised to kStatusInternal by an index outside its front or its strip, never overwritten)
+// sits in front of the result: out[0], the blocks start at out[1].  n_strip: doubles in the strip buffer Y.
+hipError_t launch_cov_path(const DevGraph& d, const CovWalk* walks, int n_walks, const CovStep* steps, int n_steps_total, int K, int max_p,
+                           int max_front, double* Y, long long n_strip, double* out, hipStream_t st);
+hipError_t launch_cov_gram(const CovPair* pairs, int n_pairs, const double* Y, long long n_strip, double* out, long long n_out, hipStream_t st);
 
 }  // namespace pps

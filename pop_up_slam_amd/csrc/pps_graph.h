@@ -205,6 +205,14 @@ struct pps_graph {
   std::vector<int> cov_epos, cov_front_of;               // delta index -> elimination-ordered scalar; that scalar -> front
   hipEvent_t cov_ev[3] = {nullptr, nullptr, nullptr};
   double cov_sec[2] = {0, 0};        // device seconds of the last recovery: whole call | root -> leaves pass alone
+  // pps_cov_block (blocks outside the pattern, by root-path solves on dev.L): per front the pivots of the front and all its ancestors,
+  // the request tables / strips / result of a query (device; the first double of cov_bout is the query's status word, zero between queries)
+  std::vector<int> cov_rootlen; int cov_max_p = 0, cov_max_rows = 0;
+  char* cov_breq = nullptr; size_t cov_breq_cap = 0;
+  double* cov_strip = nullptr; size_t cov_strip_cap = 0;
+  double* cov_bout = nullptr; size_t cov_bout_cap = 0; bool cov_bout_clean = false;
+  hipEvent_t cov_bev[2] = {nullptr, nullptr};
+  double cov_block_sec = 0; int cov_block_launches = 0;   // the two kernels of the last query: device seconds, launches
   // stats / trace
   pps_stats stats{};
   std::vector<double> tr_lambda, tr_chi2;
