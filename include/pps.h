@@ -326,7 +326,7 @@ int pps_popup_set_image(pps_popup* p, const unsigned char* bgr);
 int pps_popup_run(pps_popup* p, const float* seg2d, int n, const float T_wc[16], const float* polys,
                   const int* poly_off, int nplanes, int step, float depth_thre, float ceiling_thre, int* n_valid);
 /* The same run without waiting for it (the frame loop, Mapping.cpp:401-586 / main_3d.cpp:423-503: the graph construction needs the plane
- * equations, the pixels are nobody's input before the frame is drawn).  pps_popup_planes_wait returns the (n+1) x 4 plane equations as soon as
+ * equations, the pixels are read later: by pps_map_add_frame, or when the frame is drawn).  pps_popup_planes_wait returns the (n+1) x 4 plane equations as soon as
  * the kernel's first workgroup has written them -- a few microseconds after the launch --, pps_popup_wait the end of the run (n_valid may be
  * NULL).  Every entry point that reads results of a run (download, plane_info, fill_depth, download_segments3d, the next run) waits for a
  * run in flight by itself. */
@@ -481,6 +481,73 @@ int pps_edges_host_contour(const int16_t* cell_segs, int n, float scale, float* 
 int pps_edges_host_select(const float* contour_xy, int n_contour, int width, int height, const float* lsd_lines, int n_lines,
                           const pps_edge_params* prm, float* open_segs, int* n_open, float* closed_segs, int* n_closed,
                           float* open_in_closed);
+
+/* ---- dense map: the per-plane clouds of every frame, kept on the device and re-projected there ------------------
+ * The reference's final product.  Every frame keeps the cloud of each of its good planes (Map_plane::plane_cloud /
+ * tracking_frame::partplane_clouds, main_3d.cpp:475,493, cut out of the frame by popup_plane::matrixToCloud, popup_plane.cpp:925-985); when
+ * the sequence ends, every kept point is projected onto the current estimate of its landmark plane and published, frames and planes thinned
+ * by age and by how often the landmark was tracked (main_3d.cpp:535-588).  A pps_map is that store for one graph: pps_map_add_frame splits
+ * the cloud of the last pps_popup_run by plane id into chunks -- on the device, the cloud is not downloaded --, pps_map_build writes the map.
+ *
+ * The map belongs to a graph (same device; the graph must outlive it; one host thread drives both) and reads that graph's plane estimates.
+ * It holds `capacity_points` pps_point in one device buffer (taken by the first pps_map_add_frame) and as many for the built map (taken by
+ * the first pps_map_build); it never grows.  Creating a map, its bookkeeping calls and every argument check work without a device.
+ * The RAW points are kept: a build after further optimisation projects the original points again.  (The reference overwrites its clouds in
+ * place, main_3d.cpp:574-576 -- a second pass there would project the projections.)
+ * PPS_VERSION stays 304: a caller detects these entry points by symbol lookup (dlsym "pps_map_create"), like pps_cov_*. */
+typedef struct pps_map pps_map;
+/* one chunk = the points of one plane of one frame, `count` consecutive points from `offset` in the buffer the table describes */
+typedef struct pps_map_chunk {
+  int32_t frame;            /* frame index in insertion order (frame_ind of main_3d.cpp:538)                     */
+  int32_t frame_seq_id;     /* tracking_frame::frame_seq_id                                                       */
+  int32_t frame_plane;      /* plane index inside the frame, 0 = ground (Map_plane::frame_plane_indice)            */
+  int32_t plane_id;         /* plane node the chunk belongs to NOW (observed_planes[k]->plane_vertex)              */
+  int64_t offset, count;
+} pps_map_chunk;
+typedef struct pps_map_totals {
+  int64_t capacity, n_points;          /* points the store can hold / holds                                       */
+  int64_t built_points;                /* points of the last build                                                */
+  int32_t n_frames, n_chunks, built_chunks, reserved;
+} pps_map_totals;
+/* the thinning of main_3d.cpp:544-562 */
+typedef struct pps_map_select {
+  int32_t counter;                     /* frame_seq_id of the last frame (`counter` when the map is published)    */
+  int32_t every_frame;                 /* final_reproject_label_img: keep every frame                             */
+  int32_t old_age, old_every, new_every;   /* 10 3 2: frames with frame_seq_id <= counter - old_age keep every old_every-th frame index, newer ones every new_every-th (:545-551) */
+  int32_t age[3], min_tracked[3];      /* (15, 10) (8, 5) (4, 2): a chunk with frame_seq_id <= counter - age[i] needs tracked times >= min_tracked[i] (:554-562) */
+} pps_map_select;
+void pps_map_default_select(pps_map_select* s, int counter);
+int pps_map_create(pps_graph* g, int64_t capacity_points, pps_map** out);
+int pps_map_destroy(pps_map* m);
+const char* pps_map_last_error(const pps_map* m);
+/* The last run of `p` (a run in flight is waited for) becomes a frame of the map: one chunk per frame plane k = 0 .. nplanes-1 (ground
+ * included) with plane_node_ids[k] >= 0, holding the points whose valid bit is set and whose plane-id pixel equals k, in raster order of
+ * their pixels (after a step = 2 run: the even pixels), copied bit for bit.  plane_node_ids[k] = -1 skips the plane; a plane without a
+ * valid point still gets an (empty) chunk: it is an observation of its landmark.  counts[nplanes] (may be NULL): points per plane.
+ * The call waits for its own kernels (the pop-up context may start its next run when it returns).
+ *   PPS_ESTATE  no run yet, or the run had the plane-id output switched off (pps_popup_set_outputs)
+ *   PPS_EINVAL  NULL handle, nplanes outside 0 .. 65, an id that is not a live plane node of the graph, a context on another device
+ *   PPS_ENOMEM  the frame's kept points exceed the remaining capacity; the map is unchanged */
+int pps_map_add_frame(pps_map* m, pps_popup* p, int frame_seq_id, int nplanes, const int* plane_node_ids, int* counts);
+/* loopclose_merge / copy_plane (Mapping.cpp:659-700, Map_plane.cpp:25): every chunk of from_plane belongs to to_plane from now on (and
+ * counts towards its tracked times).  from_plane: a plane node id of the graph, live or removed; to_plane: a live one. */
+int pps_map_redirect(pps_map* m, int from_plane, int to_plane);
+int pps_map_info(const pps_map* m, pps_map_totals* out);
+/* chunk table of the store / of the last build (offsets into the built map): *n = chunks in all, the first min(cap, *n) are copied */
+int pps_map_chunks(const pps_map* m, int cap, pps_map_chunk* out, int* n);
+int pps_map_built_chunks(const pps_map* m, int cap, pps_map_chunk* out, int* n);
+/* main_3d.cpp:544-562 over a chunk table, host only: keep[i] = 1 if chunk i is published.  being_tracked_times of a landmark = the
+ * chunks of the table, empty ones included, that belong to it.  sel == NULL keeps all.  n_keep may be NULL. */
+int pps_map_select_host(const pps_map_chunk* chunks, int n, const pps_map_select* sel, int32_t* keep, int* n_keep);
+/* The map: the selected chunks (sel == NULL: all) back to back in chunk order, every point projected onto the current estimate of its
+ * landmark -- Plane3d::project_to_plane (src/isam_plane3d.h:173-178) in fp64 on the fp32 point, result cast to fp32, the device function of
+ * pps_reproject_points, bit for bit --, rgba copied.  Points of a landmark that was removed and not redirected pass through untouched.
+ * The estimate is brought to the device like pps_reproject_points does; the store is not modified. */
+int pps_map_build(pps_map* m, const pps_map_select* sel, int64_t* n_points, int* n_chunks);
+/* points [first, first + n) of the store (which = 0) or of the built map (which = 1) */
+int pps_map_download(pps_map* m, int which, int64_t first, int64_t n, pps_point* out);
+/* device seconds (HIP events): sec[0] the kernels of the last pps_map_add_frame, sec[1] the kernel of the last pps_map_build */
+int pps_map_last_times(const pps_map* m, double sec[2]);
 
 #ifdef __cplusplus
 }

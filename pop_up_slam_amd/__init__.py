@@ -90,6 +90,27 @@ class PpsAssocParams(C.Structure):
                 ("edge_asso_angle", C.c_double), ("assoc_near_frames", C.c_int)]
 
 
+class PpsMapChunk(C.Structure):
+    """pps_map_chunk (include/pps.h): the points of one plane of one frame."""
+    _fields_ = [("frame", C.c_int32), ("frame_seq_id", C.c_int32), ("frame_plane", C.c_int32), ("plane_id", C.c_int32),
+                ("offset", C.c_int64), ("count", C.c_int64)]
+
+
+class PpsMapTotals(C.Structure):
+    _fields_ = [("capacity", C.c_int64), ("n_points", C.c_int64), ("built_points", C.c_int64),
+                ("n_frames", C.c_int32), ("n_chunks", C.c_int32), ("built_chunks", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PpsMapSelect(C.Structure):
+    """pps_map_select (include/pps.h): the thinning of main_3d.cpp:544-562; defaults via pps_map_default_select."""
+    _fields_ = [("counter", C.c_int32), ("every_frame", C.c_int32), ("old_age", C.c_int32), ("old_every", C.c_int32),
+                ("new_every", C.c_int32), ("age", C.c_int32 * 3), ("min_tracked", C.c_int32 * 3)]
+
+
+CHUNK_DTYPE = np.dtype([("frame", "<i4"), ("frame_seq_id", "<i4"), ("frame_plane", "<i4"), ("plane_id", "<i4"),
+                        ("offset", "<i8"), ("count", "<i8")])
+
+
 SYMBOLS = [
     "pps_default_props", "pps_version", "pps_last_error", "pps_graph_create", "pps_graph_destroy",
     "pps_get_props", "pps_set_props", "pps_add_pose", "pps_add_plane", "pps_add_pose_prior",
@@ -111,6 +132,9 @@ SYMBOLS = [
     "pps_multi_create", "pps_multi_destroy", "pps_multi_last_error", "pps_multi_optimize", "pps_multi_rounds", "pps_multi_save_state", "pps_multi_restore_state", "pps_multi_set_profiling", "pps_multi_phase_times", "pps_popup_polygons_simple", "pps_analysis_reuse", "pps_analysis_kept",
     "pps_cov_recover", "pps_cov_marginals", "pps_cov_access", "pps_cov_joint", "pps_cov_last_times",
     "pps_cov_block", "pps_cov_block_last",
+    "pps_map_default_select", "pps_map_create", "pps_map_destroy", "pps_map_last_error", "pps_map_add_frame", "pps_map_redirect",
+    "pps_map_info", "pps_map_chunks", "pps_map_built_chunks", "pps_map_select_host", "pps_map_build", "pps_map_download",
+    "pps_map_last_times",
 ]
 
 
@@ -231,6 +255,20 @@ def lib():
         L.pps_cov_last_times.argtypes = [C.c_void_p, _dp]
         L.pps_cov_block.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int, _ip, _dp]
         L.pps_cov_block_last.argtypes = [C.c_void_p, _dp, _ip]
+        _i32p = C.POINTER(C.c_int32)
+        L.pps_map_default_select.argtypes = [C.POINTER(PpsMapSelect), C.c_int]; L.pps_map_default_select.restype = None
+        L.pps_map_create.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
+        L.pps_map_destroy.argtypes = [C.c_void_p]
+        L.pps_map_last_error.argtypes = [C.c_void_p]; L.pps_map_last_error.restype = C.c_char_p
+        L.pps_map_add_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _ip, _ip]
+        L.pps_map_redirect.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.pps_map_info.argtypes = [C.c_void_p, C.POINTER(PpsMapTotals)]
+        L.pps_map_chunks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
+        L.pps_map_built_chunks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
+        L.pps_map_select_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(PpsMapSelect), _i32p, _ip]
+        L.pps_map_build.argtypes = [C.c_void_p, C.POINTER(PpsMapSelect), _i64p, _ip]
+        L.pps_map_download.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+        L.pps_map_last_times.argtypes = [C.c_void_p, _dp]
         _LIB = L
     return _LIB
 
@@ -735,6 +773,108 @@ class Popup:
 
     def last_kernel_time(self):
         s = C.c_double(); self._ck(self.L.pps_popup_last_kernel_time(self.h, C.byref(s))); return s.value
+
+
+def map_select(counter, **kw):
+    """pps_map_select with the reference's gates (main_3d.cpp:544-562) for a map published at frame `counter`; fields by keyword
+    (age / min_tracked: sequences of 3)."""
+    s = PpsMapSelect(); lib().pps_map_default_select(C.byref(s), int(counter))
+    for k, v in kw.items():
+        if not hasattr(s, k):
+            raise KeyError(k)
+        if k in ("age", "min_tracked"):
+            v = (C.c_int32 * 3)(*[int(x) for x in v])
+        setattr(s, k, v)
+    return s
+
+
+def map_select_host(chunks, sel=None):
+    """pps_map_select_host: keep flag per row of a chunk table (CHUNK_DTYPE array); sel None keeps all.  No device needed."""
+    c = np.ascontiguousarray(chunks, dtype=CHUNK_DTYPE); n = len(c)
+    keep = np.zeros(max(n, 1), dtype=np.int32); nk = C.c_int()
+    rc = lib().pps_map_select_host(c.ctypes.data_as(C.c_void_p), n, C.byref(sel) if sel is not None else None,
+                                   keep.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nk))
+    if rc != PPS_OK:
+        raise PpsError(rc, "pps_map_select_host")
+    assert nk.value == int(keep[:n].sum())
+    return keep[:n].astype(bool)
+
+
+class Map:
+    """pps_map: the per-plane clouds of every frame kept on the device (tracking_frame::partplane_clouds), and the final map built from
+    them -- every point projected onto the current estimate of its landmark (main_3d.cpp:535-588)."""
+
+    def __init__(self, graph, capacity_points):
+        self.L = lib()
+        self.graph = graph                              # keeps the graph alive: the map reads its plane estimates
+        h = C.c_void_p()
+        rc = self.L.pps_map_create(graph.h, int(capacity_points), C.byref(h))
+        if rc != PPS_OK:
+            raise PpsError(rc, "pps_map_create failed")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pps_map_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != PPS_OK:
+            raise PpsError(rc, self.L.pps_map_last_error(self.h).decode())
+
+    def add_frame(self, popup, frame_seq_id, plane_node_ids):
+        """the last run of `popup` as a frame: one chunk per plane with plane_node_ids[k] >= 0 (-1 skips); returns the points per plane"""
+        ids = np.ascontiguousarray(plane_node_ids, dtype=np.int32).reshape(-1)
+        cnt = np.zeros(max(len(ids), 1), dtype=np.int32)
+        self._ck(self.L.pps_map_add_frame(self.h, popup.h if popup is not None else None, int(frame_seq_id), len(ids),
+                                          ids.ctypes.data_as(_ip), cnt.ctypes.data_as(_ip)))
+        return cnt[:len(ids)].copy()
+
+    def redirect(self, from_plane, to_plane):
+        self._ck(self.L.pps_map_redirect(self.h, int(from_plane), int(to_plane)))
+
+    def info(self):
+        t = PpsMapTotals(); self._ck(self.L.pps_map_info(self.h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_ if k != "reserved"}
+
+    def _table(self, fn):
+        n = C.c_int(); self._ck(fn(self.h, 0, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=CHUNK_DTYPE)
+        if n.value:
+            self._ck(fn(self.h, n.value, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out
+
+    def chunks(self):
+        """chunk table of the store (CHUNK_DTYPE rows, insertion order)"""
+        return self._table(self.L.pps_map_chunks)
+
+    def built_chunks(self):
+        """chunk table of the last build: offsets into the built map"""
+        return self._table(self.L.pps_map_built_chunks)
+
+    def build(self, sel=None):
+        """-> (points, chunks) of the map just built; sel: a PpsMapSelect (map_select) or None = every chunk"""
+        npt = C.c_int64(); nch = C.c_int()
+        self._ck(self.L.pps_map_build(self.h, C.byref(sel) if sel is not None else None, C.byref(npt), C.byref(nch)))
+        return npt.value, nch.value
+
+    def download(self, which=0, first=0, n=None):
+        """points [first, first + n) of the store (which = 0) or the built map (which = 1) as a POINT_DTYPE array"""
+        if n is None:
+            i = self.info(); n = (i["n_points"] if which == 0 else i["built_points"]) - first
+        out = np.zeros(max(int(n), 0), dtype=POINT_DTYPE)
+        self._ck(self.L.pps_map_download(self.h, int(which), int(first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def last_times(self):
+        """device seconds: (kernels of the last add_frame, kernel of the last build)"""
+        s = (C.c_double * 2)(); self._ck(self.L.pps_map_last_times(self.h, s)); return float(s[0]), float(s[1])
 
 
 class Multi:

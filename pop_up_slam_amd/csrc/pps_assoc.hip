@@ -16,6 +16,7 @@
 
 #include "pps_geom.h"
 #include "pps_popup_dev.h"
+#include "pps_project.h"
 
 namespace pps {
 namespace {
@@ -168,14 +169,10 @@ __global__ __launch_bounds__(256) void k_reproject(int n, const int* __restrict_
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int sl = slot[i];
-  const double x = (double)pts[3 * i], y = (double)pts[3 * i + 1], z = (double)pts[3 * i + 2];
   if (sl < 0) { out[3 * i] = pts[3 * i]; out[3 * i + 1] = pts[3 * i + 1]; out[3 * i + 2] = pts[3 * i + 2]; return; }   // merged / unknown landmark: untouched
   double p[4];
   for (int k = 0; k < 4; k++) p[k] = plane_est[(size_t)k * plane_ld + sl];
-  const double l = norm3(p);
-  const double nx = p[0] / l, ny = p[1] / l, nz = p[2] / l, dd = -p[3] / l;
-  const double s = (nx * x + ny * y + nz * z) - dd;
-  out[3 * i] = (float)(x - nx * s); out[3 * i + 1] = (float)(y - ny * s); out[3 * i + 2] = (float)(z - nz * s);
+  project_to_plane_f32(p, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], out + 3 * i, out + 3 * i + 1, out + 3 * i + 2);
 }
 
 }  // namespace

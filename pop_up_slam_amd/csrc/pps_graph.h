@@ -8,6 +8,7 @@
 //   pps_frames.cpp   registered frames (measurement refresh on the device), data association, point re-projection
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
 //   pps_cov.cpp      marginal covariances from the factor (isam::Covariances); kernels in pps_cov.hip
+//   pps_map.cpp      the dense map (pps_map: per-plane clouds of every frame, re-projected on the device); kernels in pps_map.hip
 #pragma once
 #include <hip/hip_runtime.h>
 

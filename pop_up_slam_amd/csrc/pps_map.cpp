@@ -1,0 +1,292 @@
+// pps_map.cpp -- host side of the dense map (include/pps.h: pps_map_*): the chunk table, the thinning of main_3d.cpp:544-562, and the calls
+// that drive the kernels of pps_map.hip.
+//
+// Streams.  A pop-up context runs on its own stream, the map's kernels on the stream of the graph it belongs to.  pps_map_add_frame first
+// waits -- on the host -- for the run of the pop-up context (popup_last_run), so the cloud and the plane-id map are complete before the
+// count kernel is enqueued on the graph's stream; it returns after a synchronisation of that stream, so the context's next run cannot
+// overwrite a cloud that is still being read.  pps_map_build follows prepare_solve on the same stream: the solver's estimate, the store's
+// last writes and the build are ordered by the stream itself.
+#include "pps_graph.h"
+#include "pps_map.h"
+#include "pps_popup_host.h"
+
+using namespace pps;
+using namespace pps_impl;
+
+static_assert(sizeof(MapPt) == sizeof(pps_point), "MapPt is pps_point");
+
+struct pps_map {
+  pps_graph* g = nullptr;
+  std::string err;
+  int64_t cap = 0, used = 0;
+  int n_frames = 0;
+  std::vector<pps_map_chunk> chunks, built;
+  int64_t built_points = 0;
+  MapPt *d_store = nullptr, *d_built = nullptr;
+  int* d_table = nullptr; size_t table_cap = 0;       // planes x wave tiles of the last frame, then kMapPlanes totals
+  int* h_totals = nullptr;                            // pinned, kMapPlanes
+  char* d_sel = nullptr; size_t sel_cap = 0;          // offset table of a build: [out_off | src_off | slot]
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  double sec[2] = {0, 0};
+};
+
+namespace {
+
+int mfail(pps_map* m, int code, const std::string& msg) { if (m) m->err = msg; return code; }
+#define MAP_TRY(m, expr)                                                                                        \
+  do {                                                                                                          \
+    hipError_t _e = (expr);                                                                                     \
+    if (_e != hipSuccess) return mfail(m, _e == hipErrorOutOfMemory ? PPS_ENOMEM : PPS_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+bool select_valid(const pps_map_select* s) { return !s || (s->old_every > 0 && s->new_every > 0); }
+
+// main_3d.cpp:544-562
+void select_chunks(const pps_map_chunk* c, int n, const pps_map_select* s, int32_t* keep) {
+  std::unordered_map<int, int> tracked;                // being_tracked_times: chunks that belong to the landmark now
+  for (int i = 0; i < n; i++) tracked[c[i].plane_id]++;
+  for (int i = 0; i < n; i++) {
+    keep[i] = 1;
+    if (!s) continue;
+    const int seq = c[i].frame_seq_id, times = tracked[c[i].plane_id];
+    if (!s->every_frame) {
+      if (seq <= s->counter - s->old_age) { if (c[i].frame % s->old_every != 0) keep[i] = 0; }
+      else if (c[i].frame % s->new_every != 0) keep[i] = 0;
+    }
+    for (int a = 0; a < 3; a++)
+      if (seq <= s->counter - s->age[a] && times < s->min_tracked[a]) keep[i] = 0;
+  }
+}
+
+int table_copy(const std::vector<pps_map_chunk>& t, int cap, pps_map_chunk* out, int* n) {
+  if (!n || cap < 0 || (cap > 0 && !out)) return PPS_EINVAL;
+  *n = (int)t.size();
+  const size_t k = std::min<size_t>((size_t)cap, t.size());
+  if (k) memcpy(out, t.data(), k * sizeof(pps_map_chunk));
+  return PPS_OK;
+}
+
+int map_events(pps_map* m) {
+  for (hipEvent_t& e : m->ev)
+    if (!e) MAP_TRY(m, hipEventCreate(&e));
+  return PPS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pps_map_default_select(pps_map_select* s, int counter) {
+  if (!s) return;
+  s->counter = counter; s->every_frame = 0;
+  s->old_age = 10; s->old_every = 3; s->new_every = 2;                          // main_3d.cpp:545-551
+  s->age[0] = 15; s->min_tracked[0] = 10;                                       // :554-556
+  s->age[1] = 8; s->min_tracked[1] = 5;                                         // :557-559
+  s->age[2] = 4; s->min_tracked[2] = 2;                                         // :560-562
+}
+
+int pps_map_create(pps_graph* g, int64_t capacity_points, pps_map** out) {
+  if (!g || !out || capacity_points < 0) return PPS_EINVAL;
+  pps_map* m = new (std::nothrow) pps_map();
+  if (!m) return PPS_ENOMEM;
+  m->g = g; m->cap = capacity_points;
+  *out = m;
+  return PPS_OK;
+}
+
+int pps_map_destroy(pps_map* m) {
+  if (!m) return PPS_EINVAL;
+  if (m->d_store || m->d_built || m->d_table || m->h_totals || m->d_sel || m->ev[0]) {
+    (void)hipSetDevice(m->g->props.device);
+    if (m->g->stream) (void)hipStreamSynchronize(m->g->stream);
+    (void)hipFree(m->d_store); (void)hipFree(m->d_built); (void)hipFree(m->d_table); (void)hipFree(m->d_sel);
+    if (m->h_totals) (void)hipHostFree(m->h_totals);
+    for (hipEvent_t e : m->ev) if (e) (void)hipEventDestroy(e);
+  }
+  delete m;
+  return PPS_OK;
+}
+
+const char* pps_map_last_error(const pps_map* m) { return m ? m->err.c_str() : "null handle"; }
+
+int pps_map_add_frame(pps_map* m, pps_popup* p, int frame_seq_id, int nplanes, const int* plane_node_ids, int* counts) {
+  if (!m || !p) return mfail(m, PPS_EINVAL, "add_frame: null handle");
+  if (nplanes < 0 || nplanes > kMapPlanes || (nplanes > 0 && !plane_node_ids)) return mfail(m, PPS_EINVAL, "add_frame: nplanes outside 0 .. 65, or no ids");
+  pps_graph* g = m->g;
+  for (int k = 0; k < nplanes; k++)
+    if (plane_node_ids[k] != -1 && !live_node(g, plane_node_ids[k], NODE_PLANE))
+      return mfail(m, PPS_EINVAL, "add_frame: plane_node_ids[" + std::to_string(k) + "] is not a live plane node");
+  PopupRunView v{};
+  int rc = popup_last_run(p, &v);
+  if (rc != PPS_OK) return mfail(m, rc, std::string("add_frame: ") + pps_popup_last_error(p));
+  if (v.device != g->props.device) return mfail(m, PPS_EINVAL, "add_frame: the pop-up context lives on another device than the graph");
+  const int npx = v.width * v.height;
+  std::vector<int> cnt((size_t)nplanes, 0);
+  int64_t kept = 0;
+  MapScatterBase base;
+  for (int k = 0; k < kMapPlanes; k++) base.base[k] = -1;
+  m->sec[0] = 0;
+  if (nplanes > 0) {
+    rc = ensure_device(g);
+    if (rc != PPS_OK) return mfail(m, rc, g->err);
+    MAP_TRY(m, hipSetDevice(g->props.device));
+    rc = map_events(m);
+    if (rc != PPS_OK) return rc;
+    const MapTiling t = map_tiling(npx);
+    const size_t need = (size_t)kMapPlanes * t.nT + kMapPlanes;
+    if (need > m->table_cap) {
+      MAP_TRY(m, hipStreamSynchronize(g->stream));
+      (void)hipFree(m->d_table); m->d_table = nullptr; m->table_cap = 0;
+      MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_table), need * sizeof(int)));
+      m->table_cap = need;
+    }
+    if (!m->h_totals) MAP_TRY(m, hipHostMalloc(reinterpret_cast<void**>(&m->h_totals), kMapPlanes * sizeof(int), hipHostMallocDefault));
+    if (!m->d_store && m->cap > 0) MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_store), (size_t)m->cap * sizeof(MapPt)));
+    int* d_totals = m->d_table + (size_t)kMapPlanes * t.nT;
+    const MapPt* cloud = reinterpret_cast<const MapPt*>(v.cloud);
+    MAP_TRY(m, hipEventRecord(m->ev[0], g->stream));
+    MAP_TRY(m, launch_map_count(cloud, v.plane_id, npx, nplanes, m->d_table, d_totals, g->stream));
+    MAP_TRY(m, hipEventRecord(m->ev[1], g->stream));
+    MAP_TRY(m, hipMemcpyAsync(m->h_totals, d_totals, (size_t)nplanes * sizeof(int), hipMemcpyDeviceToHost, g->stream));
+    MAP_TRY(m, hipStreamSynchronize(g->stream));
+    for (int k = 0; k < nplanes; k++)
+      if (plane_node_ids[k] >= 0) { cnt[k] = m->h_totals[k]; base.base[k] = m->used + kept; kept += cnt[k]; }
+    if (kept > m->cap - m->used)
+      return mfail(m, PPS_ENOMEM, "add_frame: the frame keeps " + std::to_string(kept) + " points, the store has room for " + std::to_string(m->cap - m->used));
+    float ms0 = 0, ms1 = 0;
+    (void)hipEventElapsedTime(&ms0, m->ev[0], m->ev[1]);
+    if (kept > 0) {
+      MAP_TRY(m, hipEventRecord(m->ev[2], g->stream));
+      MAP_TRY(m, launch_map_scatter(cloud, v.plane_id, npx, nplanes, m->d_table, base, m->d_store, g->stream));
+      MAP_TRY(m, hipEventRecord(m->ev[3], g->stream));
+      MAP_TRY(m, hipStreamSynchronize(g->stream));
+      (void)hipEventElapsedTime(&ms1, m->ev[2], m->ev[3]);
+    }
+    m->sec[0] = 1e-3 * ((double)ms0 + (double)ms1);
+  }
+  for (int k = 0; k < nplanes; k++) {
+    if (plane_node_ids[k] < 0) continue;
+    m->chunks.push_back(pps_map_chunk{m->n_frames, frame_seq_id, k, plane_node_ids[k], base.base[k], cnt[k]});
+  }
+  m->used += kept;
+  m->n_frames++;
+  if (counts) for (int k = 0; k < nplanes; k++) counts[k] = cnt[k];
+  return PPS_OK;
+}
+
+int pps_map_redirect(pps_map* m, int from_plane, int to_plane) {
+  if (!m) return PPS_EINVAL;
+  const pps_graph* g = m->g;
+  if (from_plane < 0 || from_plane >= (int)g->nodes.size() || g->nodes[from_plane].type != NODE_PLANE)
+    return mfail(m, PPS_EINVAL, "redirect: from_plane is not a plane node of the graph");
+  if (!live_node(g, to_plane, NODE_PLANE)) return mfail(m, PPS_EINVAL, "redirect: to_plane is not a live plane node");
+  for (pps_map_chunk& c : m->chunks)
+    if (c.plane_id == from_plane) c.plane_id = to_plane;
+  return PPS_OK;
+}
+
+int pps_map_info(const pps_map* m, pps_map_totals* out) {
+  if (!m || !out) return PPS_EINVAL;
+  out->capacity = m->cap; out->n_points = m->used; out->built_points = m->built_points;
+  out->n_frames = m->n_frames; out->n_chunks = (int)m->chunks.size(); out->built_chunks = (int)m->built.size(); out->reserved = 0;
+  return PPS_OK;
+}
+
+int pps_map_chunks(const pps_map* m, int cap, pps_map_chunk* out, int* n) { return m ? table_copy(m->chunks, cap, out, n) : PPS_EINVAL; }
+int pps_map_built_chunks(const pps_map* m, int cap, pps_map_chunk* out, int* n) { return m ? table_copy(m->built, cap, out, n) : PPS_EINVAL; }
+
+int pps_map_select_host(const pps_map_chunk* chunks, int n, const pps_map_select* sel, int32_t* keep, int* n_keep) {
+  if (n < 0 || (n > 0 && (!chunks || !keep)) || !select_valid(sel)) return PPS_EINVAL;
+  select_chunks(chunks, n, sel, keep);
+  if (n_keep) { int k = 0; for (int i = 0; i < n; i++) k += keep[i]; *n_keep = k; }
+  return PPS_OK;
+}
+
+int pps_map_build(pps_map* m, const pps_map_select* sel, int64_t* n_points, int* n_chunks) {
+  if (!m) return PPS_EINVAL;
+  if (!select_valid(sel)) return mfail(m, PPS_EINVAL, "build: old_every and new_every must be positive");
+  pps_graph* g = m->g;
+  const int n = (int)m->chunks.size();
+  std::vector<int32_t> keep((size_t)n);
+  select_chunks(m->chunks.data(), n, sel, keep.data());
+  std::vector<pps_map_chunk> built;
+  std::vector<int> src;                                  // chunks of the device table: selected and not empty
+  int64_t total = 0;
+  for (int i = 0; i < n; i++) {
+    if (!keep[i]) continue;
+    pps_map_chunk c = m->chunks[i];
+    if (c.count > 0) src.push_back(i);
+    c.offset = total; total += c.count;
+    built.push_back(c);
+  }
+  m->sec[1] = 0;
+  if (total > 0) {
+    int rc = prepare_solve(g);
+    if (rc != PPS_OK) return mfail(m, rc, g->err);
+    MAP_TRY(m, hipSetDevice(g->props.device));
+    rc = map_events(m);
+    if (rc != PPS_OK) return rc;
+    if (!m->d_built) MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_built), (size_t)m->cap * sizeof(MapPt)));
+    const size_t ns = src.size();
+    const size_t off_src = (ns + 1) * sizeof(long long), off_slot = off_src + ns * sizeof(long long), bytes = off_slot + ns * sizeof(int);
+    std::vector<char> host(bytes);
+    long long* out_off = reinterpret_cast<long long*>(host.data());
+    long long* src_off = reinterpret_cast<long long*>(host.data() + off_src);
+    int* slot = reinterpret_cast<int*>(host.data() + off_slot);
+    long long o = 0;
+    for (size_t j = 0; j < ns; j++) {
+      const pps_map_chunk& c = m->chunks[src[j]];
+      out_off[j] = o; o += c.count;
+      src_off[j] = c.offset;
+      slot[j] = live_node(g, c.plane_id, NODE_PLANE) ? g->nodes[c.plane_id].slot : -1;
+    }
+    out_off[ns] = o;
+    if (bytes > m->sel_cap) {
+      MAP_TRY(m, hipStreamSynchronize(g->stream));
+      (void)hipFree(m->d_sel); m->d_sel = nullptr; m->sel_cap = 0;
+      MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_sel), 2 * bytes));
+      m->sel_cap = 2 * bytes;
+    }
+    MAP_TRY(m, hipMemcpyAsync(m->d_sel, host.data(), bytes, hipMemcpyHostToDevice, g->stream));
+    MapBuildArgs a{};
+    a.n_out = total; a.n_sel = (int)ns;
+    a.out_off = reinterpret_cast<const long long*>(m->d_sel);
+    a.src_off = reinterpret_cast<const long long*>(m->d_sel + off_src);
+    a.slot = reinterpret_cast<const int*>(m->d_sel + off_slot);
+    a.plane_est = g->dev.plane_est; a.plane_ld = g->dev.plane_ld;
+    a.store = m->d_store; a.built = m->d_built;
+    MAP_TRY(m, hipEventRecord(m->ev[0], g->stream));
+    MAP_TRY(m, launch_map_build(a, g->stream));
+    MAP_TRY(m, hipEventRecord(m->ev[4], g->stream));
+    MAP_TRY(m, hipStreamSynchronize(g->stream));            // (`host` leaves scope; the result is complete on return)
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, m->ev[0], m->ev[4]);
+    m->sec[1] = 1e-3 * ms;
+  }
+  m->built.swap(built);
+  m->built_points = total;
+  if (n_points) *n_points = total;
+  if (n_chunks) *n_chunks = (int)m->built.size();
+  return PPS_OK;
+}
+
+int pps_map_download(pps_map* m, int which, int64_t first, int64_t n, pps_point* out) {
+  if (!m) return PPS_EINVAL;
+  if (which != 0 && which != 1) return mfail(m, PPS_EINVAL, "download: which is 0 (store) or 1 (built map)");
+  const int64_t have = which == 0 ? m->used : m->built_points;
+  if (first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !out)) return mfail(m, PPS_EINVAL, "download: range outside the buffer");
+  if (n == 0) return PPS_OK;
+  MAP_TRY(m, hipSetDevice(m->g->props.device));
+  const MapPt* src = (which == 0 ? m->d_store : m->d_built) + first;
+  MAP_TRY(m, hipMemcpyAsync(out, src, (size_t)n * sizeof(MapPt), hipMemcpyDeviceToHost, m->g->stream));
+  MAP_TRY(m, hipStreamSynchronize(m->g->stream));
+  return PPS_OK;
+}
+
+int pps_map_last_times(const pps_map* m, double sec[2]) {
+  if (!m || !sec) return PPS_EINVAL;
+  sec[0] = m->sec[0]; sec[1] = m->sec[1];
+  return PPS_OK;
+}
+
+}  // extern "C"

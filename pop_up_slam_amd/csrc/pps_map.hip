@@ -1,0 +1,178 @@
+// pps_map.hip -- the dense map on the device: the per-plane clouds of every frame kept in one store, and the final map built from them.
+//
+// The reference keeps, per frame, one pcl cloud per good plane (partplane_clouds_open_all, popup_plane.cpp:925-985 -> main_3d.cpp:475,493)
+// and, at the end, projects every kept point onto the optimised plane of its landmark (main_3d.cpp:563-577).  Here the pop-up kernel has
+// written one point per pixel (cloud) and the plane index of every pixel (plane_id); k_map_count / k_map_scan / k_map_scatter split that
+// frame into one chunk per plane -- a stable partition: the points of a chunk keep the raster order of their pixels --, k_map_build
+// projects the selected chunks.
+//
+// The partition uses no atomic cursor (the order of the points would then depend on the order the waves arrive in).  A wave owns `wt`
+// consecutive pixels (MapTiling); the lanes of a wave that hold the same plane find each other with 64-bit ballots, a lane's rank among
+// them is the population count of the ballot below its lane (mbcnt).  Pass 1 counts per wave tile and plane, pass 2 scans those counts
+// over the tiles (one workgroup per plane), pass 3 repeats the ballots and writes: chunk base + tile prefix + running count of the tile +
+// rank.  The waves of a workgroup do not talk to each other: every wave has its own row of counters in LDS, read and written by that wave
+// alone (LDS operations of one wave execute in order), so there is no workgroup barrier in pass 1 and 3.
+//
+// Compiled without contraction (Makefile): k_map_build gives the bits of k_reproject (pps_project.h).
+#include <hip/hip_runtime.h>
+
+#include "pps_map.h"
+#include "pps_project.h"
+
+namespace pps {
+namespace {
+
+// plane of pixel i if its point is kept: valid bit set and a plane index of this frame
+__device__ __forceinline__ int map_key(unsigned int rgba, int p, int nplanes) { return (((rgba >> 24) & 1u) && p >= 0 && p < nplanes) ? p : -1; }
+
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+  return (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
+}
+
+__global__ __launch_bounds__(kMapThreads) void k_map_count(const MapPt* __restrict__ cloud, const int* __restrict__ plane_id, int npx, int nplanes,
+                                                           int wt, int nT, int* __restrict__ table) {
+  __shared__ int s_cnt[kMapWaves][kMapPlanes];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int T = blockIdx.x * kMapWaves + w;
+  volatile int* cnt = s_cnt[w];
+  if (T >= nT) return;                                           // (whole waves; nothing below synchronises across waves)
+  for (int k = lane; k < nplanes; k += 64) cnt[k] = 0;
+  __builtin_amdgcn_wave_barrier();
+  const int i0 = T * wt, i1 = min(npx, i0 + wt);
+  for (int b = i0; b < i1; b += 64) {
+    const int i = b + lane;
+    int key = -1;
+    if (i < i1) key = map_key(cloud[i].rgba, plane_id[i], nplanes);
+    unsigned long long rem = __ballot(key >= 0);
+    while (rem) {                                                // one turn per distinct plane among the 64 pixels (wave-uniform)
+      const int leader = __ffsll((long long)rem) - 1;
+      const int kk = __builtin_amdgcn_readlane(key, leader);
+      const unsigned long long m = __ballot(key == kk);
+      if (lane == leader) cnt[kk] = cnt[kk] + __popcll(m);
+      rem &= ~m;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  for (int k = lane; k < nplanes; k += 64) table[(size_t)k * nT + T] = cnt[k];
+}
+
+// exclusive scan of one plane's row of tile counts, in place; one workgroup per plane
+__global__ __launch_bounds__(kMapThreads) void k_map_scan(int* __restrict__ table, int nT, int* __restrict__ totals) {
+  __shared__ int s_sum[kMapThreads];
+  const int tid = threadIdx.x;
+  int* row = table + (size_t)blockIdx.x * nT;
+  const int seg = (nT + kMapThreads - 1) / kMapThreads;
+  const int a = min(nT, tid * seg), b = min(nT, a + seg);
+  int sum = 0;
+  for (int i = a; i < b; i++) sum += row[i];
+  s_sum[tid] = sum;
+  __syncthreads();
+  for (int d = 1; d < kMapThreads; d <<= 1) {
+    const int v = tid >= d ? s_sum[tid - d] : 0;
+    __syncthreads();
+    s_sum[tid] += v;
+    __syncthreads();
+  }
+  int run = s_sum[tid] - sum;
+  for (int i = a; i < b; i++) { const int c = row[i]; row[i] = run; run += c; }
+  if (tid == kMapThreads - 1) totals[blockIdx.x] = s_sum[tid];
+}
+
+__global__ __launch_bounds__(kMapThreads) void k_map_scatter(const MapPt* __restrict__ cloud, const int* __restrict__ plane_id, int npx, int nplanes,
+                                                             int wt, int nT, const int* __restrict__ table, MapScatterBase base,
+                                                             MapPt* __restrict__ store) {
+  __shared__ int s_cur[kMapWaves][kMapPlanes];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int T = blockIdx.x * kMapWaves + w;
+  volatile int* cur = s_cur[w];
+  if (T >= nT) return;
+  for (int k = lane; k < nplanes; k += 64) cur[k] = table[(size_t)k * nT + T];
+  __builtin_amdgcn_wave_barrier();
+  const int i0 = T * wt, i1 = min(npx, i0 + wt);
+  for (int b = i0; b < i1; b += 64) {
+    const int i = b + lane;
+    int key = -1;
+    MapPt pt = {0.f, 0.f, 0.f, 0u};
+    if (i < i1) { pt = cloud[i]; key = map_key(pt.rgba, plane_id[i], nplanes); }
+    unsigned long long rem = __ballot(key >= 0);
+    while (rem) {
+      const int leader = __ffsll((long long)rem) - 1;
+      const int kk = __builtin_amdgcn_readlane(key, leader);
+      const unsigned long long m = __ballot(key == kk);
+      const int c = cur[kk];                                     // (every lane reads before the leader moves the cursor)
+      const long long cb = base.base[kk];
+      if (key == kk && cb >= 0) store[cb + c + lanes_below(m)] = pt;
+      __builtin_amdgcn_wave_barrier();
+      if (lane == leader) cur[kk] = c + __popcll(m);
+      rem &= ~m;
+    }
+  }
+}
+
+// One thread per point of the built map.  The workgroup looks up the chunk of its first point in the offset table (thread 0, binary search
+// in global memory) and stages the offsets of the next 256 chunks in LDS: chunks in the table are non-empty, so the 256 points of the
+// workgroup end inside that window; each thread then searches the window.  16 B in, 16 B out.
+__global__ __launch_bounds__(kMapThreads) void k_map_build(MapBuildArgs a) {
+  __shared__ long long s_off[kMapThreads + 1], s_src[kMapThreads];
+  __shared__ int s_slot[kMapThreads];
+  __shared__ int s_c0;
+  const int tid = threadIdx.x;
+  const long long first = (long long)blockIdx.x * kMapThreads;
+  if (tid == 0) {
+    int lo = 0, hi = a.n_sel;                                    // out_off[lo] <= first < out_off[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (a.out_off[mid] <= first) lo = mid; else hi = mid;
+    }
+    s_c0 = lo;
+  }
+  __syncthreads();
+  const int c0 = s_c0;
+  for (int j = tid; j <= kMapThreads; j += kMapThreads) s_off[j] = c0 + j <= a.n_sel ? a.out_off[c0 + j] : 0x7fffffffffffffffLL;
+  if (c0 + tid < a.n_sel) { s_src[tid] = a.src_off[c0 + tid]; s_slot[tid] = a.slot[c0 + tid]; }
+  __syncthreads();
+  const long long i = first + tid;
+  if (i >= a.n_out) return;
+  int lo = 0, hi = kMapThreads;                                  // s_off[lo] <= i < s_off[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (s_off[mid] <= i) lo = mid; else hi = mid;
+  }
+  MapPt pt = a.store[s_src[lo] + (i - s_off[lo])];
+  const int sl = s_slot[lo];
+  if (sl >= 0) {                                                 // (a landmark that is gone and was not redirected: untouched, like k_reproject)
+    double p[4];
+    for (int k = 0; k < 4; k++) p[k] = a.plane_est[(size_t)k * a.plane_ld + sl];
+    project_to_plane_f32(p, pt.x, pt.y, pt.z, &pt.x, &pt.y, &pt.z);
+  }
+  a.built[i] = pt;
+}
+
+}  // namespace
+
+hipError_t launch_map_count(const MapPt* cloud, const int* plane_id, int npx, int nplanes, int* table, int* totals, hipStream_t st) {
+  if (npx <= 0 || nplanes <= 0) return hipSuccess;
+  const MapTiling t = map_tiling(npx);
+  hipLaunchKernelGGL(k_map_count, dim3((t.nT + kMapWaves - 1) / kMapWaves), dim3(kMapThreads), 0, st, cloud, plane_id, npx, nplanes, t.wt, t.nT, table);
+  hipLaunchKernelGGL(k_map_scan, dim3(nplanes), dim3(kMapThreads), 0, st, table, t.nT, totals);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_scatter(const MapPt* cloud, const int* plane_id, int npx, int nplanes, const int* table, const MapScatterBase& base,
+                              MapPt* store, hipStream_t st) {
+  if (npx <= 0 || nplanes <= 0) return hipSuccess;
+  const MapTiling t = map_tiling(npx);
+  hipLaunchKernelGGL(k_map_scatter, dim3((t.nT + kMapWaves - 1) / kMapWaves), dim3(kMapThreads), 0, st, cloud, plane_id, npx, nplanes, t.wt, t.nT, table,
+                     base, store);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_build(const MapBuildArgs& a, hipStream_t st) {
+  if (a.n_out <= 0 || a.n_sel <= 0) return hipSuccess;
+  const long long nwg = (a.n_out + kMapThreads - 1) / kMapThreads;
+  if (nwg > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_map_build, dim3((unsigned int)nwg), dim3(kMapThreads), 0, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace pps

@@ -23,6 +23,7 @@
 
 #include "../../include/pps.h"
 #include "pps_popup_dev.h"
+#include "pps_popup_host.h"
 #include "pps_raster.h"
 
 namespace pps {
@@ -482,6 +483,7 @@ struct pps_popup {
   float last_T[16] = {0};          // pose of the last run
   int* d_pid = nullptr;
   bool want_depth = true, want_pid = true;   // optional per-pixel outputs (pps_popup_set_outputs)
+  bool last_pid = false;           // the last run wrote the plane-id map (pps_map_add_frame partitions the cloud by it)
   float* d_planes = nullptr;   // (kMaxPlanes+1) x 4 plane equations, then kMaxPlanes x 6 world ground segments, kMaxPlanes x 2 plane info; d_count behind
   float* d_seg = nullptr;      // kMaxPlanes x 4
   float* d_polys = nullptr;    // 2*kMaxVerts
@@ -600,6 +602,20 @@ static int popup_settle(pps_popup* p) {
   return PPS_OK;
 }
 
+}  // extern "C"
+// pps_popup_host.h: what pps_map_add_frame reads of the last run.  State is checked on the host first; then a run in flight is waited for.
+int pps::popup_last_run(pps_popup* p, PopupRunView* v) {
+  if (!p || !v) return PPS_EINVAL;
+  if (p->run_seq == 0) return pfail(p, PPS_ESTATE, "no pop-up run");
+  if (!p->last_pid) return pfail(p, PPS_ESTATE, "the run had the plane-id output switched off (pps_popup_set_outputs)");
+  const int rc = popup_settle(p);
+  if (rc != PPS_OK) return rc;
+  v->device = p->device; v->width = p->width; v->height = p->height; v->step = p->last_step;
+  v->cloud = p->d_cloud; v->plane_id = p->d_pid;
+  return PPS_OK;
+}
+extern "C" {
+
 // one run enqueued on the handle's stream; timed: with the event pair around the kernel (the synchronous entry point)
 static int popup_enqueue(pps_popup* p, const float* seg2d, int n, const float T_wc[16], const float* polys, const int* poly_off, int nplanes, int step,
                          float depth_thre, float ceiling_thre, bool timed) {
@@ -650,7 +666,7 @@ static int popup_enqueue(pps_popup* p, const float* seg2d, int n, const float T_
   PHIP(p, hipGetLastError());
   if (timed) PHIP(p, hipEventRecord(p->ev[1], p->stream));
   p->n_wg_last = (size_t)grid.x * grid.y;
-  p->last_n = n; p->last_step = step;
+  p->last_n = n; p->last_step = step; p->last_pid = pidp != nullptr;
   memcpy(p->last_T, T_wc, sizeof p->last_T);
   p->in_flight = true;
   return PPS_OK;
@@ -671,7 +687,7 @@ int pps_popup_run(pps_popup* p, const float* seg2d, int n, const float T_wc[16],
 }
 
 // The same run without waiting for it (round 6: the frame loop's graph construction needs the plane equations, which the kernel's first
-// workgroup publishes at once; the pixels -- cloud, depth, plane ids -- are nobody's input before the frame is drawn).
+// workgroup publishes at once; the pixels -- cloud, depth, plane ids -- are read later: by pps_map_add_frame, which waits for the run, or when the frame is drawn).
 int pps_popup_run_async(pps_popup* p, const float* seg2d, int n, const float T_wc[16], const float* polys, const int* poly_off,
                         int nplanes, int step, float depth_thre, float ceiling_thre) {
   return popup_enqueue(p, seg2d, n, T_wc, polys, poly_off, nplanes, step, depth_thre, ceiling_thre, false);
