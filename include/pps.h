@@ -37,9 +37,10 @@
 extern "C" {
 #endif
 
-#define PPS_VERSION 304   /* round.minor: bump whenever a struct of this header changes layout or an entry point is added (pps_stats grew in 200; pps_debug_front_factor: 301;
+#define PPS_VERSION 305   /* round.minor: bump whenever a struct of this header changes layout or an entry point is added (pps_stats grew in 200; pps_debug_front_factor: 301;
                               pps_multi_save_state / pps_multi_restore_state: 302; pps_debug_exmap AND pps_multi_phase_times' counts[] grown from 2 to 4
-                              entries -- a caller built against 302 that passes counts[2] must be rebuilt: 303; pps_popup_run_async / _planes_wait / _wait: 304) */
+                              entries -- a caller built against 302 that passes counts[2] must be rebuilt: 303; pps_popup_run_async / _planes_wait / _wait: 304;
+                              pps_debug_solve: 305) */
 
 typedef struct pps_graph pps_graph;
 
@@ -143,7 +144,7 @@ int pps_chi2(pps_graph* g, double* chi2);
  * numbers, never a silent recomputation.  Ids are checked first (PPS_EINVAL), on the host, before anything is launched.
  * Pairs OUTSIDE the pattern (e.g. the newest pose against a plane it has not observed) are not available from these three read calls,
  * which report them; pps_cov_block below answers for any nodes, by column solves on the same factor.
- * PPS_VERSION stays 304: a caller detects these entry points by symbol lookup (dlsym "pps_cov_recover"). */
+ * PPS_VERSION was not bumped for them (it stayed 304): a caller detects these entry points by symbol lookup (dlsym "pps_cov_recover"). */
 int pps_cov_recover(pps_graph* g);
 /* diagonal blocks: ids[n] node ids (NULL = all live nodes in insertion order, n = their number); out = concatenated row-major blocks,
  * 36 doubles per pose, 9 per plane; offsets[n + 1] (may be NULL) = start of each block in out.  Every block is exactly symmetric. */
@@ -290,6 +291,22 @@ int pps_debug_front_factor(int tiles, int strip, int p, int b, const double* A, 
  * kind 1: Plane3d::exmap_3dof (isam_plane3d.h:101-127: Exp(d) * q, then normalised); x n x 4, delta n x 3, out n x 4.  The device
  * functions every retraction and every numerical-difference step of the solver goes through.  Runs on the current device. */
 int pps_debug_exmap(int kind, int n, const double* x, const double* delta, double* out);
+
+/* ---- K3 diagnostic: the solved step of the handle's graph, for one damping value or two ---- */
+/* delta = (J'J + lambda diag(J'J))^-1 (-J'r) at the current estimate (Optimizer::compute_gauss_newton_step with the damping of
+ * Cholesky.cpp:94-97), through the launches pps_update / pps_batch_optimize issue for this graph: K1 and K2 at the estimate, then the
+ * factorisation and back-substitution of whichever K3 form the analysis chose.  The estimate stays where it is (the linearisation point
+ * moves onto it, as in pps_eval_factor); the statistics and the LM trace of the last solve are kept; a covariance recovery ends.
+ * delta: n_scalars doubles (pps_analysis_dump), one block per node at its node_voff -- 6 per pose (t, then the rotation vector), 3 per
+ * plane; it is the step the retraction applies (x <- x (+) delta).
+ * lambda2 >= 0 (band forms only, PPS_ESTATE elsewhere): both damping values in the launches of the LM loop's dual solve, delta2
+ * (required then) receives the second step.  lambda2 < 0: one damping value, delta2 is not written.
+ * form (optional): 0 band kernels, one launch per stage | 1 band kernels, the whole tree in one launch pair | 2 dense fronts | 3 one
+ * launch per tree level (LDS fronts).  not_pd (optional): the status word the factorisation left, the larger one of a dual solve -- 0 ok,
+ * 1 a pivot was not positive (delta is then no solution), >= 64 internal.  The status words are zero again when the call returns.
+ * PPS_EINVAL (before the device is touched): null handle, null delta, lambda or lambda2 not a number, lambda < 0 or infinite,
+ * lambda2 >= 0 without delta2. */
+int pps_debug_solve(pps_graph* g, double lambda, double lambda2, double* delta, double* delta2, int* form, double* not_pd);
 
 /* ---- pop-up (fp32), /root/reference/pop_up_wall --------------------------------------- */
 /* popup_plane::update_plane_equation_from_seg (libs/popup_plane.cpp:654-705).
@@ -494,7 +511,7 @@ int pps_edges_host_select(const float* contour_xy, int n_contour, int width, int
  * the first pps_map_build); it never grows.  Creating a map, its bookkeeping calls and every argument check work without a device.
  * The RAW points are kept: a build after further optimisation projects the original points again.  (The reference overwrites its clouds in
  * place, main_3d.cpp:574-576 -- a second pass there would project the projections.)
- * PPS_VERSION stays 304: a caller detects these entry points by symbol lookup (dlsym "pps_map_create"), like pps_cov_*. */
+ * PPS_VERSION was not bumped for them (it stayed 304): a caller detects these entry points by symbol lookup (dlsym "pps_map_create"), like pps_cov_*. */
 typedef struct pps_map pps_map;
 /* one chunk = the points of one plane of one frame, `count` consecutive points from `offset` in the buffer the table describes */
 typedef struct pps_map_chunk {

@@ -25,7 +25,7 @@ _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
 
 
-PPS_VERSION = 304      # include/pps.h: the struct layouts mirrored below
+PPS_VERSION = 305      # include/pps.h: the struct layouts mirrored below
 
 
 class PpsProps(C.Structure):
@@ -125,7 +125,7 @@ SYMBOLS = [
     "pps_frames_set_calibration", "pps_frames_add", "pps_refresh_measurements", "pps_get_measurement",
     "pps_popup_download_segments3d", "pps_assoc_default_params", "pps_landmark_update", "pps_landmark_set_merged",
     "pps_find_closest_planes", "pps_graph_save", "pps_graph_load", "pps_add_plane_obs2", "pps_edge_ray",
-    "pps_time_linearize", "pps_debug_front_factor", "pps_debug_exmap", "pps_reproject_points", "pps_popup_set_outputs",
+    "pps_time_linearize", "pps_debug_front_factor", "pps_debug_exmap", "pps_debug_solve", "pps_reproject_points", "pps_popup_set_outputs",
     "pps_edge_default_params", "pps_edges_create", "pps_edges_destroy", "pps_edges_last_error", "pps_edges_select",
     "pps_edges_download_label", "pps_edges_contour", "pps_edges_last_kernel_time", "pps_edges_host_contour",
     "pps_edges_host_select", "pps_popup_fill_depth", "pps_popup_plane_info", "pps_popup_mask_host",
@@ -243,6 +243,7 @@ def lib():
         L.pps_time_linearize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.pps_debug_front_factor.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_double)]
         L.pps_debug_exmap.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp]
+        L.pps_debug_solve.argtypes = [C.c_void_p, C.c_double, C.c_double, _dp, _dp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         L.pps_reproject_points.argtypes = [C.c_void_p, C.c_int, _ip, _fp, _fp]
         L.pps_graph_save.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.pps_graph_load.argtypes = [C.c_char_p, C.POINTER(PpsProps), C.POINTER(C.c_void_p)]
@@ -588,6 +589,18 @@ class Graph:
         J = np.zeros((m.value, c.value)); r = np.zeros(m.value)
         self._ck(self.L.pps_eval_factor(self.h, fid, mode, J.ctypes.data_as(_dp), r.ctypes.data_as(_dp)))
         return J, r
+
+    def debug_solve(self, lam, lam2=-1.0):
+        """pps_debug_solve: the step the shipped K3 launches solve for at the current estimate, without applying it.  Returns
+        (delta, delta2 | None, form, not_pd): delta indexed by node_voff of analysis_dump(), delta2 the step for lam2 when lam2 >= 0
+        (both damping values in one launch, band forms only), form 0 band per stage / 1 band whole tree / 2 dense fronts / 3 level form."""
+        n = self.analysis_dump()["n_scalars"] if self.h and float(lam) >= 0 else 0
+        dual = float(lam2) >= 0
+        delta = np.zeros(max(n, 1)); delta2 = np.zeros(max(n, 1)) if dual else None
+        form, bad = C.c_int(-1), C.c_double(0.0)
+        self._ck(self.L.pps_debug_solve(self.h, float(lam), float(lam2), delta.ctypes.data_as(_dp),
+                                        delta2.ctypes.data_as(_dp) if dual else None, C.byref(form), C.byref(bad)))
+        return delta[:n], (delta2[:n] if dual else None), form.value, bad.value
 
     def analysis_reuse(self):
         """(fronts kept from the previous analysis, fronts in total) of the last analysis"""

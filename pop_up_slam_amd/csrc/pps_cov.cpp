@@ -11,7 +11,7 @@
 //   pps_cov_block      Sigma(rows, cols) for ANY nodes: (L^-1 E_rows)' (L^-1 E_cols) by one walk up the elimination tree per distinct node
 //                      and one Gram product over common ancestors (pps_cov.hip) -- one upload, two launches, one copy, whatever the query
 // pps_cov_block reads the lambda = 0 factor the recovery leaves in dev.L.  dev.L is written by the factorisations alone (pps_solve.cpp:
-// enqueue_factor_solve and do_solve, reached from pps_update and pps_batch_optimize; the pps_multi launches), and each of those callers
+// enqueue_factor_solve and do_solve, reached from pps_update, pps_batch_optimize and pps_debug_solve; the pps_multi launches), and each of those callers
 // ends the recovery.  What keeps it -- pps_chi2 (K4 reads the states), the getters and pps_save_state (state copies), pps_eval_factor and
 // pps_time_linearize (K1: J and the linearisation point), pps_get_stats / pps_get_trace (host fields), pps_analysis_dump, the
 // association and reprojection calls -- launches nothing that writes dev.L, so no invalidation had to be added for it.

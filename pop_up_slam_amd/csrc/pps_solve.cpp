@@ -541,4 +541,70 @@ int pps_chi2(pps_graph* g, double* chi2) {
   return read_result(g, true, chi2, &dn, &np);
 }
 
+// The step of the shipped solve, outside any solve: K1 / K2 at the estimate (est -> lin as data, the estimate stays), then do_solve --
+// or, for two damping values, enqueue_factor_solve with the DualAlt of lm_solve_dual -- and delta comes home instead of being applied.
+// No retraction and no chi2 kernel follow, so nothing consumes the status words: they are read here and cleared again.
+static int debug_solve_impl(pps_graph* g, double lambda, double lambda2, double* delta, double* delta2, int* form, double* not_pd) {
+  int rc = prepare_solve(g);
+  if (rc != PPS_OK) return rc;
+  const bool dual = lambda2 >= 0.0;
+  if (dual && !(g->use_band && g->spec_L && g->spec_U && g->spec_delta && g->spec_result))
+    return fail(g, PPS_ESTATE, "debug_solve: two damping values in one launch need the band kernels and their second L / U / delta set (this graph runs in another K3 form)");
+  if (form) *form = g->use_band ? (g->k3_all ? 1 : 0) : (g->use_dense ? 2 : 3);
+  const DevGraph& d = g->dev;
+  if (!g->status_clean) {
+    HIP_TRY(g, launch_clear_status(d, g->stream));
+    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
+  }
+  g->status_clean = false;
+  rc = linpoint_from_estimate(g); if (rc != PPS_OK) return rc;
+  rc = do_linearize(g); if (rc != PPS_OK) return rc;
+  if (dual) {
+    DualAlt alt{g->spec_L, g->spec_U, g->spec_delta, g->spec_result, g->spec_chi2_partials, g->spec_dn_partials, g->spec_ticket,
+                lambda2};
+    rc = enqueue_factor_solve(g, d, &alt, lambda, g->stream, false); if (rc != PPS_OK) return rc;
+  } else {
+    rc = do_solve(g, lambda); if (rc != PPS_OK) return rc;
+  }
+  double status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const size_t n = (size_t)std::max(0, d.n_scalars);
+  if (n) HIP_TRY(g, hipMemcpyAsync(delta, d.delta, n * 8, hipMemcpyDeviceToHost, g->stream));
+  if (n && dual) HIP_TRY(g, hipMemcpyAsync(delta2, g->spec_delta, n * 8, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(g, hipMemcpyAsync(status, d.result_dev, 4 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+  if (dual) HIP_TRY(g, hipMemcpyAsync(status + 4, g->spec_result, 4 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  if (status[2] != 0.0 || status[6] != 0.0) {
+    HIP_TRY(g, launch_clear_status(d, g->stream));
+    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+  }
+  g->status_clean = true;
+  if (not_pd) *not_pd = std::max(status[2], status[6]);
+  return PPS_OK;
+}
+
+int pps_debug_solve(pps_graph* g, double lambda, double lambda2, double* delta, double* delta2, int* form, double* not_pd) {
+  if (!g) return PPS_EINVAL;
+  if (!delta) return fail(g, PPS_EINVAL, "debug_solve: null delta");
+  if (!(lambda >= 0.0) || !std::isfinite(lambda)) return fail(g, PPS_EINVAL, "debug_solve: lambda must be a finite number >= 0");
+  if (std::isnan(lambda2) || std::isinf(lambda2)) return fail(g, PPS_EINVAL, "debug_solve: lambda2 must be a finite number (negative: one damping value)");
+  if (lambda2 >= 0.0 && !delta2) return fail(g, PPS_EINVAL, "debug_solve: lambda2 >= 0 needs delta2");
+  if (g->n_live_nodes == 0) return fail(g, PPS_ESTATE, "empty graph");
+  if (g->n_live_factors == 0) return fail(g, PPS_ESTATE, "debug_solve: the graph has no factor");
+  cov_invalidate(g);                   // (dev.L is about to be overwritten)
+  // the figures of the last solve stay what they were: this call is no solve (as in pps_cov_recover)
+  const pps_stats saved = g->stats;
+  const int profiling = g->profiling;
+  g->profiling = 0;
+  const unsigned long long launches0 = g->launches0;
+  const int rc = debug_solve_impl(g, lambda, lambda2, delta, delta2, form, not_pd);
+  g->profiling = profiling;
+  g->launches0 = launches0;
+  { pps_stats s = saved;
+    s.n_fronts = g->stats.n_fronts; s.n_levels = g->stats.n_levels; s.max_front = g->stats.max_front; s.nnz_L = g->stats.nnz_L;
+    g->stats = s; }
+  if (rc != PPS_OK && rc != PPS_EINVAL && rc != PPS_ESTATE) abandon_device_copy(g);
+  return rc;
+}
+
 }  // extern "C"

@@ -164,7 +164,7 @@ def test_symbol_is_declared_exported_and_bound(built):
     assert re.search(r"\bpps_cov_block\s*\(", hdr)
     assert "pps_cov_block" in P.SYMBOLS
     assert getattr(lib, "pps_cov_block") is not None
-    assert P.lib().pps_version() == 304                    # detected by symbol lookup, not by a version bump
+    assert P.lib().pps_version() == 305                    # detected by symbol lookup, not by a version bump (305: pps_debug_solve)
 
 
 def test_block_without_a_recovery_and_bad_arguments(built):
