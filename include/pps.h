@@ -174,6 +174,40 @@ int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols
 /* the last pps_cov_block: device seconds (HIP events) around its two kernels, and the number of kernel launches it made (either may be NULL) */
 int pps_cov_block_last(const pps_graph* g, double* kernel_sec, int* launches);
 
+/* ---- Mahalanobis gate of plane association, from the recovered covariances -------------------------------------
+ * What isam::Covariances is for in a SLAM front end: a candidate pairing of a measurement with a landmark is accepted when its innovation
+ * is small against the innovation covariance.  For pose node pose_id, candidate landmark l, measurement m (a plane 4-vector in the sensor
+ * frame, normalised on entry like Plane3d(Vector4d)) and its packed upper-triangular sqrt information W (6 doubles, as in
+ * pps_add_plane_obs): with r (3) and Jw (3 x 9, over pose 6 | plane 3) the whitened residual and Jacobian a
+ * Pose3d_Plane3d_Factor(pose, l, m, W) would have at the current ESTIMATE -- Jw in the handle's jacobian_mode, the linearisation of
+ * pps_cov_recover -- and Sigma (9 x 9) the joint marginal of (pose, l) from the current recovery,
+ *     S = I + Jw Sigma Jw'     d2 = r' S^-1 r      (S^-1 r by a 3 x 3 Cholesky solve)
+ * d2 is chi-square distributed with 3 degrees of freedom for a correct pairing: 7.815 is the usual (0.95) threshold.
+ * d2 is n_meas x n_planes, row-major; best[i] (best may be NULL) = the index INTO plane_ids of the smallest finite d2 of measurement i,
+ * the first candidate on ties, -1 if no d2 of the row is finite.  plane_ids == NULL (n_planes ignored): all live planes in insertion order.
+ * Everything is computed on the device: one upload, two launches (the root-path walks of pps_cov_block for the 1 + n_planes nodes, the
+ * gate), one copy; no covariance block is downloaded and Sigma is never formed.  The candidate factors are not added to the graph: the
+ * estimate, the linearisation point, the LM trace, the stats and the recovery stay untouched.  A candidate's d2 does not depend on which
+ * other candidates or measurements are in the call.  In JAC_NUMERIC r and Jw are pps_eval_factor's bit for bit (the lane form of K1).
+ *   PPS_EINVAL  NULL handle, meas4, sqrtinf_ut or d2; a negative count; n_meas above 65535 (the grid's second dimension); a non-finite
+ *               input; an unknown or removed id; pose_id is not a
+ *               pose; a plane_ids entry is not a plane; a plane twice in the list (all checked on the host before anything is launched)
+ *   PPS_OK      with the outputs untouched for n_meas == 0 or n_planes == 0 -- answered after the argument checks and BEFORE the recovery
+ *               is looked at (nothing is read from it), unlike pps_cov_block, which asks for the recovery first
+ *   PPS_ESTATE  no valid recovery: the text and the validity rules of pps_cov_block (also: a dense-front graph)
+ *   PPS_ENOTPD  a pivot of a 3 x 3 factor was not positive or not finite (the outputs are untouched)
+ * Mapper_mono::findClosestPlane's geometric gate (pps_find_closest_planes) is independent of this call and unchanged.
+ * Found by symbol lookup, like the pps_cov_* calls; PPS_VERSION was not bumped. */
+int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, const double* sqrtinf_ut, int n_planes, const int* plane_ids,
+                   double* d2, int* best);
+/* the last pps_assoc_gate: device seconds (HIP events) around its two kernels, and the number of kernel launches it made (either may be NULL) */
+int pps_assoc_gate_last(const pps_graph* g, double* kernel_sec, int* launches);
+/* diagnostics: r and Jw of every candidate of the last successful pps_assoc_gate, as the gate kernel evaluated them: n_meas x n_planes
+ * records of 30 doubles [Jp 3 x 6 | Jl 3 x 3 | r 3], row-major, candidate (i, j) at (i * n_planes + j) * 30 -- the layout of K1's record
+ * of a plane observation, so that a test can compare them with pps_eval_factor bit for bit.  *needed = the number of doubles; nothing is
+ * copied when rec is NULL or cap is smaller.  PPS_ESTATE before the first successful gate call of the handle. */
+int pps_debug_assoc_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed);
+
 /* ---- many graphs side by side (BASELINE config 4 on one device; north_star reports graphs/sec) ----------------
  * One C2-size LM solve is a dependency chain that occupies a few dozen of the 256 CUs.  pps_multi runs
  * Optimizer::levenberg_marquardt (Optimizer.cpp:371-467) on n independent graphs in rounds: every kernel of an LM

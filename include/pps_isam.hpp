@@ -421,6 +421,33 @@ public:
     detail::check(pps_cov_block(handle(), (int)ids.size(), ids.data(), 0, nullptr, M.data()), handle(), "pps_cov_block");
     return M;
   }
+  // Mahalanobis gate of plane association (pps_assoc_gate): measurements[i] (sensor frame of `pose`) with noises[i] against every
+  // landmark of `planes`; entry (i, j) = r' (I + Jw Sigma Jw')^-1 r of that pairing at the estimate, chi-square with 3 degrees of
+  // freedom for a correct pairing (7.815 at 0.95).  best[i] = index into `planes` of the smallest finite entry of row i, -1 if none.
+  MatrixXd gate(Pose3d_Node* pose, const std::vector<Plane3d>& measurements, const std::vector<Noise>& noises, const std::list<Node*>& planes,
+                std::vector<int>& best) const {
+    ensure();
+    if (!pose || pose->backend_id() < 0) throw std::runtime_error("Covariances: node is not part of the graph");
+    if (measurements.size() != noises.size()) throw std::runtime_error("Covariances::gate: one noise model per measurement");
+    const std::vector<int> ids = ids_of(planes);
+    std::vector<double> m4, ut;
+    for (size_t i = 0; i < measurements.size(); i++) {
+      const Vector4d v = measurements[i].vector();
+      if (noises[i].sqrtinf_ut().size() != 6) throw std::runtime_error("Covariances::gate: a plane measurement takes a 3 x 3 noise model");
+      m4.insert(m4.end(), v.begin(), v.end());
+      ut.insert(ut.end(), noises[i].sqrtinf_ut().begin(), noises[i].sqrtinf_ut().end());
+    }
+    MatrixXd M((int)measurements.size(), (int)ids.size());
+    best.assign(measurements.size(), -1);
+    if (measurements.empty() || ids.empty()) return M;      // (nothing to compute; a null plane list would ask the library for ALL planes)
+    detail::check(pps_assoc_gate(handle(), pose->backend_id(), (int)measurements.size(), m4.data(), ut.data(), (int)ids.size(), ids.data(), M.data(),
+                                 best.data()), handle(), "pps_assoc_gate");
+    return M;
+  }
+  MatrixXd gate(Pose3d_Node* pose, const std::vector<Plane3d>& measurements, const std::vector<Noise>& noises, const std::list<Node*>& planes) const {
+    std::vector<int> best;
+    return gate(pose, measurements, noises, planes, best);
+  }
   std::list<MatrixXd> marginal(const node_lists_t& node_lists) const {
     std::list<MatrixXd> out;
     for (const std::list<Node*>& l : node_lists) out.push_back(marginal(l));

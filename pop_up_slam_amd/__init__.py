@@ -131,7 +131,7 @@ SYMBOLS = [
     "pps_edges_host_select", "pps_popup_fill_depth", "pps_popup_plane_info", "pps_popup_mask_host",
     "pps_multi_create", "pps_multi_destroy", "pps_multi_last_error", "pps_multi_optimize", "pps_multi_rounds", "pps_multi_save_state", "pps_multi_restore_state", "pps_multi_set_profiling", "pps_multi_phase_times", "pps_popup_polygons_simple", "pps_analysis_reuse", "pps_analysis_kept",
     "pps_cov_recover", "pps_cov_marginals", "pps_cov_access", "pps_cov_joint", "pps_cov_last_times",
-    "pps_cov_block", "pps_cov_block_last",
+    "pps_cov_block", "pps_cov_block_last", "pps_assoc_gate", "pps_assoc_gate_last", "pps_debug_assoc_gate_records",
     "pps_map_default_select", "pps_map_create", "pps_map_destroy", "pps_map_last_error", "pps_map_add_frame", "pps_map_redirect",
     "pps_map_info", "pps_map_chunks", "pps_map_built_chunks", "pps_map_select_host", "pps_map_build", "pps_map_download",
     "pps_map_last_times",
@@ -256,6 +256,9 @@ def lib():
         L.pps_cov_last_times.argtypes = [C.c_void_p, _dp]
         L.pps_cov_block.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int, _ip, _dp]
         L.pps_cov_block_last.argtypes = [C.c_void_p, _dp, _ip]
+        L.pps_assoc_gate.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip, _dp, _ip]
+        L.pps_assoc_gate_last.argtypes = [C.c_void_p, _dp, _ip]
+        L.pps_debug_assoc_gate_records.argtypes = [C.c_void_p, C.c_int64, _dp, C.POINTER(C.c_int64)]
         _i32p = C.POINTER(C.c_int32)
         L.pps_map_default_select.argtypes = [C.POINTER(PpsMapSelect), C.c_int]; L.pps_map_default_select.restype = None
         L.pps_map_create.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
@@ -464,6 +467,37 @@ class Graph:
     def cov_block_last(self):
         """(device seconds around the two kernels, kernel launches) of the last cov_block"""
         s = C.c_double(); n = C.c_int(); self._ck(self.L.pps_cov_block_last(self.h, C.byref(s), C.byref(n))); return s.value, n.value
+
+    def assoc_gate(self, pose_id, meas4, sqrtinf_ut, plane_ids=None):
+        """Mahalanobis gate of plane association (pps_assoc_gate): meas4 (M x 4) plane measurements of pose `pose_id` in its sensor frame,
+        sqrtinf_ut (M x 6) their packed upper-triangular sqrt information, plane_ids the L candidate landmarks (None: all live planes in
+        insertion order).  Returns (d2, best): d2 (M x L) = r' (I + Jw Sigma Jw')^-1 r of every pairing at the estimate, Sigma from the
+        last cov_recover; best (M) = index into plane_ids of the smallest finite d2 per measurement (-1: none).  A pairing passes the
+        usual gate when d2 <= 7.815 (chi-square, 3 degrees of freedom, 0.95)."""
+        m = np.ascontiguousarray(meas4, dtype=np.float64).reshape(-1, 4)
+        w = np.ascontiguousarray(sqrtinf_ut, dtype=np.float64).reshape(-1, 6)
+        if len(m) != len(w):
+            raise ValueError("assoc_gate: one sqrtinf row per measurement")
+        ids = None if plane_ids is None else np.ascontiguousarray(plane_ids, dtype=np.int32).reshape(-1)
+        n_pl = self.stats()["n_planes"] if ids is None else len(ids)
+        d2 = np.full((len(m), n_pl), np.nan); best = np.full(len(m), -1, dtype=np.int32)
+        self._ck(self.L.pps_assoc_gate(self.h, int(pose_id), len(m), m.ctypes.data_as(_dp), w.ctypes.data_as(_dp), n_pl,
+                                       None if ids is None else ids.ctypes.data_as(_ip), d2.ctypes.data_as(_dp), best.ctypes.data_as(_ip)))
+        return d2, best
+
+    def assoc_gate_records(self):
+        """diagnostics: (Jw, r) of every candidate of the last assoc_gate as the kernel evaluated them -- Jw (M*L, 3, 9) over pose 6 | plane 3,
+        r (M*L, 3), candidates in row-major (measurement, plane) order; the values pps_eval_factor gives for the same factor"""
+        n = C.c_int64(0)
+        self._ck(self.L.pps_debug_assoc_gate_records(self.h, 0, None, C.byref(n)))
+        rec = np.zeros(n.value)
+        self._ck(self.L.pps_debug_assoc_gate_records(self.h, n.value, rec.ctypes.data_as(_dp), C.byref(n)))
+        rec = rec.reshape(-1, 30)
+        return np.concatenate([rec[:, :18].reshape(-1, 3, 6), rec[:, 18:27].reshape(-1, 3, 3)], axis=2), rec[:, 27:].copy()
+
+    def assoc_gate_last(self):
+        """(device seconds around the two kernels, kernel launches) of the last assoc_gate"""
+        s = C.c_double(); n = C.c_int(); self._ck(self.L.pps_assoc_gate_last(self.h, C.byref(s), C.byref(n))); return s.value, n.value
 
     def cov_last_times(self):
         """device seconds of the last cov_recover: (whole call, root -> leaves pass alone)"""

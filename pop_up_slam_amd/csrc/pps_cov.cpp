@@ -31,6 +31,7 @@ void cov_release(pps_graph* g) {
   if (g->cov_breq) (void)hipFree(g->cov_breq);
   if (g->cov_strip) (void)hipFree(g->cov_strip);
   if (g->cov_bout) (void)hipFree(g->cov_bout);
+  gate_release(g);
   for (hipEvent_t& e : g->cov_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   for (hipEvent_t& e : g->cov_bev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   g->cov_S = nullptr; g->cov_parent = nullptr; g->cov_req = nullptr; g->cov_out = nullptr;
@@ -40,29 +41,14 @@ void cov_release(pps_graph* g) {
   g->cov_valid = false;
 }
 
-template <class T>
-static int cov_reserve(pps_graph* g, T** buf, size_t* cap, size_t count) {
-  if (count <= *cap && *buf) return PPS_OK;
-  HIP_TRY(g, hipStreamSynchronize(g->stream));          // (nothing in flight reads the old buffer)
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr; *cap = 0;
-  const size_t want = std::max<size_t>(64, count + count / 4);
-  HIP_TRY(g, hipMalloc(reinterpret_cast<void**>(buf), want * sizeof(T)));
-  *cap = want;
-  return PPS_OK;
-}
-
-static bool cov_current(const pps_graph* g) {
+bool cov_current(const pps_graph* g) {
   return g->cov_valid && g->dev_ready && !g->topo_dirty && !g->analysis_stale && !g->host_values_newer && !g->meas_dirty &&
          g->cov_version == g->upload_version;
 }
 
-static const char* kNoRecovery = "no valid covariance recovery: call pps_cov_recover (a recovery ends with every change of the estimate, the measurements or the topology)";
+const char* const kNoRecovery = "no valid covariance recovery: call pps_cov_recover (a recovery ends with every change of the estimate, the measurements or the topology)";
 
-// where a node's scalars sit in the elimination order: its front and the local index of its first pivot
-struct CovNode { int front, local, dim, epos, voff; };
-
-static int cov_node(pps_graph* g, int id, CovNode* out) {
+int cov_node(pps_graph* g, int id, CovNode* out) {
   if (id < 0 || id >= (int)g->nodes.size() || g->nodes[id].deleted) return fail(g, PPS_EINVAL, "covariance: unknown node id " + std::to_string(id));
   out->dim = g->nodes[id].type == NODE_POSE ? 6 : 3;
   out->front = -1; out->local = out->epos = out->voff = 0;
@@ -70,7 +56,7 @@ static int cov_node(pps_graph* g, int id, CovNode* out) {
 }
 
 // (only with a current recovery: the analysis is the one the tables were built from)
-static int cov_locate(pps_graph* g, int id, CovNode* n) {
+int cov_locate(pps_graph* g, int id, CovNode* n) {
   const Analysis& A = g->an;
   const int c = g->nodes[id].compact;
   if (c < 0 || c >= A.n_nodes) return fail(g, PPS_ESTATE, "covariance: node " + std::to_string(id) + " is not part of the analysed graph");
@@ -115,6 +101,37 @@ static int cov_fetch(pps_graph* g, const std::vector<CovReq>& req, size_t n_out,
   HIP_TRY(g, hipMemcpyAsync(host, g->cov_out, n_out * sizeof(double), hipMemcpyDeviceToHost, g->stream));
   HIP_TRY(g, hipStreamSynchronize(g->stream));
   return PPS_OK;
+}
+
+// paths (leaf -> root) and strips of a list of distinct, checked nodes; K = the longest path of the query in pivots
+int cov_build_walks(pps_graph* g, const std::vector<int>& ids, std::vector<CovNode>& nd, CovWalks* out) {
+  const Analysis& A = g->an;
+  const int nw = (int)ids.size();
+  out->K = 0;
+  for (int w = 0; w < nw; w++) {
+    const int rc = cov_locate(g, ids[w], &nd[w]); if (rc != PPS_OK) return rc;
+    out->K = std::max(out->K, g->cov_rootlen[nd[w].front]);
+  }
+  out->walks.assign((size_t)nw, CovWalk{});
+  out->steps.clear();
+  out->step_end.assign((size_t)nw, 0);
+  out->n_strip = 0;
+  for (int w = 0; w < nw; w++) {
+    out->walks[w] = CovWalk{out->n_strip, (int)out->steps.size(), 0, nd[w].local, nd[w].dim};
+    for (int s = nd[w].front; s >= 0; s = A.f_parent[s]) out->steps.push_back(CovStep{s, out->K - g->cov_rootlen[s]});
+    out->walks[w].n_steps = (int)out->steps.size() - out->walks[w].step0;
+    out->step_end[w] = (int)out->steps.size();
+    out->n_strip += (long long)out->K * nd[w].dim;
+  }
+  return PPS_OK;
+}
+
+// the pivots two paths have in common are a suffix of both
+int cov_common_pivots(const pps_graph* g, const CovWalks& cw, int a, int b) {
+  int len = 0;
+  for (int i = cw.step_end[a] - 1, j = cw.step_end[b] - 1; i >= cw.walks[a].step0 && j >= cw.walks[b].step0 && cw.steps[i].front == cw.steps[j].front; i--, j--)
+    len += g->an.f_p[cw.steps[i].front];
+  return len;
 }
 
 // node -> front tables of the current analysis; checks what the gather relies on: a node's scalars are consecutive pivots of ONE front
@@ -370,31 +387,14 @@ int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols
   if (joint) ci = ri;
   if (!cov_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
   if (nr == 0 || nc == 0) return PPS_OK;
-  const Analysis& A = g->an;
   const int nw = (int)ids.size();
-  // paths (leaf -> root) and strips; K = the longest path of the query in pivots
-  int K = 0;
-  for (int w = 0; w < nw; w++) {
-    const int rc = cov_locate(g, ids[w], &nd[w]); if (rc != PPS_OK) return rc;
-    K = std::max(K, g->cov_rootlen[nd[w].front]);
-  }
-  std::vector<CovWalk> walks((size_t)nw);
-  std::vector<CovStep> steps;
-  std::vector<int> step_end((size_t)nw);
-  long long n_strip = 0;
-  for (int w = 0; w < nw; w++) {
-    walks[w] = CovWalk{n_strip, (int)steps.size(), 0, nd[w].local, nd[w].dim};
-    for (int s = nd[w].front; s >= 0; s = A.f_parent[s]) steps.push_back(CovStep{s, K - g->cov_rootlen[s]});
-    walks[w].n_steps = (int)steps.size() - walks[w].step0;
-    step_end[w] = (int)steps.size();
-    n_strip += (long long)K * nd[w].dim;
-  }
-  // blocks: the pivots two paths have in common are a suffix of both
-  auto common = [&](int a, int b) {
-    int len = 0;
-    for (int i = step_end[a] - 1, j = step_end[b] - 1; i >= walks[a].step0 && j >= walks[b].step0 && steps[i].front == steps[j].front; i--, j--) len += A.f_p[steps[i].front];
-    return len;
-  };
+  CovWalks cw;
+  { const int rc = cov_build_walks(g, ids, nd, &cw); if (rc != PPS_OK) return rc; }
+  const int K = cw.K;
+  const long long n_strip = cw.n_strip;
+  const std::vector<CovWalk>& walks = cw.walks;
+  const std::vector<CovStep>& steps = cw.steps;
+  auto common = [&](int a, int b) { return cov_common_pivots(g, cw, a, b); };
   std::vector<int> roff((size_t)nr + 1, 0), coff((size_t)nc + 1, 0);
   for (int i = 0; i < nr; i++) roff[i + 1] = roff[i] + nd[ri[i]].dim;
   for (int j = 0; j < nc; j++) coff[j + 1] = coff[j] + nd[ci[j]].dim;

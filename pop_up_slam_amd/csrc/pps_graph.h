@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/pps.h"
+#include "pps_cov.h"
 #include "pps_device.h"
 #include "pps_geom.h"
 #include "pps_lm.h"
@@ -214,6 +215,13 @@ struct pps_graph {
   double* cov_bout = nullptr; size_t cov_bout_cap = 0; bool cov_bout_clean = false;
   hipEvent_t cov_bev[2] = {nullptr, nullptr};
   double cov_block_sec = 0; int cov_block_launches = 0;   // the two kernels of the last query: device seconds, launches
+  // pps_assoc_gate (pps_gate.cpp): result of a call on the device ([status | d2 | best], the status word zero between calls) and one
+  // ticket per measurement (zero between calls); the request and the strips share cov_breq / cov_strip with pps_cov_block
+  double* gate_out = nullptr; size_t gate_out_cap = 0; bool gate_clean = false;
+  unsigned int* gate_ticket = nullptr; size_t gate_ticket_cap = 0;
+  hipEvent_t gate_ev[2] = {nullptr, nullptr};
+  double gate_sec = 0; int gate_launches = 0;             // the two kernels of the last call: device seconds, launches
+  double* gate_rec = nullptr; size_t gate_rec_cap = 0; size_t gate_rec_n = 0;   // [Jp | Jl | r] per candidate of the last call (pps_debug_assoc_gate_records)
   // stats / trace
   pps_stats stats{};
   std::vector<double> tr_lambda, tr_chi2;
@@ -270,6 +278,30 @@ inline LmSink lm_sink(pps_graph* g, bool verbose) { return LmSink{&g->props, &g-
 // ---- pps_cov.cpp ----
 inline void cov_invalidate(pps_graph* g) { g->cov_valid = false; }   // estimate, measurements or topology are about to change
 void cov_release(pps_graph* g);                // pps_graph_destroy: the recovery's own device buffers
+bool cov_current(const pps_graph* g);          // is there a recovery that belongs to the estimate, the measurements and the topology as they are?
+extern const char* const kNoRecovery;          // the text of the PPS_ESTATE answer when there is none
+// where a node's scalars sit in the elimination order: its front and the local index of its first pivot
+struct CovNode { int front, local, dim, epos, voff; };
+int cov_node(pps_graph* g, int id, CovNode* out);      // id check (PPS_EINVAL) + dim; the rest by cov_locate, with a current recovery only
+int cov_locate(pps_graph* g, int id, CovNode* n);
+// the walks of a query as k_cov_path takes them (pps_cov.h), shared by pps_cov_block and pps_assoc_gate
+struct CovWalks { std::vector<pps::CovWalk> walks; std::vector<pps::CovStep> steps; std::vector<int> step_end; int K = 0; long long n_strip = 0; };
+int cov_build_walks(pps_graph* g, const std::vector<int>& ids, std::vector<CovNode>& nd, CovWalks* out);      // locates the nodes (cov_locate), too
+int cov_common_pivots(const pps_graph* g, const CovWalks& cw, int a, int b);                                    // walks a, b: pivots of their common ancestors
+// a device buffer of one of the covariance calls, grown by a quarter when it is too small
+template <class T>
+int cov_reserve(pps_graph* g, T** buf, size_t* cap, size_t count) {
+  if (count <= *cap && *buf) return PPS_OK;
+  HIP_TRY(g, hipStreamSynchronize(g->stream));          // (nothing in flight reads the old buffer)
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr; *cap = 0;
+  const size_t want = std::max<size_t>(64, count + count / 4);
+  HIP_TRY(g, hipMalloc(reinterpret_cast<void**>(buf), want * sizeof(T)));
+  *cap = want;
+  return PPS_OK;
+}
+// ---- pps_gate.cpp ----
+void gate_release(pps_graph* g);               // (from cov_release)
 // ---- pps_api.cpp ----
 void report_front_trace(pps_graph* g);        // PPS_TRACE: the per-front cycle counters of the last solve -> stderr
 
