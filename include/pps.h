@@ -208,6 +208,31 @@ int pps_assoc_gate_last(const pps_graph* g, double* kernel_sec, int* launches);
  * copied when rec is NULL or cap is smaller.  PPS_ESTATE before the first successful gate call of the handle. */
 int pps_debug_assoc_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed);
 
+/* ---- robust cost functions: Slam::set_cost_function (Slam.h; Factor::error, Factor.h:67-77; isam/robust.h) ------
+ * With a cost function set, every evaluation of a factor's error replaces each whitened component by
+ *     r_i <- sign(r_i) sqrt(rho(r_i)),  sign(0) = +1
+ * -- in all 2 n + 1 evaluations of the central differences (PPS_JAC_NUMERIC differentiates through rho), in weighted_errors and in
+ * chi2 = sum rho(r_i).  PPS_JAC_ANALYTIC scales row i of the whitened J by phi'(r_i) = rho'(r_i) / (2 sqrt(rho(r_i))), at r_i = 0 by its limit.
+ * LM itself does not change.  A function pointer cannot cross to the device: the cost is a kind and one parameter b.
+ *   PPS_COST_HUBER         rho = d^2 for |d| < b, else 2 b |d| - b^2
+ *   PPS_COST_PSEUDO_HUBER  rho = 2 b^2 (sqrt(1 + d^2 / b^2) - 1)            (iSAM's command line: -R)
+ *   PPS_COST_CAUCHY        rho = log(pi / b) * log(1 + d^2 / b^2) -- a product of two logarithms, as the reference writes it (a quirk that
+ *                          is kept); positive only for b < pi
+ * Not offered (csrc/pps_cost.h gives the reasons): Blake-Zisserman (rho(0) < 0), corrupted Gaussian (rho(0) > 0), L1 (infinite slope at 0).
+ * With a cost set, pps_batch_optimize, pps_update, pps_chi2, pps_eval_factor (the robustified r and J) and pps_cov_recover use the
+ * robustified error, for every factor type (pps_add_plane_obs2 included), both Jacobian modes, band and dense-front graphs alike: K1 and
+ * the chi2 sweeps run in kernels of their own (csrc/pps_robust.hip), everything behind them is unchanged.  pps_batch_optimize then takes
+ * the one-step-at-a-time LM loop whatever PPS_NO_DUAL says.  PPS_COST_NONE returns the handle to exactly the launches it took before.
+ *   PPS_EINVAL  NULL handle; unknown kind; b not finite or <= 0; PPS_COST_CAUCHY with b >= pi.  b is ignored for PPS_COST_NONE.
+ * The call counts as a pps_set_*: a valid covariance recovery ends.  While a cost is set, pps_multi_create over the graph (and
+ * pps_multi_optimize, if it was set later) and pps_assoc_gate return PPS_ESTATE with a text that names the cost function -- they have no
+ * robustified form --; the handle stays usable.  pps_graph_save does not write the cost function and pps_graph_load starts with
+ * PPS_COST_NONE (the reference's file format has no place for it: Slam::save writes nodes and factors).
+ * Found by symbol lookup, like the pps_cov_* calls; PPS_VERSION was not bumped. */
+enum pps_cost_kind { PPS_COST_NONE = 0, PPS_COST_HUBER = 1, PPS_COST_PSEUDO_HUBER = 2, PPS_COST_CAUCHY = 3 };
+int pps_set_cost_function(pps_graph* g, int kind, double b);
+int pps_get_cost_function(const pps_graph* g, int* kind, double* b);   /* PPS_COST_NONE reports b = 1 */
+
 /* ---- many graphs side by side (BASELINE config 4 on one device; north_star reports graphs/sec) ----------------
  * One C2-size LM solve is a dependency chain that occupies a few dozen of the 256 CUs.  pps_multi runs
  * Optimizer::levenberg_marquardt (Optimizer.cpp:371-467) on n independent graphs in rounds: every kernel of an LM

@@ -494,6 +494,13 @@ public:
   int device = 0;
 };
 
+}  // namespace isam
+namespace pps {
+// the cost functions of Slam::set_cost_function (isam/robust.h restated on the device; include/pps.h: enum pps_cost_kind)
+enum class Cost { None = PPS_COST_NONE, Huber = PPS_COST_HUBER, PseudoHuber = PPS_COST_PSEUDO_HUBER, Cauchy = PPS_COST_CAUCHY };
+}  // namespace pps
+namespace isam {
+
 class Slam {
   pps_graph* _g = nullptr;
   Properties _prop;
@@ -532,6 +539,9 @@ public:
   }
   void remove_node(Node* node) { detail::check(pps_remove_node(_g, node->_id), _g, "pps_remove_node"); node->_id = -1; node->_slam = nullptr; _num_nodes--; }
   void remove_factor(Factor* factor) { detail::check(pps_remove_factor(_g, factor->_id), _g, "pps_remove_factor"); factor->_id = -1; _num_factors--; }
+  // Slam::set_cost_function (Slam.h): a kind and its parameter instead of a function pointer, which cannot cross to the device.  Every
+  // factor's whitened error becomes sign(r) sqrt(rho(r)) (Factor::error, Factor.h:67-77); pps::Cost::None switches it off again.
+  void set_cost_function(pps::Cost kind, double b = 1.0) { detail::check(pps_set_cost_function(_g, static_cast<int>(kind), b), _g, "pps_set_cost_function"); }
   void update() { detail::check(pps_update(_g), _g, "pps_update"); }                         // Slam.cpp:157-196
   int batch_optimization() { int it = 0; detail::check(pps_batch_optimize(_g, &it), _g, "pps_batch_optimize"); return it; }   // :198-210
   double chi2() { double c = 0; detail::check(pps_chi2(_g, &c), _g, "pps_chi2"); return c; }   // :266-268

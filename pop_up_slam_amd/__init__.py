@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("PPS_LIB") or os.path.join(_HERE, "libpps.so")
 
 PPS_OK, PPS_EINVAL, PPS_ENOTPD, PPS_EHIP, PPS_ENOMEM, PPS_ESTATE = range(6)
 JAC_NUMERIC, JAC_ANALYTIC = 0, 1
+COST_NONE, COST_HUBER, COST_PSEUDO_HUBER, COST_CAUCHY = range(4)      # enum pps_cost_kind
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -135,6 +136,7 @@ SYMBOLS = [
     "pps_map_default_select", "pps_map_create", "pps_map_destroy", "pps_map_last_error", "pps_map_add_frame", "pps_map_redirect",
     "pps_map_info", "pps_map_chunks", "pps_map_built_chunks", "pps_map_select_host", "pps_map_build", "pps_map_download",
     "pps_map_last_times",
+    "pps_set_cost_function", "pps_get_cost_function",
 ]
 
 
@@ -259,6 +261,8 @@ def lib():
         L.pps_assoc_gate.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip, _dp, _ip]
         L.pps_assoc_gate_last.argtypes = [C.c_void_p, _dp, _ip]
         L.pps_debug_assoc_gate_records.argtypes = [C.c_void_p, C.c_int64, _dp, C.POINTER(C.c_int64)]
+        L.pps_set_cost_function.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.pps_get_cost_function.argtypes = [C.c_void_p, _ip, _dp]
         _i32p = C.POINTER(C.c_int32)
         L.pps_map_default_select.argtypes = [C.POINTER(PpsMapSelect), C.c_int]; L.pps_map_default_select.restype = None
         L.pps_map_create.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
@@ -395,6 +399,18 @@ class Graph:
 
     def chi2(self):
         v = C.c_double(); self._ck(self.L.pps_chi2(self.h, C.byref(v))); return v.value
+
+    # ---- robust cost function (Slam::set_cost_function) ----
+    def set_cost_function(self, kind, b=1.0):
+        """COST_HUBER / COST_PSEUDO_HUBER / COST_CAUCHY with parameter b, or COST_NONE: every whitened residual component becomes
+        sign(r) sqrt(rho(r)) in batch_optimize, update, chi2, eval_factor and cov_recover (pps_set_cost_function, include/pps.h)."""
+        self._ck(self.L.pps_set_cost_function(self.h, int(kind), float(b)))
+
+    def cost_function(self):
+        """(kind, b) as set; (COST_NONE, 1.0) on a handle that has none"""
+        k = C.c_int(); b = C.c_double()
+        self._ck(self.L.pps_get_cost_function(self.h, C.byref(k), C.byref(b)))
+        return k.value, b.value
 
     # ---- marginal covariances (Slam::covariances() -> isam::Covariances) ----
     def _node_dims(self, ids):
@@ -934,7 +950,9 @@ class Multi:
         self.h = C.c_void_p()
         rc = self.L.pps_multi_create(len(self.graphs), arr, C.byref(self.h))
         if rc != 0:
-            raise PpsError(rc, "pps_multi_create")
+            # (PPS_ESTATE: a member has a robust cost function set; the refusal's text is on that graph's handle)
+            why = [g.L.pps_last_error(g.h).decode() for g in self.graphs if rc == PPS_ESTATE and g.cost_function()[0] != COST_NONE][:1]
+            raise PpsError(rc, "pps_multi_create" + "".join(": " + w for w in why))
 
     def close(self):
         if getattr(self, "h", None):

@@ -186,6 +186,25 @@ int pps_set_props(pps_graph* g, const pps_props* p) {
   return PPS_OK;
 }
 
+// Slam::set_cost_function: an enumerated kind + one parameter instead of a function pointer (pps_cost.h)
+int pps_set_cost_function(pps_graph* g, int kind, double b) {
+  if (!g) return PPS_EINVAL;
+  if (kind != PPS_COST_NONE && kind != PPS_COST_HUBER && kind != PPS_COST_PSEUDO_HUBER && kind != PPS_COST_CAUCHY)
+    return fail(g, PPS_EINVAL, "set_cost_function: unknown kind " + std::to_string(kind));
+  if (kind != PPS_COST_NONE) {
+    if (!std::isfinite(b) || !(b > 0.0)) return fail(g, PPS_EINVAL, "set_cost_function: b must be a finite number > 0");
+    if (kind == PPS_COST_CAUCHY && b >= kPi) return fail(g, PPS_EINVAL, "set_cost_function: the Cauchy cost log(pi / b) log(1 + d^2 / b^2) is positive only for b < pi");
+  }
+  cov_invalidate(g);                     // (a recovery belongs to the error function it was linearised with)
+  g->cost = kind == PPS_COST_NONE ? CostFn{} : make_cost(kind, b);
+  return PPS_OK;
+}
+int pps_get_cost_function(const pps_graph* g, int* kind, double* b) {
+  if (!g || !kind || !b) return PPS_EINVAL;
+  *kind = g->cost.kind; *b = g->cost.b;
+  return PPS_OK;
+}
+
 static int add_node(pps_graph* g, int type, const double* v, int nv, int* id) {
   if (!g || !v) return PPS_EINVAL;
   for (int k = 0; k < nv; k++) if (!std::isfinite(v[k])) return fail(g, PPS_EINVAL, "non-finite node value");
@@ -444,7 +463,7 @@ int pps_eval_factor(pps_graph* g, int fid, int mode, double* J, double* r) {
   int rc = prepare_solve(g);
   if (rc != PPS_OK) return rc;
   rc = linpoint_from_estimate(g); if (rc != PPS_OK) return rc;
-  HIP_TRY(g, launch_linearize(g->dev, mode, true, g->stream));
+  HIP_TRY(g, lin_launch(g, mode, true));      // (with a cost function: the robustified r and J, as Factor::error / jacobian give them)
   const HostFactor& f = g->factors[fid];
   const int m = kFDim[f.type];
   const int da = g->nodes[f.a].type == NODE_POSE ? 6 : 3;

@@ -205,7 +205,7 @@ static int cov_recover_impl(pps_graph* g) {
   HIP_TRY(g, hipEventRecord(g->cov_ev[0], g->stream));
   // jacobian() at the ESTIMATE (the linearisation point stays what it is), H blocks, factorisation with lambda = 0: one launch per band
   // stage, the form whose panels all pass through d.L.  The update matrices in d.U are dead once their parents are assembled.
-  HIP_TRY(g, launch_linearize(d, g->props.jacobian_mode, true, g->stream));
+  HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, true));      // (the robustified J with a cost function set)
   HIP_TRY(g, launch_hblocks(d, g->stream, nullptr, k1_products(d, g->props.jacobian_mode)));
   for (int st = 0; st < A.n_stages; st++)
     HIP_TRY(g, launch_band_factor(d, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_factor[st], A.stage_max_front[st], 0.0, g->stream));

@@ -15,6 +15,8 @@
 
 #include <cstdint>
 
+#include "pps_cost.h"
+
 namespace pps {
 
 struct DevGraph {
@@ -252,6 +254,12 @@ hipError_t launch_chi2(const DevGraph& d, bool at_estimate, double* host_result,
 hipError_t launch_clear_status(const DevGraph& d, hipStream_t st);
 // chi2 of the one-step loop's trial, after launch_retract_trial: evaluated at est (+) delta on the spot (pps_k4.hip)
 hipError_t launch_chi2_trial(const DevGraph& d, double* host_result, double seq, hipStream_t st);
+// A handle with a robust cost function (pps_set_cost_function) takes these instead of launch_linearize / launch_chi2 / launch_chi2_trial
+// (pps_robust.hip: kernels of their own, the cost is a kernel argument); they write the same records, K2 / K3 / the retraction follow unchanged.
+hipError_t launch_linearize_robust(const DevGraph& d, const CostFn& cost, int mode, bool at_estimate, hipStream_t st, hipEvent_t ev0 = nullptr,
+                                   hipEvent_t ev1 = nullptr);
+hipError_t launch_chi2_robust(const DevGraph& d, const CostFn& cost, bool at_estimate, double* host_result, double seq, hipStream_t st);
+hipError_t launch_chi2_trial_robust(const DevGraph& d, const CostFn& cost, double* host_result, double seq, hipStream_t st);
 
 // dense-front form (pps_dense.hip): fronts of hundreds of rows, every step spread over many workgroups.
 // L must be zeroed before launch_dense_hpush; levels run leaves -> root (factor) and root -> leaves (solve).

@@ -51,6 +51,8 @@ int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, c
   if (!g || !meas4 || !sqrtinf_ut || !d2 || n_meas < 0 || (plane_ids && n_planes < 0)) return PPS_EINVAL;
   if (!live_node(g, pose_id, NODE_POSE)) return fail(g, PPS_EINVAL, "association gate: node " + std::to_string(pose_id) + " is not a live pose");
   if (n_meas > 65535) return fail(g, PPS_EINVAL, "association gate: more than 65535 measurements in one call");
+  // the candidates' r and Jw are the squared-error ones; with a cost function the recovered covariance is that of the robustified system
+  if (robust(g)) return fail(g, PPS_ESTATE, "association gate: a robust cost function is set (pps_set_cost_function); the gate has no robustified form -- set PPS_COST_NONE and recover again");
   std::vector<int> all;
   if (!plane_ids) {
     for (size_t i = 0; i < g->nodes.size(); i++) if (!g->nodes[i].deleted && g->nodes[i].type == NODE_PLANE) all.push_back((int)i);

@@ -82,6 +82,9 @@ struct pps_graph {
   pps::Analysis an;
   pps::AnalysisParams aprm;
   pps::Switches sw;                // the PPS_* environment switches as they were when the handle was created
+  // robust cost function (pps_set_cost_function; pps_cost.h).  COST_NONE: every call takes the launches it always took.  Otherwise K1 and the
+  // chi2 sweeps go through the kernels of pps_robust.hip (lin_launch / chi2_launch / chi2_trial_launch below) and LM runs one step at a time.
+  pps::CostFn cost;
   pps::AnalysisCache* acache = nullptr;   // what the last analysis left for the next one (frame loops)
   std::vector<int> pose_ids, plane_ids;   // slot -> node id
   std::vector<int> fslot_ids[4];          // per type: slot -> factor id
@@ -275,6 +278,20 @@ int read_result(pps_graph* g, bool at_estimate, double* chi2, double* dnorm, boo
 void begin_solve(pps_graph* g);                // an LM solve starts: the last one's stats and trace go
 void abandon_device_copy(pps_graph* g);
 inline LmSink lm_sink(pps_graph* g, bool verbose) { return LmSink{&g->props, &g->tr_lambda, &g->tr_chi2, &g->tr_acc, &g->stats, verbose}; }
+// the one place where a handle's cost function chooses the kernels: K1 and the two chi2 sweeps (everything else consumes J, r and delta)
+inline bool robust(const pps_graph* g) { return g->cost.kind != COST_NONE; }
+inline hipError_t lin_launch(pps_graph* g, int mode, bool at_estimate, const LinGuard* guard = nullptr, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+  if (robust(g)) return launch_linearize_robust(g->dev, g->cost, mode, at_estimate, g->stream, ev0, ev1);      // (no guard: the one-step loop does not speculate)
+  return launch_linearize(g->dev, mode, at_estimate, g->stream, guard, ev0, ev1);
+}
+inline hipError_t chi2_launch(pps_graph* g, bool at_estimate, double* host_result, double seq) {
+  if (robust(g)) return launch_chi2_robust(g->dev, g->cost, at_estimate, host_result, seq, g->stream);
+  return launch_chi2(g->dev, at_estimate, host_result, seq, g->stream);
+}
+inline hipError_t chi2_trial_launch(pps_graph* g, double* host_result, double seq) {
+  if (robust(g)) return launch_chi2_trial_robust(g->dev, g->cost, host_result, seq, g->stream);
+  return launch_chi2_trial(g->dev, host_result, seq, g->stream);
+}
 // ---- pps_cov.cpp ----
 inline void cov_invalidate(pps_graph* g) { g->cov_valid = false; }   // estimate, measurements or topology are about to change
 void cov_release(pps_graph* g);                // pps_graph_destroy: the recovery's own device buffers

@@ -6,6 +6,7 @@ using namespace pps_impl;
 
 extern "C" {
 
+// (a robust cost function -- pps_set_cost_function -- is not written: the format holds nodes and factors; a loaded handle starts with PPS_COST_NONE)
 int pps_graph_save(pps_graph* g, const char* path, int precision) {
   if (!g || !path) return PPS_EINVAL;
   if (g->dev_values_newer) { int rc = download_state(g); if (rc != PPS_OK) return rc; }

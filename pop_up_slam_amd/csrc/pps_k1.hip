@@ -15,8 +15,6 @@ hipError_t launch_linearize_lanes(const DevGraph& d, const double* pose, const d
 hipError_t launch_sweep_bench_lanes(const DevGraph& d, int replicas, double* Jbig, int part, hipStream_t st);
 hipError_t launch_batch_linearize_lanes(const BatchArgs& a, const BatchGeom& g, hipStream_t st);
 
-constexpr int kObsNumericWaves = 2;      // waves per SIMD of the numeric plane-observation launch of the thread form (see k_linearize_obs_numeric)
-
 template <int MODE, int PART>
 __global__ __launch_bounds__(kLinBlock) void k_linearize(DevGraph d, const double* __restrict__ pose,
                                                           const double* __restrict__ plane, int nb_obs, int nb_odo,

@@ -10,6 +10,7 @@
 namespace pps {
 
 constexpr int kLinBlock = 128;
+constexpr int kObsNumericWaves = 2;      // waves per SIMD of the numeric plane-observation launch of the thread form, plain (k_linearize_obs_numeric, pps_k1.hip: the measurements) and robust (pps_robust.hip)
 
 // A wave's 64 factor records (N doubles each, contiguous in global memory) are staged through LDS
 // (row stride N+1: conflict-free) and written back as one contiguous 64*N-double stream with 16-byte
@@ -88,10 +89,11 @@ __device__ __forceinline__ void obs_products(const double (&out)[30], double (&l
 // DIRECT (every launch of the solver; off in the sweep benchmark): a plane observation that is the only contribution of its (pose, plane) block writes that H
 // block itself -- the product of its own two Jacobian blocks, summed in the order the H-block kernel uses -- into H and into
 // the front-ordered copy; kb_hblocks_t then skips those segments (60 % of the segments of a C2 graph).
-template <int MODE, int PART, bool DIRECT = false>
+// ROBUST (the kernels of pps_robust.hip; off everywhere else): the factor bodies of pps_lin.h robustify every evaluation with `cost`.
+template <int MODE, int PART, bool DIRECT = false, bool ROBUST = false>
 __device__ __forceinline__ void body_linearize(const DevGraph& d, const double* __restrict__ pose,
                                                const double* __restrict__ plane, int nb_obs, int nb_odo, int nb_pp, int bx,
-                                               double* __restrict__ lin_lds) {
+                                               double* __restrict__ lin_lds, const CostFn& cost = CostFn{}) {
   double* lds_wave = lin_lds + (size_t)(threadIdx.x >> 6) * 64 * (PART == 0 ? 31 : 79);
   int b = bx + (PART == 0 ? 0 : nb_obs);
   if (b < nb_obs) {
@@ -102,7 +104,7 @@ __device__ __forceinline__ void body_linearize(const DevGraph& d, const double* 
     load_plane(plane, d.plane_ld, d.obs_plane[i], pl);
     load_soa<4>(d.obs_meas, d.obs_ld, i, ms);
     load_soa<6>(d.obs_w, d.obs_ld, i, w);
-    lin_plane_obs<MODE>(pz, pl, ms, w, out);
+    lin_plane_obs<MODE, ROBUST>(pz, pl, ms, w, out, cost);
     if (DIRECT) {
       // Round 5: the 18 entries of a direct block leave through the LDS like the Jacobian records.  Written straight from the lanes, every
       // store instruction was 64 pieces of 8 bytes in 64 different lines -- the PMC counters showed 1.2 KB written per observation for 528
@@ -163,11 +165,11 @@ __device__ __forceinline__ void body_linearize(const DevGraph& d, const double* 
     load_soa<21>(d.odo_w, d.odo_ld, i, w);
     if (MODE == 1) {
       double out[78];
-      lin_odometry<MODE>(p1, p2, ms, w, out);
+      lin_odometry<MODE, ROBUST>(p1, p2, ms, w, out, cost);
       if (i0 < d.n_odo) store_records_coalesced<78>(out, d.J + d.joff_odo + (size_t)i0 * 78, min(64, d.n_odo - i0), lds_wave);
     } else {
       // the central-difference loops stay rolled (24 residual evaluations): the record is built in LDS, not in registers
-      lin_odometry<MODE>(p1, p2, ms, w, lds_wave + (threadIdx.x & 63) * 79);
+      lin_odometry<MODE, ROBUST>(p1, p2, ms, w, lds_wave + (threadIdx.x & 63) * 79, cost);
       if (i0 < d.n_odo) flush_records_coalesced<78>(d.J + d.joff_odo + (size_t)i0 * 78, min(64, d.n_odo - i0), lds_wave);
     }
     return;
@@ -180,7 +182,7 @@ __device__ __forceinline__ void body_linearize(const DevGraph& d, const double* 
     load_pose(pose, d.pose_ld, d.pp_pose[i], pz);
     load_soa<6>(d.pp_meas, d.pp_ld, i, ms);
     load_soa<21>(d.pp_w, d.pp_ld, i, w);
-    lin_pose_prior<MODE>(pz, ms, w, d.J + d.joff_pp + (size_t)i * 42);
+    lin_pose_prior<MODE, ROBUST>(pz, ms, w, d.J + d.joff_pp + (size_t)i * 42, cost);
     return;
   }
   b -= nb_pp;
@@ -191,7 +193,7 @@ __device__ __forceinline__ void body_linearize(const DevGraph& d, const double* 
     load_plane(plane, d.plane_ld, d.lp_plane[i], pl);
     load_soa<4>(d.lp_meas, d.lp_ld, i, ms);
     load_soa<6>(d.lp_w, d.lp_ld, i, w);
-    lin_plane_prior<MODE>(pl, ms, w, d.J + d.joff_lp + (size_t)i * 12);
+    lin_plane_prior<MODE, ROBUST>(pl, ms, w, d.J + d.joff_lp + (size_t)i * 12, cost);
   }
 }
 
@@ -439,8 +441,9 @@ constexpr int kLaneParallelMaxFactors = 200000;
 
 // Pose3d_Plane3d_Factor2 edges (slots [n_obs_fixed, n_obs)): central differences in both Jacobian modes -- the
 // measurement moves with the pose perturbation (the reference differentiates it numerically too).
+template <bool ROBUST = false>
 __device__ __forceinline__ void body_linearize_repop(const DevGraph& d, const double* __restrict__ pose,
-                                                     const double* __restrict__ plane, int bx, double* __restrict__ lds_wave) {
+                                                     const double* __restrict__ plane, int bx, double* __restrict__ lds_wave, const CostFn& cost = CostFn{}) {
   const int n2 = d.n_obs - d.n_obs_fixed;
   const int k0 = bx * 64;                                             // first edge of this wave (one wave per workgroup)
   if (k0 >= n2) return;
@@ -453,22 +456,22 @@ __device__ __forceinline__ void body_linearize_repop(const DevGraph& d, const do
   load_soa<6>(d.obs_ray, n2, k, ray);
   load_soa<6>(d.obs_w, d.obs_ld, i, w);
   res_plane_obs2(pz, pl, ray, e);
-  whiten<3>(w, e, r);
+  whiten<3>(w, e, r); if (ROBUST) robustify<3>(cost, r);
   const double inv2e = 1.0 / (kNumDiffEps + kNumDiffEps);
   for (int j = 0; j < 6; j++) {
     double dl[6] = {0, 0, 0, 0, 0, 0}, pp[7], yp[3], ym[3];
     dl[j] = kNumDiffEps;
-    pose_exmap(pz, dl, pp); res_plane_obs2(pp, pl, ray, e); whiten<3>(w, e, yp);
+    pose_exmap(pz, dl, pp); res_plane_obs2(pp, pl, ray, e); whiten<3>(w, e, yp); if (ROBUST) robustify<3>(cost, yp);
     dl[j] = -kNumDiffEps;
-    pose_exmap(pz, dl, pp); res_plane_obs2(pp, pl, ray, e); whiten<3>(w, e, ym);
+    pose_exmap(pz, dl, pp); res_plane_obs2(pp, pl, ray, e); whiten<3>(w, e, ym); if (ROBUST) robustify<3>(cost, ym);
     for (int q = 0; q < 3; q++) out[q * 6 + j] = (yp[q] - ym[q]) * inv2e;
   }
   for (int j = 0; j < 3; j++) {
     double dl[3] = {0, 0, 0}, pp[4], yp[3], ym[3];
     dl[j] = kNumDiffEps;
-    plane_exmap(pl, dl, pp); res_plane_obs2(pz, pp, ray, e); whiten<3>(w, e, yp);
+    plane_exmap(pl, dl, pp); res_plane_obs2(pz, pp, ray, e); whiten<3>(w, e, yp); if (ROBUST) robustify<3>(cost, yp);
     dl[j] = -kNumDiffEps;
-    plane_exmap(pl, dl, pp); res_plane_obs2(pz, pp, ray, e); whiten<3>(w, e, ym);
+    plane_exmap(pl, dl, pp); res_plane_obs2(pz, pp, ray, e); whiten<3>(w, e, ym); if (ROBUST) robustify<3>(cost, ym);
     for (int q = 0; q < 3; q++) out[18 + q * 3 + j] = (yp[q] - ym[q]) * inv2e;
   }
   for (int q = 0; q < 3; q++) out[27 + q] = r[q];

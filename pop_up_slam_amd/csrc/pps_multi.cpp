@@ -46,6 +46,9 @@ int pps_multi_create(int n, pps_graph* const* graphs, pps_multi** out) {
     if (graphs[i]->props.device != graphs[0]->props.device) return PPS_EINVAL;
     for (int j = 0; j < i; j++) if (graphs[j] == graphs[i]) return PPS_EINVAL;
   }
+  // the batched kernels evaluate the squared error only: a handle with a robust cost function is solved through pps_batch_optimize
+  for (int i = 0; i < n; i++)
+    if (robust(graphs[i])) return fail(graphs[i], PPS_ESTATE, "pps_multi: graph " + std::to_string(i) + " has a robust cost function set (pps_set_cost_function); the batched solve has no robust kernels -- solve it through its own handle, or set PPS_COST_NONE");
   pps_multi* m = new (std::nothrow) pps_multi();
   if (!m) return PPS_ENOMEM;
   m->gs.assign(graphs, graphs + n);
@@ -179,6 +182,7 @@ static int check_graphs(pps_multi* m, int* mode_out, int* max_stages_out) {
     if (rc != PPS_OK) return mfail(m, rc, "graph " + std::to_string(i) + ": " + g->err);
     if (!g->use_band) return mfail(m, PPS_ESTATE, "graph " + std::to_string(i) + " has fronts beyond the wave-per-front kernels (loop closures): solve it through its own handle");
     if (g->n_live_factors == 0) return mfail(m, PPS_ESTATE, "graph " + std::to_string(i) + " has no factors");
+    if (robust(g)) return mfail(m, PPS_ESTATE, "graph " + std::to_string(i) + " has a robust cost function set (pps_set_cost_function); the batched solve has no robust kernels");
     if (g->props.jacobian_mode != mode) return mfail(m, PPS_EINVAL, "all graphs of a batch share one jacobian_mode");
     if (g->an.n_stages > 32) return mfail(m, PPS_ESTATE, "graph " + std::to_string(i) + ": elimination tree too deep for the batched schedule");
     rc = ensure_k2t_lists(g);

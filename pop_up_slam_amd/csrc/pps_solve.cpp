@@ -32,10 +32,10 @@ int do_linearize(pps_graph* g, const LinGuard* guard = nullptr) {
     }
     g->k1_skip.resize(g->k1_events.size() / 2, 0);
     g->k1_skip[g->k1_used / 2] = 0;
-    HIP_TRY(g, launch_linearize(g->dev, g->props.jacobian_mode, false, g->stream, guard, g->k1_events[g->k1_used], g->k1_events[g->k1_used + 1]));
+    HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, false, guard, g->k1_events[g->k1_used], g->k1_events[g->k1_used + 1]));
     g->k1_used += 2;
   } else
-  { PhaseTimer t(g, &g->stats.t_linearize); HIP_TRY(g, launch_linearize(g->dev, g->props.jacobian_mode, false, g->stream, guard)); }
+  { PhaseTimer t(g, &g->stats.t_linearize); HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, false, guard)); }
   { PhaseTimer t(g, &g->stats.t_assemble); HIP_TRY(g, launch_hblocks(g->dev, g->stream, guard, k1_products(g->dev, g->props.jacobian_mode))); }
   if (!guard) g->stats.n_linearize++;
   return PPS_OK;
@@ -187,7 +187,7 @@ int read_result(pps_graph* g, bool at_estimate, double* chi2, double* dnorm, boo
   if (g->n_live_factors == 0) { *chi2 = 0.0; if (dnorm) *dnorm = 0.0; if (notpd) *notpd = false; return PPS_OK; }
   {
     PhaseTimer t(g, &g->stats.t_retract_chi2);
-    HIP_TRY(g, launch_chi2(g->dev, at_estimate, g->host_result, 0.0, g->stream));
+    HIP_TRY(g, chi2_launch(g, at_estimate, g->host_result, 0.0));
   }
   HIP_TRY(g, hipStreamSynchronize(g->stream));
   *chi2 = g->host_result[0];
@@ -274,7 +274,7 @@ static int update_impl(pps_graph* g) {
   // apply_exmap (:183) and chi2 at the new estimate in ONE launch (round 6: the trial kernel of the LM loop with one trial -- the retraction
   // blocks write est <- lin (+) delta, the chi2 blocks evaluate at lin (+) delta on the fly, same bits; it was k_retract + k_chi2)
   double chi2 = 0.0, dn = 0.0; bool notpd = false;
-  if (g->n_live_factors > 0 && g->dev.n_pose + g->dev.n_plane > 0) {
+  if (g->n_live_factors > 0 && g->dev.n_pose + g->dev.n_plane > 0 && !robust(g)) {      // (a cost function: retraction, then the robust chi2 sweep -- the branch below)
     const DevGraph& d = g->dev;
     { PhaseTimer t(g, &g->stats.t_retract_chi2);
       HIP_TRY(g, launch_trial_dual(d, DualAlt{}, d.pose_lin, d.plane_lin, d.pose_est, d.plane_est, nullptr, nullptr, g->host_result, 0.0, nullptr, 0.0, g->stream, 1)); }
@@ -485,7 +485,7 @@ static int lm_solve(pps_graph* g, int* iterations) {
   begin_solve(g);
   int rc = prepare_solve(g);
   if (rc != PPS_OK) return rc;
-  if (g->use_band && g->profiling < 2 && !g->dev.trace && !g->sw.no_dual) return lm_solve_dual(g, iterations, t0);      // (PPS_NO_DUAL: the loop-forms parity test)
+  if (g->use_band && g->profiling < 2 && !g->dev.trace && !g->sw.no_dual && !robust(g)) return lm_solve_dual(g, iterations, t0);      // (PPS_NO_DUAL: the loop-forms parity test; a cost function: the robust kernels exist for this loop only)
   const pps_props& prop = g->props;
   if (!g->status_clean) HIP_TRY(g, launch_clear_status(g->dev, g->stream));
   g->status_clean = false;
@@ -504,14 +504,14 @@ static int lm_solve(pps_graph* g, int* iterations) {
     PhaseTimer t(g, &g->stats.t_retract_chi2);
     HIP_TRY(g, launch_retract_trial(g->dev, g->stream));                       // linpoint_to_estimate + self_exmap (:414-416)
     g->seq += 1.0;
-    HIP_TRY(g, launch_chi2_trial(g->dev, slot1, g->seq, g->stream));           // weighted_errors(LINPOINT) (:417)
+    HIP_TRY(g, chi2_trial_launch(g, slot1, g->seq));                           // weighted_errors(LINPOINT) (:417)
     return PPS_OK;
   };
   rc = copy_state(g, true); if (rc != PPS_OK) return rc;          // estimate_to_linpoint (Optimizer.cpp:376)
   rc = do_linearize(g); if (rc != PPS_OK) return rc;              // jacobian() (:379)
   g->seq += 1.0;
   const double seq0 = g->seq;
-  HIP_TRY(g, launch_chi2(g->dev, false, slot0, seq0, g->stream)); // r = weighted_errors(LINPOINT); error = |r|^2 (:382-385)
+  HIP_TRY(g, chi2_launch(g, false, slot0, seq0));                 // r = weighted_errors(LINPOINT); error = |r|^2 (:382-385)
   rc = enqueue_trial(lm.lambda); if (rc != PPS_OK) return rc;
   rc = wait_result(g, slot0, seq0); if (rc != PPS_OK) return rc;
   rc = wait_result(g, slot1, g->seq); if (rc != PPS_OK) return rc;

@@ -19,7 +19,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pop_up_slam_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
-SOLVER = {"pps_k1.hip", "pps_k2.hip", "pps_k3.hip", "pps_dense.hip"}      # (built with contraction; pps_k1_lanes.hip / pps_k4.hip without)
+SOLVER = {"pps_k1.hip", "pps_k2.hip", "pps_k3.hip", "pps_dense.hip", "pps_robust.hip"}      # (built with contraction; pps_k1_lanes.hip / pps_k4.hip without)
 
 
 def resources(src, extra, built=False):
@@ -81,6 +81,17 @@ DESIGN_KERNELS = [
     ("k_band_factor<true>", "plain walk"), ("k_band_factor<false>", "general: traces"), ("k_band_factor_r5", "fronts of 65-80 rows"),
     ("kb_band_factor<true>", ""), ("kb_band_factor_pre", ""), ("kb_level_factor2", ""), ("kb_level_factor3", ""), ("kb_level_factor4", ""),
     ("kb_level_solve", ""), ("k_trial_dual", "K4"), ("k_chi2", ""),
+    # a handle with a robust cost function (pps_robust.hip): every instantiation; the first template argument is the kind
+    # (1 Huber, 2 pseudo-Huber, 3 Cauchy), then MODE (0 numeric, 1 analytic) and PART (0 plane observations, 1 odometry / priors)
+    ("k_linearize_obs_numeric_robust<1>", "robust K1, thread form: plane observations, numeric, Huber"),
+    ("k_linearize_obs_numeric_robust<2>", "robust K1, thread form: plane observations, numeric, pseudo-Huber"),
+    ("k_linearize_obs_numeric_robust<3>", "robust K1, thread form: plane observations, numeric, Cauchy"),
+    ("k_linearize_robust<1, 0, 1>", "... odometry / priors, numeric, Huber"), ("k_linearize_robust<1, 1, 0>", "... plane observations, analytic"), ("k_linearize_robust<1, 1, 1>", "... odometry / priors, analytic"),
+    ("k_linearize_robust<2, 0, 1>", "... odometry / priors, numeric, pseudo-Huber"), ("k_linearize_robust<2, 1, 0>", "... plane observations, analytic"), ("k_linearize_robust<2, 1, 1>", "... odometry / priors, analytic"),
+    ("k_linearize_robust<3, 0, 1>", "... odometry / priors, numeric, Cauchy"), ("k_linearize_robust<3, 1, 0>", "... plane observations, analytic"), ("k_linearize_robust<3, 1, 1>", "... odometry / priors, analytic"),
+    ("k_linearize_repop_robust<1>", "... Factor2 edges, Huber"), ("k_chi2_robust<1>", "robust chi2 at the stored state"), ("k_chi2_trial_robust<1>", "... of the one-step loop's trial"),
+    ("k_linearize_repop_robust<2>", "... Factor2 edges, pseudo-Huber"), ("k_chi2_robust<2>", "robust chi2 at the stored state"), ("k_chi2_trial_robust<2>", "... of the one-step loop's trial"),
+    ("k_linearize_repop_robust<3>", "... Factor2 edges, Cauchy"), ("k_chi2_robust<3>", "robust chi2 at the stored state"), ("k_chi2_trial_robust<3>", "... of the one-step loop's trial"),
 ]
 TABLE_BEGIN, TABLE_END = "<!-- kernel-table:begin (tools/kernel_resources.py --update-design) -->", "<!-- kernel-table:end -->"
 
@@ -88,7 +99,7 @@ TABLE_BEGIN, TABLE_END = "<!-- kernel-table:begin (tools/kernel_resources.py --u
 def built_table():
     """{name: dict} of every kernel of the solver objects the Makefile built"""
     out = {}
-    for f in ("pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip"):
+    for f in ("pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip", "pps_robust.hip"):
         for r in resources(os.path.join(CSRC, f), [], built=True):
             v = int(r["vgpr_count"])
             out[short_name(r["name"])] = {"vgpr": v, "agpr": int(r["agpr_count"]), "waves": min(8, 512 // max(8, (v + 7) // 8 * 8)),
@@ -128,7 +139,7 @@ def update_design():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("files", nargs="*", default=["pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip"])
+    ap.add_argument("files", nargs="*", default=["pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip", "pps_robust.hip"])
     ap.add_argument("--filter", default="")
     ap.add_argument("--flags", default="")
     ap.add_argument("--built", action="store_true", help="read the objects under csrc/build instead of compiling")
