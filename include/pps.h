@@ -158,6 +158,35 @@ int pps_cov_access(pps_graph* g, int n, const int* rows, const int* cols, double
 int pps_cov_joint(pps_graph* g, int n, const int* ids, double* out);
 /* device seconds (HIP events) of the last pps_cov_recover: sec[0] the whole call's launches, sec[1] the root -> leaves pass alone */
 int pps_cov_last_times(const pps_graph* g, double sec[2]);
+/* pps_cov_factor: the factor-only recovery -- all that pps_cov_block and pps_assoc_gate read, and the one recovery a dense-front graph
+ * (loop closures: sphere2500, a landmark merge across the map) has.  Relinearises at the estimate in the handle's jacobian_mode (the
+ * robustified error with a cost function set), assembles H = J'J and factors it with lambda = 0 in the form the graph is solved in: the
+ * band stages of pps_cov_recover without its root -> leaves pass (about two thirds of that call's work, whose results a block or gate
+ * query never reads), or the dense-front levels of pps_batch_optimize without the back-substitution.  Like pps_cov_recover it moves
+ * neither the estimate, the linearisation point, the LM trace nor the stats of the last solve; a pps_batch_optimize after it is bit for
+ * bit the one without it.
+ *   PPS_EINVAL  NULL handle
+ *   PPS_ESTATE  empty graph; or (a text of its own) a graph solved by the one-launch-per-level LDS kernels, neither band nor dense-front
+ *   PPS_ENOTPD  no factor in the graph; a pivot of the factorisation was not positive; or a pivot of L_A was not positive, not finite, or
+ *               below 1e-7 of the largest pivot of its front -- the criterion of pps_cov_recover, applied by one launch over all fronts.
+ *               No valid factor is left behind; the handle stays usable.
+ *   PPS_EHIP    no device, or a HIP error (the handle's device copy is abandoned, as by pps_cov_recover)
+ * Validity: the handle keeps two flags, "selected inverse" and "factor".  pps_cov_recover sets both, pps_cov_factor the second alone; every
+ * call listed above as ending a recovery clears both, and so does the start of either entry point (a pps_cov_recover that is refused
+ * -- dense-front graph -- ends the factor of an earlier pps_cov_factor: call pps_cov_factor after it, not before).
+ *   pps_cov_block, pps_assoc_gate (and their _last / debug companions) ask for the factor: either entry point provides it.
+ *   pps_cov_marginals / _access / _joint ask for the selected inverse; after a pps_cov_factor alone they answer PPS_ESTATE with a text that
+ *   names pps_cov_factor and pps_cov_recover.  With neither call made every read call answers PPS_ESTATE "no valid covariance recovery".
+ * On a dense-front graph the root-path walks run in a second kernel (one workgroup of 256 threads per node, the right-hand sides in a
+ * scratch buffer of the handle sized by the widest front on the paths of the query; PPS_ENOMEM from pps_cov_block / pps_assoc_gate if
+ * it cannot be allocated); on a band graph both kernels write the same bits.  Not offered on such graphs: the selected inverse, pps_multi.
+ * pps_cov_last_times reports the call in sec[0], with sec[1] = 0.
+ * Found by symbol lookup (dlsym "pps_cov_factor"), like the calls above; PPS_VERSION was not bumped. */
+int pps_cov_factor(pps_graph* g);
+/* diagnostics, per handle: which kernel walks the root paths of pps_cov_block / pps_assoc_gate.  form 0 = automatic (the wave-per-node
+ * kernel where its LDS fits the graph's fronts, the wide kernel otherwise), 1 = always the wide kernel -- to compare the two on any band
+ * graph.  PPS_EINVAL: NULL handle, another form.  Changes no validity.  Found by symbol lookup. */
+int pps_debug_cov_path_form(pps_graph* g, int form);
 /* Sigma(rows, cols) for ANY nodes, inside the pattern of the factor or not (the reference's marginal(node_list) / access(pairs) without
  * the limit above): out is (sum dim(rows)) x (sum dim(cols)), row-major, nodes in the order given.  cols == NULL (nc ignored): cols =
  * rows, the joint marginal, exactly symmetric.  A node may appear in both lists, not twice in one.
@@ -165,9 +194,10 @@ int pps_cov_last_times(const pps_graph* g, double sec[2]);
  * solve along its path from its front to the root of the elimination tree (its columns of L^-1 are zero elsewhere), the block one
  * product over the pivots of common ancestors.  Cost: about (pivots on the path) x (front rows) x dim(node) multiply-adds per node, all
  * nodes side by side; one upload, two launches and one copy per call, whatever nr, nc and the depth of the tree.  Nothing is factored
- * again: the call reads the factor of the last pps_cov_recover and falls under the same validity rules.
+ * again: the call reads the factor of the last pps_cov_recover or pps_cov_factor and falls under the same validity rules.
  *   PPS_EINVAL  NULL handle, rows or out; a negative count; an unknown or removed node id; a node twice in rows or twice in cols
- *   PPS_ESTATE  no valid recovery (also: a dense-front graph, for which pps_cov_recover has none to give)
+ *   PPS_ESTATE  no valid factor (a dense-front graph has one after pps_cov_factor; pps_cov_recover has none to give there)
+ *   PPS_ENOMEM  dense-front graphs: no device memory for the right-hand sides of the walks
  *   PPS_OK      with out untouched for nr == 0 or nc == 0
  * pps_cov_marginals / _access / _joint keep their in-pattern contract and their refusals.  Found by symbol lookup, like the calls above. */
 int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols, double* out);
@@ -194,7 +224,7 @@ int pps_cov_block_last(const pps_graph* g, double* kernel_sec, int* launches);
  *               pose; a plane_ids entry is not a plane; a plane twice in the list (all checked on the host before anything is launched)
  *   PPS_OK      with the outputs untouched for n_meas == 0 or n_planes == 0 -- answered after the argument checks and BEFORE the recovery
  *               is looked at (nothing is read from it), unlike pps_cov_block, which asks for the recovery first
- *   PPS_ESTATE  no valid recovery: the text and the validity rules of pps_cov_block (also: a dense-front graph)
+ *   PPS_ESTATE  no valid factor: the text and the validity rules of pps_cov_block (a dense-front graph: after pps_cov_factor)
  *   PPS_ENOTPD  a pivot of a 3 x 3 factor was not positive or not finite (the outputs are untouched)
  * Mapper_mono::findClosestPlane's geometric gate (pps_find_closest_planes) is independent of this call and unchanged.
  * Found by symbol lookup, like the pps_cov_* calls; PPS_VERSION was not bumped. */

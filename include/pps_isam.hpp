@@ -376,11 +376,14 @@ protected:
 // marginal() and access() keep that strict in-pattern contract (they read the selected inverse and throw for anything outside it).
 // block() and marginal_any() are the unrestricted forms: any nodes, by root-path solves on the same factor (pps_cov_block) -- what the
 // reference's marginal(node_list) / access(pairs) answer for nodes that share no front, e.g. the current pose against an old landmark.
+// They and gate() need the factor alone: where pps_cov_recover refuses the graph (PPS_ESTATE: the dense-front form) they go on with
+// pps_cov_factor, so that they answer after a loop closure, too.  On every other graph they make the calls they always made.
 class Covariances {
   Slam* _slam;
   int _probe_id = 0;
   pps_graph* handle() const;
   void ensure() const;      // a valid recovery on the handle
+  void ensure_factor() const;   // a valid factor: the recovery, or (where it is refused: dense-front graphs) pps_cov_factor
   static std::vector<int> ids_of(const std::list<Node*>& nodes) {
     std::vector<int> ids;
     for (Node* n : nodes) { if (!n || n->backend_id() < 0) throw std::runtime_error("Covariances: node is not part of the graph"); ids.push_back(n->backend_id()); }
@@ -402,7 +405,7 @@ public:
   }
   // Sigma(rows, cols) for any nodes, in list order; a node may be in both lists, not twice in one
   MatrixXd block(const std::list<Node*>& rows, const std::list<Node*>& cols) const {
-    ensure();
+    ensure_factor();
     const std::vector<int> r = ids_of(rows), c = ids_of(cols);
     int R = 0, Cn = 0;
     for (Node* n : rows) R += n->dim();
@@ -413,7 +416,7 @@ public:
   }
   // the joint marginal over any list of distinct nodes (exactly symmetric), whether they share a front or not
   MatrixXd marginal_any(const std::list<Node*>& nodes) const {
-    ensure();
+    ensure_factor();
     const std::vector<int> ids = ids_of(nodes);
     int N = 0;
     for (Node* n : nodes) N += n->dim();
@@ -426,7 +429,7 @@ public:
   // freedom for a correct pairing (7.815 at 0.95).  best[i] = index into `planes` of the smallest finite entry of row i, -1 if none.
   MatrixXd gate(Pose3d_Node* pose, const std::vector<Plane3d>& measurements, const std::vector<Noise>& noises, const std::list<Node*>& planes,
                 std::vector<int>& best) const {
-    ensure();
+    ensure_factor();
     if (!pose || pose->backend_id() < 0) throw std::runtime_error("Covariances: node is not part of the graph");
     if (measurements.size() != noises.size()) throw std::runtime_error("Covariances::gate: one noise model per measurement");
     const std::vector<int> ids = ids_of(planes);
@@ -580,6 +583,14 @@ inline void Covariances::ensure() const {
   double none = 0.0;
   if (pps_cov_marginals(handle(), 0, &_probe_id, &none, nullptr) == PPS_OK) return;
   detail::check(pps_cov_recover(handle()), handle(), "pps_cov_recover");
+}
+inline void Covariances::ensure_factor() const {
+  // (a query with no node asks nothing but "is there a valid factor")
+  double none = 0.0;
+  if (pps_cov_block(handle(), 0, &_probe_id, 0, nullptr, &none) == PPS_OK) return;
+  const int rc = pps_cov_recover(handle());
+  if (rc == PPS_ESTATE) detail::check(pps_cov_factor(handle()), handle(), "pps_cov_factor");
+  else detail::check(rc, handle(), "pps_cov_recover");
 }
 inline void Pose3d_Plane3d_Factor::set_measurement(const Plane3d& m) {
   _measure = m;

@@ -3,6 +3,9 @@
 //
 //   pps_cov_recover    relinearise at the estimate, H = J'J factored with lambda = 0 (the launches of pps_update's factorisation, one per band
 //                      stage), then the selected inverse root -> leaves (pps_cov.hip), one launch per tree level
+//   pps_cov_factor     the same without the selected inverse: K1 at the estimate, K2, the lambda = 0 factorisation in the K3 form the graph has
+//                      (band stages or the dense-front levels), the pivot criterion in one launch (pps_cov_wide.hip).  All pps_cov_block and
+//                      pps_assoc_gate need, and the only recovery a dense-front graph has
 //   pps_cov_marginals / _access / _joint   look the requested blocks up in the fronts (host tables built at recovery time), collect them with
 //                      one gather launch and one copy
 // Every entry of Sigma inside the pattern of L is available: the diagonal block of every node and the cross block of every pair of nodes
@@ -31,22 +34,26 @@ void cov_release(pps_graph* g) {
   if (g->cov_breq) (void)hipFree(g->cov_breq);
   if (g->cov_strip) (void)hipFree(g->cov_strip);
   if (g->cov_bout) (void)hipFree(g->cov_bout);
+  if (g->cov_zscr) (void)hipFree(g->cov_zscr);
   gate_release(g);
   for (hipEvent_t& e : g->cov_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   for (hipEvent_t& e : g->cov_bev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   g->cov_S = nullptr; g->cov_parent = nullptr; g->cov_req = nullptr; g->cov_out = nullptr;
-  g->cov_breq = nullptr; g->cov_strip = nullptr; g->cov_bout = nullptr;
+  g->cov_breq = nullptr; g->cov_strip = nullptr; g->cov_bout = nullptr; g->cov_zscr = nullptr; g->cov_zscr_cap = 0;
   g->cov_S_cap = g->cov_parent_cap = g->cov_req_cap = g->cov_out_cap = 0;
   g->cov_breq_cap = g->cov_strip_cap = g->cov_bout_cap = 0; g->cov_bout_clean = false;
-  g->cov_valid = false;
+  g->cov_valid = g->cov_factor_valid = false;
 }
 
-bool cov_current(const pps_graph* g) {
-  return g->cov_valid && g->dev_ready && !g->topo_dirty && !g->analysis_stale && !g->host_values_newer && !g->meas_dirty &&
-         g->cov_version == g->upload_version;
+static bool cov_state_current(const pps_graph* g) {
+  return g->dev_ready && !g->topo_dirty && !g->analysis_stale && !g->host_values_newer && !g->meas_dirty && g->cov_version == g->upload_version;
 }
+bool cov_current(const pps_graph* g) { return g->cov_valid && cov_state_current(g); }
+bool cov_factor_current(const pps_graph* g) { return g->cov_factor_valid && cov_state_current(g); }
 
 const char* const kNoRecovery = "no valid covariance recovery: call pps_cov_recover (a recovery ends with every change of the estimate, the measurements or the topology)";
+const char* const kFactorOnly = "the handle holds the factor of pps_cov_factor, not the selected inverse: this call reads what pps_cov_recover computes (pps_cov_block and pps_assoc_gate read the factor)";
+static const char* no_selected_inverse(const pps_graph* g) { return cov_factor_current(g) ? kFactorOnly : kNoRecovery; }
 
 int cov_node(pps_graph* g, int id, CovNode* out) {
   if (id < 0 || id >= (int)g->nodes.size() || g->nodes[id].deleted) return fail(g, PPS_EINVAL, "covariance: unknown node id " + std::to_string(id));
@@ -116,9 +123,13 @@ int cov_build_walks(pps_graph* g, const std::vector<int>& ids, std::vector<CovNo
   out->steps.clear();
   out->step_end.assign((size_t)nw, 0);
   out->n_strip = 0;
+  out->max_rows = 1;
   for (int w = 0; w < nw; w++) {
     out->walks[w] = CovWalk{out->n_strip, (int)out->steps.size(), 0, nd[w].local, nd[w].dim};
-    for (int s = nd[w].front; s >= 0; s = A.f_parent[s]) out->steps.push_back(CovStep{s, out->K - g->cov_rootlen[s]});
+    for (int s = nd[w].front; s >= 0; s = A.f_parent[s]) {
+      out->steps.push_back(CovStep{s, out->K - g->cov_rootlen[s]});
+      out->max_rows = std::max(out->max_rows, A.f_p[s] + A.f_b[s]);
+    }
     out->walks[w].n_steps = (int)out->steps.size() - out->walks[w].step0;
     out->step_end[w] = (int)out->steps.size();
     out->n_strip += (long long)out->K * nd[w].dim;
@@ -231,8 +242,99 @@ static int cov_recover_impl(pps_graph* g) {
   if (status[2] != 0.0)
     return fail(g, PPS_ENOTPD, "normal equations not positive definite at lambda = 0 (a pivot was not positive, or below 1e-7 of the largest pivot of its front): no covariance");
   g->cov_version = g->upload_version;
-  g->cov_valid = true;
+  g->cov_valid = g->cov_factor_valid = true;
+  g->cov_tables_version = g->upload_version;             // (built and checked above, with the stricter shape test of the level pass)
   return PPS_OK;
+}
+
+// pps_cov_factor: the recovery without the selected inverse, in whatever K3 form the graph has
+static int cov_factor_impl(pps_graph* g) {
+  int rc;
+  if (!g->analyzed || g->analysis_stale) { rc = pps_analyze(g); if (rc != PPS_OK) return rc; }
+  if (!g->use_band && !g->use_dense)
+    return fail(g, PPS_ESTATE, "pps_cov_factor: the graph is solved by the one-launch-per-level LDS kernels (max front " + std::to_string(g->an.max_front) +
+                               " scalars, neither the band nor the dense-front form), whose panels do not pass through the factor array: no factor to keep");
+  rc = prepare_solve(g); if (rc != PPS_OK) return rc;
+  const Analysis& A = g->an;
+  const DevGraph& d = g->dev;
+  for (hipEvent_t& e : g->cov_ev) if (!e) HIP_TRY(g, hipEventCreate(&e));
+  if (g->cov_tables_version != g->upload_version && g->cov_parent_version != g->upload_version) {
+    rc = cov_build_tables(g); if (rc != PPS_OK) return rc;
+    for (int s = 0; s < A.n_fronts; s++) {               // what the path walks index with: checked here, before anything is launched
+      const int q = A.f_parent[s];
+      if (A.f_b[s] < 0 || (A.f_b[s] > 0 && (q < 0 || q >= A.n_fronts || A.f_level[q] <= A.f_level[s] || A.f_cmap_off[s + 1] - A.f_cmap_off[s] < A.f_b[s])))
+        return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (parent / child map)");
+      for (int k = 0; k < A.f_b[s]; k++) {
+        const int r = A.cmap[A.f_cmap_off[s] + k];
+        if (r < 0 || r >= A.f_p[q] + A.f_b[q]) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (child map entry)");
+      }
+      if (A.f_p[s] < 1 || A.f_p[s] > 64) return fail(g, PPS_ESTATE, "covariance: front outside the supported shapes");
+    }
+    g->cov_tables_version = g->upload_version;
+  }
+  if (!g->status_clean) {
+    HIP_TRY(g, launch_clear_status(d, g->stream));
+    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
+  }
+  g->status_clean = false;
+  HIP_TRY(g, hipEventRecord(g->cov_ev[0], g->stream));
+  HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, true));      // jacobian() at the ESTIMATE, robustified with a cost function set
+  HIP_TRY(g, launch_hblocks(d, g->stream, nullptr, k1_products(d, g->props.jacobian_mode)));
+  if (g->use_band) {                                     // one launch per band stage: the form whose panels all pass through d.L
+    for (int st = 0; st < A.n_stages; st++)
+      HIP_TRY(g, launch_band_factor(d, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_factor[st], A.stage_max_front[st], 0.0, g->stream));
+  } else {                                               // the dense-front levels, as do_solve issues them (pps_solve.cpp)
+    HIP_TRY(g, hipMemsetAsync(d.L, 0, (size_t)A.L_size * 8, g->stream));
+    HIP_TRY(g, launch_dense_hpush(d, g->max_el_per_front, 0.0, g->stream));
+    for (int l = 0; l < A.n_levels; l++) {
+      const int base = A.level_off[l] + l, cnt = A.level_off[l + 1] - A.level_off[l];
+      HIP_TRY(g, launch_dense_factor_level(d, A.level_off[l], cnt, g->d_dw_asm + base, g->dw_asm[base + cnt], g->d_dw_pan + base, g->dw_pan[base + cnt],
+                                           g->d_dw_trl + base, g->dw_trl[base + cnt], g->stream));
+    }
+  }
+  HIP_TRY(g, launch_cov_pivots(d, A.n_fronts, g->stream));
+  HIP_TRY(g, hipEventRecord(g->cov_ev[1], g->stream));
+  double status[4] = {0, 0, 0, 0};
+  HIP_TRY(g, hipMemcpyAsync(status, d.result_dev, sizeof status, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  float ms = 0;
+  g->cov_sec[1] = 0.0;
+  if (hipEventElapsedTime(&ms, g->cov_ev[0], g->cov_ev[1]) == hipSuccess) g->cov_sec[0] = 1e-3 * ms;
+  if (status[2] != 0.0) {
+    HIP_TRY(g, launch_clear_status(d, g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+  }
+  g->status_clean = true;
+  if (status[2] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: the factorisation of pps_cov_factor met an index outside its front");
+  if (status[2] != 0.0)
+    return fail(g, PPS_ENOTPD, "normal equations not positive definite at lambda = 0 (a pivot was not positive, or below 1e-7 of the largest pivot of its front): no factor");
+  g->cov_version = g->upload_version;
+  g->cov_factor_valid = true;
+  return PPS_OK;
+}
+
+bool cov_walk_wide(const pps_graph* g) {
+  return g->cov_path_form == 1 || cov_path_lds_bytes(g->cov_max_p, g->cov_max_rows) > (size_t)64 * 1024;
+}
+
+int cov_walk_scratch(pps_graph* g, const CovWalks& cw) {
+  if (!cov_walk_wide(g) || cw.walks.empty()) return PPS_OK;
+  const size_t want = cw.walks.size() * cov_wide_scratch(cw.max_rows);
+  if (want <= g->cov_zscr_cap && g->cov_zscr) return PPS_OK;
+  HIP_TRY(g, hipStreamSynchronize(g->stream));           // (so that what cov_reserve can still fail with is the allocation)
+  if (cov_reserve(g, &g->cov_zscr, &g->cov_zscr_cap, want) != PPS_OK) {
+    (void)hipGetLastError();
+    return fail(g, PPS_ENOMEM, "covariance path solves: no device memory for the right-hand sides of " + std::to_string(cw.walks.size()) + " walks through fronts of up to " +
+                               std::to_string(cw.max_rows) + " rows (" + std::to_string(want * sizeof(double)) + " bytes): ask for fewer nodes per call");
+  }
+  return PPS_OK;
+}
+
+hipError_t cov_launch_walks(pps_graph* g, const CovWalks& cw, const CovWalk* walks, const CovStep* steps, double* out) {
+  const int nw = (int)cw.walks.size(), ns = (int)cw.steps.size();
+  if (cov_walk_wide(g))
+    return launch_cov_path_wide(g->dev, walks, nw, steps, ns, cw.K, cw.max_rows, g->cov_zscr, (long long)g->cov_zscr_cap, g->cov_strip, cw.n_strip, out, g->stream);
+  return launch_cov_path(g->dev, walks, nw, steps, ns, cw.K, g->cov_max_p, g->cov_max_rows, g->cov_strip, cw.n_strip, out, g->stream);
 }
 
 }  // namespace pps_impl
@@ -259,6 +361,33 @@ int pps_cov_recover(pps_graph* g) {
   return rc;
 }
 
+int pps_cov_factor(pps_graph* g) {
+  if (!g) return PPS_EINVAL;
+  cov_invalidate(g);
+  if (g->n_live_nodes == 0) return fail(g, PPS_ESTATE, "empty graph");
+  if (g->n_live_factors == 0) return fail(g, PPS_ENOTPD, "normal equations not positive definite: the graph has no factor");
+  // like pps_cov_recover: no solve, the figures of the last one stay
+  const pps_stats saved = g->stats;
+  const int profiling = g->profiling;
+  g->profiling = 0;
+  const unsigned long long launches0 = g->launches0;
+  const int rc = cov_factor_impl(g);
+  g->profiling = profiling;
+  g->launches0 = launches0;
+  { pps_stats s = saved;
+    s.n_fronts = g->stats.n_fronts; s.n_levels = g->stats.n_levels; s.max_front = g->stats.max_front; s.nnz_L = g->stats.nnz_L;
+    g->stats = s; }
+  if (rc == PPS_EHIP) abandon_device_copy(g);
+  return rc;
+}
+
+int pps_debug_cov_path_form(pps_graph* g, int form) {
+  if (!g) return PPS_EINVAL;
+  if (form != 0 && form != 1) return fail(g, PPS_EINVAL, "pps_debug_cov_path_form: form is 0 (automatic) or 1 (always the wide kernel)");
+  g->cov_path_form = form;
+  return PPS_OK;
+}
+
 int pps_cov_last_times(const pps_graph* g, double sec[2]) {
   if (!g || !sec) return PPS_EINVAL;
   sec[0] = g->cov_sec[0]; sec[1] = g->cov_sec[1];
@@ -282,7 +411,7 @@ int pps_cov_marginals(pps_graph* g, int n, const int* ids, double* out, int64_t*
   }
   std::vector<CovNode> nd((size_t)n);
   for (int i = 0; i < n; i++) { const int rc = cov_node(g, ids[i], &nd[i]); if (rc != PPS_OK) return rc; }
-  if (!cov_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
+  if (!cov_current(g)) return fail(g, PPS_ESTATE, no_selected_inverse(g));
   std::vector<CovReq> req((size_t)n);
   long long o = 0;
   for (int i = 0; i < n; i++) {
@@ -302,7 +431,7 @@ int pps_cov_access(pps_graph* g, int n, const int* rows, const int* cols, double
     int rc = cov_node(g, rows[i], &nr[i]); if (rc != PPS_OK) return rc;
     rc = cov_node(g, cols[i], &nc[i]); if (rc != PPS_OK) return rc;
   }
-  if (!cov_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
+  if (!cov_current(g)) return fail(g, PPS_ESTATE, no_selected_inverse(g));
   // the blocks are collected densely on the device and copied to their places in `out`, so that a block outside the pattern is left untouched
   std::vector<CovReq> req;
   std::vector<long long> place;
@@ -331,7 +460,7 @@ int pps_cov_joint(pps_graph* g, int n, const int* ids, double* out) {
     const int rc = cov_node(g, ids[i], &nd[i]); if (rc != PPS_OK) return rc;
     for (int j = 0; j < i; j++) if (ids[j] == ids[i]) return fail(g, PPS_EINVAL, "covariance joint: node " + std::to_string(ids[i]) + " is listed twice");
   }
-  if (!cov_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
+  if (!cov_current(g)) return fail(g, PPS_ESTATE, no_selected_inverse(g));
   std::vector<int> off((size_t)n + 1, 0);
   for (int i = 0; i < n; i++) {
     const int rc = cov_locate(g, ids[i], &nd[i]); if (rc != PPS_OK) return rc;
@@ -385,9 +514,8 @@ int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols
     }
   }
   if (joint) ci = ri;
-  if (!cov_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
+  if (!cov_factor_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
   if (nr == 0 || nc == 0) return PPS_OK;
-  const int nw = (int)ids.size();
   CovWalks cw;
   { const int rc = cov_build_walks(g, ids, nd, &cw); if (rc != PPS_OK) return rc; }
   const int K = cw.K;
@@ -422,6 +550,7 @@ int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols
   for (hipEvent_t& e : g->cov_bev) if (!e) HIP_TRY(g, hipEventCreate(&e));
   int rc = cov_reserve(g, &g->cov_breq, &g->cov_breq_cap, req.size()); if (rc != PPS_OK) return rc;
   rc = cov_reserve(g, &g->cov_strip, &g->cov_strip_cap, (size_t)n_strip); if (rc != PPS_OK) return rc;
+  rc = cov_walk_scratch(g, cw); if (rc != PPS_OK) return rc;
   if ((size_t)n_out + 1 > g->cov_bout_cap || !g->cov_bout) g->cov_bout_clean = false;
   rc = cov_reserve(g, &g->cov_bout, &g->cov_bout_cap, (size_t)n_out + 1); if (rc != PPS_OK) return rc;
   if (!g->cov_bout_clean) HIP_TRY(g, hipMemsetAsync(g->cov_bout, 0, sizeof(double), g->stream));      // (a new buffer, or a query that failed)
@@ -429,8 +558,7 @@ int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols
   const unsigned long long launches0 = launch_count();
   HIP_TRY(g, hipMemcpyAsync(g->cov_breq, req.data(), req.size(), hipMemcpyHostToDevice, g->stream));
   HIP_TRY(g, hipEventRecord(g->cov_bev[0], g->stream));
-  HIP_TRY(g, launch_cov_path(g->dev, reinterpret_cast<const CovWalk*>(g->cov_breq), nw, reinterpret_cast<const CovStep*>(g->cov_breq + o_steps), (int)steps.size(), K,
-                             g->cov_max_p, g->cov_max_rows, g->cov_strip, n_strip, g->cov_bout, g->stream));
+  HIP_TRY(g, cov_launch_walks(g, cw, reinterpret_cast<const CovWalk*>(g->cov_breq), reinterpret_cast<const CovStep*>(g->cov_breq + o_steps), g->cov_bout));
   HIP_TRY(g, launch_cov_gram(reinterpret_cast<const CovPair*>(g->cov_breq + o_pairs), (int)pairs.size(), g->cov_strip, n_strip, g->cov_bout, n_out, g->stream));
   HIP_TRY(g, hipEventRecord(g->cov_bev[1], g->stream));
   std::vector<double> host((size_t)n_out + 1);

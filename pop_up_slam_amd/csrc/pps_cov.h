@@ -46,4 +46,17 @@ hipError_t launch_cov_path(const DevGraph& d, const CovWalk* walks, int n_walks,
                            int max_front, double* Y, long long n_strip, double* out, hipStream_t st);
 hipError_t launch_cov_gram(const CovPair* pairs, int n_pairs, const double* Y, long long n_strip, double* out, long long n_out, hipStream_t st);
 
+// ---- pps_cov_factor / the path walk for wide fronts (pps_cov_wide.hip) ----
+// a pivot of L_A that is not positive, not finite, or below this fraction of the largest pivot of its front: H is singular to 1e-14 of
+// that diagonal (the criterion of k_cov_level, and of k_cov_pivots where the level pass does not run)
+constexpr double kCovPivotRatio = 1e-7;
+// the criterion alone, on the diagonal of every L_A: one workgroup per front, all fronts in one launch; raises d.result_dev[2] to 1
+hipError_t launch_cov_pivots(const DevGraph& d, int n_fronts, hipStream_t st);
+// k_cov_path for fronts that fit neither one wave nor LDS (p <= 64, any p + b): one workgroup of 256 threads per walk, L_A and y_A in
+// LDS, the right-hand sides of the current front and of its parent in Z (global): walk w owns Z[w * cov_wide_scratch(max_front) ...).
+// Same walks, steps, strips, status word and arithmetic order as launch_cov_path: the strips are the same bits.
+inline size_t cov_wide_scratch(int max_front) { return (size_t)2 * max_front * 6; }      // doubles per walk
+hipError_t launch_cov_path_wide(const DevGraph& d, const CovWalk* walks, int n_walks, const CovStep* steps, int n_steps_total, int K, int max_front,
+                                double* Z, long long n_scratch, double* Y, long long n_strip, double* out, hipStream_t st);
+
 }  // namespace pps

@@ -21,7 +21,6 @@ namespace pps {
 namespace {
 
 constexpr int kCovThreads = 256;
-constexpr double kCovPivotRatio = 1e-7;          // a pivot of L below this fraction of its front's largest: H is singular to 1e-14 of that diagonal
 constexpr double kCovStatusInternal = 64.0;      // = kStatusInternal: an index outside its front (never with a consistent analysis)
 
 __device__ __forceinline__ void cov_raise(double* w, double v) {      // the status word is raised, never overwritten (pps_regtile.h)

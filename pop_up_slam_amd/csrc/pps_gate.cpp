@@ -6,7 +6,8 @@
 //
 // The candidate factors are never added: the call reads the estimate and the lambda = 0 factor pps_cov_recover left in dev.L, and writes
 // buffers of its own.  One request upload, the k_cov_path launch of pps_cov_block for the 1 + n_planes distinct nodes, the gate launch
-// (pps_gate.hip), one copy back ([status | d2 | best]).  Validity: that of pps_cov_block (cov_current).
+// (pps_gate.hip), one copy back ([status | d2 | best]).  Validity: that of pps_cov_block (cov_factor_current: a factor of pps_cov_recover or of
+// pps_cov_factor; the walks take k_cov_path or k_cov_path_wide as pps_cov_block's do).
 #include "pps_gate.h"
 #include "pps_graph.h"
 
@@ -74,7 +75,7 @@ int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, c
     normalize4(o);
   }
   if (n_meas == 0 || n_planes == 0) return PPS_OK;       // nothing asked for: the outputs stay untouched
-  if (!cov_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
+  if (!cov_factor_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
   // walks: the pose first, then the candidates in the order given (the tables of pps_cov_block)
   const int nw = 1 + n_planes;
   std::vector<int> ids((size_t)nw);
@@ -107,6 +108,7 @@ int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, c
   // (cov_breq / cov_strip are shared with pps_cov_block: both calls end with a synchronisation, neither is in flight here)
   int rc = cov_reserve(g, &g->cov_breq, &g->cov_breq_cap, req.size()); if (rc != PPS_OK) return rc;
   rc = cov_reserve(g, &g->cov_strip, &g->cov_strip_cap, (size_t)n_strip); if (rc != PPS_OK) return rc;
+  rc = cov_walk_scratch(g, cw); if (rc != PPS_OK) return rc;
   const double* out0 = g->gate_out; const unsigned int* ticket0 = g->gate_ticket;
   rc = cov_reserve(g, &g->gate_out, &g->gate_out_cap, n_out); if (rc != PPS_OK) return rc;
   rc = cov_reserve(g, &g->gate_ticket, &g->gate_ticket_cap, (size_t)n_meas); if (rc != PPS_OK) return rc;
@@ -128,8 +130,7 @@ int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, c
   const unsigned long long launches0 = launch_count();
   HIP_TRY(g, hipMemcpyAsync(g->cov_breq, req.data(), req.size(), hipMemcpyHostToDevice, g->stream));
   HIP_TRY(g, hipEventRecord(g->gate_ev[0], g->stream));
-  HIP_TRY(g, launch_cov_path(g->dev, reinterpret_cast<const CovWalk*>(g->cov_breq), nw, reinterpret_cast<const CovStep*>(g->cov_breq + o_steps), (int)steps.size(), K,
-                             g->cov_max_p, g->cov_max_rows, g->cov_strip, n_strip, g->gate_out, g->stream));
+  HIP_TRY(g, cov_launch_walks(g, cw, reinterpret_cast<const CovWalk*>(g->cov_breq), reinterpret_cast<const CovStep*>(g->cov_breq + o_steps), g->gate_out));
   HIP_TRY(g, launch_assoc_gate(g->dev, ga, g->stream));
   HIP_TRY(g, hipEventRecord(g->gate_ev[1], g->stream));
   std::vector<double> host(n_out);

@@ -202,6 +202,10 @@ struct pps_graph {
   // front at f_Loff; a front's Sigma_BB sits in its -- then dead -- update matrix in dev.U).  Buffers of their own, allocated on the first
   // recovery; cov_valid falls with every call that moves the estimate, the measurements or the topology (cov_invalidate)
   bool cov_valid = false;
+  // a valid lambda = 0 factor is held in dev.L (all pps_cov_block and pps_assoc_gate read): set by pps_cov_recover together with cov_valid, by
+  // pps_cov_factor alone; falls with cov_valid
+  bool cov_factor_valid = false;
+  int cov_tables_version = -1;       // upload_version the node -> front tables (cov_epos .. cov_max_rows) were built and checked for by pps_cov_factor
   int cov_version = -1;              // upload_version the recovery (and cov_parent) belongs to
   double* cov_S = nullptr; size_t cov_S_cap = 0;
   int* cov_parent = nullptr; size_t cov_parent_cap = 0; int cov_parent_version = -1;
@@ -218,6 +222,9 @@ struct pps_graph {
   double* cov_bout = nullptr; size_t cov_bout_cap = 0; bool cov_bout_clean = false;
   hipEvent_t cov_bev[2] = {nullptr, nullptr};
   double cov_block_sec = 0; int cov_block_launches = 0;   // the two kernels of the last query: device seconds, launches
+  // the path walk for wide fronts (k_cov_path_wide): the right-hand sides of the walks of one query, sized by the widest front on its paths
+  double* cov_zscr = nullptr; size_t cov_zscr_cap = 0;
+  int cov_path_form = 0;             // pps_debug_cov_path_form: 0 = k_cov_path where its LDS fits, 1 = always the wide kernel
   // pps_assoc_gate (pps_gate.cpp): result of a call on the device ([status | d2 | best], the status word zero between calls) and one
   // ticket per measurement (zero between calls); the request and the strips share cov_breq / cov_strip with pps_cov_block
   double* gate_out = nullptr; size_t gate_out_cap = 0; bool gate_clean = false;
@@ -293,18 +300,26 @@ inline hipError_t chi2_trial_launch(pps_graph* g, double* host_result, double se
   return launch_chi2_trial(g->dev, host_result, seq, g->stream);
 }
 // ---- pps_cov.cpp ----
-inline void cov_invalidate(pps_graph* g) { g->cov_valid = false; }   // estimate, measurements or topology are about to change
+inline void cov_invalidate(pps_graph* g) { g->cov_valid = g->cov_factor_valid = false; }   // estimate, measurements or topology are about to change
 void cov_release(pps_graph* g);                // pps_graph_destroy: the recovery's own device buffers
 bool cov_current(const pps_graph* g);          // is there a recovery that belongs to the estimate, the measurements and the topology as they are?
+bool cov_factor_current(const pps_graph* g);   // ... or at least its factor (pps_cov_factor)?
 extern const char* const kNoRecovery;          // the text of the PPS_ESTATE answer when there is none
+extern const char* const kFactorOnly;          // ... and when there is a factor, asked for the selected inverse
 // where a node's scalars sit in the elimination order: its front and the local index of its first pivot
 struct CovNode { int front, local, dim, epos, voff; };
 int cov_node(pps_graph* g, int id, CovNode* out);      // id check (PPS_EINVAL) + dim; the rest by cov_locate, with a current recovery only
 int cov_locate(pps_graph* g, int id, CovNode* n);
 // the walks of a query as k_cov_path takes them (pps_cov.h), shared by pps_cov_block and pps_assoc_gate
-struct CovWalks { std::vector<pps::CovWalk> walks; std::vector<pps::CovStep> steps; std::vector<int> step_end; int K = 0; long long n_strip = 0; };
+struct CovWalks { std::vector<pps::CovWalk> walks; std::vector<pps::CovStep> steps; std::vector<int> step_end; int K = 0; long long n_strip = 0;
+                  int max_rows = 1; };            // max_rows: the widest front (p + b) on the paths of this query
 int cov_build_walks(pps_graph* g, const std::vector<int>& ids, std::vector<CovNode>& nd, CovWalks* out);      // locates the nodes (cov_locate), too
 int cov_common_pivots(const pps_graph* g, const CovWalks& cw, int a, int b);                                    // walks a, b: pivots of their common ancestors
+// the walk kernel of a query -- k_cov_path where its LDS fits the graph's fronts, k_cov_path_wide otherwise (or when the handle asks for it).
+// cov_walk_scratch reserves the wide kernel's right-hand sides (PPS_ENOMEM) and belongs BEFORE the query's upload; cov_launch_walks is the launch.
+bool cov_walk_wide(const pps_graph* g);
+int cov_walk_scratch(pps_graph* g, const CovWalks& cw);
+hipError_t cov_launch_walks(pps_graph* g, const CovWalks& cw, const pps::CovWalk* walks, const pps::CovStep* steps, double* out);
 // a device buffer of one of the covariance calls, grown by a quarter when it is too small
 template <class T>
 int cov_reserve(pps_graph* g, T** buf, size_t* cap, size_t count) {
