@@ -187,6 +187,24 @@ int pps_cov_factor(pps_graph* g);
  * kernel where its LDS fits the graph's fronts, the wide kernel otherwise), 1 = always the wide kernel -- to compare the two on any band
  * graph.  PPS_EINVAL: NULL handle, another form.  Changes no validity.  Found by symbol lookup. */
 int pps_debug_cov_path_form(pps_graph* g, int form);
+/* pps_cov_select: the selected inverse in whatever K3 form the graph is solved in -- what pps_cov_recover computes, on loop-closure graphs too.
+ *   band graph         exactly pps_cov_recover: the same launches, the same bits, both validity flags.
+ *   dense-front graph  the factor stage of pps_cov_factor, then one root -> leaves pass over the dense fronts (pps_cov_dense.hip: G = L_B L_A^-1
+ *                      and L_A^-T L_A^-1 of all fronts in one launch, then per tree level a gather of Sigma_BB through the child map and the two
+ *                      products on the matrix cores: 1 + 3 x levels launches).  Afterwards pps_cov_marginals / _access / _joint answer as on a band
+ *                      graph (every node's diagonal block, every pair that shares a front), pps_cov_block and pps_assoc_gate as after pps_cov_factor.
+ *   neither form       PPS_ESTATE with the text of pps_cov_factor (the one-launch-per-level LDS kernels keep no factor).
+ * Validity, invalidation and PPS_ENOTPD are those of pps_cov_recover: the call starts by clearing both flags, sets both when it succeeds, and every
+ * call that ends a recovery ends this one.  A later pps_cov_factor keeps the factor alone (the read calls then name both entry points), a later
+ * pps_cov_recover on a dense-front graph is refused as always and ends the selection.  PPS_ENOMEM (never an abort): no device memory for the
+ * selected inverse or for the scratch of the pass (two arrays of the factor's size).  The estimate, the linearisation point, the LM trace and the
+ * stats stay untouched.  pps_cov_last_times: sec[0] the whole call, sec[1] the root -> leaves pass.
+ * Found by symbol lookup (dlsym "pps_cov_select"), like the calls above; PPS_VERSION was not bumped. */
+int pps_cov_select(pps_graph* g);
+/* diagnostics, per handle: form 1 = pps_cov_select takes the dense-front pass on a band graph too (its factor sits in the same layout), so that
+ * fronts whose shapes are no multiples of 4, 16 or 64 pass through the tiled kernels and can be compared with pps_cov_recover; 0 = as above.
+ * PPS_EINVAL: NULL handle, another form.  Changes no validity.  Found by symbol lookup. */
+int pps_debug_cov_select_form(pps_graph* g, int form);
 /* Sigma(rows, cols) for ANY nodes, inside the pattern of the factor or not (the reference's marginal(node_list) / access(pairs) without
  * the limit above): out is (sum dim(rows)) x (sum dim(cols)), row-major, nodes in the order given.  cols == NULL (nc ignored): cols =
  * rows, the joint marginal, exactly symmetric.  A node may appear in both lists, not twice in one.

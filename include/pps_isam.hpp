@@ -378,6 +378,8 @@ protected:
 // reference's marginal(node_list) / access(pairs) answer for nodes that share no front, e.g. the current pose against an old landmark.
 // They and gate() need the factor alone: where pps_cov_recover refuses the graph (PPS_ESTATE: the dense-front form) they go on with
 // pps_cov_factor, so that they answer after a loop closure, too.  On every other graph they make the calls they always made.
+// select() computes the selected inverse in whatever form the graph is solved in (pps_cov_select): after it marginal() and access() answer on
+// a dense-front graph as well, until the next change of the graph ends the recovery; without it they throw there as they always did.
 class Covariances {
   Slam* _slam;
   int _probe_id = 0;
@@ -393,6 +395,8 @@ public:
   typedef std::list<std::list<Node*> > node_lists_t;
   typedef std::list<std::pair<Node*, Node*> > node_pair_list_t;
   explicit Covariances(Slam* slam) : _slam(slam) {}
+  // the selected inverse of the current state, band or dense-front form; ensure() finds it valid afterwards
+  void select() const { detail::check(pps_cov_select(handle()), handle(), "pps_cov_select"); }
   // marginal covariance over a list of nodes (a single node: its 6 x 6 / 3 x 3 block)
   MatrixXd marginal(const std::list<Node*>& nodes) const {
     ensure();

@@ -132,7 +132,7 @@ SYMBOLS = [
     "pps_edges_host_select", "pps_popup_fill_depth", "pps_popup_plane_info", "pps_popup_mask_host",
     "pps_multi_create", "pps_multi_destroy", "pps_multi_last_error", "pps_multi_optimize", "pps_multi_rounds", "pps_multi_save_state", "pps_multi_restore_state", "pps_multi_set_profiling", "pps_multi_phase_times", "pps_popup_polygons_simple", "pps_analysis_reuse", "pps_analysis_kept",
     "pps_cov_recover", "pps_cov_marginals", "pps_cov_access", "pps_cov_joint", "pps_cov_last_times",
-    "pps_cov_factor", "pps_debug_cov_path_form",
+    "pps_cov_factor", "pps_debug_cov_path_form", "pps_cov_select", "pps_debug_cov_select_form",
     "pps_cov_block", "pps_cov_block_last", "pps_assoc_gate", "pps_assoc_gate_last", "pps_debug_assoc_gate_records",
     "pps_map_default_select", "pps_map_create", "pps_map_destroy", "pps_map_last_error", "pps_map_add_frame", "pps_map_redirect",
     "pps_map_info", "pps_map_chunks", "pps_map_built_chunks", "pps_map_select_host", "pps_map_build", "pps_map_download",
@@ -259,6 +259,8 @@ def lib():
         L.pps_cov_last_times.argtypes = [C.c_void_p, _dp]
         L.pps_cov_factor.argtypes = [C.c_void_p]
         L.pps_debug_cov_path_form.argtypes = [C.c_void_p, C.c_int]
+        L.pps_cov_select.argtypes = [C.c_void_p]
+        L.pps_debug_cov_select_form.argtypes = [C.c_void_p, C.c_int]
         L.pps_cov_block.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int, _ip, _dp]
         L.pps_cov_block_last.argtypes = [C.c_void_p, _dp, _ip]
         L.pps_assoc_gate.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip, _dp, _ip]
@@ -436,6 +438,16 @@ class Graph:
         solved in, band or dense-front.  All that cov_block and assoc_gate read; cov_marginals / cov_access / cov_joint need cov_recover."""
         self._ck(self.L.pps_cov_factor(self.h))
 
+    def cov_select(self):
+        """The selected inverse in whatever form the graph is solved in (pps_cov_select): cov_recover on a band graph, the factor of cov_factor
+        and a root -> leaves pass over the dense fronts on a loop-closure graph.  cov_marginals / cov_access / cov_joint answer afterwards,
+        cov_block and assoc_gate as after cov_factor."""
+        self._ck(self.L.pps_cov_select(self.h))
+
+    def debug_cov_select_form(self, form):
+        """diagnostics: 1 = cov_select takes the dense-front pass on a band graph too, 0 = cov_recover there"""
+        self._ck(self.L.pps_debug_cov_select_form(self.h, int(form)))
+
     def debug_cov_path_form(self, form):
         """diagnostics: 0 = cov_block / assoc_gate choose their path-walk kernel by the graph's fronts, 1 = always the kernel for wide fronts"""
         self._ck(self.L.pps_debug_cov_path_form(self.h, int(form)))
@@ -528,7 +540,7 @@ class Graph:
         s = C.c_double(); n = C.c_int(); self._ck(self.L.pps_assoc_gate_last(self.h, C.byref(s), C.byref(n))); return s.value, n.value
 
     def cov_last_times(self):
-        """device seconds of the last cov_recover: (whole call, root -> leaves pass alone); of the last cov_factor: (whole call, 0)"""
+        """device seconds of the last cov_recover or cov_select: (whole call, root -> leaves pass alone); of the last cov_factor: (whole call, 0)"""
         s = (C.c_double * 2)(); self._ck(self.L.pps_cov_last_times(self.h, s)); return float(s[0]), float(s[1])
 
     # ---- state ----

@@ -6,6 +6,8 @@
 //   pps_cov_factor     the same without the selected inverse: K1 at the estimate, K2, the lambda = 0 factorisation in the K3 form the graph has
 //                      (band stages or the dense-front levels), the pivot criterion in one launch (pps_cov_wide.hip).  All pps_cov_block and
 //                      pps_assoc_gate need, and the only recovery a dense-front graph has
+//   pps_cov_select     the selected inverse in whatever form the graph has: pps_cov_recover on a band graph; on a dense-front graph the factor
+//                      stage of pps_cov_factor, then the root -> leaves pass of pps_cov_dense.hip (one launch over all fronts, three per level)
 //   pps_cov_marginals / _access / _joint   look the requested blocks up in the fronts (host tables built at recovery time), collect them with
 //                      one gather launch and one copy
 // Every entry of Sigma inside the pattern of L is available: the diagonal block of every node and the cross block of every pair of nodes
@@ -35,6 +37,9 @@ void cov_release(pps_graph* g) {
   if (g->cov_strip) (void)hipFree(g->cov_strip);
   if (g->cov_bout) (void)hipFree(g->cov_bout);
   if (g->cov_zscr) (void)hipFree(g->cov_zscr);
+  if (g->cov_G) (void)hipFree(g->cov_G);
+  if (g->cov_dtab) (void)hipFree(g->cov_dtab);
+  g->cov_G = nullptr; g->cov_G_cap = 0; g->cov_dtab = nullptr; g->cov_dtab_cap = 0; g->cov_dtab_version = -1;
   gate_release(g);
   for (hipEvent_t& e : g->cov_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   for (hipEvent_t& e : g->cov_bev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
@@ -247,13 +252,17 @@ static int cov_recover_impl(pps_graph* g) {
   return PPS_OK;
 }
 
+static std::string no_factor_array(const pps_graph* g) {
+  return "pps_cov_factor: the graph is solved by the one-launch-per-level LDS kernels (max front " + std::to_string(g->an.max_front) +
+         " scalars, neither the band nor the dense-front form), whose panels do not pass through the factor array: no factor to keep";
+}
+
 // pps_cov_factor: the recovery without the selected inverse, in whatever K3 form the graph has
 static int cov_factor_impl(pps_graph* g) {
   int rc;
   if (!g->analyzed || g->analysis_stale) { rc = pps_analyze(g); if (rc != PPS_OK) return rc; }
   if (!g->use_band && !g->use_dense)
-    return fail(g, PPS_ESTATE, "pps_cov_factor: the graph is solved by the one-launch-per-level LDS kernels (max front " + std::to_string(g->an.max_front) +
-                               " scalars, neither the band nor the dense-front form), whose panels do not pass through the factor array: no factor to keep");
+    return fail(g, PPS_ESTATE, no_factor_array(g));
   rc = prepare_solve(g); if (rc != PPS_OK) return rc;
   const Analysis& A = g->an;
   const DevGraph& d = g->dev;
@@ -311,6 +320,131 @@ static int cov_factor_impl(pps_graph* g) {
   g->cov_version = g->upload_version;
   g->cov_factor_valid = true;
   return PPS_OK;
+}
+
+// the device buffers of the dense-front pass: PPS_ENOMEM, never an abort, when one cannot be had
+template <class T>
+static int cov_select_reserve(pps_graph* g, T** buf, size_t* cap, size_t count, const char* what) {
+  if (cov_reserve(g, buf, cap, count) == PPS_OK) return PPS_OK;
+  (void)hipGetLastError();
+  return fail(g, PPS_ENOMEM, std::string("pps_cov_select: no device memory for ") + what + " (" + std::to_string(count * sizeof(T)) + " bytes)");
+}
+
+// pps_cov_select on a dense-front tree (or, with pps_debug_cov_select_form, on a band tree): the lambda = 0 factor in the form the graph is
+// solved in, then the root -> leaves pass of pps_cov_dense.hip.  It reads L, f_p, f_b, f_Loff, f_Uoff, cmap, the parents and the level lists.
+static int cov_select_dense_impl(pps_graph* g) {
+  int rc = prepare_solve(g); if (rc != PPS_OK) return rc;
+  const Analysis& A = g->an;
+  const DevGraph& d = g->dev;
+  for (hipEvent_t& e : g->cov_ev) if (!e) HIP_TRY(g, hipEventCreate(&e));
+  const size_t n_panel = (size_t)std::max<int64_t>(1, A.L_size);
+  rc = cov_select_reserve(g, &g->cov_S, &g->cov_S_cap, n_panel, "the selected inverse"); if (rc != PPS_OK) return rc;
+  rc = cov_select_reserve(g, &g->cov_G, &g->cov_G_cap, n_panel, "the scratch of L_B L_A^-1"); if (rc != PPS_OK) return rc;
+  if (g->cov_dtab_version != g->upload_version) {
+    rc = cov_build_tables(g); if (rc != PPS_OK) return rc;
+    if ((int)A.level_off.size() < A.n_levels + 1 || A.level_off[A.n_levels] != A.n_fronts) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (level lists)");
+    std::vector<char> listed((size_t)std::max(1, A.n_fronts), 0);
+    for (int l = 0; l < A.n_levels; l++)
+      for (int k = A.level_off[l]; k < A.level_off[l + 1]; k++) {
+        const int s = A.level_fronts[k];
+        if (s < 0 || s >= A.n_fronts || listed[s] || A.f_level[s] != l) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (level lists)");
+        listed[s] = 1;
+      }
+    for (int s = 0; s < A.n_fronts; s++) {               // what the kernels index with: checked here, before anything is launched
+      const int q = A.f_parent[s], p = A.f_p[s], b = A.f_b[s];
+      if (b < 0 || (b > 0 && (q < 0 || q >= A.n_fronts || A.f_level[q] <= A.f_level[s] || A.f_cmap_off[s + 1] - A.f_cmap_off[s] < b)))
+        return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (parent / child map)");
+      for (int k = 0; k < b; k++) {
+        const int r = A.cmap[A.f_cmap_off[s] + k];
+        if (r < 0 || r >= A.f_p[q] + A.f_b[q]) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (child map entry)");
+      }
+      const int64_t u_end = s + 1 < A.n_fronts ? A.f_Uoff[s + 1] : A.U_size, l_end = s + 1 < A.n_fronts ? A.f_Loff[s + 1] : A.L_size;
+      if (p < 1 || p > 64 || A.f_Uoff[s] < 0 || u_end - A.f_Uoff[s] < (int64_t)b * b || A.f_Loff[s] < 0 || l_end - A.f_Loff[s] < (int64_t)(p + b) * p)
+        return fail(g, PPS_ESTATE, "covariance: front outside the supported shapes");
+    }
+    // work-item prefix sums: [all fronts | per level: gather, strips]
+    std::vector<int> tab;
+    tab.push_back(0);
+    for (int s = 0; s < A.n_fronts; s++) tab.push_back(tab.back() + cov_dense_pre_items(A.f_b[s]));
+    g->cov_dpre_items = tab.back();
+    g->cov_dlevel.assign((size_t)4 * std::max(1, A.n_levels), 0);
+    for (int l = 0; l < A.n_levels; l++)
+      for (int kind = 0; kind < 2; kind++) {
+        const size_t at = tab.size();
+        int sum = 0;
+        tab.push_back(0);
+        for (int k = A.level_off[l]; k < A.level_off[l + 1]; k++) {
+          const int b = A.f_b[A.level_fronts[k]];
+          sum += kind == 0 ? cov_dense_gather_items(b) : cov_dense_strip_items(b);
+          tab.push_back(sum);
+        }
+        g->cov_dlevel[4 * l + 2 * kind] = (int)at; g->cov_dlevel[4 * l + 2 * kind + 1] = sum;
+      }
+    rc = cov_select_reserve(g, &g->cov_dtab, &g->cov_dtab_cap, tab.size(), "the work lists"); if (rc != PPS_OK) return rc;
+    rc = cov_select_reserve(g, &g->cov_parent, &g->cov_parent_cap, (size_t)std::max(1, A.n_fronts), "the parent list"); if (rc != PPS_OK) return rc;
+    g->cov_parent_version = -1;                          // (pps_cov_recover has its own, stricter shape test: it checks and uploads again)
+    HIP_TRY(g, hipMemcpyAsync(g->cov_dtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(g, hipMemcpyAsync(g->cov_parent, A.f_parent.data(), (size_t)A.n_fronts * sizeof(int), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));         // (tab and f_parent are host memory that does not outlive this call)
+    g->cov_dtab_version = g->upload_version;
+    g->cov_tables_version = g->upload_version;
+  }
+  if (!g->status_clean) {
+    HIP_TRY(g, launch_clear_status(d, g->stream));
+    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
+  }
+  g->status_clean = false;
+  HIP_TRY(g, hipEventRecord(g->cov_ev[0], g->stream));
+  // the factor stage of pps_cov_factor
+  HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, true));      // jacobian() at the ESTIMATE, robustified with a cost function set
+  HIP_TRY(g, launch_hblocks(d, g->stream, nullptr, k1_products(d, g->props.jacobian_mode)));
+  if (g->use_band) {
+    for (int st = 0; st < A.n_stages; st++)
+      HIP_TRY(g, launch_band_factor(d, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_factor[st], A.stage_max_front[st], 0.0, g->stream));
+  } else {
+    HIP_TRY(g, hipMemsetAsync(d.L, 0, (size_t)A.L_size * 8, g->stream));
+    HIP_TRY(g, launch_dense_hpush(d, g->max_el_per_front, 0.0, g->stream));
+    for (int l = 0; l < A.n_levels; l++) {
+      const int base = A.level_off[l] + l, cnt = A.level_off[l + 1] - A.level_off[l];
+      HIP_TRY(g, launch_dense_factor_level(d, A.level_off[l], cnt, g->d_dw_asm + base, g->dw_asm[base + cnt], g->d_dw_pan + base, g->dw_pan[base + cnt],
+                                           g->d_dw_trl + base, g->dw_trl[base + cnt], g->stream));
+    }
+  }
+  HIP_TRY(g, launch_cov_pivots(d, A.n_fronts, g->stream));
+  HIP_TRY(g, hipEventRecord(g->cov_ev[1], g->stream));
+  // the root -> leaves pass: the update matrices in d.U are dead once their parents are assembled
+  const CovDenseExtents ext{(long long)A.L_size, (long long)A.U_size};
+  HIP_TRY(g, launch_cov_dense_pre(d, g->cov_S, g->cov_G, ext, g->cov_dtab, g->cov_dpre_items, A.n_fronts, g->stream));
+  for (int l = A.n_levels - 1; l >= 0; l--) {
+    const int* lv = g->cov_dlevel.data() + 4 * l;
+    HIP_TRY(g, launch_cov_dense_level(d, g->cov_S, g->cov_G, ext, g->cov_parent, A.level_off[l], A.level_off[l + 1] - A.level_off[l], g->cov_dtab + lv[0], lv[1],
+                                      g->cov_dtab + lv[2], lv[3], g->stream));
+  }
+  HIP_TRY(g, hipEventRecord(g->cov_ev[2], g->stream));
+  double status[4] = {0, 0, 0, 0};
+  HIP_TRY(g, hipMemcpyAsync(status, d.result_dev, sizeof status, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, g->cov_ev[0], g->cov_ev[2]) == hipSuccess) g->cov_sec[0] = 1e-3 * ms;
+  if (hipEventElapsedTime(&ms, g->cov_ev[1], g->cov_ev[2]) == hipSuccess) g->cov_sec[1] = 1e-3 * ms;
+  if (status[2] != 0.0) {
+    HIP_TRY(g, launch_clear_status(d, g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+  }
+  g->status_clean = true;
+  if (status[2] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: pps_cov_select met an index outside its front");
+  if (status[2] != 0.0)
+    return fail(g, PPS_ENOTPD, "normal equations not positive definite at lambda = 0 (a pivot was not positive, or below 1e-7 of the largest pivot of its front): no covariance");
+  g->cov_version = g->upload_version;
+  g->cov_valid = g->cov_factor_valid = true;
+  return PPS_OK;
+}
+
+static int cov_select_impl(pps_graph* g) {
+  if (!g->analyzed || g->analysis_stale) { const int rc = pps_analyze(g); if (rc != PPS_OK) return rc; }
+  if (g->use_band && g->cov_select_form == 0) return cov_recover_impl(g);      // the band form: pps_cov_recover, launch for launch
+  if (!g->use_band && !g->use_dense) return fail(g, PPS_ESTATE, no_factor_array(g));
+  return cov_select_dense_impl(g);
 }
 
 bool cov_walk_wide(const pps_graph* g) {
@@ -379,6 +513,33 @@ int pps_cov_factor(pps_graph* g) {
     g->stats = s; }
   if (rc == PPS_EHIP) abandon_device_copy(g);
   return rc;
+}
+
+int pps_cov_select(pps_graph* g) {
+  if (!g) return PPS_EINVAL;
+  cov_invalidate(g);
+  if (g->n_live_nodes == 0) return fail(g, PPS_ESTATE, "empty graph");
+  if (g->n_live_factors == 0) return fail(g, PPS_ENOTPD, "normal equations not positive definite: the graph has no factor");
+  // like pps_cov_recover: no solve, the figures of the last one stay
+  const pps_stats saved = g->stats;
+  const int profiling = g->profiling;
+  g->profiling = 0;
+  const unsigned long long launches0 = g->launches0;
+  const int rc = cov_select_impl(g);
+  g->profiling = profiling;
+  g->launches0 = launches0;
+  { pps_stats s = saved;
+    s.n_fronts = g->stats.n_fronts; s.n_levels = g->stats.n_levels; s.max_front = g->stats.max_front; s.nnz_L = g->stats.nnz_L;
+    g->stats = s; }
+  if (rc == PPS_EHIP) abandon_device_copy(g);
+  return rc;
+}
+
+int pps_debug_cov_select_form(pps_graph* g, int form) {
+  if (!g) return PPS_EINVAL;
+  if (form != 0 && form != 1) return fail(g, PPS_EINVAL, "pps_debug_cov_select_form: form is 0 (pps_cov_recover on a band graph) or 1 (always the dense-front pass)");
+  g->cov_select_form = form;
+  return PPS_OK;
 }
 
 int pps_debug_cov_path_form(pps_graph* g, int form) {

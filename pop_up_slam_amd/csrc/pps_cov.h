@@ -59,4 +59,22 @@ inline size_t cov_wide_scratch(int max_front) { return (size_t)2 * max_front * 6
 hipError_t launch_cov_path_wide(const DevGraph& d, const CovWalk* walks, int n_walks, const CovStep* steps, int n_steps_total, int K, int max_front,
                                 double* Z, long long n_scratch, double* Y, long long n_strip, double* out, hipStream_t st);
 
+// ---- pps_cov_select: the selected inverse on dense-front trees (pps_cov_dense.hip) ----
+// Same recursion and the same results in the same places as launch_cov_level -- S in the panel layout of L, Sigma_BB (b x b, ld = b) in the
+// front's update-matrix slot -- for fronts of p <= 64 pivots and any number of rows.  G = L_B L_A^-1 of every front sits in a scratch
+// buffer in the panel layout (rows p .. p + b - 1 of a front's panel; the other rows are not touched).
+struct CovDenseExtents { long long n_panel, n_U; };      // doubles in S and in G (both: L_size) | in d.U
+// work items per front: W and the 256-row slabs of G, 32-row pieces of Sigma_BB, 64-row strips of Sigma_BA
+int cov_dense_pre_items(int b);
+int cov_dense_gather_items(int b);
+int cov_dense_strip_items(int b);
+// G and W = L_A^-T L_A^-1 (into the Sigma_AA rows of S) of all fronts; off: prefix sums of cov_dense_pre_items over the fronts 0 .. n_fronts - 1
+// (n_fronts + 1 entries, device), n_items its last entry
+hipError_t launch_cov_dense_pre(const DevGraph& d, double* S, double* G, CovDenseExtents ext, const int* off, int n_items, int n_fronts, hipStream_t st);
+// one tree level, parents done: gather, Sigma_BA, Sigma_AA (three launches).  off_gather / off_strip: prefix sums of the items of the
+// level's fronts in level_fronts order (level_count + 1 entries each, device).  An index outside its front raises d.result_dev[2] to
+// kStatusInternal before anything of that front is written.
+hipError_t launch_cov_dense_level(const DevGraph& d, double* S, const double* G, CovDenseExtents ext, const int* parent, int level_begin, int level_count,
+                                  const int* off_gather, int n_gather, const int* off_strip, int n_strip, hipStream_t st);
+
 }  // namespace pps

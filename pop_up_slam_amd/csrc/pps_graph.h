@@ -225,6 +225,13 @@ struct pps_graph {
   // the path walk for wide fronts (k_cov_path_wide): the right-hand sides of the walks of one query, sized by the widest front on its paths
   double* cov_zscr = nullptr; size_t cov_zscr_cap = 0;
   int cov_path_form = 0;             // pps_debug_cov_path_form: 0 = k_cov_path where its LDS fits, 1 = always the wide kernel
+  // pps_cov_select on a dense-front tree (pps_cov_dense.hip): G = L_B L_A^-1 of every front in the panel layout of L, and the work-item
+  // prefix sums of its launches -- [all fronts: G slabs | per level: gather pieces, Sigma_BA strips] -- on the device (cov_dtab) with their places
+  double* cov_G = nullptr; size_t cov_G_cap = 0;
+  int* cov_dtab = nullptr; size_t cov_dtab_cap = 0; int cov_dtab_version = -1;      // upload_version the tables (and cov_parent) were checked and uploaded for
+  int cov_dpre_items = 0;
+  std::vector<int> cov_dlevel;       // per level, 4 ints: place of the gather sums in cov_dtab, their total, place of the strip sums, their total
+  int cov_select_form = 0;           // pps_debug_cov_select_form: 1 = pps_cov_select takes the dense-front pass on a band graph too
   // pps_assoc_gate (pps_gate.cpp): result of a call on the device ([status | d2 | best], the status word zero between calls) and one
   // ticket per measurement (zero between calls); the request and the strips share cov_breq / cov_strip with pps_cov_block
   double* gate_out = nullptr; size_t gate_out_cap = 0; bool gate_clean = false;
