@@ -256,6 +256,53 @@ int pps_assoc_gate_last(const pps_graph* g, double* kernel_sec, int* launches);
  * copied when rec is NULL or cap is smaller.  PPS_ESTATE before the first successful gate call of the handle. */
 int pps_debug_assoc_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed);
 
+/* ---- Mahalanobis merge gate between plane landmarks, from the recovered covariances ---------------------------
+ * pps_assoc_gate asks "does this measurement belong to that landmark"; this call asks what a map needs after a revisit: "are these two
+ * landmarks the same wall" -- the decision of Mapper_mono::findLoopPlane (Mapping.cpp:174-252), made there by the 2-D image distance of
+ * end points against frame 0.  For two distinct live plane nodes a, b, a the one that comes FIRST in the list, in the tangent coordinates
+ * of Plane3d::exmap_3dof (the column order of pps_eval_factor):
+ *     e   = r(a | pi_b)     residual of a Plane3d_Factor on node a with measurement pi_b (b's estimate) and identity sqrt information
+ *     J_a = its 3 x 3 Jacobian by central differences (eps = 1e-4, the device's step quaternions): pps_eval_factor's bits for such a
+ *           factor in PPS_JAC_NUMERIC
+ *     J_b = -J(b | pi_a)    the NEGATED Jacobian of the mirrored factor (node b, measurement pi_a), the same differences
+ *     S   = J_a Sigma_aa J_a' + J_b Sigma_bb J_b' + J_a Sigma_ab J_b' + J_b Sigma_ba J_a' + floor_var I
+ *     d2  = e' S^-1 e       (3 x 3 Cholesky solve); chi-square with 3 degrees of freedom for one wall: 7.815 is the usual (0.95) threshold
+ * The Jacobians are ALWAYS central differences, whatever the handle's jacobian_mode; Sigma is whatever linearisation the recovery used
+ * (jacobian_mode, and the robustified system with a cost function set -- e and the Jacobians are never robustified: the call is not
+ * refused with a cost function, unlike pps_assoc_gate).  floor_var >= 0 (rad^2, 0 allowed) stands for plane error the graph does not
+ * model and keeps S positive definite for perfectly correlated pairs.
+ *   plane_ids  n_planes node ids; NULL (n_planes ignored): all live planes in insertion order
+ *   d2         (may be NULL) n x n, row-major, diagonal 0, EXACTLY symmetric: a pair is computed once, for the list order i < j, and
+ *              mirrored.  When NULL nothing n x n is copied to the host.
+ *   best       (may be NULL) n: per row the index INTO plane_ids of the smallest finite off-diagonal d2, the first on ties, -1 if none
+ *   pairs, n_pairs  (may be NULL together) all index pairs (i < j) with finite d2 < threshold, ascending by (i, j), 2 ints each; at most
+ *              cap_pairs are written, *n_pairs is always the full count (pairs may be NULL with cap_pairs == 0: the count alone)
+ * A pair whose S is NOT positive definite (a pivot of its 3 x 3 factor not positive or not finite) gets d2 = NaN, is never `best` and
+ * never in `pairs`, and the call still returns PPS_OK; pps_merge_gate_last reports how many there were.  This differs from pps_assoc_gate
+ * (PPS_ENOTPD) on purpose: one degenerate pair among n^2 / 2 must not void the query.
+ * Everything is computed on the device: one upload, two launches (the root-path walks of pps_cov_block for the n planes, ONE pair
+ * kernel: a wave per pair, the common ancestors of a pair found on the device from the tree), one copy.  A pair's d2 does not depend on
+ * which other planes are in the call as long as the pair keeps its order.  The estimate, the linearisation point, the LM trace, the
+ * stats and the recovery stay untouched: a pps_batch_optimize after the call is bit for bit the one without it.
+ *   PPS_EINVAL  (checked on the host before any launch) NULL handle; a negative count; more than 65535 planes; floor_var not finite or
+ *               negative; threshold not finite; an unknown, removed or non-plane id; an id listed twice; d2, best and pairs / n_pairs all
+ *               NULL; pairs without n_pairs, or n_pairs without pairs and cap_pairs > 0
+ *   PPS_OK      with the outputs untouched for fewer than 2 planes -- answered before the recovery is looked at
+ *   PPS_ESTATE  no valid factor: the text and the validity rules of pps_cov_block (either recovery provides the factor; a dense-front
+ *               graph has it after pps_cov_factor)
+ *   PPS_ENOMEM  the strips, the walk scratch or the n x n result cannot be allocated
+ * Found by symbol lookup, like the pps_cov_* calls; PPS_VERSION was not bumped. */
+int pps_merge_gate(pps_graph* g, int n_planes, const int* plane_ids, double floor_var, double threshold, double* d2, int* best, int cap_pairs,
+                   int* pairs, int* n_pairs);
+/* the last pps_merge_gate: device seconds (HIP events) around its two kernels, the kernel launches it made, and the number of its pairs
+ * whose S was not positive definite (each may be NULL) */
+int pps_merge_gate_last(const pps_graph* g, double* kernel_sec, int* launches, int* n_not_pd);
+/* diagnostics: J_a, J_b and e of every pair of the last successful pps_merge_gate, as the pair kernel evaluated them: 21 doubles per pair
+ * [J_a 3 x 3 | J_b 3 x 3 | e 3], row-major, pair (i < j) at index i * n - i (i + 1) / 2 + (j - i - 1), so that a test can compare them
+ * with pps_eval_factor bit for bit.  *needed = the number of doubles; nothing is copied when rec is NULL or cap is smaller.  PPS_ESTATE
+ * before the first successful call of the handle, and after a call of more than 262144 pairs (the records of such a call are not kept). */
+int pps_debug_merge_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed);
+
 /* ---- robust cost functions: Slam::set_cost_function (Slam.h; Factor::error, Factor.h:67-77; isam/robust.h) ------
  * With a cost function set, every evaluation of a factor's error replaces each whitened component by
  *     r_i <- sign(r_i) sqrt(rho(r_i)),  sign(0) = +1

@@ -24,6 +24,7 @@
 #include <list>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pps.h"
@@ -376,7 +377,7 @@ protected:
 // marginal() and access() keep that strict in-pattern contract (they read the selected inverse and throw for anything outside it).
 // block() and marginal_any() are the unrestricted forms: any nodes, by root-path solves on the same factor (pps_cov_block) -- what the
 // reference's marginal(node_list) / access(pairs) answer for nodes that share no front, e.g. the current pose against an old landmark.
-// They and gate() need the factor alone: where pps_cov_recover refuses the graph (PPS_ESTATE: the dense-front form) they go on with
+// They, gate() and merge_gate() need the factor alone: where pps_cov_recover refuses the graph (PPS_ESTATE: the dense-front form) they go on with
 // pps_cov_factor, so that they answer after a loop closure, too.  On every other graph they make the calls they always made.
 // select() computes the selected inverse in whatever form the graph is solved in (pps_cov_select): after it marginal() and access() answer on
 // a dense-front graph as well, until the next change of the graph ends the recovery; without it they throw there as they always did.
@@ -454,6 +455,31 @@ public:
   MatrixXd gate(Pose3d_Node* pose, const std::vector<Plane3d>& measurements, const std::vector<Noise>& noises, const std::list<Node*>& planes) const {
     std::vector<int> best;
     return gate(pose, measurements, noises, planes, best);
+  }
+  // Mahalanobis merge gate between plane landmarks (pps_merge_gate): are two landmarks the same wall?  Entry (i, j) of d2 = e' S^-1 e, e the
+  // residual of a Plane3d_Factor on planes[i] (i < j: the one listed first) with planes[j]'s estimate as its measurement, S its covariance
+  // under the joint marginal of the two plus floor_var I (rad^2); chi-square with 3 degrees of freedom for one wall (7.815 at 0.95).  d2 is
+  // exactly symmetric with a zero diagonal; best[i] = index into `planes` of the smallest finite off-diagonal entry of row i, -1 if none;
+  // pairs = all (i, j), i < j, with finite d2 < threshold, ascending.  A pair whose S is not positive definite has d2 = NaN, is never best and
+  // never in pairs; n_not_pd counts them.  The Jacobians are central differences whatever the jacobian mode of the backend.
+  struct MergeGate { MatrixXd d2; std::vector<int> best; std::vector<std::pair<int, int> > pairs; int n_not_pd = 0; };
+  MergeGate merge_gate(const std::list<Node*>& planes, double floor_var = 0.0, double threshold = 7.815) const {
+    ensure_factor();
+    const std::vector<int> ids = ids_of(planes);
+    const int n = (int)ids.size();
+    MergeGate out;
+    out.d2 = MatrixXd(n, n);
+    for (int k = 0; k < n * n; k++) out.d2.data()[k] = 0.0;
+    out.best.assign(ids.size(), -1);
+    if (n < 2) return out;                                  // (no pair; a null plane list would ask the library for ALL planes)
+    const size_t cap = (size_t)n * (n - 1) / 2;
+    std::vector<int> flat(2 * cap);
+    int count = 0;
+    detail::check(pps_merge_gate(handle(), n, ids.data(), floor_var, threshold, out.d2.data(), out.best.data(), (int)cap, flat.data(), &count), handle(),
+                  "pps_merge_gate");
+    for (int k = 0; k < count; k++) out.pairs.emplace_back(flat[2 * k], flat[2 * k + 1]);
+    detail::check(pps_merge_gate_last(handle(), nullptr, nullptr, &out.n_not_pd), handle(), "pps_merge_gate_last");
+    return out;
   }
   std::list<MatrixXd> marginal(const node_lists_t& node_lists) const {
     std::list<MatrixXd> out;

@@ -134,6 +134,7 @@ SYMBOLS = [
     "pps_cov_recover", "pps_cov_marginals", "pps_cov_access", "pps_cov_joint", "pps_cov_last_times",
     "pps_cov_factor", "pps_debug_cov_path_form", "pps_cov_select", "pps_debug_cov_select_form",
     "pps_cov_block", "pps_cov_block_last", "pps_assoc_gate", "pps_assoc_gate_last", "pps_debug_assoc_gate_records",
+    "pps_merge_gate", "pps_merge_gate_last", "pps_debug_merge_gate_records",
     "pps_map_default_select", "pps_map_create", "pps_map_destroy", "pps_map_last_error", "pps_map_add_frame", "pps_map_redirect",
     "pps_map_info", "pps_map_chunks", "pps_map_built_chunks", "pps_map_select_host", "pps_map_build", "pps_map_download",
     "pps_map_last_times",
@@ -266,6 +267,9 @@ def lib():
         L.pps_assoc_gate.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, _ip, _dp, _ip]
         L.pps_assoc_gate_last.argtypes = [C.c_void_p, _dp, _ip]
         L.pps_debug_assoc_gate_records.argtypes = [C.c_void_p, C.c_int64, _dp, C.POINTER(C.c_int64)]
+        L.pps_merge_gate.argtypes = [C.c_void_p, C.c_int, _ip, C.c_double, C.c_double, _dp, _ip, C.c_int, _ip, _ip]
+        L.pps_merge_gate_last.argtypes = [C.c_void_p, _dp, _ip, _ip]
+        L.pps_debug_merge_gate_records.argtypes = [C.c_void_p, C.c_int64, _dp, C.POINTER(C.c_int64)]
         L.pps_set_cost_function.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.pps_get_cost_function.argtypes = [C.c_void_p, _ip, _dp]
         _i32p = C.POINTER(C.c_int32)
@@ -538,6 +542,44 @@ class Graph:
     def assoc_gate_last(self):
         """(device seconds around the two kernels, kernel launches) of the last assoc_gate"""
         s = C.c_double(); n = C.c_int(); self._ck(self.L.pps_assoc_gate_last(self.h, C.byref(s), C.byref(n))); return s.value, n.value
+
+    def merge_gate(self, plane_ids=None, floor_var=0.0, threshold=7.815, want_d2=True):
+        """Mahalanobis merge gate between plane landmarks (pps_merge_gate): are two landmarks the same wall?  plane_ids: the n planes
+        (None: all live planes in insertion order).  Returns (d2, best, pairs): d2 (n x n, exactly symmetric, zero diagonal; None with
+        want_d2=False -- nothing n x n is then copied from the device) = e' S^-1 e of every pair, e the plane-prior residual of the
+        first-listed plane against the other's estimate, S its covariance under their joint marginal from the last recovery plus
+        floor_var I (rad^2); best (n) = index into plane_ids of the smallest finite off-diagonal d2 per row (-1: none); pairs (m x 2) =
+        all (i, j), i < j, with finite d2 < threshold, ascending.  A pair whose S is not positive definite has d2 = NaN, is never
+        best and never in pairs (merge_gate_last counts them).  The Jacobians are central differences whatever jacobian_mode."""
+        ids = None if plane_ids is None else np.ascontiguousarray(plane_ids, dtype=np.int32).reshape(-1)
+        n = self.stats()["n_planes"] if ids is None else len(ids)
+        d2 = np.zeros((n, n)) if want_d2 else None
+        best = np.full(max(n, 1), -1, dtype=np.int32)
+        cap = min(max(n * (n - 1) // 2, 1), 4096)
+        while True:
+            pairs = np.zeros((cap, 2), dtype=np.int32); cnt = C.c_int(0)
+            self._ck(self.L.pps_merge_gate(self.h, n, None if ids is None else ids.ctypes.data_as(_ip), float(floor_var), float(threshold),
+                                           None if d2 is None else d2.ctypes.data_as(_dp), best.ctypes.data_as(_ip), cap, pairs.ctypes.data_as(_ip),
+                                           C.byref(cnt)))
+            if cnt.value <= cap:
+                return d2, best[:n].copy(), pairs[:cnt.value].copy()
+            cap = cnt.value                                  # (more pairs than the first guess: once more with room for all)
+
+    def merge_gate_records(self):
+        """diagnostics: (J_a, J_b, e) of every pair of the last merge_gate as the kernel evaluated them -- (P, 3, 3), (P, 3, 3), (P, 3), pair
+        (i < j) at index i n - i (i + 1) / 2 + (j - i - 1); J_a and e are pps_eval_factor's of a plane prior on a with measurement pi_b,
+        J_b the negated Jacobian of the mirrored prior"""
+        n = C.c_int64(0)
+        self._ck(self.L.pps_debug_merge_gate_records(self.h, 0, None, C.byref(n)))
+        rec = np.zeros(n.value)
+        self._ck(self.L.pps_debug_merge_gate_records(self.h, n.value, rec.ctypes.data_as(_dp), C.byref(n)))
+        rec = rec.reshape(-1, 21)
+        return rec[:, :9].reshape(-1, 3, 3).copy(), rec[:, 9:18].reshape(-1, 3, 3).copy(), rec[:, 18:].copy()
+
+    def merge_gate_last(self):
+        """(device seconds around the two kernels, kernel launches, pairs whose S was not positive definite) of the last merge_gate"""
+        s = C.c_double(); n = C.c_int(); k = C.c_int()
+        self._ck(self.L.pps_merge_gate_last(self.h, C.byref(s), C.byref(n), C.byref(k))); return s.value, n.value, k.value
 
     def cov_last_times(self):
         """device seconds of the last cov_recover or cov_select: (whole call, root -> leaves pass alone); of the last cov_factor: (whole call, 0)"""

@@ -41,6 +41,7 @@ void cov_release(pps_graph* g) {
   if (g->cov_dtab) (void)hipFree(g->cov_dtab);
   g->cov_G = nullptr; g->cov_G_cap = 0; g->cov_dtab = nullptr; g->cov_dtab_cap = 0; g->cov_dtab_version = -1;
   gate_release(g);
+  merge_release(g);
   for (hipEvent_t& e : g->cov_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   for (hipEvent_t& e : g->cov_bev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   g->cov_S = nullptr; g->cov_parent = nullptr; g->cov_req = nullptr; g->cov_out = nullptr;

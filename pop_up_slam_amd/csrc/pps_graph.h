@@ -8,6 +8,7 @@
 //   pps_frames.cpp   registered frames (measurement refresh on the device), data association, point re-projection
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
 //   pps_cov.cpp      marginal covariances from the factor (isam::Covariances); kernels in pps_cov.hip
+//   pps_gate.cpp     pps_assoc_gate (measurement against landmark); pps_merge.cpp: pps_merge_gate (landmark against landmark)
 //   pps_map.cpp      the dense map (pps_map: per-plane clouds of every frame, re-projected on the device); kernels in pps_map.hip
 #pragma once
 #include <hip/hip_runtime.h>
@@ -239,6 +240,14 @@ struct pps_graph {
   hipEvent_t gate_ev[2] = {nullptr, nullptr};
   double gate_sec = 0; int gate_launches = 0;             // the two kernels of the last call: device seconds, launches
   double* gate_rec = nullptr; size_t gate_rec_cap = 0; size_t gate_rec_n = 0;   // [Jp | Jl | r] per candidate of the last call (pps_debug_assoc_gate_records)
+  // pps_merge_gate (pps_merge.cpp): result of a call on the device ([status | best | flags | d2 n x n], the status word zero between calls) and
+  // one ticket per listed plane (zero between calls); the request and the strips share cov_breq / cov_strip with pps_cov_block
+  char* merge_out = nullptr; size_t merge_out_cap = 0; bool merge_clean = false;
+  unsigned int* merge_ticket = nullptr; size_t merge_ticket_cap = 0;
+  hipEvent_t merge_ev[2] = {nullptr, nullptr};
+  double merge_sec = 0; int merge_launches = 0, merge_not_pd = 0;      // the two kernels of the last call: device seconds, launches; its pairs without a positive definite S
+  double* merge_rec = nullptr; size_t merge_rec_cap = 0; size_t merge_rec_n = 0;   // [J_a | J_b | e] per pair of the last call (pps_debug_merge_gate_records)
+  bool merge_done = false;           // a call has succeeded on this handle
   // stats / trace
   pps_stats stats{};
   std::vector<double> tr_lambda, tr_chi2;
@@ -341,6 +350,8 @@ int cov_reserve(pps_graph* g, T** buf, size_t* cap, size_t count) {
 }
 // ---- pps_gate.cpp ----
 void gate_release(pps_graph* g);               // (from cov_release)
+// ---- pps_merge.cpp ----
+void merge_release(pps_graph* g);              // (from cov_release)
 // ---- pps_api.cpp ----
 void report_front_trace(pps_graph* g);        // PPS_TRACE: the per-front cycle counters of the last solve -> stderr
 
