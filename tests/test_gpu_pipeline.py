@@ -18,10 +18,13 @@ def _oracle_pipeline():
     return pl, g
 
 
-def test_popup_fused_with_incremental_solve(built):
+@pytest.mark.parametrize("async_popup", [False, True])
+def test_popup_fused_with_incremental_solve(built, async_popup):
+    """async_popup: the form bench.py and the C++ frame loop run -- the pop-up of frame k is not waited for, the graph takes its plane
+    equations as soon as the kernel has published them"""
     frames = pipeline.popup_sequence(32, seed=3)
     assert all(3 <= len(f.ids) <= 8 for f in frames)
-    pl, g, pp, stats = pipeline.gpu_pipeline(step=2)
+    pl, g, pp, stats = pipeline.gpu_pipeline(step=2, async_popup=async_popup)
     ol, og = _oracle_pipeline()
     for fr in frames:
         it = pl.process(fr)
@@ -39,6 +42,7 @@ def test_popup_fused_with_incremental_solve(built):
         ref /= np.linalg.norm(ref, axis=1, keepdims=True)
         for j, fa in enumerate(fs):
             np.testing.assert_allclose(g.get_measurement(fa), ref[j], atol=5e-7)
+    pipeline.gpu_pipeline_finish(pp, stats)      # (the last frame's run is still in flight in the asynchronous form)
     assert stats["points"] > 32 * 20000          # the per-pixel pop-up ran for every frame (half resolution)
     st = g.stats()
     assert st["n_poses"] == 32 and st["n_factors"] == og.num_factors()
@@ -109,15 +113,16 @@ def test_difference_uploads_leave_the_device_equal_to_the_mirror(built, monkeypa
         assert np.isfinite(g.chi2())
 
 
+@pytest.mark.parametrize("async_popup", [False, True])
 @pytest.mark.parametrize("seed", range(3))
-def test_frame_loop_with_random_read_only_calls(built, seed):
+def test_frame_loop_with_random_read_only_calls(built, seed, async_popup):
     """The frame loop keeps a good deal of state between calls (which copy of the estimate is current, whether the device or the
     host holds the newer values / measurements, what the upload mirror says, ...).  Calls that must not change anything --
     chi2, getters, save + restore, a re-analysis, statistics, one factor's Jacobian -- are thrown in at random between the
     frames; the loop must still follow the oracle frame by frame."""
     rng = np.random.default_rng(100 + seed)
     frames = pipeline.popup_sequence(70, seed=20 + seed)
-    pl, g, pp, stats = pipeline.gpu_pipeline(step=2)
+    pl, g, pp, stats = pipeline.gpu_pipeline(step=2, async_popup=async_popup)
     ol, og = _oracle_pipeline()
     for fr in frames:
         it, ito = pl.process(fr), ol.process(fr)
@@ -139,3 +144,5 @@ def test_frame_loop_with_random_read_only_calls(built, seed):
         assert abs(c - co) <= 1e-5 * max(co, 1e-4), (seed, pl.k, c, co)
     for a, b in zip(pl.pose_nodes, ol.pose_nodes):
         np.testing.assert_allclose(g.get_pose(a)[:3], og.get_pose(b)[:3], atol=1e-6)
+    pipeline.gpu_pipeline_finish(pp, stats)
+    assert stats["points"] > 0 and not stats.get("in_flight")
