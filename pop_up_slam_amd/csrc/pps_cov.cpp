@@ -1,20 +1,23 @@
 // pps_cov.cpp -- isam::Covariances on the handle (Thirdparty/isam/include/isam/Covariances.h:42-110, isamlib/covariance.cpp): marginal
 // covariances recovered from the multifrontal factor without a dense inverse.
 //
-//   pps_cov_recover    relinearise at the estimate, H = J'J factored with lambda = 0 (the launches of pps_update's factorisation, one per band
-//                      stage), then the selected inverse root -> leaves (pps_cov.hip), one launch per tree level
-//   pps_cov_factor     the same without the selected inverse: K1 at the estimate, K2, the lambda = 0 factorisation in the K3 form the graph has
-//                      (band stages or the dense-front levels), the pivot criterion in one launch (pps_cov_wide.hip).  All pps_cov_block and
-//                      pps_assoc_gate need, and the only recovery a dense-front graph has
-//   pps_cov_select     the selected inverse in whatever form the graph has: pps_cov_recover on a band graph; on a dense-front graph the factor
-//                      stage of pps_cov_factor, then the root -> leaves pass of pps_cov_dense.hip (one launch over all fronts, three per level)
+// One pipeline, cov_run, is behind the three recovery calls: K1 at the estimate, K2, the lambda = 0 factorisation in the K3 form the graph
+// has (enqueue_plain_factor, pps_solve.cpp), and then
+//   pps_cov_factor     nothing more than the pivot criterion in one launch (pps_cov_wide.hip).  All pps_cov_block and the gates need
+//   pps_cov_recover    the selected inverse root -> leaves by the band level pass (pps_cov.hip), one launch per tree level; band graphs only
+//   pps_cov_select     the selected inverse in whatever form the graph has: the band level pass on a band graph (pps_cov_recover, launch for
+//                      launch); on a dense-front graph the pivot criterion, then the root -> leaves pass of pps_cov_dense.hip (one launch over
+//                      all fronts, three per level)
+// What a pass needs of the tree is checked by cov_check_tree before anything is launched; what has been built, checked and uploaded for the
+// current analysis is kept in one record (pps_graph::cov_cache).
 //   pps_cov_marginals / _access / _joint   look the requested blocks up in the fronts (host tables built at recovery time), collect them with
 //                      one gather launch and one copy
 // Every entry of Sigma inside the pattern of L is available: the diagonal block of every node and the cross block of every pair of nodes
 // that share a front (in particular every pair joined by a factor).  A recovery stays valid until the estimate, the measurements or the
 // topology change (cov_invalidate, pps_graph.h); the read calls then answer PPS_ESTATE.
 //   pps_cov_block      Sigma(rows, cols) for ANY nodes: (L^-1 E_rows)' (L^-1 E_cols) by one walk up the elimination tree per distinct node
-//                      and one Gram product over common ancestors (pps_cov.hip) -- one upload, two launches, one copy, whatever the query
+//                      and one Gram product over common ancestors (pps_cov.hip) -- one upload, two launches, one copy, whatever the query.
+//                      The walk half is CovQuery (pps_graph.h), which pps_assoc_gate and pps_merge_gate run with kernels of their own
 // pps_cov_block reads the lambda = 0 factor the recovery leaves in dev.L.  dev.L is written by the factorisations alone (pps_solve.cpp:
 // enqueue_factor_solve and do_solve, reached from pps_update, pps_batch_optimize and pps_debug_solve; the pps_multi launches), and each of those callers
 // ends the recovery.  What keeps it -- pps_chi2 (K4 reads the states), the getters and pps_save_state (state copies), pps_eval_factor and
@@ -29,25 +32,14 @@ using namespace pps_impl;
 namespace pps_impl {
 
 void cov_release(pps_graph* g) {
-  if (g->cov_S) (void)hipFree(g->cov_S);
-  if (g->cov_parent) (void)hipFree(g->cov_parent);
-  if (g->cov_req) (void)hipFree(g->cov_req);
-  if (g->cov_out) (void)hipFree(g->cov_out);
-  if (g->cov_breq) (void)hipFree(g->cov_breq);
-  if (g->cov_strip) (void)hipFree(g->cov_strip);
-  if (g->cov_bout) (void)hipFree(g->cov_bout);
-  if (g->cov_zscr) (void)hipFree(g->cov_zscr);
-  if (g->cov_G) (void)hipFree(g->cov_G);
-  if (g->cov_dtab) (void)hipFree(g->cov_dtab);
-  g->cov_G = nullptr; g->cov_G_cap = 0; g->cov_dtab = nullptr; g->cov_dtab_cap = 0; g->cov_dtab_version = -1;
+  g->cov_S.release(); g->cov_parent.release(); g->cov_req.release(); g->cov_out.release(); g->cov_breq.release(); g->cov_strip.release();
+  g->cov_bout.release(); g->cov_zscr.release(); g->cov_G.release(); g->cov_dtab.release();
   gate_release(g);
   merge_release(g);
   for (hipEvent_t& e : g->cov_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-  for (hipEvent_t& e : g->cov_bev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-  g->cov_S = nullptr; g->cov_parent = nullptr; g->cov_req = nullptr; g->cov_out = nullptr;
-  g->cov_breq = nullptr; g->cov_strip = nullptr; g->cov_bout = nullptr; g->cov_zscr = nullptr; g->cov_zscr_cap = 0;
-  g->cov_S_cap = g->cov_parent_cap = g->cov_req_cap = g->cov_out_cap = 0;
-  g->cov_breq_cap = g->cov_strip_cap = g->cov_bout_cap = 0; g->cov_bout_clean = false;
+  for (hipEvent_t& e : g->cov_qev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  g->cov_cache = pps_graph::CovCache{};
+  g->cov_bout_clean = false;
   g->cov_valid = g->cov_factor_valid = false;
 }
 
@@ -107,48 +99,137 @@ static bool cov_request(const pps_graph* g, const CovNode& r, const CovNode& c, 
 static int cov_fetch(pps_graph* g, const std::vector<CovReq>& req, size_t n_out, double* host) {
   if (req.empty() || n_out == 0) return PPS_OK;
   HIP_TRY(g, hipSetDevice(g->props.device));
-  int rc = cov_reserve(g, &g->cov_req, &g->cov_req_cap, req.size() * sizeof(CovReq)); if (rc != PPS_OK) return rc;
-  rc = cov_reserve(g, &g->cov_out, &g->cov_out_cap, n_out); if (rc != PPS_OK) return rc;
-  HIP_TRY(g, hipMemcpyAsync(g->cov_req, req.data(), req.size() * sizeof(CovReq), hipMemcpyHostToDevice, g->stream));
-  HIP_TRY(g, launch_cov_gather(g->cov_S, reinterpret_cast<const CovReq*>(g->cov_req), (int)req.size(), g->cov_out, g->stream));
-  HIP_TRY(g, hipMemcpyAsync(host, g->cov_out, n_out * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+  int rc = g->cov_req.reserve(g, req.size() * sizeof(CovReq)); if (rc != PPS_OK) return rc;
+  rc = g->cov_out.reserve(g, n_out); if (rc != PPS_OK) return rc;
+  HIP_TRY(g, hipMemcpyAsync(g->cov_req.p, req.data(), req.size() * sizeof(CovReq), hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(g, launch_cov_gather(g->cov_S.p, reinterpret_cast<const CovReq*>(g->cov_req.p), (int)req.size(), g->cov_out.p, g->stream));
+  HIP_TRY(g, hipMemcpyAsync(host, g->cov_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, g->stream));
   HIP_TRY(g, hipStreamSynchronize(g->stream));
   return PPS_OK;
 }
 
-// paths (leaf -> root) and strips of a list of distinct, checked nodes; K = the longest path of the query in pivots
-int cov_build_walks(pps_graph* g, const std::vector<int>& ids, std::vector<CovNode>& nd, CovWalks* out) {
+static bool cov_walk_wide(const pps_graph* g) {
+  return g->cov_path_form == 1 || cov_path_lds_bytes(g->cov_max_p, g->cov_max_rows) > (size_t)64 * 1024;
+}
+
+int CovQuery::build(const std::vector<int>& ids) {
   const Analysis& A = g->an;
   const int nw = (int)ids.size();
-  out->K = 0;
+  nd.assign((size_t)nw, CovNode{});
+  K = 0;
   for (int w = 0; w < nw; w++) {
-    const int rc = cov_locate(g, ids[w], &nd[w]); if (rc != PPS_OK) return rc;
-    out->K = std::max(out->K, g->cov_rootlen[nd[w].front]);
+    int rc = cov_node(g, ids[w], &nd[w]); if (rc != PPS_OK) return rc;
+    rc = cov_locate(g, ids[w], &nd[w]); if (rc != PPS_OK) return rc;
+    K = std::max(K, g->cov_rootlen[nd[w].front]);
   }
-  out->walks.assign((size_t)nw, CovWalk{});
-  out->steps.clear();
-  out->step_end.assign((size_t)nw, 0);
-  out->n_strip = 0;
-  out->max_rows = 1;
+  walks.assign((size_t)nw, CovWalk{});
+  steps.clear();
+  step_end.assign((size_t)nw, 0);
+  n_strip = 0;
+  max_rows = 1;
   for (int w = 0; w < nw; w++) {
-    out->walks[w] = CovWalk{out->n_strip, (int)out->steps.size(), 0, nd[w].local, nd[w].dim};
+    walks[w] = CovWalk{n_strip, (int)steps.size(), 0, nd[w].local, nd[w].dim};
     for (int s = nd[w].front; s >= 0; s = A.f_parent[s]) {
-      out->steps.push_back(CovStep{s, out->K - g->cov_rootlen[s]});
-      out->max_rows = std::max(out->max_rows, A.f_p[s] + A.f_b[s]);
+      steps.push_back(CovStep{s, K - g->cov_rootlen[s]});
+      max_rows = std::max(max_rows, A.f_p[s] + A.f_b[s]);
     }
-    out->walks[w].n_steps = (int)out->steps.size() - out->walks[w].step0;
-    out->step_end[w] = (int)out->steps.size();
-    out->n_strip += (long long)out->K * nd[w].dim;
+    walks[w].n_steps = (int)steps.size() - walks[w].step0;
+    step_end[w] = (int)steps.size();
+    n_strip += (long long)K * nd[w].dim;
   }
+  o_steps = walks.size() * sizeof(CovWalk);
+  req.assign(o_steps + steps.size() * sizeof(CovStep), 0);
+  if (!walks.empty()) memcpy(req.data(), walks.data(), o_steps);
+  if (!steps.empty()) memcpy(req.data() + o_steps, steps.data(), steps.size() * sizeof(CovStep));
   return PPS_OK;
 }
 
 // the pivots two paths have in common are a suffix of both
-int cov_common_pivots(const pps_graph* g, const CovWalks& cw, int a, int b) {
+int CovQuery::common_pivots(int a, int b) const {
   int len = 0;
-  for (int i = cw.step_end[a] - 1, j = cw.step_end[b] - 1; i >= cw.walks[a].step0 && j >= cw.walks[b].step0 && cw.steps[i].front == cw.steps[j].front; i--, j--)
-    len += g->an.f_p[cw.steps[i].front];
+  for (int i = step_end[a] - 1, j = step_end[b] - 1; i >= walks[a].step0 && j >= walks[b].step0 && steps[i].front == steps[j].front; i--, j--)
+    len += g->an.f_p[steps[i].front];
   return len;
+}
+
+size_t CovQuery::add(const void* data, size_t bytes) {
+  const size_t off = up16(req.size());
+  req.resize(off + bytes, 0);
+  if (bytes) memcpy(req.data() + off, data, bytes);
+  return off;
+}
+
+// (cov_breq / cov_strip / cov_qev are shared by all queries: every one ends with a synchronisation, none is in flight here)
+int CovQuery::reserve(const char* who, const char* advice) {
+  HIP_TRY(g, hipSetDevice(g->props.device));
+  for (hipEvent_t& e : g->cov_qev) if (!e) HIP_TRY(g, hipEventCreate(&e));
+  int rc = g->cov_breq.reserve(g, req.size(), who, "the request", advice); if (rc != PPS_OK) return rc;
+  rc = g->cov_strip.reserve(g, (size_t)n_strip, who, "the strips", advice); if (rc != PPS_OK) return rc;
+  if (!cov_walk_wide(g) || walks.empty()) return PPS_OK;
+  // k_cov_path_wide: its right-hand sides, before the query's upload
+  const size_t want = walks.size() * cov_wide_scratch(max_rows);
+  if (want <= g->cov_zscr.cap && g->cov_zscr.p) return PPS_OK;
+  HIP_TRY(g, hipStreamSynchronize(g->stream));           // (so that what the reservation can still fail with is the allocation)
+  return g->cov_zscr.reserve(g, want, "covariance path solves: ", "the right-hand sides of " + std::to_string(walks.size()) + " walks through fronts of up to " +
+                                                                  std::to_string(max_rows) + " rows", ": ask for fewer nodes per call");
+}
+
+// k_cov_path where its LDS fits the graph's fronts, k_cov_path_wide otherwise (or when the handle asks for it)
+int CovQuery::walk(double* status) {
+  launches0 = launch_count();
+  HIP_TRY(g, hipMemcpyAsync(g->cov_breq.p, req.data(), req.size(), hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(g, hipEventRecord(g->cov_qev[0], g->stream));
+  const int nw = (int)walks.size(), ns = (int)steps.size();
+  const CovWalk* w = dev<CovWalk>(0);
+  const CovStep* s = dev<CovStep>(o_steps);
+  if (cov_walk_wide(g))
+    HIP_TRY(g, launch_cov_path_wide(g->dev, w, nw, s, ns, K, max_rows, g->cov_zscr.p, (long long)g->cov_zscr.cap, g->cov_strip.p, n_strip, status, g->stream));
+  else
+    HIP_TRY(g, launch_cov_path(g->dev, w, nw, s, ns, K, g->cov_max_p, g->cov_max_rows, g->cov_strip.p, n_strip, status, g->stream));
+  return PPS_OK;
+}
+
+int CovQuery::finish(void* host, const void* dev_src, size_t bytes, double* sec, int* launches) {
+  HIP_TRY(g, hipEventRecord(g->cov_qev[1], g->stream));
+  HIP_TRY(g, hipMemcpyAsync(host, dev_src, bytes, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  *launches = (int)(launch_count() - launches0);
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, g->cov_qev[0], g->cov_qev[1]) == hipSuccess) *sec = 1e-3 * ms;
+  return PPS_OK;
+}
+
+int plane_list(pps_graph* g, const char* prefix, const int** ids, int* n, std::vector<int>* all) {
+  if (!*ids) {
+    for (size_t i = 0; i < g->nodes.size(); i++) if (!g->nodes[i].deleted && g->nodes[i].type == NODE_PLANE) all->push_back((int)i);
+    *ids = all->data(); *n = (int)all->size();
+  }
+  std::vector<char> seen(g->nodes.size(), 0);
+  for (int i = 0; i < *n; i++) {
+    const int id = (*ids)[i];
+    if (!live_node(g, id, NODE_PLANE)) return fail(g, PPS_EINVAL, prefix + ("node " + std::to_string(id)) + " is not a live plane");
+    if (seen[id]) return fail(g, PPS_EINVAL, prefix + ("plane " + std::to_string(id)) + " is listed twice");
+    seen[id] = 1;
+  }
+  return PPS_OK;
+}
+
+int zero_between_calls(pps_graph* g, bool* clean, void* out, bool out_new, size_t status_bytes, DevBuf<unsigned int>* ticket, bool ticket_new) {
+  if (!*clean || out_new || ticket_new) {
+    HIP_TRY(g, hipMemsetAsync(out, 0, status_bytes, g->stream));
+    if (ticket) HIP_TRY(g, hipMemsetAsync(ticket->p, 0, ticket->cap * sizeof(unsigned int), g->stream));
+  }
+  *clean = false;
+  return PPS_OK;
+}
+
+int copy_records(pps_graph* g, const DevBuf<double>& rec, size_t n, int64_t cap, double* out, int64_t* needed) {
+  *needed = (int64_t)n;
+  if (!out || cap < *needed) return PPS_OK;
+  HIP_TRY(g, hipSetDevice(g->props.device));
+  HIP_TRY(g, hipMemcpyAsync(out, rec.p, n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  return PPS_OK;
 }
 
 // node -> front tables of the current analysis; checks what the gather relies on: a node's scalars are consecutive pivots of ONE front
@@ -185,164 +266,17 @@ static int cov_build_tables(pps_graph* g) {
   return PPS_OK;
 }
 
-static int cov_recover_impl(pps_graph* g) {
-  int rc;
-  if (!g->analyzed || g->analysis_stale) { rc = pps_analyze(g); if (rc != PPS_OK) return rc; }
-  if (!g->use_band)
-    return fail(g, PPS_ESTATE, "covariance recovery is limited to graphs whose fronts all fit the wave-per-front kernels (max front " +
-                               std::to_string(g->an.max_front) + " scalars here: loop-closure graphs in the dense-front form are not supported)");
-  rc = prepare_solve(g); if (rc != PPS_OK) return rc;
+// What the kernels of a pass index with, checked before anything is launched.  Always: the tables, parents, child maps and pivot counts (all
+// the path walks rely on).  needs = kCovLevelShapes adds the LDS of k_cov_level, needs = kCovDense the level lists and the L / U extents of
+// the dense-front pass (that bit itself is set by cov_run, with the upload of the work lists).
+static int cov_check_tree(pps_graph* g, unsigned needs) {
   const Analysis& A = g->an;
-  const DevGraph& d = g->dev;
-  for (hipEvent_t& e : g->cov_ev) if (!e) HIP_TRY(g, hipEventCreate(&e));
-  rc = cov_reserve(g, &g->cov_S, &g->cov_S_cap, (size_t)std::max<int64_t>(1, A.L_size)); if (rc != PPS_OK) return rc;
-  if (g->cov_parent_version != g->upload_version) {
-    rc = cov_build_tables(g); if (rc != PPS_OK) return rc;
-    for (int s = 0; s < A.n_fronts; s++) {             // what k_cov_level indexes with: checked here, before anything is launched
-      const int q = A.f_parent[s];
-      if (A.f_b[s] > 0 && (q < 0 || q >= A.n_fronts || A.f_level[q] <= A.f_level[s] || A.f_cmap_off[s + 1] - A.f_cmap_off[s] < A.f_b[s]))
-        return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (parent / child map)");
-      for (int k = 0; k < A.f_b[s]; k++) {
-        const int r = A.cmap[A.f_cmap_off[s] + k];
-        if (r < 0 || r >= A.f_p[q] + A.f_b[q]) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (child map entry)");
-      }
-      if (A.f_p[s] < 1 || A.f_p[s] > 64 || cov_level_lds_bytes(A.f_p[s], A.f_b[s]) > (size_t)159 * 1024)
-        return fail(g, PPS_ESTATE, "covariance: front outside the supported shapes");
-    }
-    rc = cov_reserve(g, &g->cov_parent, &g->cov_parent_cap, (size_t)std::max(1, A.n_fronts)); if (rc != PPS_OK) return rc;
-    HIP_TRY(g, hipMemcpyAsync(g->cov_parent, A.f_parent.data(), (size_t)A.n_fronts * sizeof(int), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(g, hipStreamSynchronize(g->stream));         // (f_parent may be reallocated by the next analysis)
-    g->cov_parent_version = g->upload_version;
-  }
-  if (!g->status_clean) {
-    HIP_TRY(g, launch_clear_status(d, g->stream));
-    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
-  }
-  g->status_clean = false;
-  HIP_TRY(g, hipEventRecord(g->cov_ev[0], g->stream));
-  // jacobian() at the ESTIMATE (the linearisation point stays what it is), H blocks, factorisation with lambda = 0: one launch per band
-  // stage, the form whose panels all pass through d.L.  The update matrices in d.U are dead once their parents are assembled.
-  HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, true));      // (the robustified J with a cost function set)
-  HIP_TRY(g, launch_hblocks(d, g->stream, nullptr, k1_products(d, g->props.jacobian_mode)));
-  for (int st = 0; st < A.n_stages; st++)
-    HIP_TRY(g, launch_band_factor(d, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_factor[st], A.stage_max_front[st], 0.0, g->stream));
-  HIP_TRY(g, hipEventRecord(g->cov_ev[1], g->stream));
-  for (int l = A.n_levels - 1; l >= 0; l--) {
-    size_t lds = 0;
-    for (int k = A.level_off[l]; k < A.level_off[l + 1]; k++) lds = std::max(lds, cov_level_lds_bytes(A.f_p[A.level_fronts[k]], A.f_b[A.level_fronts[k]]));
-    HIP_TRY(g, launch_cov_level(d, g->cov_S, g->cov_parent, A.level_off[l], A.level_off[l + 1] - A.level_off[l], lds, g->stream));
-  }
-  HIP_TRY(g, hipEventRecord(g->cov_ev[2], g->stream));
-  double status[4] = {0, 0, 0, 0};
-  HIP_TRY(g, hipMemcpyAsync(status, d.result_dev, sizeof status, hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, g->cov_ev[0], g->cov_ev[2]) == hipSuccess) g->cov_sec[0] = 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, g->cov_ev[1], g->cov_ev[2]) == hipSuccess) g->cov_sec[1] = 1e-3 * ms;
-  if (status[2] != 0.0) {
-    HIP_TRY(g, launch_clear_status(d, g->stream));
-    HIP_TRY(g, hipStreamSynchronize(g->stream));
-  }
-  g->status_clean = true;
-  if (status[2] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: the covariance recovery met an index outside its front");
-  if (status[2] != 0.0)
-    return fail(g, PPS_ENOTPD, "normal equations not positive definite at lambda = 0 (a pivot was not positive, or below 1e-7 of the largest pivot of its front): no covariance");
-  g->cov_version = g->upload_version;
-  g->cov_valid = g->cov_factor_valid = true;
-  g->cov_tables_version = g->upload_version;             // (built and checked above, with the stricter shape test of the level pass)
-  return PPS_OK;
-}
-
-static std::string no_factor_array(const pps_graph* g) {
-  return "pps_cov_factor: the graph is solved by the one-launch-per-level LDS kernels (max front " + std::to_string(g->an.max_front) +
-         " scalars, neither the band nor the dense-front form), whose panels do not pass through the factor array: no factor to keep";
-}
-
-// pps_cov_factor: the recovery without the selected inverse, in whatever K3 form the graph has
-static int cov_factor_impl(pps_graph* g) {
-  int rc;
-  if (!g->analyzed || g->analysis_stale) { rc = pps_analyze(g); if (rc != PPS_OK) return rc; }
-  if (!g->use_band && !g->use_dense)
-    return fail(g, PPS_ESTATE, no_factor_array(g));
-  rc = prepare_solve(g); if (rc != PPS_OK) return rc;
-  const Analysis& A = g->an;
-  const DevGraph& d = g->dev;
-  for (hipEvent_t& e : g->cov_ev) if (!e) HIP_TRY(g, hipEventCreate(&e));
-  if (g->cov_tables_version != g->upload_version && g->cov_parent_version != g->upload_version) {
-    rc = cov_build_tables(g); if (rc != PPS_OK) return rc;
-    for (int s = 0; s < A.n_fronts; s++) {               // what the path walks index with: checked here, before anything is launched
-      const int q = A.f_parent[s];
-      if (A.f_b[s] < 0 || (A.f_b[s] > 0 && (q < 0 || q >= A.n_fronts || A.f_level[q] <= A.f_level[s] || A.f_cmap_off[s + 1] - A.f_cmap_off[s] < A.f_b[s])))
-        return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (parent / child map)");
-      for (int k = 0; k < A.f_b[s]; k++) {
-        const int r = A.cmap[A.f_cmap_off[s] + k];
-        if (r < 0 || r >= A.f_p[q] + A.f_b[q]) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (child map entry)");
-      }
-      if (A.f_p[s] < 1 || A.f_p[s] > 64) return fail(g, PPS_ESTATE, "covariance: front outside the supported shapes");
-    }
-    g->cov_tables_version = g->upload_version;
-  }
-  if (!g->status_clean) {
-    HIP_TRY(g, launch_clear_status(d, g->stream));
-    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
-  }
-  g->status_clean = false;
-  HIP_TRY(g, hipEventRecord(g->cov_ev[0], g->stream));
-  HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, true));      // jacobian() at the ESTIMATE, robustified with a cost function set
-  HIP_TRY(g, launch_hblocks(d, g->stream, nullptr, k1_products(d, g->props.jacobian_mode)));
-  if (g->use_band) {                                     // one launch per band stage: the form whose panels all pass through d.L
-    for (int st = 0; st < A.n_stages; st++)
-      HIP_TRY(g, launch_band_factor(d, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_factor[st], A.stage_max_front[st], 0.0, g->stream));
-  } else {                                               // the dense-front levels, as do_solve issues them (pps_solve.cpp)
-    HIP_TRY(g, hipMemsetAsync(d.L, 0, (size_t)A.L_size * 8, g->stream));
-    HIP_TRY(g, launch_dense_hpush(d, g->max_el_per_front, 0.0, g->stream));
-    for (int l = 0; l < A.n_levels; l++) {
-      const int base = A.level_off[l] + l, cnt = A.level_off[l + 1] - A.level_off[l];
-      HIP_TRY(g, launch_dense_factor_level(d, A.level_off[l], cnt, g->d_dw_asm + base, g->dw_asm[base + cnt], g->d_dw_pan + base, g->dw_pan[base + cnt],
-                                           g->d_dw_trl + base, g->dw_trl[base + cnt], g->stream));
-    }
-  }
-  HIP_TRY(g, launch_cov_pivots(d, A.n_fronts, g->stream));
-  HIP_TRY(g, hipEventRecord(g->cov_ev[1], g->stream));
-  double status[4] = {0, 0, 0, 0};
-  HIP_TRY(g, hipMemcpyAsync(status, d.result_dev, sizeof status, hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  float ms = 0;
-  g->cov_sec[1] = 0.0;
-  if (hipEventElapsedTime(&ms, g->cov_ev[0], g->cov_ev[1]) == hipSuccess) g->cov_sec[0] = 1e-3 * ms;
-  if (status[2] != 0.0) {
-    HIP_TRY(g, launch_clear_status(d, g->stream));
-    HIP_TRY(g, hipStreamSynchronize(g->stream));
-  }
-  g->status_clean = true;
-  if (status[2] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: the factorisation of pps_cov_factor met an index outside its front");
-  if (status[2] != 0.0)
-    return fail(g, PPS_ENOTPD, "normal equations not positive definite at lambda = 0 (a pivot was not positive, or below 1e-7 of the largest pivot of its front): no factor");
-  g->cov_version = g->upload_version;
-  g->cov_factor_valid = true;
-  return PPS_OK;
-}
-
-// the device buffers of the dense-front pass: PPS_ENOMEM, never an abort, when one cannot be had
-template <class T>
-static int cov_select_reserve(pps_graph* g, T** buf, size_t* cap, size_t count, const char* what) {
-  if (cov_reserve(g, buf, cap, count) == PPS_OK) return PPS_OK;
-  (void)hipGetLastError();
-  return fail(g, PPS_ENOMEM, std::string("pps_cov_select: no device memory for ") + what + " (" + std::to_string(count * sizeof(T)) + " bytes)");
-}
-
-// pps_cov_select on a dense-front tree (or, with pps_debug_cov_select_form, on a band tree): the lambda = 0 factor in the form the graph is
-// solved in, then the root -> leaves pass of pps_cov_dense.hip.  It reads L, f_p, f_b, f_Loff, f_Uoff, cmap, the parents and the level lists.
-static int cov_select_dense_impl(pps_graph* g) {
-  int rc = prepare_solve(g); if (rc != PPS_OK) return rc;
-  const Analysis& A = g->an;
-  const DevGraph& d = g->dev;
-  for (hipEvent_t& e : g->cov_ev) if (!e) HIP_TRY(g, hipEventCreate(&e));
-  const size_t n_panel = (size_t)std::max<int64_t>(1, A.L_size);
-  rc = cov_select_reserve(g, &g->cov_S, &g->cov_S_cap, n_panel, "the selected inverse"); if (rc != PPS_OK) return rc;
-  rc = cov_select_reserve(g, &g->cov_G, &g->cov_G_cap, n_panel, "the scratch of L_B L_A^-1"); if (rc != PPS_OK) return rc;
-  if (g->cov_dtab_version != g->upload_version) {
-    rc = cov_build_tables(g); if (rc != PPS_OK) return rc;
+  const unsigned want = pps_graph::kCovTables | needs;
+  unsigned& have = g->cov_cache.have;
+  if ((have & want) == want) return PPS_OK;
+  if (!(have & pps_graph::kCovTables)) { const int rc = cov_build_tables(g); if (rc != PPS_OK) return rc; }
+  const bool level = (needs & pps_graph::kCovLevelShapes) != 0, dense = (needs & pps_graph::kCovDense) != 0;
+  if (dense) {
     if ((int)A.level_off.size() < A.n_levels + 1 || A.level_off[A.n_levels] != A.n_fronts) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (level lists)");
     std::vector<char> listed((size_t)std::max(1, A.n_fronts), 0);
     for (int l = 0; l < A.n_levels; l++)
@@ -351,190 +285,159 @@ static int cov_select_dense_impl(pps_graph* g) {
         if (s < 0 || s >= A.n_fronts || listed[s] || A.f_level[s] != l) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (level lists)");
         listed[s] = 1;
       }
-    for (int s = 0; s < A.n_fronts; s++) {               // what the kernels index with: checked here, before anything is launched
-      const int q = A.f_parent[s], p = A.f_p[s], b = A.f_b[s];
-      if (b < 0 || (b > 0 && (q < 0 || q >= A.n_fronts || A.f_level[q] <= A.f_level[s] || A.f_cmap_off[s + 1] - A.f_cmap_off[s] < b)))
-        return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (parent / child map)");
-      for (int k = 0; k < b; k++) {
-        const int r = A.cmap[A.f_cmap_off[s] + k];
-        if (r < 0 || r >= A.f_p[q] + A.f_b[q]) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (child map entry)");
-      }
+  }
+  for (int s = 0; s < A.n_fronts; s++) {
+    const int q = A.f_parent[s], p = A.f_p[s], b = A.f_b[s];
+    if (b < 0 || (b > 0 && (q < 0 || q >= A.n_fronts || A.f_level[q] <= A.f_level[s] || A.f_cmap_off[s + 1] - A.f_cmap_off[s] < b)))
+      return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (parent / child map)");
+    for (int k = 0; k < b; k++) {
+      const int r = A.cmap[A.f_cmap_off[s] + k];
+      if (r < 0 || r >= A.f_p[q] + A.f_b[q]) return fail(g, PPS_ESTATE, "covariance: inconsistent analysis (child map entry)");
+    }
+    bool ok = p >= 1 && p <= 64;
+    if (ok && level) ok = cov_level_lds_bytes(p, b) <= (size_t)159 * 1024;
+    if (ok && dense) {
       const int64_t u_end = s + 1 < A.n_fronts ? A.f_Uoff[s + 1] : A.U_size, l_end = s + 1 < A.n_fronts ? A.f_Loff[s + 1] : A.L_size;
-      if (p < 1 || p > 64 || A.f_Uoff[s] < 0 || u_end - A.f_Uoff[s] < (int64_t)b * b || A.f_Loff[s] < 0 || l_end - A.f_Loff[s] < (int64_t)(p + b) * p)
-        return fail(g, PPS_ESTATE, "covariance: front outside the supported shapes");
+      ok = A.f_Uoff[s] >= 0 && u_end - A.f_Uoff[s] >= (int64_t)b * b && A.f_Loff[s] >= 0 && l_end - A.f_Loff[s] >= (int64_t)(p + b) * p;
     }
-    // work-item prefix sums: [all fronts | per level: gather, strips]
-    std::vector<int> tab;
-    tab.push_back(0);
-    for (int s = 0; s < A.n_fronts; s++) tab.push_back(tab.back() + cov_dense_pre_items(A.f_b[s]));
-    g->cov_dpre_items = tab.back();
-    g->cov_dlevel.assign((size_t)4 * std::max(1, A.n_levels), 0);
-    for (int l = 0; l < A.n_levels; l++)
-      for (int kind = 0; kind < 2; kind++) {
-        const size_t at = tab.size();
-        int sum = 0;
-        tab.push_back(0);
-        for (int k = A.level_off[l]; k < A.level_off[l + 1]; k++) {
-          const int b = A.f_b[A.level_fronts[k]];
-          sum += kind == 0 ? cov_dense_gather_items(b) : cov_dense_strip_items(b);
-          tab.push_back(sum);
-        }
-        g->cov_dlevel[4 * l + 2 * kind] = (int)at; g->cov_dlevel[4 * l + 2 * kind + 1] = sum;
+    if (!ok) return fail(g, PPS_ESTATE, "covariance: front outside the supported shapes");
+  }
+  have |= want & ~(unsigned)pps_graph::kCovDense;
+  return PPS_OK;
+}
+
+// the work-item prefix sums of the dense-front pass: [all fronts | per level: gather, strips]
+static std::vector<int> cov_dense_work_lists(pps_graph* g) {
+  const Analysis& A = g->an;
+  std::vector<int> tab;
+  tab.push_back(0);
+  for (int s = 0; s < A.n_fronts; s++) tab.push_back(tab.back() + cov_dense_pre_items(A.f_b[s]));
+  g->cov_dpre_items = tab.back();
+  g->cov_dlevel.assign((size_t)4 * std::max(1, A.n_levels), 0);
+  for (int l = 0; l < A.n_levels; l++)
+    for (int kind = 0; kind < 2; kind++) {
+      const size_t at = tab.size();
+      int sum = 0;
+      tab.push_back(0);
+      for (int k = A.level_off[l]; k < A.level_off[l + 1]; k++) {
+        const int b = A.f_b[A.level_fronts[k]];
+        sum += kind == 0 ? cov_dense_gather_items(b) : cov_dense_strip_items(b);
+        tab.push_back(sum);
       }
-    rc = cov_select_reserve(g, &g->cov_dtab, &g->cov_dtab_cap, tab.size(), "the work lists"); if (rc != PPS_OK) return rc;
-    rc = cov_select_reserve(g, &g->cov_parent, &g->cov_parent_cap, (size_t)std::max(1, A.n_fronts), "the parent list"); if (rc != PPS_OK) return rc;
-    g->cov_parent_version = -1;                          // (pps_cov_recover has its own, stricter shape test: it checks and uploads again)
-    HIP_TRY(g, hipMemcpyAsync(g->cov_dtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(g, hipMemcpyAsync(g->cov_parent, A.f_parent.data(), (size_t)A.n_fronts * sizeof(int), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(g, hipStreamSynchronize(g->stream));         // (tab and f_parent are host memory that does not outlive this call)
-    g->cov_dtab_version = g->upload_version;
-    g->cov_tables_version = g->upload_version;
-  }
-  if (!g->status_clean) {
-    HIP_TRY(g, launch_clear_status(d, g->stream));
-    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
-  }
-  g->status_clean = false;
-  HIP_TRY(g, hipEventRecord(g->cov_ev[0], g->stream));
-  // the factor stage of pps_cov_factor
-  HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, true));      // jacobian() at the ESTIMATE, robustified with a cost function set
-  HIP_TRY(g, launch_hblocks(d, g->stream, nullptr, k1_products(d, g->props.jacobian_mode)));
-  if (g->use_band) {
-    for (int st = 0; st < A.n_stages; st++)
-      HIP_TRY(g, launch_band_factor(d, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_factor[st], A.stage_max_front[st], 0.0, g->stream));
-  } else {
-    HIP_TRY(g, hipMemsetAsync(d.L, 0, (size_t)A.L_size * 8, g->stream));
-    HIP_TRY(g, launch_dense_hpush(d, g->max_el_per_front, 0.0, g->stream));
-    for (int l = 0; l < A.n_levels; l++) {
-      const int base = A.level_off[l] + l, cnt = A.level_off[l + 1] - A.level_off[l];
-      HIP_TRY(g, launch_dense_factor_level(d, A.level_off[l], cnt, g->d_dw_asm + base, g->dw_asm[base + cnt], g->d_dw_pan + base, g->dw_pan[base + cnt],
-                                           g->d_dw_trl + base, g->dw_trl[base + cnt], g->stream));
+      g->cov_dlevel[4 * l + 2 * kind] = (int)at; g->cov_dlevel[4 * l + 2 * kind + 1] = sum;
     }
-  }
-  HIP_TRY(g, launch_cov_pivots(d, A.n_fronts, g->stream));
-  HIP_TRY(g, hipEventRecord(g->cov_ev[1], g->stream));
-  // the root -> leaves pass: the update matrices in d.U are dead once their parents are assembled
-  const CovDenseExtents ext{(long long)A.L_size, (long long)A.U_size};
-  HIP_TRY(g, launch_cov_dense_pre(d, g->cov_S, g->cov_G, ext, g->cov_dtab, g->cov_dpre_items, A.n_fronts, g->stream));
-  for (int l = A.n_levels - 1; l >= 0; l--) {
-    const int* lv = g->cov_dlevel.data() + 4 * l;
-    HIP_TRY(g, launch_cov_dense_level(d, g->cov_S, g->cov_G, ext, g->cov_parent, A.level_off[l], A.level_off[l + 1] - A.level_off[l], g->cov_dtab + lv[0], lv[1],
-                                      g->cov_dtab + lv[2], lv[3], g->stream));
-  }
-  HIP_TRY(g, hipEventRecord(g->cov_ev[2], g->stream));
+  return tab;
+}
+
+// which pass follows the factor.  Select: the band level pass on a band graph, the dense-front pass otherwise (or when the handle asks for it)
+enum class CovPass { FactorOnly, BandLevels, DenseFronts, Select };
+
+// the end of a recovery: the status record comes home (one synchronisation), the times are read, a raised status is cleared and answered
+static int cov_read_status(pps_graph* g, bool pass, const char* who, const char* lost) {
   double status[4] = {0, 0, 0, 0};
-  HIP_TRY(g, hipMemcpyAsync(status, d.result_dev, sizeof status, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(g, hipMemcpyAsync(status, g->dev.result_dev, sizeof status, hipMemcpyDeviceToHost, g->stream));
   HIP_TRY(g, hipStreamSynchronize(g->stream));
   float ms = 0;
-  if (hipEventElapsedTime(&ms, g->cov_ev[0], g->cov_ev[2]) == hipSuccess) g->cov_sec[0] = 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, g->cov_ev[1], g->cov_ev[2]) == hipSuccess) g->cov_sec[1] = 1e-3 * ms;
+  if (!pass) g->cov_sec[1] = 0.0;
+  if (hipEventElapsedTime(&ms, g->cov_ev[0], g->cov_ev[pass ? 2 : 1]) == hipSuccess) g->cov_sec[0] = 1e-3 * ms;
+  if (pass && hipEventElapsedTime(&ms, g->cov_ev[1], g->cov_ev[2]) == hipSuccess) g->cov_sec[1] = 1e-3 * ms;
   if (status[2] != 0.0) {
-    HIP_TRY(g, launch_clear_status(d, g->stream));
+    HIP_TRY(g, launch_clear_status(g->dev, g->stream));
     HIP_TRY(g, hipStreamSynchronize(g->stream));
   }
   g->status_clean = true;
-  if (status[2] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: pps_cov_select met an index outside its front");
+  if (status[2] >= kStatusInternal) return fail(g, PPS_EHIP, std::string("internal error: ") + who + " met an index outside its front");
   if (status[2] != 0.0)
-    return fail(g, PPS_ENOTPD, "normal equations not positive definite at lambda = 0 (a pivot was not positive, or below 1e-7 of the largest pivot of its front): no covariance");
-  g->cov_version = g->upload_version;
-  g->cov_valid = g->cov_factor_valid = true;
+    return fail(g, PPS_ENOTPD, std::string("normal equations not positive definite at lambda = 0 (a pivot was not positive, or below 1e-7 of the largest pivot of its front): ") + lost);
   return PPS_OK;
 }
 
-static int cov_select_impl(pps_graph* g) {
-  if (!g->analyzed || g->analysis_stale) { const int rc = pps_analyze(g); if (rc != PPS_OK) return rc; }
-  if (g->use_band && g->cov_select_form == 0) return cov_recover_impl(g);      // the band form: pps_cov_recover, launch for launch
-  if (!g->use_band && !g->use_dense) return fail(g, PPS_ESTATE, no_factor_array(g));
-  return cov_select_dense_impl(g);
-}
-
-bool cov_walk_wide(const pps_graph* g) {
-  return g->cov_path_form == 1 || cov_path_lds_bytes(g->cov_max_p, g->cov_max_rows) > (size_t)64 * 1024;
-}
-
-int cov_walk_scratch(pps_graph* g, const CovWalks& cw) {
-  if (!cov_walk_wide(g) || cw.walks.empty()) return PPS_OK;
-  const size_t want = cw.walks.size() * cov_wide_scratch(cw.max_rows);
-  if (want <= g->cov_zscr_cap && g->cov_zscr) return PPS_OK;
-  HIP_TRY(g, hipStreamSynchronize(g->stream));           // (so that what cov_reserve can still fail with is the allocation)
-  if (cov_reserve(g, &g->cov_zscr, &g->cov_zscr_cap, want) != PPS_OK) {
-    (void)hipGetLastError();
-    return fail(g, PPS_ENOMEM, "covariance path solves: no device memory for the right-hand sides of " + std::to_string(cw.walks.size()) + " walks through fronts of up to " +
-                               std::to_string(cw.max_rows) + " rows (" + std::to_string(want * sizeof(double)) + " bytes): ask for fewer nodes per call");
+// The recovery.  It reads L, f_p, f_b, f_Loff, f_Uoff, cmap, the parents and the level lists; the update matrices in d.U are dead once their
+// parents are assembled, which is where the passes put Sigma_BB.
+static int cov_run(pps_graph* g, CovPass what) {
+  int rc;
+  if (!g->analyzed || g->analysis_stale) { rc = pps_analyze(g); if (rc != PPS_OK) return rc; }
+  if (what == CovPass::Select) what = g->use_band && g->cov_select_form == 0 ? CovPass::BandLevels : CovPass::DenseFronts;
+  if (what == CovPass::BandLevels && !g->use_band)
+    return fail(g, PPS_ESTATE, "covariance recovery is limited to graphs whose fronts all fit the wave-per-front kernels (max front " +
+                               std::to_string(g->an.max_front) + " scalars here: loop-closure graphs in the dense-front form are not supported)");
+  if (!g->use_band && !g->use_dense)
+    return fail(g, PPS_ESTATE, "pps_cov_factor: the graph is solved by the one-launch-per-level LDS kernels (max front " + std::to_string(g->an.max_front) +
+                               " scalars, neither the band nor the dense-front form), whose panels do not pass through the factor array: no factor to keep");
+  rc = prepare_solve(g); if (rc != PPS_OK) return rc;
+  const Analysis& A = g->an;
+  const DevGraph& d = g->dev;
+  const bool levels = what == CovPass::BandLevels, fronts = what == CovPass::DenseFronts, pass = levels || fronts;
+  for (hipEvent_t& e : g->cov_ev) if (!e) HIP_TRY(g, hipEventCreate(&e));
+  if (g->cov_cache.version != g->upload_version) g->cov_cache = pps_graph::CovCache{g->upload_version, 0};
+  unsigned& have = g->cov_cache.have;
+  // the dense-front pass answers PPS_ENOMEM, never an abort, when a buffer cannot be had
+  const char* who = fronts ? "pps_cov_select: " : nullptr;
+  const size_t n_panel = (size_t)std::max<int64_t>(1, A.L_size);
+  if (pass) { rc = g->cov_S.reserve(g, n_panel, who, "the selected inverse"); if (rc != PPS_OK) return rc; }
+  if (fronts) { rc = g->cov_G.reserve(g, n_panel, who, "the scratch of L_B L_A^-1"); if (rc != PPS_OK) return rc; }
+  rc = cov_check_tree(g, levels ? pps_graph::kCovLevelShapes : fronts && !(have & pps_graph::kCovDense) ? pps_graph::kCovDense : 0u); if (rc != PPS_OK) return rc;
+  { const bool up_tab = fronts && !(have & pps_graph::kCovDense), up_parent = pass && !(have & pps_graph::kCovParent);
+    std::vector<int> tab;
+    if (up_tab) { tab = cov_dense_work_lists(g); rc = g->cov_dtab.reserve(g, tab.size(), who, "the work lists"); if (rc != PPS_OK) return rc; }
+    if (up_parent) { rc = g->cov_parent.reserve(g, (size_t)std::max(1, A.n_fronts), who, "the parent list"); if (rc != PPS_OK) return rc; }
+    if (up_tab) HIP_TRY(g, hipMemcpyAsync(g->cov_dtab.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, g->stream));
+    if (up_parent) HIP_TRY(g, hipMemcpyAsync(g->cov_parent.p, A.f_parent.data(), (size_t)A.n_fronts * sizeof(int), hipMemcpyHostToDevice, g->stream));
+    if (up_tab || up_parent) HIP_TRY(g, hipStreamSynchronize(g->stream));      // (tab and f_parent are host memory that does not outlive the analysis)
+    if (up_tab) have |= pps_graph::kCovDense;
+    if (up_parent) have |= pps_graph::kCovParent; }
+  rc = clear_stale_status(g); if (rc != PPS_OK) return rc;
+  HIP_TRY(g, hipEventRecord(g->cov_ev[0], g->stream));
+  // jacobian() at the ESTIMATE (the linearisation point stays what it is; the robustified J with a cost function set), H blocks, factorisation
+  // with lambda = 0 in the form whose panels all pass through d.L
+  HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, true));
+  HIP_TRY(g, launch_hblocks(d, g->stream, nullptr, k1_products(d, g->props.jacobian_mode)));
+  rc = enqueue_plain_factor(g, 0.0); if (rc != PPS_OK) return rc;
+  if (!levels) HIP_TRY(g, launch_cov_pivots(d, A.n_fronts, g->stream));      // (k_cov_level applies the pivot criterion itself)
+  HIP_TRY(g, hipEventRecord(g->cov_ev[1], g->stream));
+  if (levels)
+    for (int l = A.n_levels - 1; l >= 0; l--) {
+      size_t lds = 0;
+      for (int k = A.level_off[l]; k < A.level_off[l + 1]; k++) lds = std::max(lds, cov_level_lds_bytes(A.f_p[A.level_fronts[k]], A.f_b[A.level_fronts[k]]));
+      HIP_TRY(g, launch_cov_level(d, g->cov_S.p, g->cov_parent.p, A.level_off[l], A.level_off[l + 1] - A.level_off[l], lds, g->stream));
+    }
+  if (fronts) {
+    const CovDenseExtents ext{(long long)A.L_size, (long long)A.U_size};
+    HIP_TRY(g, launch_cov_dense_pre(d, g->cov_S.p, g->cov_G.p, ext, g->cov_dtab.p, g->cov_dpre_items, A.n_fronts, g->stream));
+    for (int l = A.n_levels - 1; l >= 0; l--) {
+      const int* lv = g->cov_dlevel.data() + 4 * l;
+      HIP_TRY(g, launch_cov_dense_level(d, g->cov_S.p, g->cov_G.p, ext, g->cov_parent.p, A.level_off[l], A.level_off[l + 1] - A.level_off[l], g->cov_dtab.p + lv[0], lv[1],
+                                        g->cov_dtab.p + lv[2], lv[3], g->stream));
+    }
   }
+  if (pass) HIP_TRY(g, hipEventRecord(g->cov_ev[2], g->stream));
+  rc = cov_read_status(g, pass, levels ? "the covariance recovery" : fronts ? "pps_cov_select" : "the factorisation of pps_cov_factor", pass ? "no covariance" : "no factor");
+  if (rc != PPS_OK) return rc;
+  g->cov_version = g->upload_version;
+  g->cov_factor_valid = true;
+  if (pass) g->cov_valid = true;
   return PPS_OK;
 }
 
-hipError_t cov_launch_walks(pps_graph* g, const CovWalks& cw, const CovWalk* walks, const CovStep* steps, double* out) {
-  const int nw = (int)cw.walks.size(), ns = (int)cw.steps.size();
-  if (cov_walk_wide(g))
-    return launch_cov_path_wide(g->dev, walks, nw, steps, ns, cw.K, cw.max_rows, g->cov_zscr, (long long)g->cov_zscr_cap, g->cov_strip, cw.n_strip, out, g->stream);
-  return launch_cov_path(g->dev, walks, nw, steps, ns, cw.K, g->cov_max_p, g->cov_max_rows, g->cov_strip, cw.n_strip, out, g->stream);
+// the three recovery calls: no solve, so the figures of the last one stay (NoSolveScope)
+static int cov_entry(pps_graph* g, CovPass what) {
+  if (!g) return PPS_EINVAL;
+  cov_invalidate(g);
+  if (g->n_live_nodes == 0) return fail(g, PPS_ESTATE, "empty graph");
+  if (g->n_live_factors == 0) return fail(g, PPS_ENOTPD, "normal equations not positive definite: the graph has no factor");
+  int rc;
+  { NoSolveScope scope(g); rc = cov_run(g, what); }
+  if (rc == PPS_EHIP) abandon_device_copy(g);
+  return rc;
 }
 
 }  // namespace pps_impl
 
 extern "C" {
 
-int pps_cov_recover(pps_graph* g) {
-  if (!g) return PPS_EINVAL;
-  cov_invalidate(g);
-  if (g->n_live_nodes == 0) return fail(g, PPS_ESTATE, "empty graph");
-  if (g->n_live_factors == 0) return fail(g, PPS_ENOTPD, "normal equations not positive definite: the graph has no factor");
-  // the figures of the last solve stay what they were: this call is no solve (the fields that describe the analysis follow the analysis)
-  const pps_stats saved = g->stats;
-  const int profiling = g->profiling;
-  g->profiling = 0;
-  const unsigned long long launches0 = g->launches0;
-  const int rc = cov_recover_impl(g);
-  g->profiling = profiling;
-  g->launches0 = launches0;
-  { pps_stats s = saved;
-    s.n_fronts = g->stats.n_fronts; s.n_levels = g->stats.n_levels; s.max_front = g->stats.max_front; s.nnz_L = g->stats.nnz_L;
-    g->stats = s; }
-  if (rc == PPS_EHIP) abandon_device_copy(g);
-  return rc;
-}
-
-int pps_cov_factor(pps_graph* g) {
-  if (!g) return PPS_EINVAL;
-  cov_invalidate(g);
-  if (g->n_live_nodes == 0) return fail(g, PPS_ESTATE, "empty graph");
-  if (g->n_live_factors == 0) return fail(g, PPS_ENOTPD, "normal equations not positive definite: the graph has no factor");
-  // like pps_cov_recover: no solve, the figures of the last one stay
-  const pps_stats saved = g->stats;
-  const int profiling = g->profiling;
-  g->profiling = 0;
-  const unsigned long long launches0 = g->launches0;
-  const int rc = cov_factor_impl(g);
-  g->profiling = profiling;
-  g->launches0 = launches0;
-  { pps_stats s = saved;
-    s.n_fronts = g->stats.n_fronts; s.n_levels = g->stats.n_levels; s.max_front = g->stats.max_front; s.nnz_L = g->stats.nnz_L;
-    g->stats = s; }
-  if (rc == PPS_EHIP) abandon_device_copy(g);
-  return rc;
-}
-
-int pps_cov_select(pps_graph* g) {
-  if (!g) return PPS_EINVAL;
-  cov_invalidate(g);
-  if (g->n_live_nodes == 0) return fail(g, PPS_ESTATE, "empty graph");
-  if (g->n_live_factors == 0) return fail(g, PPS_ENOTPD, "normal equations not positive definite: the graph has no factor");
-  // like pps_cov_recover: no solve, the figures of the last one stay
-  const pps_stats saved = g->stats;
-  const int profiling = g->profiling;
-  g->profiling = 0;
-  const unsigned long long launches0 = g->launches0;
-  const int rc = cov_select_impl(g);
-  g->profiling = profiling;
-  g->launches0 = launches0;
-  { pps_stats s = saved;
-    s.n_fronts = g->stats.n_fronts; s.n_levels = g->stats.n_levels; s.max_front = g->stats.max_front; s.nnz_L = g->stats.nnz_L;
-    g->stats = s; }
-  if (rc == PPS_EHIP) abandon_device_copy(g);
-  return rc;
-}
+int pps_cov_recover(pps_graph* g) { return cov_entry(g, CovPass::BandLevels); }
+int pps_cov_factor(pps_graph* g) { return cov_entry(g, CovPass::FactorOnly); }
+int pps_cov_select(pps_graph* g) { return cov_entry(g, CovPass::Select); }
 
 int pps_debug_cov_select_form(pps_graph* g, int form) {
   if (!g) return PPS_EINVAL;
@@ -661,7 +564,6 @@ int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols
   if (joint) { cols = rows; nc = nr; }
   // distinct nodes of the query: every one is walked once, however often it is asked for
   std::vector<int> walk_of(g->nodes.size(), -1), ids, ri((size_t)nr), ci((size_t)nc);
-  std::vector<CovNode> nd;
   for (int pass = 0; pass < (joint ? 1 : 2); pass++) {
     const int n = pass ? nc : nr;
     const int* list = pass ? cols : rows;
@@ -671,20 +573,16 @@ int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols
       const int rc = cov_node(g, list[i], &c); if (rc != PPS_OK) return rc;
       if (seen[list[i]]) return fail(g, PPS_EINVAL, "covariance block: node " + std::to_string(list[i]) + " is listed twice among the " + (pass ? "columns" : "rows"));
       seen[list[i]] = 1;
-      if (walk_of[list[i]] < 0) { walk_of[list[i]] = (int)ids.size(); ids.push_back(list[i]); nd.push_back(c); }
+      if (walk_of[list[i]] < 0) { walk_of[list[i]] = (int)ids.size(); ids.push_back(list[i]); }
       (pass ? ci : ri)[i] = walk_of[list[i]];
     }
   }
   if (joint) ci = ri;
   if (!cov_factor_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
   if (nr == 0 || nc == 0) return PPS_OK;
-  CovWalks cw;
-  { const int rc = cov_build_walks(g, ids, nd, &cw); if (rc != PPS_OK) return rc; }
-  const int K = cw.K;
-  const long long n_strip = cw.n_strip;
-  const std::vector<CovWalk>& walks = cw.walks;
-  const std::vector<CovStep>& steps = cw.steps;
-  auto common = [&](int a, int b) { return cov_common_pivots(g, cw, a, b); };
+  CovQuery q(g);
+  int rc = q.build(ids); if (rc != PPS_OK) return rc;
+  const std::vector<CovNode>& nd = q.nd;
   std::vector<int> roff((size_t)nr + 1, 0), coff((size_t)nc + 1, 0);
   for (int i = 0; i < nr; i++) roff[i + 1] = roff[i] + nd[ri[i]].dim;
   for (int j = 0; j < nc; j++) coff[j + 1] = coff[j] + nd[ci[j]].dim;
@@ -694,41 +592,23 @@ int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols
   pairs.reserve(joint ? (size_t)nr * (nr + 1) / 2 : (size_t)nr * nc);
   for (int i = 0; i < nr; i++)
     for (int j = 0; j < (joint ? i + 1 : nc); j++) {
-      const int a = ri[i], b = ci[j], len = common(a, b);
-      CovPair q;
-      q.yi = walks[a].strip + (long long)(K - len) * nd[a].dim; q.yj = walks[b].strip + (long long)(K - len) * nd[b].dim;
-      q.dst = (long long)roff[i] * ld + coff[j];
-      q.dst_t = joint ? (long long)roff[j] * ld + coff[i] : -1;          // (cols = rows: the lower triangle, mirrored)
-      q.di = nd[a].dim; q.dj = nd[b].dim; q.len = len; q.ld = ld;
-      pairs.push_back(q);
+      const int a = ri[i], b = ci[j], len = q.common_pivots(a, b);
+      CovPair pr;
+      pr.yi = q.walks[a].strip + (long long)(q.K - len) * nd[a].dim; pr.yj = q.walks[b].strip + (long long)(q.K - len) * nd[b].dim;
+      pr.dst = (long long)roff[i] * ld + coff[j];
+      pr.dst_t = joint ? (long long)roff[j] * ld + coff[i] : -1;          // (cols = rows: the lower triangle, mirrored)
+      pr.di = nd[a].dim; pr.dj = nd[b].dim; pr.len = len; pr.ld = ld;
+      pairs.push_back(pr);
     }
-  // one request: [walks | steps | pairs]
-  const size_t o_steps = walks.size() * sizeof(CovWalk), o_pairs = (o_steps + steps.size() * sizeof(CovStep) + 15) & ~(size_t)15;
-  std::vector<char> req(o_pairs + pairs.size() * sizeof(CovPair));
-  memcpy(req.data(), walks.data(), walks.size() * sizeof(CovWalk));
-  memcpy(req.data() + o_steps, steps.data(), steps.size() * sizeof(CovStep));
-  memcpy(req.data() + o_pairs, pairs.data(), pairs.size() * sizeof(CovPair));
-  HIP_TRY(g, hipSetDevice(g->props.device));
-  for (hipEvent_t& e : g->cov_bev) if (!e) HIP_TRY(g, hipEventCreate(&e));
-  int rc = cov_reserve(g, &g->cov_breq, &g->cov_breq_cap, req.size()); if (rc != PPS_OK) return rc;
-  rc = cov_reserve(g, &g->cov_strip, &g->cov_strip_cap, (size_t)n_strip); if (rc != PPS_OK) return rc;
-  rc = cov_walk_scratch(g, cw); if (rc != PPS_OK) return rc;
-  if ((size_t)n_out + 1 > g->cov_bout_cap || !g->cov_bout) g->cov_bout_clean = false;
-  rc = cov_reserve(g, &g->cov_bout, &g->cov_bout_cap, (size_t)n_out + 1); if (rc != PPS_OK) return rc;
-  if (!g->cov_bout_clean) HIP_TRY(g, hipMemsetAsync(g->cov_bout, 0, sizeof(double), g->stream));      // (a new buffer, or a query that failed)
-  g->cov_bout_clean = false;
-  const unsigned long long launches0 = launch_count();
-  HIP_TRY(g, hipMemcpyAsync(g->cov_breq, req.data(), req.size(), hipMemcpyHostToDevice, g->stream));
-  HIP_TRY(g, hipEventRecord(g->cov_bev[0], g->stream));
-  HIP_TRY(g, cov_launch_walks(g, cw, reinterpret_cast<const CovWalk*>(g->cov_breq), reinterpret_cast<const CovStep*>(g->cov_breq + o_steps), g->cov_bout));
-  HIP_TRY(g, launch_cov_gram(reinterpret_cast<const CovPair*>(g->cov_breq + o_pairs), (int)pairs.size(), g->cov_strip, n_strip, g->cov_bout, n_out, g->stream));
-  HIP_TRY(g, hipEventRecord(g->cov_bev[1], g->stream));
+  const size_t o_pairs = q.add(pairs.data(), pairs.size() * sizeof(CovPair));
+  rc = q.reserve(); if (rc != PPS_OK) return rc;
+  const size_t bout_cap = g->cov_bout.cap;
+  rc = g->cov_bout.reserve(g, (size_t)n_out + 1); if (rc != PPS_OK) return rc;
+  rc = zero_between_calls(g, &g->cov_bout_clean, g->cov_bout.p, g->cov_bout.cap != bout_cap, sizeof(double), nullptr, false); if (rc != PPS_OK) return rc;
+  rc = q.walk(g->cov_bout.p); if (rc != PPS_OK) return rc;
+  HIP_TRY(g, launch_cov_gram(q.dev<CovPair>(o_pairs), (int)pairs.size(), g->cov_strip.p, q.n_strip, g->cov_bout.p, n_out, g->stream));
   std::vector<double> host((size_t)n_out + 1);
-  HIP_TRY(g, hipMemcpyAsync(host.data(), g->cov_bout, host.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  g->cov_block_launches = (int)(launch_count() - launches0);
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, g->cov_bev[0], g->cov_bev[1]) == hipSuccess) g->cov_block_sec = 1e-3 * ms;
+  rc = q.finish(host.data(), g->cov_bout.p, host.size() * sizeof(double), &g->cov_block_sec, &g->cov_block_launches); if (rc != PPS_OK) return rc;
   if (host[0] != 0.0) return fail(g, PPS_EHIP, "internal error: a covariance path solve met an index outside its front or its strip");
   g->cov_bout_clean = true;
   memcpy(out, host.data() + 1, (size_t)n_out * sizeof(double));

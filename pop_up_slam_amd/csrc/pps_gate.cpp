@@ -5,9 +5,10 @@
 // a pairing is accepted when d2 is below a chi-square quantile (3 degrees of freedom: 7.815 at 0.95).
 //
 // The candidate factors are never added: the call reads the estimate and the lambda = 0 factor pps_cov_recover left in dev.L, and writes
-// buffers of its own.  One request upload, the k_cov_path launch of pps_cov_block for the 1 + n_planes distinct nodes, the gate launch
-// (pps_gate.hip), one copy back ([status | d2 | best]).  Validity: that of pps_cov_block (cov_factor_current: a factor of pps_cov_recover or of
-// pps_cov_factor; the walks take k_cov_path or k_cov_path_wide as pps_cov_block's do).
+// buffers of its own.  A CovQuery (pps_graph.h) over the 1 + n_planes distinct nodes does the protocol -- one request upload, the walk launch of
+// pps_cov_block, the copy back ([status | d2 | best]) --; what is written here are the argument checks, the request's candidate and measurement
+// sections, the arguments of the gate launch (pps_gate.hip) and the decoding of the result.  Validity: that of pps_cov_block
+// (cov_factor_current: a factor of any of the three recovery calls).
 #include "pps_gate.h"
 #include "pps_graph.h"
 
@@ -17,12 +18,8 @@ using namespace pps_impl;
 namespace pps_impl {
 
 void gate_release(pps_graph* g) {
-  if (g->gate_out) (void)hipFree(g->gate_out);
-  if (g->gate_ticket) (void)hipFree(g->gate_ticket);
-  if (g->gate_rec) (void)hipFree(g->gate_rec);
-  for (hipEvent_t& e : g->gate_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-  g->gate_out = nullptr; g->gate_ticket = nullptr; g->gate_rec = nullptr;
-  g->gate_out_cap = g->gate_ticket_cap = g->gate_rec_cap = 0; g->gate_rec_n = 0; g->gate_clean = false;
+  g->gate_out.release(); g->gate_ticket.release(); g->gate_rec.release();
+  g->gate_rec_n = 0; g->gate_clean = false;
 }
 
 }  // namespace pps_impl
@@ -38,13 +35,8 @@ int pps_assoc_gate_last(const pps_graph* g, double* kernel_sec, int* launches) {
 
 int pps_debug_assoc_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed) {
   if (!g || !needed) return PPS_EINVAL;
-  if (g->gate_rec_n == 0 || !g->gate_rec) return fail(g, PPS_ESTATE, "no association gate has been computed on this handle");
-  *needed = (int64_t)g->gate_rec_n * 30;
-  if (!rec || cap < *needed) return PPS_OK;
-  HIP_TRY(g, hipSetDevice(g->props.device));
-  HIP_TRY(g, hipMemcpyAsync(rec, g->gate_rec, (size_t)*needed * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  return PPS_OK;
+  if (g->gate_rec_n == 0 || !g->gate_rec.p) return fail(g, PPS_ESTATE, "no association gate has been computed on this handle");
+  return copy_records(g, g->gate_rec, g->gate_rec_n * 30, cap, rec, needed);
 }
 
 int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, const double* sqrtinf_ut, int n_planes, const int* plane_ids,
@@ -55,17 +47,7 @@ int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, c
   // the candidates' r and Jw are the squared-error ones; with a cost function the recovered covariance is that of the robustified system
   if (robust(g)) return fail(g, PPS_ESTATE, "association gate: a robust cost function is set (pps_set_cost_function); the gate has no robustified form -- set PPS_COST_NONE and recover again");
   std::vector<int> all;
-  if (!plane_ids) {
-    for (size_t i = 0; i < g->nodes.size(); i++) if (!g->nodes[i].deleted && g->nodes[i].type == NODE_PLANE) all.push_back((int)i);
-    plane_ids = all.data(); n_planes = (int)all.size();
-  }
-  { std::vector<char> seen(g->nodes.size(), 0);
-    for (int i = 0; i < n_planes; i++) {
-      const int id = plane_ids[i];
-      if (!live_node(g, id, NODE_PLANE)) return fail(g, PPS_EINVAL, "association gate: node " + std::to_string(id) + " is not a live plane");
-      if (seen[id]) return fail(g, PPS_EINVAL, "association gate: plane " + std::to_string(id) + " is listed twice");
-      seen[id] = 1;
-    } }
+  { const int rc = plane_list(g, "association gate: ", &plane_ids, &n_planes, &all); if (rc != PPS_OK) return rc; }
   // measurements: normalised like Plane3d(Vector4d), as pps_add_plane_obs stores them
   std::vector<double> meas((size_t)n_meas * 10);
   for (int i = 0; i < n_meas; i++) {
@@ -76,69 +58,37 @@ int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, c
   }
   if (n_meas == 0 || n_planes == 0) return PPS_OK;       // nothing asked for: the outputs stay untouched
   if (!cov_factor_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
-  // walks: the pose first, then the candidates in the order given (the tables of pps_cov_block)
-  const int nw = 1 + n_planes;
-  std::vector<int> ids((size_t)nw);
-  std::vector<CovNode> nd((size_t)nw);
-  for (int w = 0; w < nw; w++) {
-    ids[w] = w == 0 ? pose_id : plane_ids[w - 1];
-    const int rc = cov_node(g, ids[w], &nd[w]); if (rc != PPS_OK) return rc;
-  }
-  CovWalks cw;
-  { const int rc = cov_build_walks(g, ids, nd, &cw); if (rc != PPS_OK) return rc; }
-  const int K = cw.K;
-  const long long n_strip = cw.n_strip;
-  const std::vector<CovWalk>& walks = cw.walks;
-  const std::vector<CovStep>& steps = cw.steps;
+  // walks: the pose first, then the candidates in the order given
+  std::vector<int> ids((size_t)1 + n_planes);
+  ids[0] = pose_id;
+  std::copy(plane_ids, plane_ids + n_planes, ids.begin() + 1);
+  CovQuery q(g);
+  int rc = q.build(ids); if (rc != PPS_OK) return rc;
   std::vector<GatePlane> cand((size_t)n_planes);
   for (int l = 0; l < n_planes; l++)
-    cand[l] = GatePlane{walks[1 + l].strip, g->nodes[plane_ids[l]].slot, g->cov_rootlen[nd[1 + l].front], cov_common_pivots(g, cw, 0, 1 + l), 0};
-  // one request: [walks | steps | candidates | measurements]
-  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t o_steps = walks.size() * sizeof(CovWalk), o_cand = up16(o_steps + steps.size() * sizeof(CovStep)),
-               o_meas = up16(o_cand + cand.size() * sizeof(GatePlane));
-  std::vector<char> req(o_meas + meas.size() * sizeof(double));
-  memcpy(req.data(), walks.data(), walks.size() * sizeof(CovWalk));
-  memcpy(req.data() + o_steps, steps.data(), steps.size() * sizeof(CovStep));
-  memcpy(req.data() + o_cand, cand.data(), cand.size() * sizeof(GatePlane));
-  memcpy(req.data() + o_meas, meas.data(), meas.size() * sizeof(double));
+    cand[l] = GatePlane{q.walks[1 + l].strip, g->nodes[plane_ids[l]].slot, g->cov_rootlen[q.nd[1 + l].front], q.common_pivots(0, 1 + l), 0};
+  // the request's own sections: [candidates | measurements]
+  const size_t o_cand = q.add(cand.data(), cand.size() * sizeof(GatePlane)), o_meas = q.add(meas.data(), meas.size() * sizeof(double));
   const size_t n_d2 = (size_t)n_meas * n_planes, n_out = 1 + n_d2 + ((size_t)n_meas + 1) / 2;      // doubles: status | d2 | best (ints)
-  HIP_TRY(g, hipSetDevice(g->props.device));
-  for (hipEvent_t& e : g->gate_ev) if (!e) HIP_TRY(g, hipEventCreate(&e));
-  // (cov_breq / cov_strip are shared with pps_cov_block: both calls end with a synchronisation, neither is in flight here)
-  int rc = cov_reserve(g, &g->cov_breq, &g->cov_breq_cap, req.size()); if (rc != PPS_OK) return rc;
-  rc = cov_reserve(g, &g->cov_strip, &g->cov_strip_cap, (size_t)n_strip); if (rc != PPS_OK) return rc;
-  rc = cov_walk_scratch(g, cw); if (rc != PPS_OK) return rc;
-  const double* out0 = g->gate_out; const unsigned int* ticket0 = g->gate_ticket;
-  rc = cov_reserve(g, &g->gate_out, &g->gate_out_cap, n_out); if (rc != PPS_OK) return rc;
-  rc = cov_reserve(g, &g->gate_ticket, &g->gate_ticket_cap, (size_t)n_meas); if (rc != PPS_OK) return rc;
+  rc = q.reserve(); if (rc != PPS_OK) return rc;
+  const size_t out_cap = g->gate_out.cap, ticket_cap = g->gate_ticket.cap;
+  rc = g->gate_out.reserve(g, n_out); if (rc != PPS_OK) return rc;
+  rc = g->gate_ticket.reserve(g, (size_t)n_meas); if (rc != PPS_OK) return rc;
   g->gate_rec_n = 0;
-  rc = cov_reserve(g, &g->gate_rec, &g->gate_rec_cap, n_d2 * 30); if (rc != PPS_OK) return rc;
-  const bool fresh = !g->gate_clean || g->gate_out != out0 || g->gate_ticket != ticket0 || !out0 || !ticket0;
-  if (fresh) {                                           // (a new buffer, or a call that failed)
-    HIP_TRY(g, hipMemsetAsync(g->gate_out, 0, sizeof(double), g->stream));
-    HIP_TRY(g, hipMemsetAsync(g->gate_ticket, 0, g->gate_ticket_cap * sizeof(unsigned int), g->stream));
-  }
-  g->gate_clean = false;
+  rc = g->gate_rec.reserve(g, n_d2 * 30); if (rc != PPS_OK) return rc;
+  rc = zero_between_calls(g, &g->gate_clean, g->gate_out.p, g->gate_out.cap != out_cap, sizeof(double), &g->gate_ticket, g->gate_ticket.cap != ticket_cap);
+  if (rc != PPS_OK) return rc;
   GateArgs ga;
-  ga.planes = reinterpret_cast<const GatePlane*>(g->cov_breq + o_cand); ga.n_planes = n_planes;
-  ga.meas = reinterpret_cast<const double*>(g->cov_breq + o_meas); ga.n_meas = n_meas;
-  ga.strip_x = walks[0].strip; ga.pose_slot = g->nodes[pose_id].slot; ga.rootlen_x = g->cov_rootlen[nd[0].front];
-  ga.K = K; ga.Y = g->cov_strip; ga.n_strip = n_strip;
+  ga.planes = q.dev<GatePlane>(o_cand); ga.n_planes = n_planes;
+  ga.meas = q.dev<double>(o_meas); ga.n_meas = n_meas;
+  ga.strip_x = q.walks[0].strip; ga.pose_slot = g->nodes[pose_id].slot; ga.rootlen_x = g->cov_rootlen[q.nd[0].front];
+  ga.K = q.K; ga.Y = g->cov_strip.p; ga.n_strip = q.n_strip;
   ga.mode = g->props.jacobian_mode;
-  ga.ticket = g->gate_ticket; ga.out = g->gate_out; ga.rec = g->gate_rec;
-  const unsigned long long launches0 = launch_count();
-  HIP_TRY(g, hipMemcpyAsync(g->cov_breq, req.data(), req.size(), hipMemcpyHostToDevice, g->stream));
-  HIP_TRY(g, hipEventRecord(g->gate_ev[0], g->stream));
-  HIP_TRY(g, cov_launch_walks(g, cw, reinterpret_cast<const CovWalk*>(g->cov_breq), reinterpret_cast<const CovStep*>(g->cov_breq + o_steps), g->gate_out));
+  ga.ticket = g->gate_ticket.p; ga.out = g->gate_out.p; ga.rec = g->gate_rec.p;
+  rc = q.walk(g->gate_out.p); if (rc != PPS_OK) return rc;
   HIP_TRY(g, launch_assoc_gate(g->dev, ga, g->stream));
-  HIP_TRY(g, hipEventRecord(g->gate_ev[1], g->stream));
   std::vector<double> host(n_out);
-  HIP_TRY(g, hipMemcpyAsync(host.data(), g->gate_out, n_out * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  g->gate_launches = (int)(launch_count() - launches0);
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, g->gate_ev[0], g->gate_ev[1]) == hipSuccess) g->gate_sec = 1e-3 * ms;
+  rc = q.finish(host.data(), g->gate_out.p, n_out * sizeof(double), &g->gate_sec, &g->gate_launches); if (rc != PPS_OK) return rc;
   if (host[0] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: the association gate met an index outside its front, its strip or the state arrays");
   if (host[0] != 0.0)
     return fail(g, PPS_ENOTPD, "association gate: the innovation covariance of a candidate is not positive definite (a pivot of the 3 x 3 factor was not positive or not finite)");

@@ -7,8 +7,8 @@
 //   pps_lm.h         the LM rule the loops of pps_solve.cpp and pps_multi.cpp share (accept / reject / stop, lambda schedule, trace, counters): host only, no HIP
 //   pps_frames.cpp   registered frames (measurement refresh on the device), data association, point re-projection
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
-//   pps_cov.cpp      marginal covariances from the factor (isam::Covariances); kernels in pps_cov.hip
-//   pps_gate.cpp     pps_assoc_gate (measurement against landmark); pps_merge.cpp: pps_merge_gate (landmark against landmark)
+//   pps_cov.cpp      marginal covariances from the factor (isam::Covariances): the recovery pipeline and the query scaffold (CovQuery); kernels in pps_cov*.hip
+//   pps_gate.cpp     pps_assoc_gate (measurement against landmark); pps_merge.cpp: pps_merge_gate (landmark against landmark): queries on the factor
 //   pps_map.cpp      the dense map (pps_map: per-plane clouds of every frame, re-projected on the device); kernels in pps_map.hip
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,6 +58,14 @@ inline double now_s() {
   using namespace std::chrono;
   return duration_cast<duration<double>>(steady_clock::now().time_since_epoch()).count();
 }
+
+// a device buffer of one of the covariance calls (reserve / release: below, with the handle they take)
+template <class T>
+struct DevBuf {
+  T* p = nullptr; size_t cap = 0;      // cap in elements
+  int reserve(pps_graph* g, size_t count, const char* who = nullptr, const std::string& what = std::string(), const char* advice = "");
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
 
 }  // namespace pps_impl
 
@@ -199,54 +207,59 @@ struct pps_graph {
   pps::AssocQuery* d_queries = nullptr; pps::AssocResult* d_results = nullptr; size_t d_q_cap = 0;   // PINNED host memory: k_assoc reads the queries and writes the results over the bus
   double* d_lm_planes = nullptr; size_t d_lm_planes_cap = 0;   // [4][n] landmark planes when the solver state is not current
   char* rp_pin = nullptr; size_t rp_cap = 0;                  // pinned block of pps_reproject_points: [slots | points in | points out], read and written by the kernel
-  // marginal covariances (pps_cov.cpp): the selected inverse of the last pps_cov_recover, in the panel layout of L ([Sigma_AA; Sigma_BA] per
+  // marginal covariances (pps_cov.cpp): the selected inverse of the last recovery pass, in the panel layout of L ([Sigma_AA; Sigma_BA] per
   // front at f_Loff; a front's Sigma_BB sits in its -- then dead -- update matrix in dev.U).  Buffers of their own, allocated on the first
   // recovery; cov_valid falls with every call that moves the estimate, the measurements or the topology (cov_invalidate)
   bool cov_valid = false;
-  // a valid lambda = 0 factor is held in dev.L (all pps_cov_block and pps_assoc_gate read): set by pps_cov_recover together with cov_valid, by
+  // a valid lambda = 0 factor is held in dev.L (all pps_cov_block and the gates read): set by a recovery pass together with cov_valid, by
   // pps_cov_factor alone; falls with cov_valid
   bool cov_factor_valid = false;
-  int cov_tables_version = -1;       // upload_version the node -> front tables (cov_epos .. cov_max_rows) were built and checked for by pps_cov_factor
-  int cov_version = -1;              // upload_version the recovery (and cov_parent) belongs to
-  double* cov_S = nullptr; size_t cov_S_cap = 0;
-  int* cov_parent = nullptr; size_t cov_parent_cap = 0; int cov_parent_version = -1;
-  char* cov_req = nullptr; size_t cov_req_cap = 0;       // gather requests of a read call (device)
-  double* cov_out = nullptr; size_t cov_out_cap = 0;     // ... and the blocks they collect
+  int cov_version = -1;              // upload_version the recovery belongs to
+  // what of the recovery's preparation is current: everything in `have` was built, checked or uploaded for the analysis of upload_version
+  // `version` (cov_run forgets it all when the versions differ)
+  enum : unsigned { kCovTables = 1,  // node -> front tables (cov_epos .. cov_max_rows) built, the tree checked for the path walks
+                    kCovLevelShapes = 2,   // ... and for k_cov_level (its LDS)
+                    kCovParent = 4,        // cov_parent holds f_parent
+                    kCovDense = 8 };       // the tree checked for the dense-front pass; cov_dtab, cov_dpre_items and cov_dlevel hold its work lists
+  struct CovCache { int version = -1; unsigned have = 0; } cov_cache;
+  pps_impl::DevBuf<double> cov_S;
+  pps_impl::DevBuf<int> cov_parent;
+  pps_impl::DevBuf<char> cov_req;    // gather requests of a read call (device)
+  pps_impl::DevBuf<double> cov_out;  // ... and the blocks they collect
   std::vector<int> cov_epos, cov_front_of;               // delta index -> elimination-ordered scalar; that scalar -> front
   hipEvent_t cov_ev[3] = {nullptr, nullptr, nullptr};
   double cov_sec[2] = {0, 0};        // device seconds of the last recovery: whole call | root -> leaves pass alone
-  // pps_cov_block (blocks outside the pattern, by root-path solves on dev.L): per front the pivots of the front and all its ancestors,
-  // the request tables / strips / result of a query (device; the first double of cov_bout is the query's status word, zero between queries)
+  // the queries on the factor (CovQuery below: pps_cov_block, pps_assoc_gate, pps_merge_gate): per front the pivots of the front and all its
+  // ancestors; the request blob, the strips and the event pair of the query in flight (every query ends with a synchronisation)
   std::vector<int> cov_rootlen; int cov_max_p = 0, cov_max_rows = 0;
-  char* cov_breq = nullptr; size_t cov_breq_cap = 0;
-  double* cov_strip = nullptr; size_t cov_strip_cap = 0;
-  double* cov_bout = nullptr; size_t cov_bout_cap = 0; bool cov_bout_clean = false;
-  hipEvent_t cov_bev[2] = {nullptr, nullptr};
-  double cov_block_sec = 0; int cov_block_launches = 0;   // the two kernels of the last query: device seconds, launches
+  pps_impl::DevBuf<char> cov_breq;
+  pps_impl::DevBuf<double> cov_strip;
+  hipEvent_t cov_qev[2] = {nullptr, nullptr};
   // the path walk for wide fronts (k_cov_path_wide): the right-hand sides of the walks of one query, sized by the widest front on its paths
-  double* cov_zscr = nullptr; size_t cov_zscr_cap = 0;
+  pps_impl::DevBuf<double> cov_zscr;
   int cov_path_form = 0;             // pps_debug_cov_path_form: 0 = k_cov_path where its LDS fits, 1 = always the wide kernel
-  // pps_cov_select on a dense-front tree (pps_cov_dense.hip): G = L_B L_A^-1 of every front in the panel layout of L, and the work-item
-  // prefix sums of its launches -- [all fronts: G slabs | per level: gather pieces, Sigma_BA strips] -- on the device (cov_dtab) with their places
-  double* cov_G = nullptr; size_t cov_G_cap = 0;
-  int* cov_dtab = nullptr; size_t cov_dtab_cap = 0; int cov_dtab_version = -1;      // upload_version the tables (and cov_parent) were checked and uploaded for
+  // pps_cov_block: the result of a query on the device (the first double is the query's status word, zero between queries)
+  pps_impl::DevBuf<double> cov_bout; bool cov_bout_clean = false;
+  double cov_block_sec = 0; int cov_block_launches = 0;   // the two kernels of the last query: device seconds, launches
+  // the dense-front pass (pps_cov_dense.hip): G = L_B L_A^-1 of every front in the panel layout of L, and the work-item prefix sums of its
+  // launches -- [all fronts: G slabs | per level: gather pieces, Sigma_BA strips] -- on the device (cov_dtab) with their places
+  pps_impl::DevBuf<double> cov_G;
+  pps_impl::DevBuf<int> cov_dtab;
   int cov_dpre_items = 0;
   std::vector<int> cov_dlevel;       // per level, 4 ints: place of the gather sums in cov_dtab, their total, place of the strip sums, their total
   int cov_select_form = 0;           // pps_debug_cov_select_form: 1 = pps_cov_select takes the dense-front pass on a band graph too
   // pps_assoc_gate (pps_gate.cpp): result of a call on the device ([status | d2 | best], the status word zero between calls) and one
-  // ticket per measurement (zero between calls); the request and the strips share cov_breq / cov_strip with pps_cov_block
-  double* gate_out = nullptr; size_t gate_out_cap = 0; bool gate_clean = false;
-  unsigned int* gate_ticket = nullptr; size_t gate_ticket_cap = 0;
-  hipEvent_t gate_ev[2] = {nullptr, nullptr};
+  // ticket per measurement (zero between calls)
+  pps_impl::DevBuf<double> gate_out; bool gate_clean = false;
+  pps_impl::DevBuf<unsigned int> gate_ticket;
   double gate_sec = 0; int gate_launches = 0;             // the two kernels of the last call: device seconds, launches
-  double* gate_rec = nullptr; size_t gate_rec_cap = 0; size_t gate_rec_n = 0;   // [Jp | Jl | r] per candidate of the last call (pps_debug_assoc_gate_records)
+  pps_impl::DevBuf<double> gate_rec; size_t gate_rec_n = 0;   // [Jp | Jl | r] per candidate of the last call (pps_debug_assoc_gate_records)
   // pps_merge_gate (pps_merge.cpp): result of a call on the device ([status | best | flags | d2 n x n], the status word zero between calls) and
-  // one ticket per listed plane (zero between calls); the request and the strips share cov_breq / cov_strip with pps_cov_block
-  char* merge_out = nullptr; size_t merge_out_cap = 0; bool merge_clean = false;
-  unsigned int* merge_ticket = nullptr; size_t merge_ticket_cap = 0;
-  hipEvent_t merge_ev[2] = {nullptr, nullptr};
+  // one ticket per listed plane (zero between calls)
+  pps_impl::DevBuf<char> merge_out; bool merge_clean = false;
+  pps_impl::DevBuf<unsigned int> merge_ticket;
   double merge_sec = 0; int merge_launches = 0, merge_not_pd = 0;      // the two kernels of the last call: device seconds, launches; its pairs without a positive definite S
-  double* merge_rec = nullptr; size_t merge_rec_cap = 0; size_t merge_rec_n = 0;   // [J_a | J_b | e] per pair of the last call (pps_debug_merge_gate_records)
+  pps_impl::DevBuf<double> merge_rec; size_t merge_rec_n = 0;   // [J_a | J_b | e] per pair of the last call (pps_debug_merge_gate_records)
   bool merge_done = false;           // a call has succeeded on this handle
   // stats / trace
   pps_stats stats{};
@@ -270,6 +283,8 @@ inline int hip_fail(pps_graph* g, hipError_t e, const char* what) {
     if (_e != hipSuccess) return hip_fail(g, _e, #expr);   \
   } while (0)
 
+
+inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }      // sections of a request or a result sit at multiples of 16 bytes
 
 inline bool live_node(const pps_graph* g, int id, int type) {
   return id >= 0 && id < (int)g->nodes.size() && !g->nodes[id].deleted && g->nodes[id].type == type;
@@ -300,6 +315,21 @@ int prepare_solve(pps_graph* g);
 int read_result(pps_graph* g, bool at_estimate, double* chi2, double* dnorm, bool* notpd);
 void begin_solve(pps_graph* g);                // an LM solve starts: the last one's stats and trace go
 void abandon_device_copy(pps_graph* g);
+int clear_stale_status(pps_graph* g);          // result_dev / spec_result zeroed unless they are (status_clean), which then no longer holds
+int enqueue_plain_factor(pps_graph* g, double lambda);      // the factorisation alone, plain launches: the band stages, or memset + hpush + dense levels
+// "this call is no solve": the figures of the last solve, the profiling level and launches0 come back when the scope ends; only the fields
+// that describe the analysis follow the analysis
+struct NoSolveScope {
+  pps_graph* g; pps_stats saved; int profiling; unsigned long long launches0;
+  explicit NoSolveScope(pps_graph* g_) : g(g_), saved(g_->stats), profiling(g_->profiling), launches0(g_->launches0) { g->profiling = 0; }
+  ~NoSolveScope() {
+    g->profiling = profiling;
+    g->launches0 = launches0;
+    pps_stats s = saved;
+    s.n_fronts = g->stats.n_fronts; s.n_levels = g->stats.n_levels; s.max_front = g->stats.max_front; s.nnz_L = g->stats.nnz_L;
+    g->stats = s;
+  }
+};
 inline LmSink lm_sink(pps_graph* g, bool verbose) { return LmSink{&g->props, &g->tr_lambda, &g->tr_chi2, &g->tr_acc, &g->stats, verbose}; }
 // the one place where a handle's cost function chooses the kernels: K1 and the two chi2 sweeps (everything else consumes J, r and delta)
 inline bool robust(const pps_graph* g) { return g->cost.kind != COST_NONE; }
@@ -326,28 +356,53 @@ extern const char* const kFactorOnly;          // ... and when there is a factor
 struct CovNode { int front, local, dim, epos, voff; };
 int cov_node(pps_graph* g, int id, CovNode* out);      // id check (PPS_EINVAL) + dim; the rest by cov_locate, with a current recovery only
 int cov_locate(pps_graph* g, int id, CovNode* n);
-// the walks of a query as k_cov_path takes them (pps_cov.h), shared by pps_cov_block and pps_assoc_gate
-struct CovWalks { std::vector<pps::CovWalk> walks; std::vector<pps::CovStep> steps; std::vector<int> step_end; int K = 0; long long n_strip = 0;
-                  int max_rows = 1; };            // max_rows: the widest front (p + b) on the paths of this query
-int cov_build_walks(pps_graph* g, const std::vector<int>& ids, std::vector<CovNode>& nd, CovWalks* out);      // locates the nodes (cov_locate), too
-int cov_common_pivots(const pps_graph* g, const CovWalks& cw, int a, int b);                                    // walks a, b: pivots of their common ancestors
-// the walk kernel of a query -- k_cov_path where its LDS fits the graph's fronts, k_cov_path_wide otherwise (or when the handle asks for it).
-// cov_walk_scratch reserves the wide kernel's right-hand sides (PPS_ENOMEM) and belongs BEFORE the query's upload; cov_launch_walks is the launch.
-bool cov_walk_wide(const pps_graph* g);
-int cov_walk_scratch(pps_graph* g, const CovWalks& cw);
-hipError_t cov_launch_walks(pps_graph* g, const CovWalks& cw, const pps::CovWalk* walks, const pps::CovStep* steps, double* out);
-// a device buffer of one of the covariance calls, grown by a quarter when it is too small
+// a device buffer of one of the covariance calls, grown by a quarter when it is too small.  Without `who` a failure answers as HIP_TRY does; with
+// it, PPS_ENOMEM and "<who>no device memory for <what> (<n> bytes)<advice>"
 template <class T>
-int cov_reserve(pps_graph* g, T** buf, size_t* cap, size_t count) {
-  if (count <= *cap && *buf) return PPS_OK;
-  HIP_TRY(g, hipStreamSynchronize(g->stream));          // (nothing in flight reads the old buffer)
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr; *cap = 0;
-  const size_t want = std::max<size_t>(64, count + count / 4);
-  HIP_TRY(g, hipMalloc(reinterpret_cast<void**>(buf), want * sizeof(T)));
-  *cap = want;
-  return PPS_OK;
+int DevBuf<T>::reserve(pps_graph* g, size_t count, const char* who, const std::string& what, const char* advice) {
+  if (count <= cap && p) return PPS_OK;
+  const auto grow = [&]() -> int {
+    HIP_TRY(g, hipStreamSynchronize(g->stream));          // (nothing in flight reads the old buffer)
+    release();
+    const size_t want = std::max<size_t>(64, count + count / 4);
+    HIP_TRY(g, hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T)));
+    cap = want;
+    return PPS_OK;
+  };
+  const int rc = grow();
+  if (rc == PPS_OK || !who) return rc;
+  (void)hipGetLastError();
+  return fail(g, PPS_ENOMEM, std::string(who) + "no device memory for " + what + " (" + std::to_string(count * sizeof(T)) + " bytes)" + advice);
 }
+// A query on the factor: walks up the tree for a list of distinct, checked nodes (k_cov_path / k_cov_path_wide, pps_cov.h), then the caller's
+// own kernel over the strips the walks leave.  The order of a call: build -> add (its own sections) -> reserve -> its own buffers ->
+// walk -> its own launch -> finish.
+struct CovQuery {
+  pps_graph* g;
+  std::vector<CovNode> nd;                       // the nodes, located
+  std::vector<pps::CovWalk> walks; std::vector<pps::CovStep> steps; std::vector<int> step_end;
+  int K = 0;                                     // the longest path of the query in pivots
+  long long n_strip = 0;
+  int max_rows = 1;                              // the widest front (p + b) on the paths of this query
+  std::vector<char> req;                         // [walks | steps | the caller's sections ...], every section at a multiple of 16 bytes
+  size_t o_steps = 0;
+  unsigned long long launches0 = 0;
+  explicit CovQuery(pps_graph* g_) : g(g_) {}
+  int build(const std::vector<int>& ids);                      // id check (cov_node), cov_locate, paths leaf -> root; starts the request
+  int common_pivots(int a, int b) const;                       // walks a, b: pivots of their common ancestors
+  size_t add(const void* data, size_t bytes);                  // a section of the caller's; its offset in the request
+  template <class T> const T* dev(size_t off) const { return reinterpret_cast<const T*>(g->cov_breq.p + off); }   // (after reserve)
+  int reserve(const char* who = nullptr, const char* advice = "");   // device, events, cov_breq, cov_strip, the wide scratch (that one always PPS_ENOMEM)
+  int walk(double* status);                                    // upload -> event -> the walk launch; the caller's launch comes next
+  int finish(void* host, const void* dev_src, size_t bytes, double* sec, int* launches);      // event -> copy back -> synchronise -> the _last figures
+};
+// the default list (ids == NULL: all live planes) and the check of a given one: live planes, none listed twice
+int plane_list(pps_graph* g, const char* prefix, const int** ids, int* n, std::vector<int>* all);
+// the status word (the first status_bytes of `out`) and the tickets of a call are zero between calls: zeroed here after a call that failed
+// (!*clean) or when a buffer is new (its capacity is not what it was before the call reserved it); *clean is false until the call succeeds
+int zero_between_calls(pps_graph* g, bool* clean, void* out, bool out_new, size_t status_bytes, DevBuf<unsigned int>* ticket, bool ticket_new);
+// pps_debug_*_records: n doubles of the last call's records
+int copy_records(pps_graph* g, const DevBuf<double>& rec, size_t n, int64_t cap, double* out, int64_t* needed);
 // ---- pps_gate.cpp ----
 void gate_release(pps_graph* g);               // (from cov_release)
 // ---- pps_merge.cpp ----

@@ -81,6 +81,26 @@ static int enqueue_factor_solve(pps_graph* g, const DevGraph& dv, const DualAlt*
 
 int do_solve_on(pps_graph* g, const DevGraph& dv, double lambda, hipStream_t st_) { return enqueue_factor_solve(g, dv, nullptr, lambda, st_, false); }
 
+// The factorisation alone, every launch a plain one on g->stream: one launch per band stage, or -- dense fronts -- L zeroed, the H blocks
+// pushed, one launch per level.  The profiled forms of do_solve and the covariance recovery (pps_cov.cpp: lambda = 0) factor with it.
+int enqueue_plain_factor(pps_graph* g, double lambda) {
+  const Analysis& A = g->an;
+  const DevGraph& d = g->dev;
+  if (g->use_band) {
+    for (int st = 0; st < A.n_stages; st++)
+      HIP_TRY(g, launch_band_factor(d, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_factor[st], A.stage_max_front[st], lambda, g->stream));
+    return PPS_OK;
+  }
+  HIP_TRY(g, hipMemsetAsync(d.L, 0, (size_t)A.L_size * 8, g->stream));
+  HIP_TRY(g, launch_dense_hpush(d, g->max_el_per_front, lambda, g->stream));
+  for (int l = 0; l < A.n_levels; l++) {
+    const int base = A.level_off[l] + l, cnt = A.level_off[l + 1] - A.level_off[l];
+    HIP_TRY(g, launch_dense_factor_level(d, A.level_off[l], cnt, g->d_dw_asm + base, g->dw_asm[base + cnt], g->d_dw_pan + base, g->dw_pan[base + cnt],
+                                         g->d_dw_trl + base, g->dw_trl[base + cnt], g->stream));
+  }
+  return PPS_OK;
+}
+
 int do_solve(pps_graph* g, double lambda) {
   const Analysis& A = g->an;
   if (g->use_band) {
@@ -92,9 +112,7 @@ int do_solve(pps_graph* g, double lambda) {
     }
     {
       PhaseTimer t(g, &g->stats.t_factor);
-      for (int st = 0; st < A.n_stages; st++)
-        HIP_TRY(g, launch_band_factor(g->dev, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_factor[st],
-                                      A.stage_max_front[st], lambda, g->stream));
+      const int rc = enqueue_plain_factor(g, lambda); if (rc != PPS_OK) return rc;
     }
     {
       PhaseTimer t(g, &g->stats.t_backsolve);
@@ -108,13 +126,7 @@ int do_solve(pps_graph* g, double lambda) {
   if (g->use_dense) {
     {
       PhaseTimer t(g, &g->stats.t_factor);
-      HIP_TRY(g, hipMemsetAsync(g->dev.L, 0, (size_t)A.L_size * 8, g->stream));
-      HIP_TRY(g, launch_dense_hpush(g->dev, g->max_el_per_front, lambda, g->stream));
-      for (int l = 0; l < A.n_levels; l++) {
-        const int base = A.level_off[l] + l, cnt = A.level_off[l + 1] - A.level_off[l];
-        HIP_TRY(g, launch_dense_factor_level(g->dev, A.level_off[l], cnt, g->d_dw_asm + base, g->dw_asm[base + cnt], g->d_dw_pan + base,
-                                             g->dw_pan[base + cnt], g->d_dw_trl + base, g->dw_trl[base + cnt], g->stream));
-      }
+      const int rc = enqueue_plain_factor(g, lambda); if (rc != PPS_OK) return rc;
     }
     {
       PhaseTimer t(g, &g->stats.t_backsolve);
@@ -230,6 +242,15 @@ void begin_solve(pps_graph* g) {
 // the device copy of a handle is given up after a failed solve: streams drained, nothing on the device is trusted any more --
 // the next upload sends the whole arena (up_unknown: the mirror says nothing about the device, measurements included) and the
 // estimate falls back to the host's node values
+int clear_stale_status(pps_graph* g) {
+  if (!g->status_clean) {
+    HIP_TRY(g, launch_clear_status(g->dev, g->stream));
+    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
+  }
+  g->status_clean = false;
+  return PPS_OK;
+}
+
 void abandon_device_copy(pps_graph* g) {
   if (!g->dev_ready) return;
   (void)hipStreamSynchronize(g->stream);
@@ -552,11 +573,7 @@ static int debug_solve_impl(pps_graph* g, double lambda, double lambda2, double*
     return fail(g, PPS_ESTATE, "debug_solve: two damping values in one launch need the band kernels and their second L / U / delta set (this graph runs in another K3 form)");
   if (form) *form = g->use_band ? (g->k3_all ? 1 : 0) : (g->use_dense ? 2 : 3);
   const DevGraph& d = g->dev;
-  if (!g->status_clean) {
-    HIP_TRY(g, launch_clear_status(d, g->stream));
-    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
-  }
-  g->status_clean = false;
+  rc = clear_stale_status(g); if (rc != PPS_OK) return rc;
   rc = linpoint_from_estimate(g); if (rc != PPS_OK) return rc;
   rc = do_linearize(g); if (rc != PPS_OK) return rc;
   if (dual) {
@@ -592,17 +609,8 @@ int pps_debug_solve(pps_graph* g, double lambda, double lambda2, double* delta, 
   if (g->n_live_nodes == 0) return fail(g, PPS_ESTATE, "empty graph");
   if (g->n_live_factors == 0) return fail(g, PPS_ESTATE, "debug_solve: the graph has no factor");
   cov_invalidate(g);                   // (dev.L is about to be overwritten)
-  // the figures of the last solve stay what they were: this call is no solve (as in pps_cov_recover)
-  const pps_stats saved = g->stats;
-  const int profiling = g->profiling;
-  g->profiling = 0;
-  const unsigned long long launches0 = g->launches0;
-  const int rc = debug_solve_impl(g, lambda, lambda2, delta, delta2, form, not_pd);
-  g->profiling = profiling;
-  g->launches0 = launches0;
-  { pps_stats s = saved;
-    s.n_fronts = g->stats.n_fronts; s.n_levels = g->stats.n_levels; s.max_front = g->stats.max_front; s.nnz_L = g->stats.nnz_L;
-    g->stats = s; }
+  int rc;
+  { NoSolveScope scope(g); rc = debug_solve_impl(g, lambda, lambda2, delta, delta2, form, not_pd); }      // (no solve: the figures of the last one stay)
   if (rc != PPS_OK && rc != PPS_EINVAL && rc != PPS_ESTATE) abandon_device_copy(g);
   return rc;
 }

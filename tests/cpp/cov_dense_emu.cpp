@@ -62,7 +62,7 @@ template <class K, class... A> void emu_launch(K k, dim3 grid, dim3 block, A... 
 namespace pps { unsigned long long launch_count() { return 0; } void count_launch() {} }
 using namespace pps;
 
-// the launches of pps_cov_select's pass (pps_cov.cpp: cov_select_dense_impl) after the pivot criterion; result4: the status record of the device
+// the launches of pps_cov_select's pass (pps_cov.cpp: cov_run, the dense-front pass) after the pivot criterion; result4: the status record of the device
 extern "C" int emu_cov_dense(int n_fronts, int n_levels, int* f_p, int* f_b, int64_t* f_Loff, int64_t* f_Uoff, int* f_cmap_off, int* cmap, int* parent, int* level_off,
                              int* level_fronts, double* L, double* U, long long n_U, double* S, double* G, long long n_panel, double* result4) {
   DevGraph d; d.n_fronts = n_fronts; d.n_levels = n_levels; d.f_p = f_p; d.f_b = f_b; d.f_Loff = f_Loff; d.f_Uoff = f_Uoff; d.f_cmap_off = f_cmap_off; d.cmap = cmap;
