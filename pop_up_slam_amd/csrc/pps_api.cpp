@@ -20,6 +20,8 @@ Switches read_switches() {
   }
   s.no_spec_lin = on("PPS_NO_SPEC_LIN");
   s.no_dual = on("PPS_NO_DUAL");
+  s.lm_plain_host = on("PPS_LM_PLAIN_HOST");
+  s.no_early_record = on("PPS_NO_EARLY_RECORD");
   s.no_strip = on("PPS_NO_STRIP");
   s.no_incremental = on("PPS_NO_INCREMENTAL");
   s.no_incr_compact = on("PPS_NO_INCR_COMPACT");
@@ -34,6 +36,7 @@ Switches read_switches() {
     long long tm = num("PPS_TIMING", 0);
     if (on("PPS_TIMING") && tm <= 0) tm = 7;
     s.analysis_timing = (tm & 1) != 0; s.upload_timing = (tm & 2) != 0; s.multi_timing = (tm & 8) ? 2 : ((tm & 4) ? 1 : 0);
+    s.lm_timing = (tm & 16) != 0;
   }
   s.multi_split = (int)num("PPS_MULTI_SPLIT", 0);
   s.multi_thread_factors = num("PPS_MULTI_THREAD_FACTORS", 120000);

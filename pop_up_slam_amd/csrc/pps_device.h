@@ -108,8 +108,8 @@ struct DevGraph {
 // pps_multi_create / pps_popup_create ... call read_switches() -- and never on a launch path: a handle keeps the schedule it was
 // created with whatever the environment does later (A/B tools and the parity tests set the variable before they create the handle).
 constexpr double kStatusInternal = 64.0;   // result_dev[2] at or above this: an internal time-out inside a kernel (PPS_EHIP), not a not-PD pivot
-enum : unsigned { SW_K1_THREAD_FORM = 1u, SW_NO_SOLVE_FLOW = 2u, SW_NO_ROOT_FUSE = 4u, SW_DEBUG_DROP_FLAG = 8u, SW_DEBUG_DROP_XFLAG = 16u };
-// Fifteen variables (INTEGRATION.md lists them): each one selects a path that some graph shape takes anyway (so the parity tests can put every
+enum : unsigned { SW_K1_THREAD_FORM = 1u, SW_NO_SOLVE_FLOW = 2u, SW_NO_ROOT_FUSE = 4u, SW_DEBUG_DROP_FLAG = 8u, SW_DEBUG_DROP_XFLAG = 16u, SW_NO_EARLY_RECORD = 32u };
+// Seventeen variables (INTEGRATION.md lists them): each one selects a path that some graph shape takes anyway (so the parity tests can put every
 // graph through it) or a diagnostic.  A/B switches of experiments whose losing side was deleted do not exist.
 struct Switches {
   bool k1_thread_form = false;      // PPS_K1_THREAD_FORM: thread-per-factor K1 (no product records) on graphs of any size
@@ -120,6 +120,10 @@ struct Switches {
   bool split_expand = false;        //   8  list expansion as two launches + a fill
   bool no_spec_lin = false;         // PPS_NO_SPEC_LIN: nothing of the next linearisation is computed before the trials' verdict is known
   bool no_dual = false;             // PPS_NO_DUAL: the one-step-at-a-time LM loop
+  bool no_early_record = false;     // PPS_NO_EARLY_RECORD: the trial blocks of k_trial_lin publish their partial sums and the result record behind release
+                                    // fences, which write the sweep's output back from the L2 first (the record then leaves when the sweep has ended)
+  bool lm_plain_host = false;       // PPS_LM_PLAIN_HOST: the dual LM loop does all of a trial's host work (trace, counters, launch geometry) between the
+                                    // record's arrival and the factor launch, as it did before that stretch was cleared
   bool no_strip = false;            // PPS_NO_STRIP: fronts of 65 .. 80 rows through the LDS-tile path
   bool no_incremental = false;      // PPS_NO_INCREMENTAL: every analysis from scratch
   bool no_incr_compact = false;     // PPS_NO_INCR_COMPACT: compacted tables rebuilt per analysis
@@ -128,8 +132,9 @@ struct Switches {
   int debug_drop_flag = 0;          // PPS_DEBUG_DROP_FLAG (tests of the time-out path): 1 = the data-flow back-substitution withholds the hand-over flag of every
                                     // group's top front (LDS), 2 = the whole-tree factor launch withholds the flag a group's top front raises for its parent's workgroup
   int trace = 0;                    // PPS_TRACE: 1 = phase timestamps of the factorisation, 2 = of the back-substitution
-  // PPS_TIMING=<bits>: host-side timing printed to stderr -- 1 analysis phases, 2 upload phases, 4 pps_multi totals, 8 pps_multi rounds
-  bool analysis_timing = false, upload_timing = false;
+  // PPS_TIMING=<bits>: host-side timing printed to stderr -- 1 analysis phases, 2 upload phases, 4 pps_multi totals, 8 pps_multi rounds,
+  // 16 the dual LM loop's host time from a trial record's arrival to the factor launch it triggers
+  bool analysis_timing = false, upload_timing = false, lm_timing = false;
   int multi_timing = 0;             //   (0 off, 1 totals, 2 rounds)
   int multi_split = 0;              // PPS_MULTI_SPLIT: chunks a batch is cut into (0 = by size)
   long long multi_thread_factors = 120000;   // PPS_MULTI_THREAD_FACTORS: factors per chunk above which a batch takes the throughput forms (round 6: 120 000,
@@ -137,7 +142,8 @@ struct Switches {
                                              // 1 229 against 1 401, G = 32 1 384 against 1 581; it was 200 000)
   unsigned dev_bits() const {
     return (k1_thread_form ? SW_K1_THREAD_FORM : 0u) | (no_solve_flow ? SW_NO_SOLVE_FLOW : 0u) | (no_root_fuse ? SW_NO_ROOT_FUSE : 0u) |
-           (debug_drop_flag == 1 ? SW_DEBUG_DROP_FLAG : 0u) | (debug_drop_flag == 2 ? SW_DEBUG_DROP_XFLAG : 0u);
+           (debug_drop_flag == 1 ? SW_DEBUG_DROP_FLAG : 0u) | (debug_drop_flag == 2 ? SW_DEBUG_DROP_XFLAG : 0u) |
+           (no_early_record ? SW_NO_EARLY_RECORD : 0u);
   }
 };
 Switches read_switches();           // pps_api.cpp: the only place of the library that calls getenv
@@ -203,6 +209,12 @@ struct DualAlt {
 // DevGraph::k3_flag); epoch: the number of this launch pair (> 0, growing)
 hipError_t launch_band_all(const DevGraph& d, const DualAlt* alt, int n_groups, int nwaves_factor, int nwaves_solve, int max_front, int max_panel,
                            int max_group_fronts, double lambda, int epoch, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// ... and in pieces: the launch geometry, fixed per analysis (band_all_plan makes the attribute check as well), and one function per launch
+struct BandAllPlan { int n_groups, nw_factor, nw_solve, pwf, pws, max_group_fronts; size_t lds_factor, lds_solve; };
+hipError_t band_all_plan(int n_groups, int nwaves_factor, int nwaves_solve, int max_front, int max_panel, int max_group_fronts, BandAllPlan* p);
+hipError_t launch_band_all_factor(const DevGraph& d, const DualAlt* alt, const BandAllPlan& p, double lambda, int epoch, hipStream_t st,
+                                  hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t launch_band_all_solve(const DevGraph& d, const DualAlt* alt, const BandAllPlan& p, int epoch, hipStream_t st);
 int band_all_solve_waves(int max_panel, int max_group_fronts);
 // pre: every group of the stage has the shape the pre-assembling walk needs (k_band_factor_pre)
 hipError_t launch_band_factor(const DevGraph& d, int grp_begin, int grp_count, int nwaves, int max_front, double lambda, hipStream_t st,

@@ -1271,12 +1271,31 @@ hipError_t launch_band_root(const DevGraph& d, const DualAlt* alt, int grp, int 
 // nwaves_factor / max_front / max_panel / max_group_fronts: maxima over the stages; epoch: number of this launch pair (> 0, never repeated)
 hipError_t launch_band_all(const DevGraph& d, const DualAlt* alt, int n_groups, int nwaves_factor, int nwaves_solve, int max_front, int max_panel,
                            int max_group_fronts, double lambda, int epoch, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+  BandAllPlan p;
+  { const hipError_t e = band_all_plan(n_groups, nwaves_factor, nwaves_solve, max_front, max_panel, max_group_fronts, &p); if (e != hipSuccess) return e; }
+  { const hipError_t e = launch_band_all_factor(d, alt, p, lambda, epoch, st, ev0, ev1); if (e != hipSuccess) return e; }
+  return launch_band_all_solve(d, alt, p, epoch, st);
+}
+// The same in pieces, for a caller that launches the pair many times over one analysis and has the first launch waiting for a verdict (the dual
+// LM loop): the geometry and the attribute check once, then nothing but the two launches.
+hipError_t band_all_plan(int n_groups, int nwaves_factor, int nwaves_solve, int max_front, int max_panel, int max_group_fronts, BandAllPlan* p) {
   { const hipError_t e = ensure_band_attrs(); if (e != hipSuccess) return e; }
-  const int pwf = (int)(band_lds_bytes(max_front, true) / sizeof(double)), pws = (int)(band_solve_lds_bytes(max_panel) / sizeof(double));
-  const DualAlt a2 = alt ? *alt : DualAlt{};
-  PPS_LAUNCH_EV(ev0, ev1, k_band_factor_all, dim3(n_groups, alt ? 2 : 1), dim3(64 * nwaves_factor), (size_t)pwf * nwaves_factor * sizeof(double), st, d, a2, lambda, pwf, epoch);
+  p->n_groups = n_groups; p->nw_factor = nwaves_factor; p->nw_solve = nwaves_solve; p->max_group_fronts = max_group_fronts;
+  p->pwf = (int)(band_lds_bytes(max_front, true) / sizeof(double)); p->pws = (int)(band_solve_lds_bytes(max_panel) / sizeof(double));
+  p->lds_factor = (size_t)p->pwf * nwaves_factor * sizeof(double);
   const size_t fixed = ((size_t)max_group_fronts * kBandMaxRows + (size_t)(max_group_fronts + 1) / 2) * sizeof(double);
-  PPS_LAUNCH(k_band_solve_all, dim3(n_groups, alt ? 2 : 1), dim3(64 * nwaves_solve), (size_t)pws * nwaves_solve * sizeof(double) + fixed, st, d, a2, n_groups, pws, max_group_fronts, epoch);
+  p->lds_solve = (size_t)p->pws * nwaves_solve * sizeof(double) + fixed;
+  return hipSuccess;
+}
+hipError_t launch_band_all_factor(const DevGraph& d, const DualAlt* alt, const BandAllPlan& p, double lambda, int epoch, hipStream_t st, hipEvent_t ev0,
+                                  hipEvent_t ev1) {
+  const DualAlt a2 = alt ? *alt : DualAlt{};
+  PPS_LAUNCH_EV(ev0, ev1, k_band_factor_all, dim3(p.n_groups, alt ? 2 : 1), dim3(64 * p.nw_factor), p.lds_factor, st, d, a2, lambda, p.pwf, epoch);
+  return hipGetLastError();
+}
+hipError_t launch_band_all_solve(const DevGraph& d, const DualAlt* alt, const BandAllPlan& p, int epoch, hipStream_t st) {
+  const DualAlt a2 = alt ? *alt : DualAlt{};
+  PPS_LAUNCH(k_band_solve_all, dim3(p.n_groups, alt ? 2 : 1), dim3(64 * p.nw_solve), p.lds_solve, st, d, a2, p.n_groups, p.pws, p.max_group_fronts, epoch);
   return hipGetLastError();
 }
 // waves of the data-flow back-substitution of such a launch (0: the LDS does not hold a group): as launch_band_solve picks them per stage

@@ -84,9 +84,9 @@ __global__ __launch_bounds__(kChiBlock) void k_chi2(DevGraph d, const double* __
   body_chi2(d, pose, plane, nb_obs, nb_odo, nb_pp, n_dn, out, seq, blockIdx.x, gridDim.x);
 }
 
-// out <- base (+) delta for one block of nodes; the block's |delta|^2 partial goes to d.dn_partials[bx]
+// out <- base (+) delta for one block of nodes; the block's |delta|^2 partial goes to d.dn_partials[bx] (light: by publish_partial, pps_k4_body.h)
 __device__ __forceinline__ void body_retract_to(const DevGraph& d, const double* __restrict__ base_pose, const double* __restrict__ base_plane,
-                                                double* __restrict__ out_pose, double* __restrict__ out_plane, int bx, double* red) {
+                                                double* __restrict__ out_pose, double* __restrict__ out_plane, int bx, double* red, bool light = false) {
   const int i = bx * blockDim.x + threadIdx.x;
   double dn = 0.0;
   if (i < d.n_pose) {
@@ -113,7 +113,10 @@ __device__ __forceinline__ void body_retract_to(const DevGraph& d, const double*
   for (int o2 = 32; o2 > 0; o2 >>= 1) dn += __shfl_down(dn, o2, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dn;
   __syncthreads();
-  if (threadIdx.x == 0) d.dn_partials[bx] = red[0] + red[1] + red[2] + red[3];
+  if (threadIdx.x == 0) {
+    const double t = red[0] + red[1] + red[2] + red[3];
+    if (light) publish_partial(&d.dn_partials[bx], t); else d.dn_partials[bx] = t;
+  }
 }
 
 // Both trials of a dual solve in ONE launch (grid y = trial): blocks [0, nb_ret) write out_k <- base (+) delta_k and their
@@ -169,6 +172,13 @@ hipError_t launch_trial_dual(const DevGraph& d, const DualAlt& alt, const double
 // records and direct H blocks into the spare set (SpecLin).  Nothing in the launch waits for anything else in it: the sweep that used to
 // start after the trial kernel had ended -- and after its verdict had been tested by a guard -- runs beside it.  Whether that linearisation
 // is the one LM wants the host decides from the records as before (Optimizer.cpp:425-458).
+// The sweep's blocks take no ticket, and the trial blocks have the lowest indices: a trial's record is due when ITS blocks are done.  That alone
+// did not let it leave early: every release fence on the way -- one per trial block in front of the ticket, one in front of the sequence number --
+// first writes back what the sweep's blocks have left in the XCD's L2 by then, and the record reached the host when the sweep had ended (last
+// ticket 7.8 - 11.0 us after the launch's first block started, record 10.7 - 12.8, sweep's end 12.6 - 13.8).  The trial blocks of this launch therefore publish without fences
+// (`light`: publish_partial / chi2_finish, pps_k4_body.h) and run at raised wave priority.  The record no longer implies that the sweep has ended:
+// every reader of the spare set, and every writer of the state copies, is queued behind this launch on its stream or synchronises the stream.
+// PPS_NO_EARLY_RECORD (SW_NO_EARLY_RECORD): fences as in k_trial_dual.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kChiBlock) void k_trial_lin(DevGraph d, DualAlt alt, SpecLin sl, const double* __restrict__ base_pose, const double* __restrict__ base_plane,
                                                          double* __restrict__ out_pose, double* __restrict__ out_plane, double* __restrict__ out_pose1,
@@ -189,15 +199,17 @@ __global__ __launch_bounds__(kChiBlock) void k_trial_lin(DevGraph d, DualAlt alt
     body_linearize_lanes(d, base_pose, base_plane, lb_obs, lb_odo, lb_pp, bx0, apply != 0);      // (1: see k_linearize_lanes)
     return;
   }
+  const bool light = (d.sw & SW_NO_EARLY_RECORD) == 0;
+  if (light) __builtin_amdgcn_s_setprio(3);               // the host waits for these few waves, nobody for a single wave of the sweep
   if (bx0 >= nb_ret) {
-    body_chi2<true, true>(d, base_pose, base_plane, nb_obs, nb_odo, nb_pp, nb_ret, out, seq, bx0 - nb_ret, nb_chi, total);
+    body_chi2<true, true>(d, base_pose, base_plane, nb_obs, nb_odo, nb_pp, nb_ret, out, seq, bx0 - nb_ret, nb_chi, total, CostFn{}, light);
     return;
   }
   __shared__ double red[4];
-  body_retract_to(d, base_pose, base_plane, out_pose, out_plane, bx0, red);
+  body_retract_to(d, base_pose, base_plane, out_pose, out_plane, bx0, red, light);
   __shared__ bool last;
   if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (!light) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     last = atomicAdd(d.ticket, 1u) == (unsigned int)(total - 1);
   }
@@ -205,7 +217,7 @@ __global__ __launch_bounds__(kChiBlock) void k_trial_lin(DevGraph d, DualAlt alt
   if (!last) return;
   if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   __syncthreads();
-  chi2_finish(d, nb_chi, nb_ret, out, seq);
+  chi2_finish(d, nb_chi, nb_ret, out, seq, light);
   if (threadIdx.x == 0) *d.ticket = 0u;
 }
 

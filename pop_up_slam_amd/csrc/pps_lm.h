@@ -45,26 +45,37 @@ struct LmControl {
     n_notpd += last_notpd ? 1 : 0;
   }
 
-  // one pass of the loop body (:400-456) for the trial whose chi2 is error_new.  Forced inline: with its three push_backs the compiler
-  // otherwise emits it out of line, a call per trial between a record's arrival and the next launch that the loops did not have before
-  __attribute__((always_inline)) LmVerdict judge(const LmSink& s, double error_new) {
-    const pps_props& p = *s.prop;
+  // One pass of the loop body (:400-456) for the trial whose chi2 is error_new, in two halves.  decide() is the rule -- verdict, lambda
+  // schedule, the new error -- and touches nothing but this object; note() is what the trial leaves behind (trace, counters, the verbose
+  // line) and needs nothing the rule changes: a loop that has a launch waiting for the verdict calls decide(), launches, then note().
+  struct Trial { double lambda, chi2; int iter; bool accepted; };      // a judged trial as note() records it
+  __attribute__((always_inline)) LmVerdict decide(const pps_props& p, double error_new, Trial* t) {
     num_iter++;
     const double error_diff = error - error_new;
     const bool accepted = error_diff > 0.;
-    s.tr_lambda->push_back(lambda); s.tr_chi2->push_back(error_new); s.tr_acc->push_back(accepted ? 1 : 0);
-    if (s.verbose) fprintf(stderr, "LM Iteration %d: (lambda=%g) %s %.12g\n", num_iter, lambda, accepted ? "residual:" : "rejected", error_new);
+    *t = Trial{lambda, error_new, num_iter, accepted};
     if (!accepted) {
-      s.stats->lm_trials_rejected++;
       lambda *= p.lm_lambda_factor;                              // (:452)
       return LmVerdict::Rejected;
     }
-    s.stats->lm_trials_accepted++;
     const bool converged = error_diff < p.epsilon_rel * error;   // (:431-434) against the chi2 the step started from
     error = error_new;
     if (converged) return LmVerdict::Converged;
     lambda /= p.lm_lambda_factor;                                // (:438)
     return LmVerdict::Accepted;
+  }
+  static void note(const LmSink& s, const Trial& t) {
+    s.tr_lambda->push_back(t.lambda); s.tr_chi2->push_back(t.chi2); s.tr_acc->push_back(t.accepted ? 1 : 0);
+    if (s.verbose) fprintf(stderr, "LM Iteration %d: (lambda=%g) %s %.12g\n", t.iter, t.lambda, t.accepted ? "residual:" : "rejected", t.chi2);
+    if (t.accepted) s.stats->lm_trials_accepted++; else s.stats->lm_trials_rejected++;
+  }
+  // both halves at once (the one-step loop, the batched rounds, tests/cpp/lm_host.cpp).  Forced inline: with its three push_backs the compiler
+  // otherwise emits it out of line, a call per trial between a record's arrival and the next launch that the loops did not have before
+  __attribute__((always_inline)) LmVerdict judge(const LmSink& s, double error_new) {
+    Trial t;
+    const LmVerdict v = decide(*s.prop, error_new, &t);
+    note(s, t);
+    return v;
   }
 
   // the solve is over: its figures -> stats; PPS_ENOTPD (the caller sets kLmNotPdMessage on its handle) when the last trial was not PD

@@ -45,14 +45,20 @@ int do_linearize(pps_graph* g, const LinGuard* guard = nullptr) {
 // Factor stages leaves -> root, back-substitution stages root -> leaves, for one damping value (alt == nullptr) or two.  The root stage
 // is one launch for both directions where its fronts allow it (band_root_fusable).  events: the factor launches carry their own start /
 // stop events (profiling level 1; the fused root launch's pair spans its back-substitution as well).
+// the start / stop events of a factor launch (profiling level 1: resolve_k1_events sums the pairs into t_factor)
+static int take_factor_events(pps_graph* g, bool events, hipEvent_t* e0, hipEvent_t* e1) {
+  *e0 = *e1 = nullptr;
+  if (!events) return PPS_OK;
+  if (g->fk_used + 2 > (int)g->fk_events.size()) for (int k = 0; k < 2; k++) { hipEvent_t e; HIP_TRY(g, hipEventCreate(&e)); g->fk_events.push_back(e); }
+  *e0 = g->fk_events[g->fk_used]; *e1 = g->fk_events[g->fk_used + 1]; g->fk_used += 2;
+  return PPS_OK;
+}
+
 static int enqueue_factor_solve(pps_graph* g, const DevGraph& dv, const DualAlt* alt, double lambda, hipStream_t st_, bool events) {
   const Analysis& A = g->an;
   if (g->k3_all) {                                                 // the whole tree: two launches (pps_k3.hip, XGroup)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (events) {
-      if (g->fk_used + 2 > (int)g->fk_events.size()) for (int k = 0; k < 2; k++) { hipEvent_t e; HIP_TRY(g, hipEventCreate(&e)); g->fk_events.push_back(e); }
-      e0 = g->fk_events[g->fk_used]; e1 = g->fk_events[g->fk_used + 1]; g->fk_used += 2;
-    }
+    hipEvent_t e0, e1;
+    { const int rc = take_factor_events(g, events, &e0, &e1); if (rc != PPS_OK) return rc; }
     g->k3_epoch = g->k3_epoch >= (1 << 30) ? 1 : g->k3_epoch + 1;
     HIP_TRY(g, launch_band_all(dv, alt, A.n_groups, g->k3_nw_factor, g->k3_nw_solve, g->k3_max_front, g->k3_max_panel, g->k3_max_grp, lambda, g->k3_epoch, st_, e0, e1));
     return PPS_OK;
@@ -60,11 +66,8 @@ static int enqueue_factor_solve(pps_graph* g, const DevGraph& dv, const DualAlt*
   const int top = A.n_stages - 1;
   const bool fuse = top >= 0 && band_root_fusable(dv, A.stage_grp_off[top + 1] - A.stage_grp_off[top], A.stage_max_front[top]);
   for (int st = 0; st < A.n_stages; st++) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (events) {                                                  // the launch's own start / stop: resolve_k1_events sums them into t_factor
-      if (g->fk_used + 2 > (int)g->fk_events.size()) for (int k = 0; k < 2; k++) { hipEvent_t e; HIP_TRY(g, hipEventCreate(&e)); g->fk_events.push_back(e); }
-      e0 = g->fk_events[g->fk_used]; e1 = g->fk_events[g->fk_used + 1]; g->fk_used += 2;
-    }
+    hipEvent_t e0, e1;
+    { const int rc = take_factor_events(g, events, &e0, &e1); if (rc != PPS_OK) return rc; }
     const int g0 = A.stage_grp_off[st], ng = A.stage_grp_off[st + 1] - g0;
     const bool pre = st < (int)g->stage_pre.size() && g->stage_pre[st] != 0;
     if (fuse && st == top)
@@ -413,6 +416,29 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
     HIP_TRY(g, launch_hblocks_spec(d, sl, g->stream, &gd));
     return PPS_OK;
   };
+  // The stretch between a trial record's arrival and the factor launch it triggers is on the solve's critical path -- the device has nothing
+  // queued behind K2 until that launch arrives -- so the host does there only what depends on the verdict: the rule (LmControl::decide), the
+  // pointer rotation, the launch.  The launch geometry of a whole-tree pair is worked out once per solve (BandAllPlan), and what the trial leaves
+  // in the trace and the counters (LmControl::note) is written behind the launch.  PPS_LM_PLAIN_HOST: everything in its old place.
+  const bool plain_host = g->sw.lm_plain_host;
+  BandAllPlan plan{};
+  const bool planned = !plain_host && g->k3_all;
+  if (planned) HIP_TRY(g, band_all_plan(A.n_groups, g->k3_nw_factor, g->k3_nw_solve, g->k3_max_front, g->k3_max_panel, g->k3_max_grp, &plan));
+  struct PendingNote {                   // the judged trial whose bookkeeping is still owed (written at the latest when the loop is left, however)
+    const LmSink& s; LmControl::Trial t{}; bool owed = false;
+    void flush() { if (owed) { LmControl::note(s, t); owed = false; } }
+    ~PendingNote() { flush(); }
+  } pending{sink};
+  // PPS_TIMING & 16: host seconds from the record's arrival to the factor launch call | inside that call (it returns when the doorbell has rung)
+  const bool lm_timing = g->sw.lm_timing;
+  // (launch sets whose prediction failed relinearise in between -- two launches more --: counted apart)
+  double t_rec = 0.0, rt_pre = 0.0, rt_call = 0.0, rt_relin = 0.0; int rt_n = 0, rt_n_relin = 0; bool relin = false;
+  auto rt_note = [&](double t_pre) {
+    if (!lm_timing || t_rec <= 0.0) return;
+    const double t = now_s();
+    if (relin) { rt_relin += t - t_rec; rt_n_relin++; } else { rt_pre += t_pre - t_rec; rt_call += t - t_pre; rt_n++; }
+    t_rec = 0.0; relin = false;
+  };
   auto enqueue_dual = [&](double lam) -> int {
     DualAlt alt{g->spec_L, g->spec_U, g->spec_delta, g->spec_result, g->spec_chi2_partials, g->spec_dn_partials, g->spec_ticket,
                 lam * prop.lm_lambda_factor};
@@ -421,7 +447,20 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
     // second one with a stale delta that nothing read -- twice the retraction and chi2 work of a launch that C3 pays 22 us for; have_next is
     // false, the second record is never waited for)
     const int n_trials = use_alt ? 2 : 1;
-    { const int rc2 = enqueue_factor_solve(g, d, use_alt ? &alt : nullptr, lam, g->stream, g->profiling == 1); if (rc2 != PPS_OK) return rc2; }
+    const double t_pre = lm_timing ? now_s() : 0.0;
+    if (planned) {
+      hipEvent_t e0, e1;
+      { const int rc2 = take_factor_events(g, g->profiling == 1, &e0, &e1); if (rc2 != PPS_OK) return rc2; }
+      g->k3_epoch = g->k3_epoch >= (1 << 30) ? 1 : g->k3_epoch + 1;
+      HIP_TRY(g, launch_band_all_factor(d, use_alt ? &alt : nullptr, plan, lam, g->k3_epoch, g->stream, e0, e1));
+      rt_note(t_pre);
+      pending.flush();
+      HIP_TRY(g, launch_band_all_solve(d, use_alt ? &alt : nullptr, plan, g->k3_epoch, g->stream));
+    } else {
+      const int rc2 = enqueue_factor_solve(g, d, use_alt ? &alt : nullptr, lam, g->stream, g->profiling == 1); if (rc2 != PPS_OK) return rc2;
+      rt_note(t_pre);                    // (this form's call covers all the launches of the factorisation and the walk back)
+      pending.flush();
+    }
     g->stats.n_factorize += n_trials;
     g->seq += 1.0; seqs[0] = g->seq;
     g->seq2 += 1.0; seqs[1] = g->seq2;
@@ -458,7 +497,10 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
   lm.take_step(slot[0]);
   bool trial_taken = false;              // the loop ended on an accepted, converged step: the estimate is that trial
   while (lm.running(prop)) {
-    const LmVerdict v = lm.judge(sink, slot[cur][0]);
+    if (lm_timing) t_rec = now_s();
+    LmVerdict v;
+    if (plain_host) v = lm.judge(sink, slot[cur][0]);
+    else { v = lm.decide(prop, slot[cur][0], &pending.t); pending.owed = true; }      // (its note: behind the launch, in enqueue_dual)
     if (v == LmVerdict::Converged) { trial_taken = true; break; }
     if (v == LmVerdict::Accepted) {
       if (adaptive) use_alt = cur != 0;                           // (accepted at once: no speculation next time; after a rejection: keep it)
@@ -470,7 +512,7 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
         g->stats.n_linearize++;
         if (fused_pair >= 0 && (size_t)fused_pair < g->k1_skip.size()) g->k1_skip[fused_pair] = 0;
       }
-      else if (fuse_lin) { rc = do_linearize(g); if (rc != PPS_OK) return rc; }      // (the other trial was accepted: the plain way)
+      else if (fuse_lin) { relin = true; rc = do_linearize(g); if (rc != PPS_OK) return rc; }      // (the other trial was accepted: the plain way)
       else if (spec_lin) { g->stats.n_linearize++; spec_pair = -1; }    // ... queued already, at this very copy
       else { rc = do_linearize(g); if (rc != PPS_OK) return rc; }
       rc = enqueue_dual(lm.lambda); if (rc != PPS_OK) return rc;   // (:458)
@@ -479,7 +521,8 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
       rc = wait_result(g, slot[0], seqs[0]); if (rc != PPS_OK) return rc;
     } else {                                                       // estimate_to_linpoint (:454): x was never overwritten
       if (have_next) {                                             // computed alongside: nothing to launch
-        cur = 1; have_next = false;
+        cur = 1; have_next = false; t_rec = 0.0;
+        pending.flush();
         rc = wait_result(g, slot[1], seqs[1]); if (rc != PPS_OK) return rc;
       } else {
         drop_spec_lin();                                           // both trials rejected: its kernels left J and H alone
@@ -494,6 +537,10 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
   }
   // linpoint_to_estimate (:466): the estimate is the accepted trial, or the linearisation point when the pending step is dropped
   drop_spec_lin();                       // (a linearisation queued behind the last trials is not one the solve asked for)
+  pending.flush();
+  if (lm_timing && rt_n > 0)
+    fprintf(stderr, "[lm] record -> factor launch: %d launch sets, mean %.2f us before the launch call + %.2f us inside it; %d sets that relinearised first, mean %.2f us\n",
+            rt_n, 1e6 * rt_pre / rt_n, 1e6 * rt_call / rt_n, rt_n_relin, rt_n_relin ? 1e6 * rt_relin / rt_n_relin : 0.0);
   if (trial_taken) { std::swap(d.pose_lin, t_pose[cur]); std::swap(d.plane_lin, t_plane[cur]); }
   d.pose_est = d.pose_lin; d.plane_est = d.plane_lin;
   d.pose_lin = t_pose[0]; d.plane_lin = t_plane[0];
