@@ -303,6 +303,55 @@ int pps_merge_gate_last(const pps_graph* g, double* kernel_sec, int* launches, i
  * before the first successful call of the handle, and after a call of more than 262144 pairs (the records of such a call are not kept). */
 int pps_debug_merge_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed);
 
+/* ---- leave-one-out chi-square test of every factor, from the recovered covariances ----------------------------
+ * pps_assoc_gate and pps_merge_gate judge candidates; this call asks what a front end asks after a solve: "which factor already in the
+ * graph is wrong?" (plane association is greedy and geometric, and one wrong pps_add_plane_obs bends the corridor).  For factor f, at
+ * the current ESTIMATE and in the handle's jacobian_mode, with r (m = 3 or 6) and J (m x c, c = 3, 6, 9 or 12 over its one or two nodes)
+ * the whitened residual and Jacobian in the column order of pps_eval_factor, and Sigma_ff (c x c) the joint marginal of its nodes from
+ * the current selected inverse (every pair joined by a factor lies in its pattern):
+ *     P   = J Sigma_ff J'       the factor's block of the hat matrix, eigenvalues in [0, 1]
+ *     lev = trace(P)            how much of its own m rows the factor determines (m - lev: its redundancy); the sum over all factors
+ *                               is the state dimension
+ *     d2  = r' (I - P)^-1 r     (m x m Cholesky solve)
+ * At a converged estimate d2 is the squared Mahalanobis distance of the factor's residual at the solution of the graph WITHOUT this factor,
+ * against that graph's innovation covariance (Woodbury: I + J Sigma_- J' = (I - P)^-1, r_- = (I - P)^-1 r): chi-square with m degrees of
+ * freedom for a correct factor, 7.815 (m = 3) and 12.592 (m = 6) at 0.95.  A factor that is the only constraint on some direction (the
+ * gauge prior, the single observation of a plane) has a singular I - P: when a pivot of the Cholesky factor, taken before its square root,
+ * is not finite or <= 1e-7 (the pivot criterion of the recovery on a matrix of scale 1), d2 = NaN -- "untestable" --, the leverage is
+ * still written, the entry is never flagged and the call still returns PPS_OK, as pps_merge_gate treats a degenerate pair;
+ * pps_factor_gate_last reports how many there were.
+ *   fids       n factor ids; NULL (n ignored): all live factors in insertion order.  A fid may appear more than once; each entry is
+ *              answered on its own, and its d2 and leverage do not depend on what else is in the list (the same bits)
+ *   d2, leverage   (either may be NULL) n each
+ *   flagged, n_flagged  (may be NULL together) the indices INTO the list, ascending, of the entries whose finite d2 exceeds thr3 (m = 3)
+ *              or thr6 (m = 6); at most cap_flagged are written, *n_flagged is always the full count (flagged may be NULL with
+ *              cap_flagged == 0: the count alone)
+ * Every factor type is answered; a pps_add_plane_obs2 factor has its J by central differences in both modes, as pps_eval_factor gives it.
+ * In PPS_JAC_NUMERIC r and J are pps_eval_factor's lane form (compiled without contraction).  Everything is computed on the device: the
+ * table that says where each factor's blocks sit in the selected inverse is built and uploaded once per analysis, a call uploads its fid
+ * list, makes ONE launch (a wave per entry) and one copy; no covariance block is downloaded.  Nothing is added to the graph: the estimate,
+ * the linearisation point, the LM trace, the stats, both validity flags and the recovery stay untouched, and a pps_batch_optimize after
+ * the call is bit for bit the one without it.
+ *   PPS_EINVAL  (checked on the host before any launch, without a device) NULL handle; negative n or cap_flagged; d2, leverage and
+ *               flagged / n_flagged all NULL; flagged without n_flagged, or n_flagged without flagged and cap_flagged > 0; a threshold
+ *               that is not finite while n_flagged is given; an unknown or removed fid
+ *   PPS_ESTATE  a robust cost function is set (after the argument checks, without a device: the robustified statistic is not offered);
+ *               no valid SELECTED INVERSE: the texts of pps_cov_marginals (pps_cov_recover or pps_cov_select provide it, so a
+ *               dense-front graph is served after pps_cov_select; the factor of pps_cov_factor alone is not enough)
+ *   PPS_OK      with the outputs untouched for n == 0 (or no live factor with fids NULL) -- answered before the recovery is looked at
+ *   PPS_ENOMEM  a buffer of the call cannot be had
+ * Found by symbol lookup, like the pps_cov_* calls; PPS_VERSION was not bumped. */
+int pps_factor_gate(pps_graph* g, int n, const int* fids, double thr3, double thr6, double* d2, double* leverage, int cap_flagged, int* flagged,
+                    int* n_flagged);
+/* the last pps_factor_gate: device seconds (HIP events) around its kernel, the kernel launches it made (1), and the number of its
+ * untestable entries (each may be NULL) */
+int pps_factor_gate_last(const pps_graph* g, double* kernel_sec, int* launches, int* n_untestable);
+/* diagnostics: J and r of every entry of the last successful pps_factor_gate, as the kernel evaluated them: one slot of 78 doubles per list
+ * entry, [J m x c row-major, packed | r m], the rest of the slot unspecified, so that a test can compare them with pps_eval_factor.
+ * *needed = the number of doubles; nothing is copied when rec is NULL or cap is smaller.  PPS_ESTATE before the first successful call of
+ * the handle, and after a call of more than 65536 entries (the records of such a call are not kept). */
+int pps_debug_factor_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed);
+
 /* ---- robust cost functions: Slam::set_cost_function (Slam.h; Factor::error, Factor.h:67-77; isam/robust.h) ------
  * With a cost function set, every evaluation of a factor's error replaces each whitened component by
  *     r_i <- sign(r_i) sqrt(rho(r_i)),  sign(0) = +1

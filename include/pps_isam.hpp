@@ -481,6 +481,32 @@ public:
     detail::check(pps_merge_gate_last(handle(), nullptr, nullptr, &out.n_not_pd), handle(), "pps_merge_gate_last");
     return out;
   }
+  // Leave-one-out chi-square test of the graph's own factors (pps_factor_gate): which factor already in the graph is wrong?  Per entry of
+  // `factors` (an empty list: ALL factors of the graph in insertion order), d2 = r' (I - P)^-1 r and leverage = trace(P), P = J Sigma_ff J',
+  // with r, J the factor's whitened residual and Jacobian at the estimate and Sigma_ff the joint marginal of its nodes; d2 is chi-square
+  // with as many degrees of freedom as the factor has rows when the factor is right (7.815 for 3 rows, 12.592 for 6 at 0.95).  flagged =
+  // the indices into the list, ascending, of the entries whose finite d2 exceeds its threshold.  A factor that alone constrains a direction
+  // (the gauge prior, the single observation of a plane) has d2 = NaN and is never flagged; n_untestable counts them.  Needs the selected
+  // inverse: where none is valid the call computes it first, in whatever form the graph is solved in (pps_cov_select).
+  struct FactorGate { std::vector<double> d2, leverage; std::vector<int> flagged; int n_untestable = 0; };
+  FactorGate factor_gate(const std::list<Factor*>& factors = std::list<Factor*>(), double thr3 = 7.815, double thr6 = 12.592) const {
+    double none = 0.0;
+    if (pps_cov_marginals(handle(), 0, &_probe_id, &none, nullptr) != PPS_OK) select();
+    std::vector<int> ids;
+    for (Factor* f : factors) { if (!f || f->backend_id() < 0) throw std::runtime_error("Covariances: factor is not part of the graph"); ids.push_back(f->backend_id()); }
+    int n = (int)ids.size();
+    if (factors.empty()) detail::check(pps_num_factors(handle(), &n), handle(), "pps_num_factors");
+    FactorGate out;
+    out.d2.assign((size_t)n, 0.0); out.leverage.assign((size_t)n, 0.0);
+    if (n == 0) return out;
+    std::vector<int> flat((size_t)n);
+    int count = 0;
+    detail::check(pps_factor_gate(handle(), n, factors.empty() ? nullptr : ids.data(), thr3, thr6, out.d2.data(), out.leverage.data(), n, flat.data(), &count),
+                  handle(), "pps_factor_gate");
+    out.flagged.assign(flat.begin(), flat.begin() + count);
+    detail::check(pps_factor_gate_last(handle(), nullptr, nullptr, &out.n_untestable), handle(), "pps_factor_gate_last");
+    return out;
+  }
   std::list<MatrixXd> marginal(const node_lists_t& node_lists) const {
     std::list<MatrixXd> out;
     for (const std::list<Node*>& l : node_lists) out.push_back(marginal(l));

@@ -135,6 +135,7 @@ SYMBOLS = [
     "pps_cov_factor", "pps_debug_cov_path_form", "pps_cov_select", "pps_debug_cov_select_form",
     "pps_cov_block", "pps_cov_block_last", "pps_assoc_gate", "pps_assoc_gate_last", "pps_debug_assoc_gate_records",
     "pps_merge_gate", "pps_merge_gate_last", "pps_debug_merge_gate_records",
+    "pps_factor_gate", "pps_factor_gate_last", "pps_debug_factor_gate_records",
     "pps_map_default_select", "pps_map_create", "pps_map_destroy", "pps_map_last_error", "pps_map_add_frame", "pps_map_redirect",
     "pps_map_info", "pps_map_chunks", "pps_map_built_chunks", "pps_map_select_host", "pps_map_build", "pps_map_download",
     "pps_map_last_times",
@@ -270,6 +271,9 @@ def lib():
         L.pps_merge_gate.argtypes = [C.c_void_p, C.c_int, _ip, C.c_double, C.c_double, _dp, _ip, C.c_int, _ip, _ip]
         L.pps_merge_gate_last.argtypes = [C.c_void_p, _dp, _ip, _ip]
         L.pps_debug_merge_gate_records.argtypes = [C.c_void_p, C.c_int64, _dp, C.POINTER(C.c_int64)]
+        L.pps_factor_gate.argtypes = [C.c_void_p, C.c_int, _ip, C.c_double, C.c_double, _dp, _dp, C.c_int, _ip, _ip]
+        L.pps_factor_gate_last.argtypes = [C.c_void_p, _dp, _ip, _ip]
+        L.pps_debug_factor_gate_records.argtypes = [C.c_void_p, C.c_int64, _dp, C.POINTER(C.c_int64)]
         L.pps_set_cost_function.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.pps_get_cost_function.argtypes = [C.c_void_p, _ip, _dp]
         _i32p = C.POINTER(C.c_int32)
@@ -580,6 +584,37 @@ class Graph:
         """(device seconds around the two kernels, kernel launches, pairs whose S was not positive definite) of the last merge_gate"""
         s = C.c_double(); n = C.c_int(); k = C.c_int()
         self._ck(self.L.pps_merge_gate_last(self.h, C.byref(s), C.byref(n), C.byref(k))); return s.value, n.value, k.value
+
+    def factor_gate(self, fids=None, thr3=7.815, thr6=12.592):
+        """Leave-one-out chi-square test of the graph's own factors (pps_factor_gate): which factor already in the graph is wrong?  fids:
+        the n factor ids (None: all live factors in insertion order; an id may repeat).  Returns (d2, lev, flagged): d2 (n) =
+        r' (I - P)^-1 r, lev (n) = trace(P), P = J Sigma_ff J' with r, J of the factor at the estimate and Sigma_ff the joint marginal of
+        its nodes from the last cov_recover / cov_select; flagged = indices into the list, ascending, of the entries whose finite d2
+        exceeds thr3 (3 rows) or thr6 (6 rows).  d2 is chi-square with as many degrees of freedom as the factor has rows when the factor
+        is right.  A factor that alone constrains a direction (the gauge prior) has d2 = NaN and is never flagged (factor_gate_last
+        counts them)."""
+        ids = None if fids is None else np.ascontiguousarray(fids, dtype=np.int32).reshape(-1)
+        n = self.num_factors() if ids is None else len(ids)
+        d2 = np.full(n, np.nan); lev = np.full(n, np.nan)
+        flagged = np.zeros(max(n, 1), dtype=np.int32); cnt = C.c_int(0)
+        self._ck(self.L.pps_factor_gate(self.h, n, None if ids is None else ids.ctypes.data_as(_ip), float(thr3), float(thr6), d2.ctypes.data_as(_dp),
+                                        lev.ctypes.data_as(_dp), n, flagged.ctypes.data_as(_ip), C.byref(cnt)))
+        return d2, lev, flagged[:cnt.value].copy()
+
+    def factor_gate_records(self):
+        """diagnostics: J and r of every entry of the last factor_gate as the kernel evaluated them -- (n, 78), one slot per entry holding
+        [J m x c row-major, packed | r m] (the rest of the slot unspecified), columns of the factor's first node, then of its second:
+        slot[:m * c].reshape(m, c) and slot[m * c:m * c + m] are what pps_eval_factor gives for the factor"""
+        n = C.c_int64(0)
+        self._ck(self.L.pps_debug_factor_gate_records(self.h, 0, None, C.byref(n)))
+        rec = np.zeros(n.value)
+        self._ck(self.L.pps_debug_factor_gate_records(self.h, n.value, rec.ctypes.data_as(_dp), C.byref(n)))
+        return rec.reshape(-1, 78)
+
+    def factor_gate_last(self):
+        """(device seconds around the kernel, kernel launches, untestable entries) of the last factor_gate"""
+        s = C.c_double(); n = C.c_int(); k = C.c_int()
+        self._ck(self.L.pps_factor_gate_last(self.h, C.byref(s), C.byref(n), C.byref(k))); return s.value, n.value, k.value
 
     def cov_last_times(self):
         """device seconds of the last cov_recover or cov_select: (whole call, root -> leaves pass alone); of the last cov_factor: (whole call, 0)"""

@@ -36,6 +36,7 @@ void cov_release(pps_graph* g) {
   g->cov_bout.release(); g->cov_zscr.release(); g->cov_G.release(); g->cov_dtab.release();
   gate_release(g);
   merge_release(g);
+  fgate_release(g);
   for (hipEvent_t& e : g->cov_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   for (hipEvent_t& e : g->cov_qev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   g->cov_cache = pps_graph::CovCache{};
@@ -73,7 +74,7 @@ int cov_locate(pps_graph* g, int id, CovNode* n) {
 }
 
 // the block Sigma(rows, cols) as a gather request; false: the pair is outside the pattern of L
-static bool cov_request(const pps_graph* g, const CovNode& r, const CovNode& c, long long dst, CovReq* q) {
+bool cov_request(const pps_graph* g, const CovNode& r, const CovNode& c, long long dst, CovReq* q) {
   const Analysis& A = g->an;
   const bool r_first = r.epos <= c.epos;               // the earlier-eliminated node owns the columns of the panel
   const CovNode& e = r_first ? r : c;

@@ -9,6 +9,7 @@
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
 //   pps_cov.cpp      marginal covariances from the factor (isam::Covariances): the recovery pipeline and the query scaffold (CovQuery); kernels in pps_cov*.hip
 //   pps_gate.cpp     pps_assoc_gate (measurement against landmark); pps_merge.cpp: pps_merge_gate (landmark against landmark): queries on the factor
+//   pps_fgate.cpp    pps_factor_gate (every factor of the graph against the rest of it): a query on the selected inverse
 //   pps_map.cpp      the dense map (pps_map: per-plane clouds of every frame, re-projected on the device); kernels in pps_map.hip
 #pragma once
 #include <hip/hip_runtime.h>
@@ -261,6 +262,15 @@ struct pps_graph {
   double merge_sec = 0; int merge_launches = 0, merge_not_pd = 0;      // the two kernels of the last call: device seconds, launches; its pairs without a positive definite S
   pps_impl::DevBuf<double> merge_rec; size_t merge_rec_n = 0;   // [J_a | J_b | e] per pair of the last call (pps_debug_merge_gate_records)
   bool merge_done = false;           // a call has succeeded on this handle
+  // pps_factor_gate (pps_fgate.cpp): one FgateFactor per factor id on the device -- where the blocks of its joint marginal sit in cov_S --, built
+  // for the analysis of upload_version fgate_tab_version (like cov_cache); the fid list, the result ([d2 n | lev n | status: n ints]) and the
+  // records ([J m x c | r m] in slots of 78 doubles) of the last call
+  pps_impl::DevBuf<char> fgate_tab; int fgate_tab_version = -1, fgate_tab_n = 0;
+  pps_impl::DevBuf<int> fgate_list;
+  pps_impl::DevBuf<double> fgate_out;
+  pps_impl::DevBuf<double> fgate_rec; size_t fgate_rec_n = 0;
+  bool fgate_done = false;           // a call has succeeded on this handle
+  double fgate_sec = 0; int fgate_launches = 0, fgate_untestable = 0;      // the kernel of the last call: device seconds, launches; its entries with d2 = NaN
   // stats / trace
   pps_stats stats{};
   std::vector<double> tr_lambda, tr_chi2;
@@ -356,6 +366,9 @@ extern const char* const kFactorOnly;          // ... and when there is a factor
 struct CovNode { int front, local, dim, epos, voff; };
 int cov_node(pps_graph* g, int id, CovNode* out);      // id check (PPS_EINVAL) + dim; the rest by cov_locate, with a current recovery only
 int cov_locate(pps_graph* g, int id, CovNode* n);
+// the block Sigma(rows r, columns c) of the selected inverse as a gather request (pps_cov.h: source offset, leading dimension, transpose flag;
+// dst as given); false: the pair is outside the pattern of L
+bool cov_request(const pps_graph* g, const CovNode& r, const CovNode& c, long long dst, pps::CovReq* q);
 // a device buffer of one of the covariance calls, grown by a quarter when it is too small.  Without `who` a failure answers as HIP_TRY does; with
 // it, PPS_ENOMEM and "<who>no device memory for <what> (<n> bytes)<advice>"
 template <class T>
@@ -407,6 +420,8 @@ int copy_records(pps_graph* g, const DevBuf<double>& rec, size_t n, int64_t cap,
 void gate_release(pps_graph* g);               // (from cov_release)
 // ---- pps_merge.cpp ----
 void merge_release(pps_graph* g);              // (from cov_release)
+// ---- pps_fgate.cpp ----
+void fgate_release(pps_graph* g);              // (from cov_release)
 // ---- pps_api.cpp ----
 void report_front_trace(pps_graph* g);        // PPS_TRACE: the per-front cycle counters of the last solve -> stderr
 
