@@ -88,7 +88,7 @@ __device__ __forceinline__ double wave_segment_sum(const DevGraph& d, int rec, i
     double pacc = 0.0;
 #pragma unroll
     for (int u = 0; u < 16; u++) pacc += (live && sl + S * u < np) ? v0[u] : 0.0;
-    for (int k0 = 16 * S; k0 < np; k0 += 16 * S) {              // (more than 16 records per slice: the ground plane's segments)
+    for (int k0 = 16 * S; k0 < np; k0 += 16 * S) {              // (a pose that sees more than 16 planes: S = 1.  A plane's 12 entries have S = 5, and 80 records are more than a segment holds)
       double v[16];
 #pragma unroll
       for (int u = 0; u < 16; u++) { const int k = k0 + sl + S * u; v[u] = P[plist[k < np ? k : np - 1] + enc]; }
@@ -499,9 +499,10 @@ __device__ __forceinline__ void body_hblocks_tc(const DevGraph& d, int bx) {
 }
 
 // Fold the partial sums of a multi-segment block (the ground plane's diagonal: a hundred segments on C2) into its first slot.
-// The segments are summed as four interleaved partial sums -- p_w = segments w, w + 4, w + 8, ... in order -- combined as
-// (p0 + p1) + (p2 + p3): the same bits in every form.  NW = 4 (one graph): a 256-thread workgroup per block, one partial sum
-// per wave, up to 32 independent loads per thread in flight -- two memory round trips for the ground plane instead of one per
+// Up to sixteen segments they are summed as four interleaved partial sums -- p_w = segments w, w + 4, w + 8, ... in order -- combined
+// as (p0 + p1) + (p2 + p3); a longer block is added sixteen segments at a time in that order and the chunks' sums one after the other,
+// which is how body_hblocks2 and body_hfinish add it: the same bits in every form.  NW = 4 (one graph): a 256-thread workgroup per
+// block, one partial sum per wave, up to 32 independent loads per thread in flight -- two memory round trips for the ground plane instead of one per
 // 16 segments -- and the combination through LDS.  NW = 1 (batches, where the launch is wide anyway): one wave computes the four
 // partial sums one after the other.
 template <int NW>
@@ -512,6 +513,28 @@ __device__ __forceinline__ void body_hreduce(const DevGraph& d, int bx) {
   double* __restrict__ h = d.H + d.blk_hoff[blk];
   const int lane = threadIdx.x & 63, w0 = NW == 4 ? (int)(threadIdx.x >> 6) : 0;
   const int ln = lane < size ? lane : 0;                       // (idle lanes shadow entry 0: no predicated loads)
+  if (NW == 1 && nseg > kK2Chunk) {
+    // a block of more than sixteen segments: chunk by chunk, as body_hblocks2 and body_hfinish add it -- inside a chunk the four
+    // interleaved sums q_w = segments w, w + 4, w + 8, w + 12 combined as (q0 + q1) + (q2 + q3), then the chunks' sums one after the
+    // other.  (The interleaving over the WHOLE block below is that order only while the block is one chunk.)
+    double tot = 0.0;
+    for (int c0 = 0; c0 < nseg; c0 += kK2Chunk) {
+      double x[kK2Chunk];
+#pragma unroll
+      for (int u = 0; u < kK2Chunk; u++) { const int sg = c0 + u; const double t = h[(size_t)(sg < nseg ? sg : 0) * size + ln]; x[u] = sg < nseg ? t : 0.0; }
+      double q[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int w = 0; w < 4; w++)
+#pragma unroll
+        for (int v = w; v < kK2Chunk; v += 4) q[w] += x[v];
+      tot += (q[0] + q[1]) + (q[2] + q[3]);
+    }
+    if (lane >= size) return;
+    h[lane] = tot;
+    const int dst = d.blk_dst[d.blk_doff[blk] + lane];
+    if (dst >= 0) d.Hf[dst] = tot;
+    return;
+  }
   double pv[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int w = 0; w < 4; w++) {

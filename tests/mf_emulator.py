@@ -4,9 +4,9 @@ pps_analysis_dump exports.  Used by the CPU tests to validate the host-side symb
 import numpy as np
 
 
-def solve_with_analysis(A, Jbuf, lam):
-    """A: parsed dump (pop_up_slam_amd.parse_analysis_dump); Jbuf: flat J buffer in the device layout.
-    Returns delta in elimination order."""
+def solve_with_analysis(A, Jbuf, lam, Pbuf=None):
+    """A: parsed dump (pop_up_slam_amd.parse_analysis_dump); Jbuf: flat J buffer in the device layout; Pbuf: the product records
+    (then the contributions that name one are summed from it, as K2 does).  Returns delta in elimination order."""
     nseg = A["n_segs"]
     H = np.zeros(A["H_size"])
     ctr = A["contrib"].reshape(-1, 4)
@@ -16,7 +16,11 @@ def solve_with_analysis(A, Jbuf, lam):
         acc = np.zeros(size)
         for c in range(A["seg_c0"][s], A["seg_c0"][s] + A["seg_cnt"][s]):
             jv, ju, roff, m = ctr[c]
-            m = m & 255                      # (bit 8: the contribution also names a product record in ju -- this emulation multiplies the Jacobians)
+            if m >= 256 and Pbuf is not None:
+                assert size > rows * cols
+                acc += Pbuf[ju:ju + size]
+                continue
+            m = m & 255                      # (bit 8: the contribution also names a product record in ju -- without Pbuf this emulation multiplies the Jacobians)
             Jv = Jbuf[jv:jv + m * rows].reshape(m, rows)
             Ju = Jv if size > rows * cols else Jbuf[ju:ju + m * cols].reshape(m, cols)
             acc[:rows * cols] += (Jv.T @ Ju).ravel()
