@@ -26,6 +26,12 @@ size_t cov_level_lds_bytes(int p, int b);      // dynamic LDS one front of this 
 // largest pivot of its front raises d.result_dev[2] to 1 (not positive definite), like the factorisation.
 hipError_t launch_cov_level(const DevGraph& d, double* S, const int* parent, int level_begin, int level_count, size_t lds_bytes, hipStream_t st);
 hipError_t launch_cov_gather(const double* S, const CovReq* req, int n, double* out, hipStream_t st);
+// entry (r, c) of a front's full block [Sigma_AA Sigma_BA'; Sigma_BA Sigma_BB]: panel Sp (ld = p), boundary block Bs (ld = b)
+// (what a child gathers its Sigma_BB from, in k_cov_level and in k_cov_dense_gather)
+__device__ __forceinline__ double cov_full(const double* __restrict__ Sp, const double* __restrict__ Bs, int p, int b, int r, int c) {
+  if (r < c) { const int t = r; r = c; c = t; }
+  return c < p ? Sp[(size_t)r * p + c] : Bs[(size_t)(r - p) * b + (c - p)];
+}
 
 // ---- pps_cov_block: root-path solves ----
 // A strip holds K rows of dim doubles (row k, column a at strip + k * dim + a), K = the longest requested path in pivots, and is filled

@@ -15,23 +15,14 @@
 #include <algorithm>
 
 #include "pps_cov.h"
+#include "pps_status.h"
 
 namespace pps {
 
 namespace {
 
 constexpr int kCovThreads = 256;
-constexpr double kCovStatusInternal = 64.0;      // = kStatusInternal: an index outside its front (never with a consistent analysis)
-
-__device__ __forceinline__ void cov_raise(double* w, double v) {      // the status word is raised, never overwritten (pps_regtile.h)
-  atomicMax(reinterpret_cast<unsigned long long*>(w), (unsigned long long)__double_as_longlong(v));
-}
-
-// entry (r, c) of a front's full block [Sigma_AA Sigma_BA'; Sigma_BA Sigma_BB]: panel Sp (ld = p), boundary block Bs (ld = b)
-__device__ __forceinline__ double cov_full(const double* __restrict__ Sp, const double* __restrict__ Bs, int p, int b, int r, int c) {
-  if (r < c) { const int t = r; r = c; c = t; }
-  return c < p ? Sp[(size_t)r * p + c] : Bs[(size_t)(r - p) * b + (c - p)];
-}
+// (the status word raised to kStatusInternal: an index outside its front or its strip -- never with a consistent analysis)
 
 __global__ __launch_bounds__(kCovThreads) void k_cov_level(DevGraph d, double* __restrict__ S, const int* __restrict__ parent, int level_begin) {
   extern __shared__ __attribute__((aligned(16))) double cov_lds[];
@@ -48,7 +39,7 @@ __global__ __launch_bounds__(kCovThreads) void k_cov_level(DevGraph d, double* _
   // ---- Sigma_BB from the parent's full block, through cmap (its entry b is the rhs row) ----
   const int q = parent[s];
   if (b > 0) {
-    if (q < 0) { if (tid == 0) cov_raise(&d.result_dev[2], kCovStatusInternal); return; }
+    if (q < 0) { if (tid == 0) raise_status(&d.result_dev[2], kStatusInternal); return; }
     const int pq = d.f_p[q], bq = d.f_b[q];
     const double* __restrict__ Sq = S + d.f_Loff[q];
     const double* __restrict__ Bq = d.U + d.f_Uoff[q];
@@ -58,7 +49,7 @@ __global__ __launch_bounds__(kCovThreads) void k_cov_level(DevGraph d, double* _
       const int r = cm[i], c = cm[j];
       double v = 0.0;
       if (r >= 0 && c >= 0 && r < pq + bq && c < pq + bq) v = cov_full(Sq, Bq, pq, bq, r, c);
-      else cov_raise(&d.result_dev[2], kCovStatusInternal);
+      else raise_status(&d.result_dev[2], kStatusInternal);
       Bs[idx] = v;
     }
   }
@@ -73,10 +64,10 @@ __global__ __launch_bounds__(kCovThreads) void k_cov_level(DevGraph d, double* _
     bool bad = false;
     for (int k = 0; k < p; k++) {
       const double v = LA[k * p + k];
-      if (!(v > 0.0) || !(v <= 1.79769313486231570e308)) bad = true;
+      if (!finite_pos(v)) bad = true;
       mn = v < mn ? v : mn; mx = v > mx ? v : mx;
     }
-    if (bad || !(mn >= kCovPivotRatio * mx)) cov_raise(&d.result_dev[2], 1.0);
+    if (bad || !(mn >= kCovPivotRatio * mx)) raise_status(&d.result_dev[2], 1.0);
   }
   // ---- X = L_A^-1: thread j solves L_A x = e_j (its own column: no hand-over between threads) ----
   if (tid < p) {
@@ -155,11 +146,11 @@ __device__ void cov_walk(const DevGraph& d, const CovWalk w, const CovStep* __re
     const bool last = t + 1 == w.n_steps;
     const int q = last ? -1 : steps[w.step0 + t + 1].front;
     // (every test below is the same in all lanes: the wave leaves together)
-    if (s < 0 || s >= d.n_fronts || (!last && (q < 0 || q >= d.n_fronts))) { if (tid == 0) cov_raise(status, kCovStatusInternal); return; }
+    if (s < 0 || s >= d.n_fronts || (!last && (q < 0 || q >= d.n_fronts))) { if (tid == 0) raise_status(status, kStatusInternal); return; }
     const int p = d.f_p[s], b = d.f_b[s];
     const int nq = last ? 0 : d.f_p[q] + d.f_b[q];
     if (p < 1 || p > max_p || b < 0 || p + b > max_front || nq > max_front || st.row < 0 || st.row + p > K || (b > 0 && last) || m0 < 0 ||
-        (t == 0 && m0 + D > p)) { if (tid == 0) cov_raise(status, kCovStatusInternal); return; }
+        (t == 0 && m0 + D > p)) { if (tid == 0) raise_status(status, kStatusInternal); return; }
     const double* __restrict__ Lp = d.L + d.f_Loff[s];
     if (t == 0) {                                // E_node in the local rows of the node's front
       for (int idx = tid; idx < (p + b) * D; idx += kPathThreads) zc[idx] = 0.0;
@@ -199,7 +190,7 @@ __device__ void cov_walk(const DevGraph& d, const CovWalk w, const CovStep* __re
           for (int a = 0; a < D; a++) acc[a] += l * ysh[m * D + a];
         }
         const int tgt = cm[r];
-        if (tgt < 0 || tgt >= nq) { cov_raise(status, kCovStatusInternal); continue; }
+        if (tgt < 0 || tgt >= nq) { raise_status(status, kStatusInternal); continue; }
         for (int a = 0; a < D; a++) zn[tgt * D + a] = zc[(p + r) * D + a] - acc[a];
       }
     }
@@ -216,7 +207,7 @@ __global__ __launch_bounds__(kPathThreads) void k_cov_path(DevGraph d, const Cov
   if ((int)blockIdx.x >= n_walks) return;
   const CovWalk w = walks[blockIdx.x];
   if ((w.dim != 3 && w.dim != 6) || w.n_steps < 1 || w.step0 < 0 || w.step0 + w.n_steps > n_steps_total || w.strip < 0 ||
-      w.strip + (long long)K * w.dim > n_strip) { if (threadIdx.x == 0) cov_raise(&out[0], kCovStatusInternal); return; }
+      w.strip + (long long)K * w.dim > n_strip) { if (threadIdx.x == 0) raise_status(&out[0], kStatusInternal); return; }
   if (w.dim == 6) cov_walk<6>(d, w, steps, K, max_p, max_front, Y + w.strip, &out[0], cov_lds);
   else cov_walk<3>(d, w, steps, K, max_p, max_front, Y + w.strip, &out[0], cov_lds);
 }
@@ -236,7 +227,7 @@ __global__ __launch_bounds__(kGramThreads) void k_cov_gram(const CovPair* __rest
                   r.yi + (long long)r.len * r.di <= n_strip && r.yj + (long long)r.len * r.dj <= n_strip && r.dst >= 0 &&
                   r.dst + (long long)(r.di - 1) * r.ld + r.dj <= n_out &&
                   (r.dst_t < 0 || (r.ld >= r.di && r.dst_t + (long long)(r.dj - 1) * r.ld + r.di <= n_out));
-  if (!ok) { if (tid == 0) cov_raise(&out[0], kCovStatusInternal); return; }
+  if (!ok) { if (tid == 0) raise_status(&out[0], kStatusInternal); return; }
   const int a = e / r.dj, c = e - a * r.dj;
   double acc = 0.0;
   if (e < r.di * r.dj) {

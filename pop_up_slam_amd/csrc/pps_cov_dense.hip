@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pps_cov.h"
+#include "pps_status.h"
 
 namespace pps {
 
@@ -36,11 +37,6 @@ constexpr int kDcLdA = kDcMaxP + 1;
 constexpr int kDcSlab = 32;                      // k per staged slab
 constexpr int kDcLdK = kDcSlab + 1;              // 64 x 32 slab of the left operand
 constexpr int kDcLdP = kDcMaxP + 1;              // 32 x 64 slab of the right operand
-constexpr double kDcStatusInternal = 64.0;       // = kStatusInternal
-
-__device__ __forceinline__ void dc_raise(double* w, double v) {       // the status word is raised, never overwritten (pps_regtile.h)
-  atomicMax(reinterpret_cast<unsigned long long*>(w), (unsigned long long)__double_as_longlong(v));
-}
 
 // workgroup -> (position in the list, work item of that front): the prefix-sum search of pps_dense.hip
 __device__ __forceinline__ int dc_locate(const int* __restrict__ off, int count, int wg, int* item) {
@@ -77,7 +73,7 @@ __global__ __launch_bounds__(kDcThreads) void k_cov_dense_pre(DevGraph d, double
   int slab;
   const int s = dc_locate(off, n_fronts, blockIdx.x, &slab);
   const int tid = threadIdx.x;
-  if (!dc_front_ok(d, s, ext)) { if (tid == 0) dc_raise(&d.result_dev[2], kDcStatusInternal); return; }
+  if (!dc_front_ok(d, s, ext)) { if (tid == 0) raise_status(&d.result_dev[2], kStatusInternal); return; }
   const int p = d.f_p[s], b = d.f_b[s];
   const double* __restrict__ Lp = d.L + d.f_Loff[s];
   for (int i = tid; i < kDcMaxP * kDcLdA; i += kDcThreads) A[i] = 0.0;
@@ -129,12 +125,6 @@ __global__ __launch_bounds__(kDcThreads) void k_cov_dense_pre(DevGraph d, double
   }
 }
 
-// entry (r, c) of a front's full block [Sigma_AA Sigma_BA'; Sigma_BA Sigma_BB]: panel Sp (ld = p), boundary block Bs (ld = b)
-__device__ __forceinline__ double dc_full(const double* __restrict__ Sp, const double* __restrict__ Bs, int p, int b, int r, int c) {
-  if (r < c) { const int t = r; r = c; c = t; }
-  return c < p ? Sp[(size_t)r * p + c] : Bs[(size_t)(r - p) * b + (c - p)];
-}
-
 constexpr int kDcGatherRows = 32;                // rows of Sigma_BB per workgroup of the gather
 
 __global__ __launch_bounds__(kDcThreads) void k_cov_dense_gather(DevGraph d, const double* __restrict__ S, CovDenseExtents ext, const int* __restrict__ parent,
@@ -143,25 +133,25 @@ __global__ __launch_bounds__(kDcThreads) void k_cov_dense_gather(DevGraph d, con
   int item;
   const int s = d.level_fronts[level_begin + dc_locate(off, count, blockIdx.x, &item)];
   const int tid = threadIdx.x;
-  if (!dc_front_ok(d, s, ext)) { if (tid == 0) dc_raise(&d.result_dev[2], kDcStatusInternal); return; }
+  if (!dc_front_ok(d, s, ext)) { if (tid == 0) raise_status(&d.result_dev[2], kStatusInternal); return; }
   const int b = d.f_b[s];
   if (b == 0) return;
   const int q = parent[s];
-  if (!dc_front_ok(d, q, ext) || q == s || d.f_cmap_off[s + 1] - d.f_cmap_off[s] < b) { if (tid == 0) dc_raise(&d.result_dev[2], kDcStatusInternal); return; }
+  if (!dc_front_ok(d, q, ext) || q == s || d.f_cmap_off[s + 1] - d.f_cmap_off[s] < b) { if (tid == 0) raise_status(&d.result_dev[2], kStatusInternal); return; }
   const int pq = d.f_p[q], bq = d.f_b[q];
   const int* __restrict__ cm = d.cmap + d.f_cmap_off[s];
   if (tid == 0) bad = 0;
   __syncthreads();
   for (int i = tid; i < b; i += kDcThreads) if (cm[i] < 0 || cm[i] >= pq + bq) bad = 1;      // every target of the front, before any of its entries is written
   __syncthreads();
-  if (bad) { if (tid == 0) dc_raise(&d.result_dev[2], kDcStatusInternal); return; }
+  if (bad) { if (tid == 0) raise_status(&d.result_dev[2], kStatusInternal); return; }
   const double* __restrict__ Sq = S + d.f_Loff[q];
   const double* __restrict__ Bq = d.U + d.f_Uoff[q];
   double* __restrict__ Bs = d.U + d.f_Uoff[s];
   const int r0 = item * kDcGatherRows, nr = b - r0 < kDcGatherRows ? b - r0 : kDcGatherRows;
   for (int idx = tid; idx < nr * b; idx += kDcThreads) {
     const int i = r0 + idx / b, j = idx - (idx / b) * b;
-    Bs[(size_t)i * b + j] = dc_full(Sq, Bq, pq, bq, cm[i], cm[j]);
+    Bs[(size_t)i * b + j] = cov_full(Sq, Bq, pq, bq, cm[i], cm[j]);
   }
 }
 
@@ -197,7 +187,7 @@ __global__ __launch_bounds__(kDcThreads) void k_cov_dense_sba(DevGraph d, double
   const int s = d.level_fronts[level_begin + dc_locate(off, count, blockIdx.x, &item)];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int l16 = lane & 15, lq = lane >> 4;
-  if (!dc_front_ok(d, s, ext)) { if (tid == 0) dc_raise(&d.result_dev[2], kDcStatusInternal); return; }
+  if (!dc_front_ok(d, s, ext)) { if (tid == 0) raise_status(&d.result_dev[2], kStatusInternal); return; }
   const int p = d.f_p[s], b = d.f_b[s];
   if (b == 0) return;
   const int nt = (p + 15) >> 4;
@@ -240,7 +230,7 @@ __global__ __launch_bounds__(kDcThreads) void k_cov_dense_saa(DevGraph d, double
   const int s = d.level_fronts[level_begin + blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int l16 = lane & 15, lq = lane >> 4;
-  if (!dc_front_ok(d, s, ext)) { if (tid == 0) dc_raise(&d.result_dev[2], kDcStatusInternal); return; }
+  if (!dc_front_ok(d, s, ext)) { if (tid == 0) raise_status(&d.result_dev[2], kStatusInternal); return; }
   const int p = d.f_p[s], b = d.f_b[s];
   if (b == 0) return;                            // (the root: Sigma_AA = W, written by the pre-pass)
   const int nt = (p + 15) >> 4;

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pps_cov.h"
+#include "pps_status.h"
 
 namespace pps {
 
@@ -24,18 +25,14 @@ constexpr int kWideThreads = 256;
 constexpr int kWideMaxP = 64;                    // pivots per front (the tables are checked against it before anything is launched)
 constexpr int kWideLdA = kWideMaxP | 1;
 constexpr int kPivotThreads = 64;
-constexpr double kWideStatusInternal = 64.0;     // = kStatusInternal: an index outside its front (never with a consistent analysis)
-
-__device__ __forceinline__ void wide_raise(double* w, double v) {     // the status word is raised, never overwritten (pps_regtile.h)
-  atomicMax(reinterpret_cast<unsigned long long*>(w), (unsigned long long)__double_as_longlong(v));
-}
+// (the status word raised to kStatusInternal: an index outside its front -- never with a consistent analysis)
 
 __global__ __launch_bounds__(kPivotThreads) void k_cov_pivots(DevGraph d, int n_fronts) {
   extern __shared__ __attribute__((aligned(16))) double cov_lds[];
   const int s = blockIdx.x, tid = threadIdx.x;
   if (s >= n_fronts || s >= d.n_fronts) return;
   const int p = d.f_p[s];
-  if (p < 1 || p > kPivotThreads) { if (tid == 0) wide_raise(&d.result_dev[2], kWideStatusInternal); return; }
+  if (p < 1 || p > kPivotThreads) { if (tid == 0) raise_status(&d.result_dev[2], kStatusInternal); return; }
   const double* __restrict__ Lp = d.L + d.f_Loff[s];
   if (tid < p) cov_lds[tid] = Lp[(size_t)tid * p + tid];
   __syncthreads();
@@ -44,10 +41,10 @@ __global__ __launch_bounds__(kPivotThreads) void k_cov_pivots(DevGraph d, int n_
     bool bad = false;
     for (int k = 0; k < p; k++) {
       const double v = cov_lds[k];
-      if (!(v > 0.0) || !(v <= 1.79769313486231570e308)) bad = true;
+      if (!finite_pos(v)) bad = true;
       mn = v < mn ? v : mn; mx = v > mx ? v : mx;
     }
-    if (bad || !(mn >= kCovPivotRatio * mx)) wide_raise(&d.result_dev[2], 1.0);
+    if (bad || !(mn >= kCovPivotRatio * mx)) raise_status(&d.result_dev[2], 1.0);
   }
 }
 
@@ -64,11 +61,11 @@ __device__ void cov_walk_wide(const DevGraph& d, const CovWalk w, const CovStep*
     const bool last = t + 1 == w.n_steps;
     const int q = last ? -1 : steps[w.step0 + t + 1].front;
     // (every test below is the same in all threads: the workgroup leaves together, before anything of this front is touched)
-    if (s < 0 || s >= d.n_fronts || (!last && (q < 0 || q >= d.n_fronts))) { if (tid == 0) wide_raise(status, kWideStatusInternal); return; }
+    if (s < 0 || s >= d.n_fronts || (!last && (q < 0 || q >= d.n_fronts))) { if (tid == 0) raise_status(status, kStatusInternal); return; }
     const int p = d.f_p[s], b = d.f_b[s];
     const int nq = last ? 0 : d.f_p[q] + d.f_b[q];
     if (p < 1 || p > kWideMaxP || b < 0 || p + b > max_front || nq < 0 || nq > max_front || st.row < 0 || st.row + p > K || (b > 0 && last) || m0 < 0 ||
-        (t == 0 && m0 + D > p)) { if (tid == 0) wide_raise(status, kWideStatusInternal); return; }
+        (t == 0 && m0 + D > p)) { if (tid == 0) raise_status(status, kStatusInternal); return; }
     const double* __restrict__ Lp = d.L + d.f_Loff[s];
     if (t == 0) {                                // E_node in the local rows of the node's front
       for (int idx = tid; idx < (p + b) * D; idx += kWideThreads) zc[idx] = 0.0;
@@ -108,7 +105,7 @@ __device__ void cov_walk_wide(const DevGraph& d, const CovWalk w, const CovStep*
           for (int a = 0; a < D; a++) acc[a] += l * ysh[m * D + a];
         }
         const int tgt = cm[r];
-        if (tgt < 0 || tgt >= nq) { wide_raise(status, kWideStatusInternal); continue; }
+        if (tgt < 0 || tgt >= nq) { raise_status(status, kStatusInternal); continue; }
         for (int a = 0; a < D; a++) zn[(size_t)tgt * D + a] = zc[(size_t)(p + r) * D + a] - acc[a];
       }
     }
@@ -127,7 +124,7 @@ __global__ __launch_bounds__(kWideThreads) void k_cov_path_wide(DevGraph d, cons
   const long long per_walk = (long long)2 * max_front * 6;
   if ((w.dim != 3 && w.dim != 6) || w.n_steps < 1 || w.step0 < 0 || w.step0 + w.n_steps > n_steps_total || w.strip < 0 ||
       w.strip + (long long)K * w.dim > n_strip || max_front < 1 || ((long long)blockIdx.x + 1) * per_walk > n_scratch) {
-    if (threadIdx.x == 0) wide_raise(&out[0], kWideStatusInternal);
+    if (threadIdx.x == 0) raise_status(&out[0], kStatusInternal);
     return;
   }
   double* zc = Z + (long long)blockIdx.x * per_walk;

@@ -6,22 +6,22 @@
 // three blocks of Sigma_ff, and writes its own d2, lev, status and record: no entry waits for another, nothing is accumulated across
 // entries, so an entry's answer does not depend on what else is in the list.
 //   1. r and J at the estimate by the device functions K1 runs for the factor's type.  Numeric mode: the 2 c + 1 evaluations of the lane
-//      form side by side on lanes (body_linearize_lanes, pps_k1_body.h: perturb6 / perturb3 with the device's step quaternions, the
-//      residual, whiten), the column differences through LDS.  Analytic mode: the closed form of pps_lin.h in one lane.  This file is
-//      compiled without contraction like pps_k1_lanes.hip, pps_gate.hip and pps_merge.hip.  A re-popping plane observation
-//      (Pose3d_Plane3d_Factor2) takes the 19 evaluations of body_linearize_repop in both modes: the steps by pose_exmap / plane_exmap,
+//      form side by side on lanes (eval_odometry / eval_pose_prior / eval_plane_prior of pps_gate_dev.h, the gate kernels' copy of
+//      body_linearize_lanes; the plane observation's chain is written out next to its contracted sibling, see there), the column
+//      differences through LDS.  Analytic mode: the closed form of pps_lin.h in one lane.  This file is compiled without contraction
+//      like pps_k1_lanes.hip, pps_gate.hip and pps_merge.hip.  A re-popping plane observation (Pose3d_Plane3d_Factor2) takes the 19 evaluations of body_linearize_repop in both modes: the steps by pose_exmap / plane_exmap,
 //      the residual by fgate_repop_eval below, which carries the contraction of the one kernel pps_eval_factor has for such a factor.
 //   2. the record [J m x c row-major | r m]: columns of node a, then of node b -- the order of pps_eval_factor.
 //   3. Sigma_ff (c x c) straight from the selected inverse into LDS: lanes over its entries, each through the block descriptor of its
 //      quadrant (source offset, leading dimension, transpose flag; the lower-left quadrant is the transposed upper-right one).
 //   4. T = J Sigma_ff (m x c) and P = T J' (m x m), lanes over the entries, the inner sums in ascending order.
-//   5. one lane: lev, the Cholesky factor of I - P in place with the forward substitution alongside, d2.
+//   5. one lane: lev, I - P in place, then chol_d2<3> or <6> (pps_gate_dev.h) on the wave-uniform m with pivot floor kFgatePivotMin.
 // LDS per wave: Sigma 144 | T 72 | record 78 doubles (2 352 bytes); the evaluations of step 1 use the first two areas before Sigma arrives,
 // P takes Sigma's place once T is complete.  Plain fp64 multiply-add loops: 6 x 12 against 12 x 12 is no MFMA shape.
 #include <hip/hip_runtime.h>
 
 #include "pps_fgate.h"
-#include "pps_k1_body.h"
+#include "pps_gate_dev.h"
 #include "pps_symbolic.h"
 
 namespace pps {
@@ -29,7 +29,6 @@ namespace pps {
 namespace {
 
 constexpr int kFgateThreads = 64 * kFgateWaves;
-constexpr double kFgateDblMax = 1.79769313486231570e308;
 // dynamic LDS per wave, in doubles
 constexpr int kFgateLdsS = 0, kFgateLdsT = kFgateLdsS + 144, kFgateLdsJ = kFgateLdsT + 72, kFgateLdsWave = kFgateLdsJ + kFgateRecord;
 constexpr int kFgateEvalStride = 6;              // doubles per evaluation (m <= 6), 25 evaluations at most
@@ -184,6 +183,10 @@ __global__ __launch_bounds__(kFgateThreads) void k_factor_gate(DevGraph d, Fgate
       load_pose(d.pose_est, d.pose_ld, ia, pz); load_plane(d.plane_est, d.plane_ld, ib, pl);
       load_soa<6>(d.obs_w, d.obs_ld, f.slot, sw);
       if (!repop) {
+        // eval_plane_obs (pps_gate_dev.h), statement for statement, written out HERE: this arm ends in the same whiten as the contracted
+        // arm below, and the compiler merges part of the two tails.  With the shared function in this place the merge came out another
+        // way and the nominal residual of re-popping observations left pps_eval_factor's bits (1e-13 relative on the mixed graph of
+        // tests/test_gpu_factor_gate.py, measured on the device), although the function's arithmetic is the same.
         double ms[4], pp[7], lp[4], ev[3];
         load_soa<4>(d.obs_meas, d.obs_ld, f.slot, ms);
         perturb6(pz, q3, s3, d.step_ac, pp);
@@ -217,29 +220,20 @@ __global__ __launch_bounds__(kFgateThreads) void k_factor_gate(DevGraph d, Fgate
       const int q = lane >> 1;
       const double sgn = (lane & 1) ? -1.0 : 1.0;
       if (f.type == F_ODOMETRY) {
-        double p1[7], p2[7], ms[6], sw[21], pa[7], pb[7], ev[6];
+        double p1[7], p2[7], ms[6], sw[21];
         load_pose(d.pose_est, d.pose_ld, ia, p1); load_pose(d.pose_est, d.pose_ld, ib, p2);
         load_soa<6>(d.odo_meas, d.odo_ld, f.slot, ms); load_soa<21>(d.odo_w, d.odo_ld, f.slot, sw);
-        perturb6(p1, q, sgn, d.step_ac, pa);
-        perturb6(p2, q - 6, sgn, d.step_ac, pb);
-        res_odometry(pa, pb, ms, ev);
-        whiten<6>(sw, ev, y);
+        eval_odometry(p1, p2, ms, sw, q, sgn, d.step_ac, y);
       } else if (f.type == F_POSE_PRIOR) {
-        double pz[7], ms[6], sw[21], pp[7], ev[6];
+        double pz[7], ms[6], sw[21];
         load_pose(d.pose_est, d.pose_ld, ia, pz);
         load_soa<6>(d.pp_meas, d.pp_ld, f.slot, ms); load_soa<21>(d.pp_w, d.pp_ld, f.slot, sw);
-        perturb6(pz, q, sgn, d.step_ac, pp);
-        res_pose_prior(pp, ms, ev);
-        whiten<6>(sw, ev, y);
+        eval_pose_prior(pz, ms, sw, q, sgn, d.step_ac, y);
       } else {
-        double pl[4], ms[4], sw[6], lp[4], ev[3];
+        double pl[4], ms[4], sw[6];
         load_plane(d.plane_est, d.plane_ld, ia, pl);
         load_soa<4>(d.lp_meas, d.lp_ld, f.slot, ms); load_soa<6>(d.lp_w, d.lp_ld, f.slot, sw);
-        perturb3(pl, q, sgn, d.step_ac, lp);
-#pragma unroll
-        for (int k = 0; k < 4; k++) lp[k] = q < 3 ? lp[k] : pl[k];
-        res_plane_prior(lp, ms, ev);
-        whiten<3>(sw, ev, y);
+        eval_plane_prior(pl, ms, sw, q, sgn, d.step_ac, y);
       }
     }
 #pragma unroll
@@ -307,32 +301,15 @@ __global__ __launch_bounds__(kFgateThreads) void k_factor_gate(DevGraph d, Fgate
     Pm[lane] = t;
   }
   __syncthreads();
-  // ---- 5. lev, the Cholesky factor of I - P on and below the diagonal, L y = r alongside, d2 = y' y ----
+  // ---- 5. lev, I - P on and below the diagonal, d2 = r' (I - P)^-1 r ----
   if (valid && lane == 0) {
-    const double* r = J + m * c;
-    double* y = T;
-    double lev = 0.0;
+    double lev = 0.0, d2;
     for (int i = 0; i < m; i++) lev += Pm[i * m + i];
     for (int i = 0; i < m; i++)
       for (int j = 0; j <= i; j++) Pm[i * m + j] = (i == j ? 1.0 : 0.0) - Pm[i * m + j];
-    bool ok = true;
-    double d2 = 0.0;
-    for (int j = 0; j < m && ok; j++) {
-      double s = Pm[j * m + j], t = r[j];
-      for (int k = 0; k < j; k++) { s -= Pm[j * m + k] * Pm[j * m + k]; t -= Pm[j * m + k] * y[k]; }
-      ok = s > kFgatePivotMin && s <= kFgateDblMax;                      // (false for NaN)
-      if (!ok) break;
-      const double l = sqrt(s);
-      Pm[j * m + j] = l;
-      y[j] = t / l;
-      d2 += y[j] * y[j];
-      for (int i = j + 1; i < m; i++) {
-        double u = Pm[i * m + j];
-        for (int k = 0; k < j; k++) u -= Pm[i * m + k] * Pm[j * m + k];
-        Pm[i * m + j] = u / l;
-      }
-    }
-    a.d2[e] = ok ? d2 : __builtin_nan("");
+    if (m == 3) chol_d2<3>(Pm, J + m * c, kFgatePivotMin, d2);           // (d2 = NaN at a pivot that fails)
+    else chol_d2<6>(Pm, J + m * c, kFgatePivotMin, d2);
+    a.d2[e] = d2;
     a.lev[e] = lev;
   }
 }

@@ -8,10 +8,8 @@
 //   Sigma_xx = Y_x' Y_x,  Sigma_ll = Y_l' Y_l,  Sigma_xl = Y_x' Y_l over the rows of the COMMON ancestors only,
 // so with Z_x = Y_x Jp', Z_l = Y_l Jl' (K x 3 each)
 //   S = I + Z_x' Z_x + Z_l' Z_l + (Z_x' Z_l + Z_l' Z_x over the common suffix).
-// The kernel adds z_x + z_l on the rows of the common suffix before it multiplies -- the same four products, (z_x + z_l)(z_x + z_l)', with
-// the cancellation between a pose and a landmark it is strongly correlated with taken in the 3-vectors instead of in their squares.
-// Rows of two different non-common fronts can sit at the same strip index (strips are end-aligned), so the two strips are NOT added
-// row by row ahead of the product: that would count cross terms of fronts the two paths do not share.
+// strip_gram3 (pps_gate_dev.h) evaluates this per strip row, and says why the sum z_x + z_l comes before the product on the common suffix
+// and why the strips are not added row by row.
 #pragma once
 #include "pps_cov.h"
 

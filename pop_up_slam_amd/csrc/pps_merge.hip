@@ -2,29 +2,29 @@
 // of plane nodes, the best partner per plane and the pairs below a threshold, from the strips k_cov_path (pps_cov.hip) has just written
 // for the listed planes.  pps_merge.h has the algebra.
 //
-// One wave per pair, kMergeWaves pairs per workgroup, the grid over the linear pair index ((i, j) ascending, i < j):
-//   1. lanes 0 .. 12 evaluate the plane-prior residual by the device functions K1 runs for a Plane3d_Factor (perturb3 with the device's
-//      step quaternions, res_plane_prior, whiten with the identity): lane 0 r(a | pi_b) at the estimate, lanes 1 .. 6 the six (+) / (-)
-//      steps of a against pi_b, lanes 7 .. 12 the six of b against pi_a.  The column differences go through LDS.  The "measurement" of
-//      a pair is the other plane's estimate normalised like Plane3d(Vector4d) (normalize4), as pps_add_plane_prior would store it.  This
-//      file is compiled without contraction like pps_k1_lanes.hip and pps_gate.hip: the bits are those of pps_eval_factor's lane form.
-//      The Jacobians are central differences whatever the handle's jacobian_mode.
+// One wave per pair, kMergeWaves pairs per workgroup, the grid over the linear pair index ((i, j) ascending, i < j).  Steps 1, 3, 4 and the
+// scan of 5 are the shared device functions of pps_gate_dev.h, which state their operation orders:
+//   1. lanes 0 .. 12 evaluate the plane-prior residual by the device functions K1 runs for a Plane3d_Factor (eval_plane_prior, whitened
+//      with the identity): lane 0 r(a | pi_b) at the estimate, lanes 1 .. 6 the six (+) / (-) steps of a against pi_b, lanes 7 .. 12
+//      the six of b against pi_a.  The column differences go through LDS.  The "measurement" of a pair is the other plane's estimate
+//      normalised like Plane3d(Vector4d) (normalize4), as pps_add_plane_prior would store it.  This file is compiled without contraction
+//      like pps_k1_lanes.hip and pps_gate.hip: the bits are those of pps_eval_factor's lane form.  The Jacobians are central differences
+//      whatever the handle's jacobian_mode.
 //   2. the pivots the two root paths have in common, from the parent table and the per-front root lengths: the front with the longer
 //      path steps to its parent until the two meet (same front; one an ancestor of the other; disjoint subtrees -- or no common root).
-//   3. lanes over the strip rows, counted from the strips' END (row K - 1 - j in lane j % 64, j ascending): the products of a lane and
-//      the order they are added in depend on the pair alone, not on K -- not on which other planes are in the call.  Rows of common
-//      ancestors add (z_a + z_b)(z_a + z_b)', all other rows z_a z_a' + z_b z_b' (pps_gate.hip on why the sum comes first).
-//   4. the 64 partial sums of an entry are added in lane order by one lane, then one lane factors the 3 x 3 S and solves.  A pivot that
+//   3. strip_gram3<3, 3>: lanes over the strip rows, counted from the strips' END, so that a pair's sums do not depend on which other
+//      planes are in the call.  Rows of common ancestors add (z_a + z_b)(z_a + z_b)', all other rows z_a z_a' + z_b z_b'.
+//   4. lane_order_sum per entry, then one lane adds floor_var to the diagonal and solves: chol_d2<3> with pivot floor 0.  A pivot that
 //      is not positive or not finite gives d2 = NaN and flag 2 for that pair alone: no status is raised.
 //   5. the wave writes d2 twice ((i, j) and (j, i): exactly symmetric), the pair's flag byte, and takes a ticket of row i and of row j;
-//      the wave that draws a row's last ticket scans the row for the smallest finite off-diagonal d2 (the barriers stay workgroup-wide).
-//      The flags are indexed by the linear pair index, which IS the (i, j) order: the host reads the thresholded pairs off them in
-//      order -- no atomic orders anything.
+//      the wave that draws a row's last ticket scans the row's off-diagonal d2 (best_scan_thread over its lanes, best_scan_final in
+//      lane 0; the barriers stay workgroup-wide).  The flags are indexed by the linear pair index, which IS the (i, j) order: the host
+//      reads the thresholded pairs off them in order -- no atomic orders anything.
 // Plain fp64 multiply-add loops: 3 + 3 columns against 3 rows of J over a few hundred strip rows is no MFMA shape.
 #include <hip/hip_runtime.h>
 
 #include "pps_merge.h"
-#include "pps_k1_body.h"
+#include "pps_gate_dev.h"
 
 namespace pps {
 
@@ -32,17 +32,11 @@ namespace {
 
 constexpr int kMergeThreads = 64 * kMergeWaves;
 constexpr int kMergeEvals = 13;                  // the nominal residual + 2 x 3 steps of a + 2 x 3 steps of b
-constexpr double kMergeStatusInternal = 64.0;    // = kStatusInternal
-constexpr double kMergeDblMax = 1.79769313486231570e308;
 // dynamic LDS, in doubles: the 13 evaluations per wave | the records [J_a 3 x 3 | J_b 3 x 3 | e 3] | partial sums [wave][entry][lane] | S entries |
 // the rows a wave has to scan (2 ints per wave)
 constexpr int kMergeLdsY = 0, kMergeLdsJ = kMergeLdsY + kMergeWaves * kMergeEvals * 3, kMergeLdsRed = kMergeLdsJ + kMergeWaves * 24,
               kMergeLdsS = kMergeLdsRed + kMergeWaves * 6 * 64, kMergeLdsRow = kMergeLdsS + kMergeWaves * 8, kMergeLdsDoubles = kMergeLdsRow + kMergeWaves;
 
-__device__ __forceinline__ void merge_raise(double* w, double v) {     // the status word is raised, never overwritten (pps_cov.hip)
-  atomicMax(reinterpret_cast<unsigned long long*>(w), (unsigned long long)__double_as_longlong(v));
-}
-__device__ __forceinline__ bool merge_pivot_ok(double p) { return p > 0.0 && p <= kMergeDblMax; }     // positive and finite (false for NaN)
 __device__ __forceinline__ long long merge_row_start(long long i, long long n) { return i * n - i * (i + 1) / 2; }
 
 __global__ __launch_bounds__(kMergeThreads) void k_merge_gate(DevGraph d, MergeArgs a) {
@@ -93,7 +87,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_gate(DevGraph d, MergeA
         ok = common >= 0 && common <= (len_a < len_b ? len_a : len_b);
       }
     }
-    if (!ok) { if (lane == 0) merge_raise(a.status, kMergeStatusInternal); valid = false; }
+    if (!ok) { if (lane == 0) raise_status(a.status, kStatusInternal); valid = false; }
   }
   // ---- 1. e, J_a, J_b at the estimate ----
   if (valid && lane < kMergeEvals) {
@@ -108,14 +102,10 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_gate(DevGraph d, MergeA
     const int q = t >> 1;
     const double sgn = (t & 1) ? -1.0 : 1.0;
     const double sw[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0};    // identity, packed upper triangle
-    double base[4], ms[4], lp[4], e[3], y[3];
+    double base[4], ms[4], y[3];
 #pragma unroll
     for (int k = 0; k < 4; k++) { base[k] = on_a ? pa[k] : pb[k]; ms[k] = on_a ? mb[k] : ma[k]; }
-    perturb3(base, q, sgn, d.step_ac, lp);
-#pragma unroll
-    for (int k = 0; k < 4; k++) lp[k] = q < 3 ? lp[k] : base[k];
-    res_plane_prior(lp, ms, e);
-    whiten<3>(sw, e, y);
+    eval_plane_prior(base, ms, sw, q, sgn, d.step_ac, y);
 #pragma unroll
     for (int r = 0; r < 3; r++) yb[lane * 3 + r] = y[r];
   }
@@ -139,82 +129,24 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_gate(DevGraph d, MergeA
     double Ja[9], Jb[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) { Ja[k] = J[k]; Jb[k] = J[9 + k]; }
-    const double* __restrict__ Ya = a.Y + ca.strip;
-    const double* __restrict__ Yb = a.Y + cb.strip;
-    const int len = len_a > len_b ? len_a : len_b;
-    for (int j = lane; j < len; j += 64) {
-      const size_t k = (size_t)(a.K - 1 - j);
-      double za[3] = {0.0, 0.0, 0.0}, zb[3] = {0.0, 0.0, 0.0};
-      if (j < len_a) {
-        double y[3];
-#pragma unroll
-        for (int q = 0; q < 3; q++) y[q] = Ya[k * 3 + q];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-          double t = 0.0;
-#pragma unroll
-          for (int q = 0; q < 3; q++) t += Ja[i * 3 + q] * y[q];
-          za[i] = t;
-        }
-      }
-      if (j < len_b) {
-        double y[3];
-#pragma unroll
-        for (int q = 0; q < 3; q++) y[q] = Yb[k * 3 + q];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-          double t = 0.0;
-#pragma unroll
-          for (int q = 0; q < 3; q++) t += Jb[i * 3 + q] * y[q];
-          zb[i] = t;
-        }
-      }
-      // a row of a front both paths pass through carries all four products = (z_a + z_b)(z_a + z_b)': added BEFORE they are multiplied.
-      // Rows of fronts the paths do not share keep their two squares apart (no cross term exists there, whatever sits at the same index).
-      const bool cross = j < common;
-      const double z[3] = {za[0] + zb[0], za[1] + zb[1], za[2] + zb[2]};
-      int e = 0;
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int jj = 0; jj <= i; jj++, e++) s[e] += cross ? z[i] * z[jj] : za[i] * za[jj] + zb[i] * zb[jj];
-    }
+    strip_gram3<3, 3>(Ja, Jb, a.Y + ca.strip, a.Y + cb.strip, len_a, len_b, common, a.K, lane, s);
   }
 #pragma unroll
   for (int e = 0; e < 6; e++) red[e * 64 + lane] = s[e];
   __syncthreads();
   // ---- 4. one fixed order of additions per entry, then the 3 x 3 Cholesky solve ----
-  if (lane < 6) {
-    double t = 0.0;
-    for (int k = 0; k < 64; k++) t += red[lane * 64 + k];
-    Sw[lane] = t;
-  }
+  if (lane < 6) Sw[lane] = lane_order_sum(red + lane * 64);
   __syncthreads();
   if (lane == 0) {
     rows[0] = rows[1] = -1;
     if (valid) {
-      const double S00 = Sw[0] + a.floor_var, S10 = Sw[1], S11 = Sw[2] + a.floor_var, S20 = Sw[3], S21 = Sw[4], S22 = Sw[5] + a.floor_var;
-      const double r0 = J[18], r1 = J[19], r2 = J[20];
-      double d2 = __builtin_nan("");
-      bool pd = false;
-      if (merge_pivot_ok(S00)) {
-        const double l00 = sqrt(S00), l10 = S10 / l00, l20 = S20 / l00;
-        const double p1 = S11 - l10 * l10;
-        if (merge_pivot_ok(p1)) {
-          const double l11 = sqrt(p1), l21 = (S21 - l20 * l10) / l11;
-          const double p2 = S22 - l20 * l20 - l21 * l21;
-          if (merge_pivot_ok(p2)) {
-            const double l22 = sqrt(p2);
-            const double y0 = r0 / l00, y1 = (r1 - l10 * y0) / l11, y2 = (r2 - l20 * y0 - l21 * y1) / l22;
-            d2 = y0 * y0 + y1 * y1 + y2 * y2;
-            pd = true;
-          }
-        }
-      }
+      const double S[9] = {Sw[0] + a.floor_var, 0.0, 0.0, Sw[1], Sw[2] + a.floor_var, 0.0, Sw[3], Sw[4], Sw[5] + a.floor_var};
+      double d2;
+      const bool pd = chol_d2<3>(S, J + 18, 0.0, d2);
       // ---- 5. publish, take the two tickets: the wave that draws a row's last one picks the row's best partner ----
       __hip_atomic_store(&a.d2[(size_t)pi * a.n + pj], d2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&a.d2[(size_t)pj * a.n + pi], d2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      a.flag[p] = !pd ? (unsigned char)2 : (fabs(d2) <= kMergeDblMax && d2 < a.threshold) ? (unsigned char)1 : (unsigned char)0;
+      a.flag[p] = !pd ? (unsigned char)2 : (is_finite(d2) && d2 < a.threshold) ? (unsigned char)1 : (unsigned char)0;
       __threadfence();
       if (atomicAdd(&a.ticket[pi], 1u) == (unsigned int)(a.n - 2)) rows[0] = pi;
       if (atomicAdd(&a.ticket[pj], 1u) == (unsigned int)(a.n - 2)) rows[1] = pj;
@@ -222,27 +154,18 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_gate(DevGraph d, MergeA
     }
   }
   __syncthreads();
-  // smallest finite off-diagonal d2 of a row, the first column on ties (a NaN or an infinity never becomes the best): ascending columns per
-  // lane with strict <, the 64 candidates compared in lane order by one lane.  (every wave passes the barriers; few have a row)
+  // the best partner of a row: its off-diagonal d2 per lane, the 64 candidates in lane order by one lane.  (every wave passes the
+  // barriers; few have a row)
   for (int h = 0; h < 2; h++) {
     const int r = rows[h];
     int bi = -1;
     double bv = 0.0;
-    if (r >= 0)
-      for (int k = lane; k < a.n; k += 64) {
-        if (k == r) continue;
-        const double v = __hip_atomic_load(&a.d2[(size_t)r * a.n + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (fabs(v) <= kMergeDblMax && (bi < 0 || v < bv)) { bi = k; bv = v; }
-      }
+    if (r >= 0) best_scan_thread(a.d2 + (size_t)r * a.n, a.n, r, lane, 64, bi, bv);
     int* __restrict__ ri = reinterpret_cast<int*>(red + 64);
     red[lane] = bv; ri[lane] = bi;
     __syncthreads();
     if (r >= 0 && lane == 0) {
-      for (int k = 1; k < 64; k++) {
-        const int ki = ri[k];
-        const double kv = red[k];
-        if (ki >= 0 && (bi < 0 || kv < bv || (kv == bv && ki < bi))) { bi = ki; bv = kv; }
-      }
+      bi = best_scan_final(red, ri, 64, bi, bv);
       a.best[r] = bi;
       a.d2[(size_t)r * a.n + r] = 0.0;
       a.ticket[r] = 0u;

@@ -19,7 +19,7 @@ def _emu_lib(fused):
     MFMA accumulates with fused multiply-adds like the hardware"""
     src = os.path.join(ROOT, "tests", "cpp", "front_emu.cpp")
     out = os.path.join(ROOT, "tests", "cpp", "libfront_emu_fma.so" if fused else "libfront_emu.so")
-    deps = [src, os.path.join(ROOT, "tests", "cpp", "wave_emu.h")] + [os.path.join(ROOT, "pop_up_slam_amd", "csrc", h) for h in ("pps_front_reg.h", "pps_regtile.h")]
+    deps = [src, os.path.join(ROOT, "tests", "cpp", "wave_emu.h")] + [os.path.join(ROOT, "pop_up_slam_amd", "csrc", h) for h in ("pps_front_reg.h", "pps_regtile.h", "pps_status.h")]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
         fp = ["-mfma", "-ffp-contract=fast"] if fused else ["-ffp-contract=off"]
         subprocess.check_call(["g++", "-O2" if fused else "-O1", "-std=c++17", "-fPIC", "-shared", "-Wno-psabi", "-Wno-unknown-pragmas"] + fp +
