@@ -358,11 +358,11 @@ static int cov_read_status(pps_graph* g, bool pass, const char* who, const char*
 static int cov_run(pps_graph* g, CovPass what) {
   int rc;
   if (!g->analyzed || g->analysis_stale) { rc = pps_analyze(g); if (rc != PPS_OK) return rc; }
-  if (what == CovPass::Select) what = g->use_band && g->cov_select_form == 0 ? CovPass::BandLevels : CovPass::DenseFronts;
-  if (what == CovPass::BandLevels && !g->use_band)
+  if (what == CovPass::Select) what = g->use_band() && g->cov_select_form == 0 ? CovPass::BandLevels : CovPass::DenseFronts;
+  if (what == CovPass::BandLevels && !g->use_band())
     return fail(g, PPS_ESTATE, "covariance recovery is limited to graphs whose fronts all fit the wave-per-front kernels (max front " +
                                std::to_string(g->an.max_front) + " scalars here: loop-closure graphs in the dense-front form are not supported)");
-  if (!g->use_band && !g->use_dense)
+  if (!g->use_band() && !g->use_dense())
     return fail(g, PPS_ESTATE, "pps_cov_factor: the graph is solved by the one-launch-per-level LDS kernels (max front " + std::to_string(g->an.max_front) +
                                " scalars, neither the band nor the dense-front form), whose panels do not pass through the factor array: no factor to keep");
   rc = prepare_solve(g); if (rc != PPS_OK) return rc;

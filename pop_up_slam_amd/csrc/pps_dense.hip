@@ -28,6 +28,7 @@ namespace pps {
 namespace {
 
 constexpr int kMaxPiv = 64;            // pivots per front (AnalysisParams::max_pivots <= 64)
+static_assert(kMaxPiv == kDenseMaxPivots, "plan_k3 (pps_k3_plan.h) sends a graph to these kernels by this figure");
 constexpr int kLdA = kMaxPiv + 1;
 
 

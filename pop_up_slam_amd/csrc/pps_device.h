@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "pps_cost.h"
+#include "pps_k3_plan.h"
 
 namespace pps {
 
@@ -122,7 +123,7 @@ struct Switches {
   bool no_dual = false;             // PPS_NO_DUAL: the one-step-at-a-time LM loop
   bool no_early_record = false;     // PPS_NO_EARLY_RECORD: the trial blocks of k_trial_lin publish their partial sums and the result record behind release
                                     // fences, which write the sweep's output back from the L2 first (the record then leaves when the sweep has ended)
-  bool lm_plain_host = false;       // PPS_LM_PLAIN_HOST: the dual LM loop does all of a trial's host work (trace, counters, launch geometry) between the
+  bool lm_plain_host = false;       // PPS_LM_PLAIN_HOST: the dual LM loop does all of a trial's host bookkeeping (trace, counters) between the
                                     // record's arrival and the factor launch, as it did before that stretch was cleared
   bool no_strip = false;            // PPS_NO_STRIP: fronts of 65 .. 80 rows through the LDS-tile path
   bool no_incremental = false;      // PPS_NO_INCREMENTAL: every analysis from scratch
@@ -205,29 +206,21 @@ struct DualAlt {
   unsigned int* ticket;
   double lambda;
 };
-// the whole tree in one factor launch + one back-substitution launch (k_band_factor_all / k_band_solve_all: hand-over between workgroups through
-// DevGraph::k3_flag); epoch: the number of this launch pair (> 0, growing)
-hipError_t launch_band_all(const DevGraph& d, const DualAlt* alt, int n_groups, int nwaves_factor, int nwaves_solve, int max_front, int max_panel,
-                           int max_group_fronts, double lambda, int epoch, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-// ... and in pieces: the launch geometry, fixed per analysis (band_all_plan makes the attribute check as well), and one function per launch
-struct BandAllPlan { int n_groups, nw_factor, nw_solve, pwf, pws, max_group_fronts; size_t lds_factor, lds_solve; };
-hipError_t band_all_plan(int n_groups, int nwaves_factor, int nwaves_solve, int max_front, int max_panel, int max_group_fronts, BandAllPlan* p);
-hipError_t launch_band_all_factor(const DevGraph& d, const DualAlt* alt, const BandAllPlan& p, double lambda, int epoch, hipStream_t st,
+// The launchers below launch by the K3Plan of the analysis (pps_k3_plan.h); what they still choose is what only the run knows -- a trace buffer, a second
+// damping value.  ensure_k3_attrs: the dynamic-LDS attribute of every K3 kernel, once per device -- called where a solve begins, not by the launchers.
+hipError_t ensure_k3_attrs();
+// one band stage; pre_ok = false: the plain walk even where the stage fits the pre-assembling one (the factorisation on its own: profiled solves, covariances)
+hipError_t launch_band_factor(const DevGraph& d, const DualAlt* alt, const K3StagePlan& sp, double lambda, hipStream_t st, hipEvent_t ev0 = nullptr,
+                              hipEvent_t ev1 = nullptr, bool pre_ok = true);      // ev0 / ev1: the dispatch's start / stop (profiling level 1)
+hipError_t launch_band_solve(const DevGraph& d, const DualAlt* alt, const K3StagePlan& sp, hipStream_t st);
+// the last factor stage and the first back-substitution stage as one launch, where p.root.fusable
+hipError_t launch_band_root(const DevGraph& d, const DualAlt* alt, const K3Plan& p, double lambda, hipStream_t st, hipEvent_t ev0 = nullptr,
+                            hipEvent_t ev1 = nullptr);
+// the whole tree in one factor launch + one back-substitution launch (p.form == K3Form::BandAll; k_band_factor_all / k_band_solve_all: hand-over
+// between workgroups through DevGraph::k3_flag); epoch: the number of this launch pair (> 0, growing)
+hipError_t launch_band_all_factor(const DevGraph& d, const DualAlt* alt, const K3Plan& p, double lambda, int epoch, hipStream_t st,
                                   hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-hipError_t launch_band_all_solve(const DevGraph& d, const DualAlt* alt, const BandAllPlan& p, int epoch, hipStream_t st);
-int band_all_solve_waves(int max_panel, int max_group_fronts);
-// pre: every group of the stage has the shape the pre-assembling walk needs (k_band_factor_pre)
-hipError_t launch_band_factor(const DevGraph& d, int grp_begin, int grp_count, int nwaves, int max_front, double lambda, hipStream_t st,
-                              hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, bool pre = false);
-hipError_t launch_band_solve(const DevGraph& d, int grp_begin, int grp_count, int nwaves, int max_panel, int max_group_fronts, hipStream_t st,
-                             const DualAlt* alt = nullptr);
-hipError_t launch_band_factor_dual(const DevGraph& d, const DualAlt& alt, int grp_begin, int grp_count, int nwaves, int max_front, double lambda,
-                                   hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, bool pre = false);
-// the last factor stage and the first back-substitution stage as one launch, where band_root_fusable says so
-bool band_root_fusable(const DevGraph& d, int grp_count, int max_front);
-hipError_t launch_band_root(const DevGraph& d, const DualAlt* alt, int grp, int nwaves_factor, int nwaves_solve, int max_front, int max_panel,
-                            int max_group_fronts, double lambda, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,      // ev0 / ev1: the dispatch's start / stop (profiling level 1)
-                            bool pre = false);                                                                                          // pre: the group fits the pre-assembling walk (stage_pre)
+hipError_t launch_band_all_solve(const DevGraph& d, const DualAlt* alt, const K3Plan& p, int epoch, hipStream_t st);
 // both trials of a dual solve: out_k <- base (+) delta_k, chi2 and |delta|^2 of each into its own result record
 hipError_t launch_trial_dual(const DevGraph& d, const DualAlt& alt, const double* base_pose, const double* base_plane, double* out_pose0,
                              double* out_plane0, double* out_pose1, double* out_plane1, double* host_result0, double seq0, double* host_result1,
@@ -248,14 +241,9 @@ hipError_t launch_expand_ea(const DevGraph& d, int n_fronts, double* zero, size_
 // blk_dst must be filled with -1 beforehand
 hipError_t launch_expand_el(const DevGraph& d, int n_asm, hipStream_t st);
 hipError_t launch_expand_lists(const DevGraph& d, int n_fronts, int n_asm, double* zero, size_t n_zero, hipStream_t st);   // both + the zero fill, one launch
-int band_max_rows();
 bool band_level_solve_direct_ok(int p, int b);   // a front whose level back-substitution may load L_B straight into registers (kb_level_solve)
-size_t band_solve_lds_bytes(int max_panel);      // max_panel = largest (f+1)*p of the stage
-int band_front_limit();                         // largest front (scalars, without rhs row) of the band kernels
 int debug_front_factor(int tiles, int strip, int p, int b, const double* A_host, double* L_host, double* U_host, double* not_pd);   // pps_debug_front_factor
 int debug_exmap(int kind, int n, const double* x_host, const double* delta_host, double* out_host);   // pps_debug_exmap (pps_k4.hip)
-int band_reg_rows();                            // fronts up to this many rows (incl. rhs) take the register-resident path
-size_t band_lds_bytes(int max_front, bool reg_only_kernel = false);   // LDS bytes one wave needs for the factor kernel
 // est <- lin ; lin <- lin (+) delta          (LM trial: Optimizer.cpp:414-416)
 hipError_t launch_retract_trial(const DevGraph& d, hipStream_t st);
 // est <- lin (+) delta                        (GN step: Optimizer.cpp:183)

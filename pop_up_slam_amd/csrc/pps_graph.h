@@ -4,6 +4,7 @@
 //   pps_upload.cpp   compaction + symbolic analysis, device arenas, difference upload, state / measurement transfers
 //   pps_solve.cpp    pps_update (Optimizer::relinearize), pps_batch_optimize (Optimizer::levenberg_marquardt), chi2
 //   pps_multi.cpp    pps_multi: G graphs per launch, lockstep LM rounds
+//   pps_k3_plan.h    how K3 is launched on an analysis (plan_k3 -> K3Plan: form, waves, LDS of every launch): host only, no HIP
 //   pps_lm.h         the LM rule the loops of pps_solve.cpp and pps_multi.cpp share (accept / reject / stop, lambda schedule, trace, counters): host only, no HIP
 //   pps_frames.cpp   registered frames (measurement refresh on the device), data association, point re-projection
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
@@ -55,6 +56,16 @@ struct HostFactor {
   double ray[6]; // K^-1 (u,v,1) of the two ground-edge end points
 };
 
+// what plan_k3 / band_group_fits_pre read of an analysis (pps_k3_plan.h)
+inline pps::BandTreeView k3_tree_view(const pps::Analysis& A) {
+  pps::BandTreeView v;
+  v.n_stages = A.n_stages; v.n_groups = A.n_groups; v.n_levels = A.n_levels; v.n_fronts = A.n_fronts; v.band_levels = A.band_levels;
+  v.stage_grp_off = A.stage_grp_off.data(); v.grp_lvl_off = A.grp_lvl_off.data(); v.glvl_front_off = A.glvl_front_off.data(); v.glvl_fronts = A.glvl_fronts.data();
+  v.stage_max_front = A.stage_max_front.data(); v.stage_max_width = A.stage_max_width.data(); v.f_p = A.f_p.data(); v.f_b = A.f_b.data(); v.f_level = A.f_level.data();
+  v.level_off = A.level_off.data(); v.level_fronts = A.level_fronts.data(); v.f_el_off = A.f_el_off.data();
+  return v;
+}
+
 inline double now_s() {
   using namespace std::chrono;
   return duration_cast<duration<double>>(steady_clock::now().time_since_epoch()).count();
@@ -98,16 +109,11 @@ struct pps_graph {
   pps::AnalysisCache* acache = nullptr;   // what the last analysis left for the next one (frame loops)
   std::vector<int> pose_ids, plane_ids;   // slot -> node id
   std::vector<int> fslot_ids[4];          // per type: slot -> factor id
-  std::vector<int> level_max_front;
-  bool use_band = false;                  // wave-per-front band kernels (fronts <= 127 rows)
-  bool use_dense = false;                 // dense-front kernels (pps_dense.hip) when the band kernels do not apply
-  std::vector<int> level_max_b;           // widest boundary per level
-  int max_el_per_front = 0;
-  // dense-front work lists: per level a prefix sum over its fronts (count+1 entries at level_off[l] + l)
-  std::vector<int> dw_asm, dw_pan, dw_trl;
-  int *d_dw_asm = nullptr, *d_dw_pan = nullptr, *d_dw_trl = nullptr;
-  std::vector<int> stage_max_piv, stage_nw_factor, stage_nw_solve, stage_max_grp_fronts, stage_max_panel;
-  std::vector<char> stage_pre;      // every group of the stage fits the pre-assembling walk of k_band_factor_pre
+  // how K3 is launched on this analysis (pps_k3_plan.h): the form, the geometry of every launch, the dense-front work lists
+  pps::K3Plan plan;
+  bool use_band() const { return plan.band(); }                           // wave-per-front band kernels (fronts <= 127 rows)
+  bool use_dense() const { return plan.form == pps::K3Form::Dense; }      // dense-front kernels (pps_dense.hip) when the band kernels do not apply
+  int *d_dw_asm = nullptr, *d_dw_pan = nullptr, *d_dw_trl = nullptr;      // device copies of plan.dw_*
   // device
   bool dev_ready = false;
   hipStream_t stream = nullptr;
@@ -165,10 +171,7 @@ struct pps_graph {
   // the spare set of J / P / H / Hf that the fused trial + linearisation launch writes (SpecLin, pps_device.h); when LM accepts the trial it was
   // made for, the set trades places with dev.J / P / H / Hf by pointer.  Null where the dual LM loop does not apply (no band schedule).
   double *spec_J = nullptr, *spec_P = nullptr, *spec_H = nullptr, *spec_Hf = nullptr;
-  // the whole tree in one factor launch + one back-substitution launch (run_analysis decides; launch_band_all): maxima over the stages, and the
-  // number of the last launch pair (its hand-over flags carry it: DevGraph::k3_flag)
-  bool k3_all = false;
-  int k3_nw_factor = 0, k3_nw_solve = 0, k3_max_front = 0, k3_max_panel = 0, k3_max_grp = 0, k3_epoch = 0;
+  int k3_epoch = 0;                // number of the last whole-tree launch pair (its hand-over flags carry it: DevGraph::k3_flag)
   double *snap_pose = nullptr, *snap_plane = nullptr;   // pps_save_state
   int snap_version = -1, upload_version = 0;
   int k2t_version = -1;              // upload_version the class lists of K2's throughput form (dev.k2t) were built for

@@ -25,11 +25,10 @@ namespace pps {
 // Cholesky.cpp:94-97) -> extend-add children update matrices -> right-looking elimination of the
 // p pivot columns -> store factor panel and update matrix.
 // ------------------------------------------------------------------------------------------
-constexpr int kLdsLimitBytes = 160 * 1024 - 1024;
 
 int lds_front_limit() {
   int fa = 1;
-  while ((size_t)(fa + 1) * ((fa + 1) | 1) * 8 <= (size_t)kLdsLimitBytes) fa++;
+  while ((size_t)(fa + 1) * ((fa + 1) | 1) * 8 <= (size_t)kLdsLaunchCeilingBytes) fa++;
   return fa - 1;   // largest f with (f+1) rows
 }
 
@@ -123,12 +122,12 @@ hipError_t launch_factor_level(const DevGraph& d, int level_begin, int level_cou
   if (level_count == 0) return hipSuccess;
   const int fa = level_max_front + 1;
   const size_t bytes = (size_t)fa * (fa | 1) * 8;
-  if (bytes <= (size_t)kLdsLimitBytes) {
+  if (bytes <= (size_t)kLdsLaunchCeilingBytes) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (!g_attr_set[dev & 63]) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_front_factor<true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLaunchCeilingBytes);
       if (e != hipSuccess) return e;
       g_attr_set[dev & 63] = true;
     }
@@ -148,7 +147,7 @@ hipError_t launch_factor_level(const DevGraph& d, int level_begin, int level_cou
 // elimination needs no barrier at all: column k is scaled, written back and re-read as LDS
 // broadcasts by the same wave, in program order.
 // ------------------------------------------------------------------------------------------
-constexpr int kBandMaxRows = 128;   // rows per front including the rhs row
+static_assert(kPlanRegRows == kRegRows && kPlanRegRowsMax == kRegRowsMax && kPlanP8Stride == kP8Stride, "pps_k3_plan.h sizes the LDS of these kernels");
 
 // One workgroup per front: row i of its (b+1)-row packed update matrix goes to row cmap[i] of the parent.
 // The launch also clears what an upload needs cleared -- the zeroed block behind delta (tickets, result records, partial sums) and
@@ -246,19 +245,6 @@ hipError_t launch_expand_ea(const DevGraph& d, int n_fronts, double* zero, size_
   return hipGetLastError();
 }
 
-int band_front_limit() { return kBandMaxRows - 1; }
-bool band_level_solve_direct_ok(int p, int b);
-int band_reg_rows() { return kRegRows; }
-int band_max_rows() { return kBandMaxRows; }
-// LDS of one wave in the factor kernels.  Register-only kernels (every front of the stage <= 64 rows; the level kernels): the packed
-// triangle, whose first 64 x kP8Stride doubles double as the panel buffer once the tiles are loaded (the triangle is dead from then
-// on), and one spare double at the end (where masked-off items of a scatter-add land).  The other kernels (LDS strip, fifth tile
-// row, LDS-tile path): triangle | spare | panel buffer of 80 rows.
-size_t band_lds_bytes(int max_front, bool reg_only_kernel) {
-  const size_t fa = (size_t)max_front + 1, ntri = fa * (fa + 1) / 2;
-  const size_t n = reg_only_kernel ? std::max<size_t>(ntri, (size_t)kRegRows * kP8Stride) + 1 : ntri + 1 + (size_t)kRegRowsMax * kP8Stride;
-  return ((n + 1) & ~size_t(1)) * sizeof(double);      // (an even number of doubles: every wave's triangle starts 16-byte aligned)
-}
 // One row of 16x16 tiles (I, J = o, o+16, ..., I) of the trailing lower triangle gets its rank-nb
 // update C -= P_I P_J^T: all LDS reads are issued unconditionally from clamped (always valid)
 // addresses and masked by selects afterwards, so the NT tiles' loads overlap; then NT back-to-back
@@ -951,14 +937,24 @@ __device__ __forceinline__ void body_band_solve(const DevGraph& d, int g, int ld
   }
 }
 
+// blockIdx.y = 1 of a dual launch: the second damping value's buffers (RESULT: and its status record; the barrier back-substitution raises none)
+// (k_band_factor<>, k_band_root<>, k_band_factor_all, k_band_solve_all and the kb_band_* kernels keep the swap written out: through a helper their
+// code objects come out a few instructions different -- tools/kernel_resources.py, code bytes and scalar spills -- and no kernel is to change here)
+template <bool RESULT = true>
+__device__ __forceinline__ void take_alt(DevGraph& d, const DualAlt& a) {
+  if (blockIdx.y) { d.L = a.L; d.U = a.U; d.delta = a.delta; if (RESULT) d.result_dev = a.result_dev; }
+}
+__device__ __forceinline__ void take_alt(DevGraph& d, const DualAlt& a, double& lambda) {
+  if (blockIdx.y) { d.L = a.L; d.U = a.U; d.delta = a.delta; d.result_dev = a.result_dev; lambda = a.lambda; }
+}
 __global__ __launch_bounds__(512) void k_band_solve(DevGraph d, DualAlt alt, int grp_begin, int lds_doubles_per_wave) {
   extern __shared__ double lds[];
-  if (blockIdx.y) { d.L = alt.L; d.U = alt.U; d.delta = alt.delta; }
+  take_alt<false>(d, alt);
   body_band_solve(d, grp_begin + blockIdx.x, lds_doubles_per_wave, lds);
 }
 __global__ __launch_bounds__(768) void k_band_solve_flow(DevGraph d, DualAlt alt, int grp_begin, int lds_doubles_per_wave, int mg) {
   extern __shared__ double lds[];
-  if (blockIdx.y) { d.L = alt.L; d.U = alt.U; d.delta = alt.delta; d.result_dev = alt.result_dev; }
+  take_alt(d, alt);
   body_band_solve_flow(d, grp_begin + blockIdx.x, lds_doubles_per_wave, lds, mg);
 }
 __global__ __launch_bounds__(768) void k_band_solve_flow_trace(DevGraph d, int grp_begin, int lds_doubles_per_wave, int mg) {     // PPS_TRACE=2
@@ -1043,7 +1039,7 @@ __device__ __forceinline__ int front_orig_entries_sized(const DevGraph& d, int r
 // group's top front raises its flag behind its update matrix
 template <bool XG = false>
 __device__ __forceinline__ void body_band_factor_pre(const DevGraph& d, int g, double lambda, int lds_doubles_per_wave, double* __restrict__ lds, const XGroup* xg = nullptr) {
-  // (the host has checked the shape of every group of the stage: stage_pre in pps_upload.cpp.  Few values stay live across the levels:
+  // (the host has checked the shape of every group of the stage: band_group_fits_pre, pps_k3_plan.h.  Few values stay live across the levels:
   // this kernel's register allocation is at its limit, see body_band_factor)
   const int wave = uni(threadIdx.x >> 6), lane = threadIdx.x & 63, nw = uni(blockDim.x >> 6);
   const int4 ga = reinterpret_cast<const int4*>(d.grp_span)[2 * (size_t)g], gb = reinterpret_cast<const int4*>(d.grp_span)[2 * (size_t)g + 1];
@@ -1102,7 +1098,7 @@ __global__ __launch_bounds__(512) void k_band_factor(DevGraph d, DualAlt alt, in
 // The root stage of a tree whose top is ONE group of register-resident fronts (C2: the root front), factored and solved by one launch:
 // the workgroup that has eliminated the top fronts walks back down them.  L and the forward-solved rhs rows reach the back-substitution
 // through the CU's own cache behind the workgroup barrier that ends the last level of the factorisation.
-// PRE: the group has the shape of the pre-assembling walk (stage_pre); FLOW: the walk back down as a data flow (a top group of several
+// PRE: the group has the shape of the pre-assembling walk (K3StagePlan::pre); FLOW: the walk back down as a data flow (a top group of several
 // fronts: 4 + 2 + 1 when the tree is banded three levels per launch), mg = fronts of the group.
 template <bool PRE, bool FLOW>
 __global__ __launch_bounds__(512) void k_band_root(DevGraph d, DualAlt alt, int grp, double lambda, int per_wave_factor, int per_wave_solve, int mg) {
@@ -1132,7 +1128,7 @@ __global__ __launch_bounds__(768) void k_band_solve_all(DevGraph d, DualAlt alt,
 
 __global__ __launch_bounds__(512) void k_band_factor_pre(DevGraph d, DualAlt alt, int grp_begin, double lambda, int lds_doubles_per_wave) {
   extern __shared__ double lds[];
-  if (blockIdx.y) { d.L = alt.L; d.U = alt.U; d.delta = alt.delta; d.result_dev = alt.result_dev; lambda = alt.lambda; }
+  take_alt(d, alt, lambda);
   body_band_factor_pre(d, grp_begin + blockIdx.x, lambda, lds_doubles_per_wave, lds);
 }
 
@@ -1147,163 +1143,64 @@ __global__ __launch_bounds__(512) void k_band_factor_lean_trace(DevGraph d, Dual
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_band_factor_r5(DevGraph d, DualAlt alt, int grp_begin, double lambda, int lds_doubles_per_wave) {
   extern __shared__ double lds[];
-  if (blockIdx.y) { d.L = alt.L; d.U = alt.U; d.delta = alt.delta; d.result_dev = alt.result_dev; lambda = alt.lambda; }
+  take_alt(d, alt, lambda);
   body_band_factor<true, true, false, true>(d, grp_begin + blockIdx.x, lambda, lds_doubles_per_wave, lds);
 }
 
-static std::atomic<bool> g_band_attr_set[64];   // per device ordinal
+// ---- launchers of the band kernels ----
+// The geometry of every launch -- waves, doubles per wave, dynamic LDS -- is the K3Plan of the analysis (pps_k3_plan.h).  A launcher picks the
+// kernel by what only the run knows: a trace buffer, a second damping value (alt: blockIdx.y = 0 / 1).  The dynamic-LDS attribute of the
+// kernels is set where a solve begins (ensure_k3_attrs), not here.
+static inline DualAlt alt_arg(const DualAlt* alt) { return alt ? *alt : DualAlt{}; }
 
-static hipError_t ensure_band_attrs() {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!g_band_attr_set[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_factor<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_factor<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_solve), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_solve_trace), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_solve_flow), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_factor_pre), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_solve_flow_trace), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_factor_r5), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_factor_lean_trace), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_root<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_root<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_root<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_root<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_factor_all), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_solve_all), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e != hipSuccess) return e;
-    g_band_attr_set[dev & 63] = true;
-  }
-  return hipSuccess;
-}
-
-// one launcher for both: ny = 1 (alt unused) or 2 (dual)
-static hipError_t launch_band_factor_impl(const DevGraph& d, const DualAlt& alt, int ny, int grp_begin, int grp_count, int nwaves, int max_front, double lambda,
-                                          hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, bool pre = false) {
-  if (grp_count == 0) return hipSuccess;
-  { const hipError_t e = ensure_band_attrs(); if (e != hipSuccess) return e; }
-  const bool reg_only = max_front + 1 <= kRegRows && !(ny == 2 && d.trace != nullptr);     // (a traced dual solve runs the general kernel)
-  const int per_wave = (int)(band_lds_bytes(max_front, reg_only) / sizeof(double));
-  const size_t bytes = (size_t)per_wave * nwaves * sizeof(double);
-  if (reg_only && d.trace != nullptr)      // phase trace of the register-only kernel
-    PPS_LAUNCH(k_band_factor_lean_trace, dim3(grp_count, ny), dim3(64 * nwaves), bytes, st, d, alt, grp_begin, lambda, per_wave);
-  else if (reg_only && pre)
-    PPS_LAUNCH_EV(ev0, ev1, k_band_factor_pre, dim3(grp_count, ny), dim3(64 * nwaves), bytes, st, d, alt, grp_begin, lambda, per_wave);
-  else if (reg_only)
-    PPS_LAUNCH_EV(ev0, ev1, k_band_factor<true>, dim3(grp_count, ny), dim3(64 * nwaves), bytes, st, d, alt, grp_begin, lambda, per_wave);
-  else if (max_front + 1 <= kRegRowsMax && d.trace == nullptr && !d.no_strip) {
-    const int nw5 = nwaves < 4 ? nwaves : 4;                // (one wave per SIMD: see k_band_factor_r5)
-    PPS_LAUNCH_EV(ev0, ev1, k_band_factor_r5, dim3(grp_count, ny), dim3(64 * nw5), (size_t)per_wave * nw5 * sizeof(double), st, d, alt, grp_begin, lambda, per_wave);
-  } else
-    PPS_LAUNCH_EV(ev0, ev1, k_band_factor<false>, dim3(grp_count, ny), dim3(64 * nwaves), bytes, st, d, alt, grp_begin, lambda, per_wave);
+hipError_t launch_band_factor(const DevGraph& d, const DualAlt* alt, const K3StagePlan& sp, double lambda, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
+                              bool pre_ok) {
+  if (sp.grp_count == 0) return hipSuccess;
+  // the register-only family (its phase trace compiled into a kernel of its own; a traced dual solve runs the general kernel), the fifteen-tile kernel, the general one
+  const bool reg = sp.reg_only && !(alt && d.trace != nullptr), r5 = !reg && sp.r5_ok;
+  const auto kernel = reg ? (d.trace != nullptr ? &k_band_factor_lean_trace : sp.pre && pre_ok ? &k_band_factor_pre : &k_band_factor<true>)
+                          : (r5 ? &k_band_factor_r5 : &k_band_factor<false>);
+  PPS_LAUNCH_EV(ev0, ev1, kernel, dim3(sp.grp_count, alt ? 2 : 1), dim3(64 * (r5 ? sp.nw_factor_r5 : sp.nw_factor)),
+                reg ? sp.lds_factor_reg : r5 ? sp.lds_factor_r5 : sp.lds_factor_gen, st, d, alt_arg(alt), sp.grp_begin, lambda, reg ? sp.pw_factor_reg : sp.pw_factor_gen);
   return hipGetLastError();
 }
 
-hipError_t launch_band_factor(const DevGraph& d, int grp_begin, int grp_count, int nwaves, int max_front, double lambda, hipStream_t st, hipEvent_t ev0,
-                              hipEvent_t ev1, bool pre) {
-  return launch_band_factor_impl(d, DualAlt{}, 1, grp_begin, grp_count, nwaves, max_front, lambda, st, ev0, ev1, pre);
-}
-
-hipError_t launch_band_factor_dual(const DevGraph& d, const DualAlt& alt, int grp_begin, int grp_count, int nwaves, int max_front, double lambda,
-                                   hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, bool pre) {
-  return launch_band_factor_impl(d, alt, 2, grp_begin, grp_count, nwaves, max_front, lambda, st, ev0, ev1, pre);
-}
-
-size_t band_solve_lds_bytes(int max_panel) { return (size_t)(kBandMaxRows + max_panel) * sizeof(double); }   // xb + the factor panel
-
-hipError_t launch_band_solve(const DevGraph& d, int grp_begin, int grp_count, int nwaves, int max_panel, int max_group_fronts, hipStream_t st,
-                             const DualAlt* alt) {
-  if (grp_count == 0) return hipSuccess;
-  // per wave: xb + the largest factor panel of the stage; per workgroup: one local solution vector per front of a group
-  const int per_wave = (int)(band_solve_lds_bytes(max_panel) / sizeof(double));
-  { const hipError_t e = ensure_band_attrs(); if (e != hipSuccess) return e; }
-  const size_t bytes = ((size_t)per_wave * nwaves + (size_t)max_group_fronts * kBandMaxRows) * sizeof(double);
-  const bool no_flow = (d.sw & SW_NO_SOLVE_FLOW) != 0;
-  if (!no_flow && !(d.trace != nullptr && d.trace_solve && alt) && max_group_fronts > 1) {
-    // data-flow form: up to twelve waves (three per SIMD), as many as the group has fronts and the LDS holds
-    const size_t fixed = ((size_t)max_group_fronts * kBandMaxRows + (size_t)(max_group_fronts + 1) / 2) * sizeof(double);
-    const size_t room = (size_t)kLdsLimitBytes > fixed ? ((size_t)kLdsLimitBytes - fixed) / ((size_t)per_wave * sizeof(double)) : 0;
-    const int nwf = (int)std::min<size_t>(std::min<size_t>(12, (size_t)max_group_fronts), room);
-    if (nwf >= 1) {
-      if (d.trace != nullptr && d.trace_solve)
-        PPS_LAUNCH(k_band_solve_flow_trace, dim3(grp_count), dim3(64 * nwf), (size_t)per_wave * nwf * sizeof(double) + fixed, st, d, grp_begin, per_wave, max_group_fronts);
-      else
-        PPS_LAUNCH(k_band_solve_flow, dim3(grp_count, alt ? 2 : 1), dim3(64 * nwf), (size_t)per_wave * nwf * sizeof(double) + fixed, st, d, alt ? *alt : DualAlt{}, grp_begin,
-                   per_wave, max_group_fronts);
-      return hipGetLastError();
-    }
+hipError_t launch_band_solve(const DevGraph& d, const DualAlt* alt, const K3StagePlan& sp, hipStream_t st) {
+  if (sp.grp_count == 0) return hipSuccess;
+  const bool trace = d.trace != nullptr && d.trace_solve;
+  const dim3 grid(sp.grp_count, alt ? 2 : 1);
+  if (sp.nw_flow > 0 && !(trace && alt)) {                               // (the traced kernels take one damping value)
+    if (trace) PPS_LAUNCH(k_band_solve_flow_trace, dim3(sp.grp_count), dim3(64 * sp.nw_flow), sp.lds_flow, st, d, sp.grp_begin, sp.pw_solve, sp.max_grp_fronts);
+    else PPS_LAUNCH(k_band_solve_flow, grid, dim3(64 * sp.nw_flow), sp.lds_flow, st, d, alt_arg(alt), sp.grp_begin, sp.pw_solve, sp.max_grp_fronts);
   }
-  if (d.trace != nullptr && d.trace_solve && !alt) PPS_LAUNCH(k_band_solve_trace, dim3(grp_count), dim3(64 * nwaves), bytes, st, d, grp_begin, per_wave);
-  else PPS_LAUNCH(k_band_solve, dim3(grp_count, alt ? 2 : 1), dim3(64 * nwaves), bytes, st, d, alt ? *alt : DualAlt{}, grp_begin, per_wave);
+  else if (trace && !alt) PPS_LAUNCH(k_band_solve_trace, dim3(sp.grp_count), dim3(64 * sp.nw_solve), sp.lds_solve, st, d, sp.grp_begin, sp.pw_solve);
+  else PPS_LAUNCH(k_band_solve, grid, dim3(64 * sp.nw_solve), sp.lds_solve, st, d, alt_arg(alt), sp.grp_begin, sp.pw_solve);
   return hipGetLastError();
 }
 
-// the root stage as one launch (k_band_root): one group, every front register-resident, no trace
-bool band_root_fusable(const DevGraph& d, int grp_count, int max_front) {
-  const bool off = (d.sw & SW_NO_ROOT_FUSE) != 0;
-  return !off && grp_count == 1 && max_front + 1 <= kRegRows && d.trace == nullptr;
-}
-hipError_t launch_band_root(const DevGraph& d, const DualAlt* alt, int grp, int nwaves_factor, int nwaves_solve, int max_front, int max_panel,
-                            int max_group_fronts, double lambda, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, bool pre) {
-  { const hipError_t e = ensure_band_attrs(); if (e != hipSuccess) return e; }
-  const int pwf = (int)(band_lds_bytes(max_front, true) / sizeof(double)), pws = (int)(band_solve_lds_bytes(max_panel) / sizeof(double));
-  // the walk back down: as a data flow when the group has more than one front and the LDS holds a wave per front (at most eight here)
-  const size_t flow_fixed = ((size_t)max_group_fronts * kBandMaxRows + (size_t)(max_group_fronts + 1) / 2) * sizeof(double);
-  int nw = nwaves_factor > nwaves_solve ? nwaves_factor : nwaves_solve;
-  bool flow = !(d.sw & SW_NO_SOLVE_FLOW) && max_group_fronts > 1;
-  if (flow) {
-    const int want = nwaves_factor > (max_group_fronts < 8 ? max_group_fronts : 8) ? nwaves_factor : (max_group_fronts < 8 ? max_group_fronts : 8);
-    if ((size_t)pws * want * sizeof(double) + flow_fixed <= (size_t)kLdsLimitBytes) nw = want; else flow = false;
-  }
-  const size_t bf = (size_t)pwf * nw * sizeof(double);
-  const size_t bs = flow ? (size_t)pws * nw * sizeof(double) + flow_fixed : ((size_t)pws * nw + (size_t)max_group_fronts * kBandMaxRows) * sizeof(double);
-  const size_t bytes = bf > bs ? bf : bs;
-  const DualAlt a2 = alt ? *alt : DualAlt{};
-  if (pre && flow) PPS_LAUNCH_EV(ev0, ev1, (k_band_root<true, true>), dim3(1, alt ? 2 : 1), dim3(64 * nw), bytes, st, d, a2, grp, lambda, pwf, pws, max_group_fronts);
-  else if (pre) PPS_LAUNCH_EV(ev0, ev1, (k_band_root<true, false>), dim3(1, alt ? 2 : 1), dim3(64 * nw), bytes, st, d, a2, grp, lambda, pwf, pws, max_group_fronts);
-  else if (flow) PPS_LAUNCH_EV(ev0, ev1, (k_band_root<false, true>), dim3(1, alt ? 2 : 1), dim3(64 * nw), bytes, st, d, a2, grp, lambda, pwf, pws, max_group_fronts);
-  else PPS_LAUNCH_EV(ev0, ev1, (k_band_root<false, false>), dim3(1, alt ? 2 : 1), dim3(64 * nw), bytes, st, d, a2, grp, lambda, pwf, pws, max_group_fronts);
+// the root stage as one launch (k_band_root), where K3Plan::root says fusable
+hipError_t launch_band_root(const DevGraph& d, const DualAlt* alt, const K3Plan& p, double lambda, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+  const K3RootPlan& r = p.root;
+  const int grp = p.stages.back().grp_begin;
+  const dim3 grid(1, alt ? 2 : 1), block(64 * r.nw);
+  const DualAlt a2 = alt_arg(alt);
+  const auto kernel = r.pre ? (r.flow ? &k_band_root<true, true> : &k_band_root<true, false>) : (r.flow ? &k_band_root<false, true> : &k_band_root<false, false>);
+  PPS_LAUNCH_EV(ev0, ev1, kernel, grid, block, r.lds, st, d, a2, grp, lambda, r.pw_factor, r.pw_solve, r.max_grp_fronts);
   return hipGetLastError();
 }
 
-// the whole tree: one factor launch + one back-substitution launch (k_band_factor_all / k_band_solve_all)
-// nwaves_factor / max_front / max_panel / max_group_fronts: maxima over the stages; epoch: number of this launch pair (> 0, never repeated)
-hipError_t launch_band_all(const DevGraph& d, const DualAlt* alt, int n_groups, int nwaves_factor, int nwaves_solve, int max_front, int max_panel,
-                           int max_group_fronts, double lambda, int epoch, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-  BandAllPlan p;
-  { const hipError_t e = band_all_plan(n_groups, nwaves_factor, nwaves_solve, max_front, max_panel, max_group_fronts, &p); if (e != hipSuccess) return e; }
-  { const hipError_t e = launch_band_all_factor(d, alt, p, lambda, epoch, st, ev0, ev1); if (e != hipSuccess) return e; }
-  return launch_band_all_solve(d, alt, p, epoch, st);
-}
-// The same in pieces, for a caller that launches the pair many times over one analysis and has the first launch waiting for a verdict (the dual
-// LM loop): the geometry and the attribute check once, then nothing but the two launches.
-hipError_t band_all_plan(int n_groups, int nwaves_factor, int nwaves_solve, int max_front, int max_panel, int max_group_fronts, BandAllPlan* p) {
-  { const hipError_t e = ensure_band_attrs(); if (e != hipSuccess) return e; }
-  p->n_groups = n_groups; p->nw_factor = nwaves_factor; p->nw_solve = nwaves_solve; p->max_group_fronts = max_group_fronts;
-  p->pwf = (int)(band_lds_bytes(max_front, true) / sizeof(double)); p->pws = (int)(band_solve_lds_bytes(max_panel) / sizeof(double));
-  p->lds_factor = (size_t)p->pwf * nwaves_factor * sizeof(double);
-  const size_t fixed = ((size_t)max_group_fronts * kBandMaxRows + (size_t)(max_group_fronts + 1) / 2) * sizeof(double);
-  p->lds_solve = (size_t)p->pws * nwaves_solve * sizeof(double) + fixed;
-  return hipSuccess;
-}
-hipError_t launch_band_all_factor(const DevGraph& d, const DualAlt* alt, const BandAllPlan& p, double lambda, int epoch, hipStream_t st, hipEvent_t ev0,
+// the whole tree: one factor launch + one back-substitution launch (k_band_factor_all / k_band_solve_all); epoch: number of this launch
+// pair (> 0, never repeated)
+hipError_t launch_band_all_factor(const DevGraph& d, const DualAlt* alt, const K3Plan& p, double lambda, int epoch, hipStream_t st, hipEvent_t ev0,
                                   hipEvent_t ev1) {
-  const DualAlt a2 = alt ? *alt : DualAlt{};
-  PPS_LAUNCH_EV(ev0, ev1, k_band_factor_all, dim3(p.n_groups, alt ? 2 : 1), dim3(64 * p.nw_factor), p.lds_factor, st, d, a2, lambda, p.pwf, epoch);
+  const K3AllPlan& a = p.all;
+  PPS_LAUNCH_EV(ev0, ev1, k_band_factor_all, dim3(a.n_groups, alt ? 2 : 1), dim3(64 * a.nw_factor), a.lds_factor, st, d, alt_arg(alt), lambda, a.pw_factor, epoch);
   return hipGetLastError();
 }
-hipError_t launch_band_all_solve(const DevGraph& d, const DualAlt* alt, const BandAllPlan& p, int epoch, hipStream_t st) {
-  const DualAlt a2 = alt ? *alt : DualAlt{};
-  PPS_LAUNCH(k_band_solve_all, dim3(p.n_groups, alt ? 2 : 1), dim3(64 * p.nw_solve), p.lds_solve, st, d, a2, p.n_groups, p.pws, p.max_group_fronts, epoch);
+hipError_t launch_band_all_solve(const DevGraph& d, const DualAlt* alt, const K3Plan& p, int epoch, hipStream_t st) {
+  const K3AllPlan& a = p.all;
+  PPS_LAUNCH(k_band_solve_all, dim3(a.n_groups, alt ? 2 : 1), dim3(64 * a.nw_solve), a.lds_solve, st, d, alt_arg(alt), a.n_groups, a.pw_solve, a.max_grp_fronts, epoch);
   return hipGetLastError();
-}
-// waves of the data-flow back-substitution of such a launch (0: the LDS does not hold a group): as launch_band_solve picks them per stage
-int band_all_solve_waves(int max_panel, int max_group_fronts) {
-  const size_t per_wave = band_solve_lds_bytes(max_panel);
-  const size_t fixed = ((size_t)max_group_fronts * kBandMaxRows + (size_t)(max_group_fronts + 1) / 2) * sizeof(double);
-  const size_t room = (size_t)kLdsLimitBytes > fixed ? ((size_t)kLdsLimitBytes - fixed) / per_wave : 0;
-  return (int)std::min<size_t>(std::min<size_t>(12, (size_t)max_group_fronts), room);
 }
 
 // Back-substitution for one level (parents already solved): x_p = L_A^-T (y - L_B^T x_b).
@@ -1543,31 +1440,33 @@ __global__ __launch_bounds__(256) void kb_level_solve(BatchArgs a, int level, in
   wave_front_solve<false>(d2, rec, W, nullptr, 0);
 }
 
-// level-per-launch kernels: the packed triangle of a front of <= 16 nt rows (+ rhs), whose head doubles as the 8-column panel buffer, + the spare double
 bool band_level_solve_direct_ok(int p, int b) { return level_solve_direct_ok(p, b); }
-static int level_lds_doubles(int nt) {
-  const size_t fa = (size_t)16 * nt + 1, n = std::max<size_t>(fa * (fa + 1) / 2, (size_t)kRegRows * kP8Stride) + 1;
-  return (int)((n + 1) & ~size_t(1));
-}
 
-static std::atomic<bool> g_batch_attr_set[64];
-
-hipError_t launch_batch_solve(const BatchArgs& a, const BatchGeom& g, hipStream_t st, hipEvent_t after_factor) {
+// Every kernel above that is launched with dynamic LDS may ask for the launch ceiling.  Once per device; called where a solve begins
+// (prepare_solve, launch_batch_solve), never between two launches of one.
+hipError_t ensure_k3_attrs() {
+  static std::atomic<bool> done[64];       // per device ordinal (idempotent set-up: a race only repeats it)
+  static const void* const kernels[] = {
+      (const void*)&k_band_factor<false>, (const void*)&k_band_factor<true>, (const void*)&k_band_factor_pre, (const void*)&k_band_factor_r5,
+      (const void*)&k_band_factor_lean_trace, (const void*)&k_band_solve, (const void*)&k_band_solve_trace, (const void*)&k_band_solve_flow,
+      (const void*)&k_band_solve_flow_trace, (const void*)&k_band_root<false, false>, (const void*)&k_band_root<true, false>,
+      (const void*)&k_band_root<false, true>, (const void*)&k_band_root<true, true>, (const void*)&k_band_factor_all, (const void*)&k_band_solve_all,
+      (const void*)&kb_band_factor<false>, (const void*)&kb_band_factor<true>, (const void*)&kb_band_factor_pre, (const void*)&kb_band_solve,
+      (const void*)&kb_band_solve_flow, (const void*)&kb_level_factor2, (const void*)&kb_level_factor3, (const void*)&kb_level_factor4,
+      (const void*)&kb_level_solve};
   int dev = 0;
   (void)hipGetDevice(&dev);
-  if (!g_batch_attr_set[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kb_band_factor<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kb_band_factor<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kb_band_solve), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kb_band_solve_flow), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kb_band_factor_pre), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kb_level_factor2), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kb_level_factor3), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kb_level_factor4), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kb_level_solve), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes);
+  if (done[dev & 63]) return hipSuccess;
+  for (const void* k : kernels) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLaunchCeilingBytes);
     if (e != hipSuccess) return e;
-    g_batch_attr_set[dev & 63] = true;
   }
+  done[dev & 63] = true;
+  return hipSuccess;
+}
+
+hipError_t launch_batch_solve(const BatchArgs& a, const BatchGeom& g, hipStream_t st, hipEvent_t after_factor) {
+  { const hipError_t e = ensure_k3_attrs(); if (e != hipSuccess) return e; }
   if (g.level_form) {
     const int nz = a.alt ? 2 : 1;
     for (int l = 0; l < g.n_levels; l++) {
@@ -1591,12 +1490,8 @@ hipError_t launch_batch_solve(const BatchArgs& a, const BatchGeom& g, hipStream_
     if (g.stage_groups[stg] <= 0) continue;
     const int per_wave = g.stage_per_wave_factor[stg], nw = g.stage_nw_factor[stg];
     const size_t bytes = (size_t)per_wave * nw * sizeof(double);
-    if (g.stage_reg_only[stg] && g.stage_pre[stg])
-      PPS_LAUNCH(kb_band_factor_pre, dim3(g.stage_groups[stg], a.n, a.alt ? 2 : 1), dim3(64 * nw), bytes, st, a, stg, per_wave);
-    else if (g.stage_reg_only[stg])
-      PPS_LAUNCH(kb_band_factor<true>, dim3(g.stage_groups[stg], a.n, a.alt ? 2 : 1), dim3(64 * nw), bytes, st, a, stg, per_wave);
-    else
-      PPS_LAUNCH(kb_band_factor<false>, dim3(g.stage_groups[stg], a.n, a.alt ? 2 : 1), dim3(64 * nw), bytes, st, a, stg, per_wave);
+    const auto kernel = !g.stage_reg_only[stg] ? &kb_band_factor<false> : g.stage_pre[stg] ? &kb_band_factor_pre : &kb_band_factor<true>;
+    PPS_LAUNCH(kernel, dim3(g.stage_groups[stg], a.n, a.alt ? 2 : 1), dim3(64 * nw), bytes, st, a, stg, per_wave);
   }
   if (after_factor) (void)hipEventRecord(after_factor, st);
   for (int stg = g.n_stages - 1; stg >= 0; stg--) {
@@ -1605,7 +1500,7 @@ hipError_t launch_batch_solve(const BatchArgs& a, const BatchGeom& g, hipStream_
     const size_t bytes = ((size_t)per_wave * nw + (size_t)g.stage_grp_fronts[stg] * kBandMaxRows) * sizeof(double);
     if (g.stage_nw_flow[stg] > 0) {
       const int nwf = g.stage_nw_flow[stg], mg = g.stage_grp_fronts[stg];
-      const size_t fb = ((size_t)per_wave * nwf + (size_t)mg * kBandMaxRows + (size_t)(mg + 1) / 2) * sizeof(double);
+      const size_t fb = (size_t)per_wave * nwf * sizeof(double) + band_flow_fixed_bytes(mg);
       PPS_LAUNCH(kb_band_solve_flow, dim3(g.stage_groups[stg], a.n, a.alt ? 2 : 1), dim3(64 * nwf), fb, st, a, stg, per_wave, mg);
       continue;
     }
@@ -1659,7 +1554,7 @@ int debug_front_factor(int tiles, int strip, int p, int b, const double* A_host,
     const size_t bytes = (size_t)per_wave * 8;
 #define PPS_DBG_FRONT(NT_, STRIP_)                                                                                                      \
     do {                                                                                                                                \
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_debug_front<NT_, STRIP_>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimitBytes); \
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_debug_front<NT_, STRIP_>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLaunchCeilingBytes); \
       if (e == hipSuccess) { hipLaunchKernelGGL((k_debug_front<NT_, STRIP_>), dim3(1), dim3(64), bytes, 0, d, p, b, A, per_wave); e = hipGetLastError(); } \
     } while (0)
     if (tiles == 5) PPS_DBG_FRONT(5, true);

@@ -180,7 +180,7 @@ static int check_graphs(pps_multi* m, int* mode_out, int* max_stages_out) {
     begin_solve(g);
     int rc = prepare_solve(g);
     if (rc != PPS_OK) return mfail(m, rc, "graph " + std::to_string(i) + ": " + g->err);
-    if (!g->use_band) return mfail(m, PPS_ESTATE, "graph " + std::to_string(i) + " has fronts beyond the wave-per-front kernels (loop closures): solve it through its own handle");
+    if (!g->use_band()) return mfail(m, PPS_ESTATE, "graph " + std::to_string(i) + " has fronts beyond the wave-per-front kernels (loop closures): solve it through its own handle");
     if (g->n_live_factors == 0) return mfail(m, PPS_ESTATE, "graph " + std::to_string(i) + " has no factors");
     if (robust(g)) return mfail(m, PPS_ESTATE, "graph " + std::to_string(i) + " has a robust cost function set (pps_set_cost_function); the batched solve has no robust kernels");
     if (g->props.jacobian_mode != mode) return mfail(m, PPS_EINVAL, "all graphs of a batch share one jacobian_mode");
@@ -259,7 +259,7 @@ static bool plan_chunks(const std::vector<pps_graph*>& gs, int max_stages, int n
   const int n_chunks = (G + CH - 1) / CH;
   plan->n_split = n_split; plan->CH = CH; plan->n_chunks = n_chunks;
   plan->geom.assign(n_chunks, BatchGeom{});
-  const size_t lds_budget = 150 * 1024;
+  const size_t lds_budget = kLdsPlanBudgetBytes;
   for (int c = 0; c < n_chunks; c++) {
     BatchGeom& q = plan->geom[c];
     q.n_stages = max_stages;
@@ -300,12 +300,12 @@ static bool plan_chunks(const std::vector<pps_graph*>& gs, int max_stages, int n
       }
       for (int stg = 0; stg < A.n_stages; stg++) {
         q.stage_groups[stg] = std::max(q.stage_groups[stg], A.stage_grp_off[stg + 1] - A.stage_grp_off[stg]);
-        q.stage_nw_factor[stg] = std::max(q.stage_nw_factor[stg], g->stage_nw_factor[stg]);
-        q.stage_nw_solve[stg] = std::max(q.stage_nw_solve[stg], g->stage_nw_solve[stg]);
+        q.stage_nw_factor[stg] = std::max(q.stage_nw_factor[stg], g->plan.stages[stg].nw_factor);
+        q.stage_nw_solve[stg] = std::max(q.stage_nw_solve[stg], g->plan.stages[stg].nw_solve);
         q.stage_per_wave_factor[stg] = std::max(q.stage_per_wave_factor[stg], A.stage_max_front[stg]);   // (max front for now: sized below)
         q.stage_max_front[stg] = std::max(q.stage_max_front[stg], A.stage_max_front[stg]);
-        max_panel[stg] = std::max(max_panel[stg], g->stage_max_panel[stg]);
-        q.stage_grp_fronts[stg] = std::max(q.stage_grp_fronts[stg], g->stage_max_grp_fronts[stg]);
+        max_panel[stg] = std::max(max_panel[stg], g->plan.stages[stg].max_panel);
+        q.stage_grp_fronts[stg] = std::max(q.stage_grp_fronts[stg], g->plan.stages[stg].max_grp_fronts);
         if (A.stage_max_front[stg] + 1 > band_reg_rows() || g->dev.trace) q.stage_reg_only[stg] = false;
       }
     }
@@ -321,7 +321,7 @@ static bool plan_chunks(const std::vector<pps_graph*>& gs, int max_stages, int n
       q.stage_per_wave_factor[stg] = (int)(band_lds_bytes(q.stage_per_wave_factor[stg], q.stage_reg_only[stg]) / sizeof(double));
       q.stage_per_wave_solve[stg] = (int)(band_solve_lds_bytes(max_panel[stg]) / sizeof(double));
       const size_t fw = (size_t)q.stage_per_wave_factor[stg] * sizeof(double), sv = (size_t)q.stage_per_wave_solve[stg] * sizeof(double);
-      const size_t xbytes = (size_t)q.stage_grp_fronts[stg] * band_max_rows() * sizeof(double);
+      const size_t xbytes = (size_t)q.stage_grp_fronts[stg] * kBandMaxRows * sizeof(double);
       if (fw > lds_budget || xbytes + sv > lds_budget) return false;
       q.stage_nw_factor[stg] = (int)std::max<size_t>(1, std::min<size_t>(q.stage_nw_factor[stg], lds_budget / fw));
       q.stage_nw_solve[stg] = (int)std::max<size_t>(1, std::min<size_t>(q.stage_nw_solve[stg], (lds_budget - xbytes) / sv));
@@ -354,31 +354,16 @@ static bool plan_chunks(const std::vector<pps_graph*>& gs, int max_stages, int n
       for (int i = c * CH; pre && i < std::min(G, (c + 1) * CH); i++) {
         const Analysis& A = gs[i]->an;
         if (stg >= A.n_stages) continue;
-        for (int gi = A.stage_grp_off[stg]; pre && gi < A.stage_grp_off[stg + 1]; gi++) {
-          const int l0 = A.grp_lvl_off[gi], nl = A.grp_lvl_off[gi + 1] - l0;
-          pre = nl >= 1 && nl <= 4;
-          int upper = 0, c0 = 0;
-          for (int k = 0; pre && k < nl; k++) {
-            const int cnt = A.glvl_front_off[l0 + k + 1] - A.glvl_front_off[l0 + k];
-            if (k == 0) c0 = cnt; else upper += cnt;
-          }
-          pre = pre && (c0 + upper <= nw || (nl >= 3 && c0 <= nw && upper <= nw));      // (shape B | shape A of body_band_factor_pre)
-        }
+        const BandTreeView v = k3_tree_view(A);
+        for (int gi = A.stage_grp_off[stg]; pre && gi < A.stage_grp_off[stg + 1]; gi++) pre = band_group_fits_pre(v, gi, nw);
       }
       q.stage_pre[stg] = pre;
       // data flow: as many waves as the largest group has fronts, at most twelve and what the LDS holds.  A stage whose groups were
       // narrowed to fill the device with groups (throughput: G = 32 and up) keeps the barrier form -- waves that spin on a flag hold
       // wave slots other groups could use (G = 32: 3.9 against 3.7 ms of back-substitution per batch solve)
       q.stage_nw_flow[stg] = 0;
-      if (!sw.no_solve_flow && q.stage_grp_fronts[stg] > 1 && q.stage_nw_solve[stg] >= std::min(8, q.stage_grp_fronts[stg])) {
-        const size_t per_wave = (size_t)q.stage_per_wave_solve[stg] * sizeof(double);
-        const size_t fixed = ((size_t)q.stage_grp_fronts[stg] * band_max_rows() + (size_t)(q.stage_grp_fronts[stg] + 1) / 2) * sizeof(double);
-        if (fixed + per_wave <= lds_budget) {
-          const int room = (int)((lds_budget - fixed) / per_wave);
-          int nwf = std::min(std::min(12, q.stage_grp_fronts[stg]), room);
-          q.stage_nw_flow[stg] = std::max(1, nwf);
-        }
-      }
+      if (!sw.no_solve_flow && q.stage_grp_fronts[stg] > 1 && q.stage_nw_solve[stg] >= std::min(8, q.stage_grp_fronts[stg]))
+        q.stage_nw_flow[stg] = band_flow_waves((size_t)q.stage_per_wave_solve[stg] * sizeof(double), q.stage_grp_fronts[stg], kFlowWaveCap, lds_budget);
     }
   }
   return true;

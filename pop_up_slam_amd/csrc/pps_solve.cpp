@@ -43,7 +43,7 @@ int do_linearize(pps_graph* g, const LinGuard* guard = nullptr) {
 
 // delta = (J'J + lambda diag(J'J))^-1 J'b  (Optimizer::compute_gauss_newton_step, Optimizer.cpp:49-67)
 // Factor stages leaves -> root, back-substitution stages root -> leaves, for one damping value (alt == nullptr) or two.  The root stage
-// is one launch for both directions where its fronts allow it (band_root_fusable).  events: the factor launches carry their own start /
+// is one launch for both directions where its fronts allow it (K3Plan::root).  events: the factor launches carry their own start /
 // stop events (profiling level 1; the fused root launch's pair spans its back-substitution as well).
 // the start / stop events of a factor launch (profiling level 1: resolve_k1_events sums the pairs into t_factor)
 static int take_factor_events(pps_graph* g, bool events, hipEvent_t* e0, hipEvent_t* e1) {
@@ -54,31 +54,29 @@ static int take_factor_events(pps_graph* g, bool events, hipEvent_t* e0, hipEven
   return PPS_OK;
 }
 
-static int enqueue_factor_solve(pps_graph* g, const DevGraph& dv, const DualAlt* alt, double lambda, hipStream_t st_, bool events) {
-  const Analysis& A = g->an;
-  if (g->k3_all) {                                                 // the whole tree: two launches (pps_k3.hip, XGroup)
-    hipEvent_t e0, e1;
+// first_launched: called once, behind the first launch (the dual LM loop does there what it kept off the stretch in front of that launch)
+struct NoHook { void operator()() const {} };
+template <class Hook = NoHook>
+static int enqueue_factor_solve(pps_graph* g, const DevGraph& dv, const DualAlt* alt, double lambda, hipStream_t st_, bool events, Hook first_launched = Hook()) {
+  const K3Plan& P = g->plan;
+  hipEvent_t e0, e1;
+  if (P.form == K3Form::BandAll) {                                 // the whole tree: two launches (pps_k3.hip, XGroup)
     { const int rc = take_factor_events(g, events, &e0, &e1); if (rc != PPS_OK) return rc; }
     g->k3_epoch = g->k3_epoch >= (1 << 30) ? 1 : g->k3_epoch + 1;
-    HIP_TRY(g, launch_band_all(dv, alt, A.n_groups, g->k3_nw_factor, g->k3_nw_solve, g->k3_max_front, g->k3_max_panel, g->k3_max_grp, lambda, g->k3_epoch, st_, e0, e1));
+    HIP_TRY(g, launch_band_all_factor(dv, alt, P, lambda, g->k3_epoch, st_, e0, e1));
+    first_launched();
+    HIP_TRY(g, launch_band_all_solve(dv, alt, P, g->k3_epoch, st_));
     return PPS_OK;
   }
-  const int top = A.n_stages - 1;
-  const bool fuse = top >= 0 && band_root_fusable(dv, A.stage_grp_off[top + 1] - A.stage_grp_off[top], A.stage_max_front[top]);
-  for (int st = 0; st < A.n_stages; st++) {
-    hipEvent_t e0, e1;
+  const int top = (int)P.stages.size() - 1;
+  const bool fuse = P.root.fusable;
+  for (int st = 0; st <= top; st++) {
     { const int rc = take_factor_events(g, events, &e0, &e1); if (rc != PPS_OK) return rc; }
-    const int g0 = A.stage_grp_off[st], ng = A.stage_grp_off[st + 1] - g0;
-    const bool pre = st < (int)g->stage_pre.size() && g->stage_pre[st] != 0;
-    if (fuse && st == top)
-      HIP_TRY(g, launch_band_root(dv, alt, g0, g->stage_nw_factor[st], g->stage_nw_solve[st], A.stage_max_front[st], g->stage_max_panel[st],
-                                  g->stage_max_grp_fronts[st], lambda, st_, e0, e1, pre));
-    else if (alt) HIP_TRY(g, launch_band_factor_dual(dv, *alt, g0, ng, g->stage_nw_factor[st], A.stage_max_front[st], lambda, st_, e0, e1, pre));
-    else HIP_TRY(g, launch_band_factor(dv, g0, ng, g->stage_nw_factor[st], A.stage_max_front[st], lambda, st_, e0, e1, pre));
+    if (fuse && st == top) HIP_TRY(g, launch_band_root(dv, alt, P, lambda, st_, e0, e1));
+    else HIP_TRY(g, launch_band_factor(dv, alt, P.stages[st], lambda, st_, e0, e1));
+    if (st == 0) first_launched();
   }
-  for (int st = fuse ? top - 1 : top; st >= 0; st--)
-    HIP_TRY(g, launch_band_solve(dv, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_solve[st],
-                                 g->stage_max_panel[st], g->stage_max_grp_fronts[st], st_, alt));
+  for (int st = fuse ? top - 1 : top; st >= 0; st--) HIP_TRY(g, launch_band_solve(dv, alt, P.stages[st], st_));
   return PPS_OK;
 }
 
@@ -89,24 +87,23 @@ int do_solve_on(pps_graph* g, const DevGraph& dv, double lambda, hipStream_t st_
 int enqueue_plain_factor(pps_graph* g, double lambda) {
   const Analysis& A = g->an;
   const DevGraph& d = g->dev;
-  if (g->use_band) {
-    for (int st = 0; st < A.n_stages; st++)
-      HIP_TRY(g, launch_band_factor(d, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_factor[st], A.stage_max_front[st], lambda, g->stream));
+  if (g->use_band()) {
+    for (const K3StagePlan& sp : g->plan.stages) HIP_TRY(g, launch_band_factor(d, nullptr, sp, lambda, g->stream, nullptr, nullptr, false));
     return PPS_OK;
   }
   HIP_TRY(g, hipMemsetAsync(d.L, 0, (size_t)A.L_size * 8, g->stream));
-  HIP_TRY(g, launch_dense_hpush(d, g->max_el_per_front, lambda, g->stream));
+  HIP_TRY(g, launch_dense_hpush(d, g->plan.max_el_per_front, lambda, g->stream));
   for (int l = 0; l < A.n_levels; l++) {
     const int base = A.level_off[l] + l, cnt = A.level_off[l + 1] - A.level_off[l];
-    HIP_TRY(g, launch_dense_factor_level(d, A.level_off[l], cnt, g->d_dw_asm + base, g->dw_asm[base + cnt], g->d_dw_pan + base, g->dw_pan[base + cnt],
-                                         g->d_dw_trl + base, g->dw_trl[base + cnt], g->stream));
+    HIP_TRY(g, launch_dense_factor_level(d, A.level_off[l], cnt, g->d_dw_asm + base, g->plan.dw_asm[base + cnt], g->d_dw_pan + base, g->plan.dw_pan[base + cnt],
+                                         g->d_dw_trl + base, g->plan.dw_trl[base + cnt], g->stream));
   }
   return PPS_OK;
 }
 
 int do_solve(pps_graph* g, double lambda) {
   const Analysis& A = g->an;
-  if (g->use_band) {
+  if (g->use_band()) {
     if (g->profiling < 2) {            // no per-phase timing
       int rc = do_solve_on(g, g->dev, lambda, g->stream);
       if (rc != PPS_OK) return rc;
@@ -119,14 +116,12 @@ int do_solve(pps_graph* g, double lambda) {
     }
     {
       PhaseTimer t(g, &g->stats.t_backsolve);
-      for (int st = A.n_stages - 1; st >= 0; st--)
-        HIP_TRY(g, launch_band_solve(g->dev, A.stage_grp_off[st], A.stage_grp_off[st + 1] - A.stage_grp_off[st], g->stage_nw_solve[st],
-                                     g->stage_max_panel[st], g->stage_max_grp_fronts[st], g->stream));
+      for (int st = A.n_stages - 1; st >= 0; st--) HIP_TRY(g, launch_band_solve(g->dev, nullptr, g->plan.stages[st], g->stream));
     }
     g->stats.n_factorize++;
     return PPS_OK;
   }
-  if (g->use_dense) {
+  if (g->use_dense()) {
     {
       PhaseTimer t(g, &g->stats.t_factor);
       const int rc = enqueue_plain_factor(g, lambda); if (rc != PPS_OK) return rc;
@@ -134,7 +129,7 @@ int do_solve(pps_graph* g, double lambda) {
     {
       PhaseTimer t(g, &g->stats.t_backsolve);
       for (int l = A.n_levels - 1; l >= 0; l--)
-        HIP_TRY(g, launch_dense_solve_level(g->dev, A.level_off[l], A.level_off[l + 1] - A.level_off[l], g->level_max_b[l], g->stream));
+        HIP_TRY(g, launch_dense_solve_level(g->dev, A.level_off[l], A.level_off[l + 1] - A.level_off[l], g->plan.level_max_b[l], g->stream));
     }
     g->stats.n_factorize++;
     return PPS_OK;
@@ -142,7 +137,7 @@ int do_solve(pps_graph* g, double lambda) {
   {
     PhaseTimer t(g, &g->stats.t_factor);
     for (int l = 0; l < A.n_levels; l++)
-      HIP_TRY(g, launch_factor_level(g->dev, A.level_off[l], A.level_off[l + 1] - A.level_off[l], g->level_max_front[l], lambda,
+      HIP_TRY(g, launch_factor_level(g->dev, A.level_off[l], A.level_off[l + 1] - A.level_off[l], g->plan.level_max_front[l], lambda,
                                      g->stream));
   }
   {
@@ -418,12 +413,9 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
   };
   // The stretch between a trial record's arrival and the factor launch it triggers is on the solve's critical path -- the device has nothing
   // queued behind K2 until that launch arrives -- so the host does there only what depends on the verdict: the rule (LmControl::decide), the
-  // pointer rotation, the launch.  The launch geometry of a whole-tree pair is worked out once per solve (BandAllPlan), and what the trial leaves
+  // pointer rotation, the launch.  The launch geometry of every form is worked out once per analysis (K3Plan), and what the trial leaves
   // in the trace and the counters (LmControl::note) is written behind the launch.  PPS_LM_PLAIN_HOST: everything in its old place.
   const bool plain_host = g->sw.lm_plain_host;
-  BandAllPlan plan{};
-  const bool planned = !plain_host && g->k3_all;
-  if (planned) HIP_TRY(g, band_all_plan(A.n_groups, g->k3_nw_factor, g->k3_nw_solve, g->k3_max_front, g->k3_max_panel, g->k3_max_grp, &plan));
   struct PendingNote {                   // the judged trial whose bookkeeping is still owed (written at the latest when the loop is left, however)
     const LmSink& s; LmControl::Trial t{}; bool owed = false;
     void flush() { if (owed) { LmControl::note(s, t); owed = false; } }
@@ -448,18 +440,10 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
     // false, the second record is never waited for)
     const int n_trials = use_alt ? 2 : 1;
     const double t_pre = lm_timing ? now_s() : 0.0;
-    if (planned) {
-      hipEvent_t e0, e1;
-      { const int rc2 = take_factor_events(g, g->profiling == 1, &e0, &e1); if (rc2 != PPS_OK) return rc2; }
-      g->k3_epoch = g->k3_epoch >= (1 << 30) ? 1 : g->k3_epoch + 1;
-      HIP_TRY(g, launch_band_all_factor(d, use_alt ? &alt : nullptr, plan, lam, g->k3_epoch, g->stream, e0, e1));
-      rt_note(t_pre);
-      pending.flush();
-      HIP_TRY(g, launch_band_all_solve(d, use_alt ? &alt : nullptr, plan, g->k3_epoch, g->stream));
-    } else {
-      const int rc2 = enqueue_factor_solve(g, d, use_alt ? &alt : nullptr, lam, g->stream, g->profiling == 1); if (rc2 != PPS_OK) return rc2;
-      rt_note(t_pre);                    // (this form's call covers all the launches of the factorisation and the walk back)
-      pending.flush();
+    {
+      // (timed: the host's work up to the first launch call | that call; the rest of the launch set is queued behind the bookkeeping)
+      const int rc2 = enqueue_factor_solve(g, d, use_alt ? &alt : nullptr, lam, g->stream, g->profiling == 1, [&] { rt_note(t_pre); pending.flush(); });
+      if (rc2 != PPS_OK) return rc2;
     }
     g->stats.n_factorize += n_trials;
     g->seq += 1.0; seqs[0] = g->seq;
@@ -553,7 +537,7 @@ static int lm_solve(pps_graph* g, int* iterations) {
   begin_solve(g);
   int rc = prepare_solve(g);
   if (rc != PPS_OK) return rc;
-  if (g->use_band && g->profiling < 2 && !g->dev.trace && !g->sw.no_dual && !robust(g)) return lm_solve_dual(g, iterations, t0);      // (PPS_NO_DUAL: the loop-forms parity test; a cost function: the robust kernels exist for this loop only)
+  if (g->use_band() && g->profiling < 2 && !g->dev.trace && !g->sw.no_dual && !robust(g)) return lm_solve_dual(g, iterations, t0);      // (PPS_NO_DUAL: the loop-forms parity test; a cost function: the robust kernels exist for this loop only)
   const pps_props& prop = g->props;
   if (!g->status_clean) HIP_TRY(g, launch_clear_status(g->dev, g->stream));
   g->status_clean = false;
@@ -616,9 +600,9 @@ static int debug_solve_impl(pps_graph* g, double lambda, double lambda2, double*
   int rc = prepare_solve(g);
   if (rc != PPS_OK) return rc;
   const bool dual = lambda2 >= 0.0;
-  if (dual && !(g->use_band && g->spec_L && g->spec_U && g->spec_delta && g->spec_result))
+  if (dual && !(g->use_band() && g->spec_L && g->spec_U && g->spec_delta && g->spec_result))
     return fail(g, PPS_ESTATE, "debug_solve: two damping values in one launch need the band kernels and their second L / U / delta set (this graph runs in another K3 form)");
-  if (form) *form = g->use_band ? (g->k3_all ? 1 : 0) : (g->use_dense ? 2 : 3);
+  if (form) *form = g->use_band() ? (g->plan.form == K3Form::BandAll ? 1 : 0) : (g->use_dense() ? 2 : 3);
   const DevGraph& d = g->dev;
   rc = clear_stale_status(g); if (rc != PPS_OK) return rc;
   rc = linpoint_from_estimate(g); if (rc != PPS_OK) return rc;

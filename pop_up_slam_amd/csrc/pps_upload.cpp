@@ -307,106 +307,9 @@ static int run_analysis_impl(pps_graph* g) {
     g->an = Analysis();
     return fail(g, PPS_ENOMEM, "symbolic analysis ran out of host memory (fronts too wide for this ordering)");
   }
-  g->level_max_front.assign(g->an.n_levels, 0);
-  for (int s = 0; s < g->an.n_fronts; s++) {
-    int& m = g->level_max_front[g->an.f_level[s]];
-    m = std::max(m, g->an.f_p[s] + g->an.f_b[s]);
-  }
-  {
-    const Analysis& A = g->an;
-    const int Bn = std::max(1, A.band_levels);
-    g->stage_max_piv.assign(A.n_stages, 1);
-    for (int s = 0; s < A.n_fronts; s++) { int& m = g->stage_max_piv[A.f_level[s] / Bn]; m = std::max(m, A.f_p[s]); }
-    int max_piv = 0;
-    for (int m : g->stage_max_piv) max_piv = std::max(max_piv, m);
-    g->use_band = A.max_front <= band_front_limit() && max_piv <= 64;
-    // the dense-front solve keeps a front's boundary values in LDS: 15 000 scalars is the ceiling (2-D loop-closure
-    // meshes such as torus10000 reach 24 540 under this chain-based dissection and are refused, see below)
-    g->use_dense = !g->use_band && max_piv <= dense_front_max_pivots() && A.max_front <= 15000;
-    g->level_max_b.assign(A.n_levels, 0);
-    g->max_el_per_front = 0;
-    for (int s = 0; s < A.n_fronts; s++) {
-      g->level_max_b[A.f_level[s]] = std::max(g->level_max_b[A.f_level[s]], A.f_b[s]);
-      g->max_el_per_front = std::max(g->max_el_per_front, A.f_el_off[s + 1] - A.f_el_off[s]);
-    }
-    g->dw_asm.clear(); g->dw_pan.clear(); g->dw_trl.clear();
-    if (g->use_dense)
-      for (int l = 0; l < A.n_levels; l++) {
-        int a = 0, pn = 0, t = 0;
-        g->dw_asm.push_back(0); g->dw_pan.push_back(0); g->dw_trl.push_back(0);
-        for (int k = A.level_off[l]; k < A.level_off[l + 1]; k++) {
-          const int s = A.level_fronts[k];
-          const int fa = A.f_p[s] + A.f_b[s] + 1, b1 = A.f_b[s] + 1;
-          const int T32 = (fa + 31) / 32, T64 = (b1 + 63) / 64;
-          a += T32 * ((A.f_p[s] + 31) / 32); pn += (fa - A.f_p[s] + 255) / 256; t += T64 * (T64 + 1) / 2;
-          g->dw_asm.push_back(a); g->dw_pan.push_back(pn); g->dw_trl.push_back(t);
-        }
-      }
-    g->stage_nw_factor.assign(A.n_stages, 1); g->stage_nw_solve.assign(A.n_stages, 1);
-    g->stage_max_grp_fronts.assign(A.n_stages, 1); g->stage_max_panel.assign(A.n_stages, 1);
-    for (int s = 0; s < A.n_fronts; s++) { int& m = g->stage_max_panel[A.f_level[s] / Bn]; m = std::max(m, (A.f_p[s] + A.f_b[s] + 1) * A.f_p[s]); }
-    const size_t lds_budget = 150 * 1024;
-    const int max_waves = 8;
-    for (int st = 0; st < A.n_stages; st++) {
-      int mg = 1;
-      for (int gi = A.stage_grp_off[st]; gi < A.stage_grp_off[st + 1]; gi++)
-        mg = std::max(mg, A.glvl_front_off[A.grp_lvl_off[gi + 1]] - A.glvl_front_off[A.grp_lvl_off[gi]]);
-      g->stage_max_grp_fronts[st] = mg;
-      // waves per group: one per front of its widest level -- or, when the whole group fits (4 + 2 + 1 on eight waves), one per front
-      // of the group: every upper front is then assembled ahead of its level by a wave of its own (body_band_factor_pre, shape B)
-      const bool reg_stage = A.stage_max_front[st] + 1 <= band_reg_rows() && g->sw.trace == 0;
-      const int want = std::max(1, std::min(max_waves, reg_stage && mg <= max_waves && !g->sw.no_preassemble ? mg : A.stage_max_width[st]));
-      g->stage_nw_factor[st] = (int)std::max<size_t>(1, std::min<size_t>(want, lds_budget / band_lds_bytes(A.stage_max_front[st], reg_stage)));
-      // per workgroup: one local solution vector per front of a group + per wave xb and the factor panel.  A group that does
-      // not fit (very wide elimination trees: hundreds of fronts in one band group) takes the graph off the band kernels.
-      const size_t xbytes = (size_t)mg * band_max_rows() * sizeof(double);
-      const size_t per_wave = band_solve_lds_bytes(g->stage_max_panel[st]);
-      if (xbytes + per_wave > lds_budget) { g->use_band = false; g->stage_nw_solve[st] = 1; continue; }
-      g->stage_nw_solve[st] = (int)std::max<size_t>(1, std::min<size_t>(want, (lds_budget - xbytes) / per_wave));
-    }
-    // k_band_factor_pre: every level in one round of the stage's waves, and either the whole group on waves of its own (shape B: 4 + 2 + 1
-    // on eight waves) or three to four local levels with the fronts of local levels 2 and up on waves that idle from level 1 on (shape A:
-    // 8 + 4 + 2 + 1 on eight waves, 4 + 2 + 1 <= 8) -- body_band_factor_pre tells the two apart the same way
-    g->stage_pre.assign(A.n_stages, 0);
-    if (!g->sw.no_preassemble)
-      for (int st = 0; st < A.n_stages; st++) {
-        bool ok = A.stage_grp_off[st + 1] > A.stage_grp_off[st] && A.stage_max_front[st] + 1 <= band_reg_rows();
-        const int nw = g->stage_nw_factor[st];
-        for (int gi = A.stage_grp_off[st]; ok && gi < A.stage_grp_off[st + 1]; gi++) {
-          const int l0 = A.grp_lvl_off[gi], nl = A.grp_lvl_off[gi + 1] - l0;
-          ok = nl >= 1 && nl <= 4;
-          int upper = 0, c0 = 0;
-          for (int k = 0; ok && k < nl; k++) {
-            const int c = A.glvl_front_off[l0 + k + 1] - A.glvl_front_off[l0 + k];
-            if (k == 0) c0 = c; else upper += c;
-          }
-          ok = ok && (c0 + upper <= nw || (nl >= 3 && c0 <= nw && upper <= nw));
-        }
-        g->stage_pre[st] = ok ? 1 : 0;
-      }
-    // The whole tree in one factor launch + one back-substitution launch (k_band_factor_all / k_band_solve_all, round 6): every stage takes the
-    // pre-assembling walk on register-resident fronts, the data-flow back-substitution holds a group of any stage, and the groups fit the chip
-    // a few times over -- a graph of thousands of groups (C3) keeps a launch per stage: its upper workgroups would sit on wave slots its leaves
-    // need.  Measured over corridor graphs of 500 .. 3 500 poses (tools/size_probe.py, same box, us per LM iteration, whole tree | a launch per
-    // band): 75 groups and fewer (up to 1 250 poses; C2 and every frame of C5: 73) 52.2 | 55.9, 56.5 | 57.3, 82.0 | 88.3; 127 groups and
-    // more 87.7 | 77.0, 81.4 | 71.0, 85.5 | 74.9, 140.8 | 110.2 (every group's top front releases at agent scope, every waiting group acquires:
-    // hundreds of L2 write-backs and invalidations inside one launch instead of one per band): at most 100 groups (it was 512).
-    g->k3_all = false;
-    if (g->use_band && A.n_stages >= 2 && g->sw.trace == 0 && !g->sw.no_preassemble && !g->sw.no_solve_flow && !g->sw.no_root_fuse && A.n_groups <= 100) {
-      bool ok = true;
-      int nwf = 1, mf = 0, mp = 1, mg = 1;
-      for (int st = 0; st < A.n_stages; st++) {
-        ok = ok && g->stage_pre[st] != 0 && A.stage_max_front[st] + 1 <= band_reg_rows();
-        nwf = std::max(nwf, g->stage_nw_factor[st]); mf = std::max(mf, A.stage_max_front[st]);
-        mp = std::max(mp, g->stage_max_panel[st]); mg = std::max(mg, g->stage_max_grp_fronts[st]);
-      }
-      const int nws = ok ? band_all_solve_waves(mp, mg) : 0;
-      ok = ok && mg > 1 && nws >= std::min(8, mg) && band_lds_bytes(mf, true) * (size_t)nwf <= lds_budget;
-      if (ok) { g->k3_all = true; g->k3_nw_factor = nwf; g->k3_nw_solve = nws; g->k3_max_front = mf; g->k3_max_panel = mp; g->k3_max_grp = mg; }
-    }
-    // (such a graph then runs on the level-per-launch kernels: its fronts are <= 127 rows by the use_band test above)
-  }
-  if (!g->use_band && !g->use_dense && g->an.max_front > 4096)
+  // how K3 runs on this tree -- band kernels per stage or whole tree, dense fronts, or a launch per level -- and the geometry of every launch
+  g->plan = plan_k3(k3_tree_view(g->an), K3Switches{g->sw.no_preassemble, g->sw.no_solve_flow, g->sw.no_root_fuse, g->sw.no_strip, g->sw.trace});
+  if (!g->use_band() && !g->use_dense() && g->an.max_front > 4096)
     return fail(g, PPS_ENOMEM, "fronts too wide for this ordering (max front " + std::to_string(g->an.max_front) +
                                " scalars): the pose chain is not a good dissection backbone for this graph");
   if (g->sw.analysis_timing) fprintf(stderr, "[analysis] %-22s %8.3f ms\n", "total incl. api", 1e3 * (now_s() - t0));
@@ -733,7 +636,7 @@ int upload_all(pps_graph* g) {
   TRY(dev_upload(g, &d.f_ea_off, A.f_ea_off, kF ? kF + 1 : 0)); TRY(dev_alloc(g, &d.ea_tgt, (size_t)std::max<int64_t>(1, A.ea_total)));   // filled by k_expand_ea below
   TRY(dev_upload(g, &d.blk_doff, A.blk_doff, kB ? kB + 1 : 0)); TRY(dev_alloc(g, &d.blk_dst, (size_t)std::max(1, A.blk_doff[A.n_blocks])));
   TRY(dev_alloc(g, &d.Hf, (size_t)A.el_total));
-  if (g->use_band && !g->sw.no_spec_lin) {                        // the spare set of the fused trial + linearisation launch (lm_solve_dual)
+  if (g->use_band() && !g->sw.no_spec_lin) {                        // the spare set of the fused trial + linearisation launch (lm_solve_dual)
     TRY(dev_alloc(g, &g->spec_J, (size_t)A.J_size)); TRY(dev_alloc(g, &g->spec_P, (size_t)std::max<int64_t>(1, A.P_size)));
     TRY(dev_alloc(g, &g->spec_H, (size_t)A.H_size)); TRY(dev_alloc(g, &g->spec_Hf, (size_t)A.el_total));
   }
@@ -754,7 +657,7 @@ int upload_all(pps_graph* g) {
   TRY(dev_upload(g, &d.frec, A.frec)); TRY(dev_upload(g, &d.crec, A.crec)); TRY(dev_upload(g, &d.srec, A.srec, 8 * kS));
   TRY(dev_upload(g, &d.obs_dir, A.obs_dir)); TRY(dev_upload(g, &d.nd_segs, A.nd_segs, (size_t)K.nd_segs)); d.n_nd_segs = (int)A.nd_segs.size();
   TRY(dev_upload(g, &d.cls_off, A.cls_off)); TRY(dev_upload(g, &d.cls_fronts, A.cls_fronts));
-  if (g->use_dense) { TRY(dev_upload(g, &g->d_dw_asm, g->dw_asm)); TRY(dev_upload(g, &g->d_dw_pan, g->dw_pan)); TRY(dev_upload(g, &g->d_dw_trl, g->dw_trl)); }
+  if (g->use_dense()) { TRY(dev_upload(g, &g->d_dw_asm, g->plan.dw_asm)); TRY(dev_upload(g, &g->d_dw_pan, g->plan.dw_pan)); TRY(dev_upload(g, &g->d_dw_trl, g->plan.dw_trl)); }
   d.chi2_blocks = (d.n_obs + 255) / 256 + (d.n_odo + 255) / 256 + (d.n_pp + 255) / 256 + (d.n_lp + 255) / 256;
   TRY(dev_alloc(g, &d.chi2_partials, (size_t)std::max(1, d.chi2_blocks)));
 
@@ -781,12 +684,12 @@ int upload_all(pps_graph* g) {
   d.trace_solve = g->sw.trace >= 2 ? 1 : 0;
   if (g->sw.trace) { TRY(dev_alloc(g, &d.trace, (size_t)A.n_fronts * 8)); HIP_TRY(g, hipMemset(d.trace, 0, (size_t)A.n_fronts * 64)); }
   // fronts that exceed the LDS limit run from a global workspace (one slab per front of the widest level)
-  if (!g->use_band && !g->use_dense && A.max_front > lds_front_limit()) {
+  if (!g->use_band() && !g->use_dense() && A.max_front > lds_front_limit()) {
     const int fa = A.max_front + 1;
     d.gwork_stride = (int64_t)fa * (fa | 1);
     int widest = 0;
     for (int l = 0; l < A.n_levels; l++)
-      if (g->level_max_front[l] > lds_front_limit()) widest = std::max(widest, A.level_off[l + 1] - A.level_off[l]);
+      if (g->plan.level_max_front[l] > lds_front_limit()) widest = std::max(widest, A.level_off[l + 1] - A.level_off[l]);
     TRY(dev_alloc(g, &d.gwork, (size_t)d.gwork_stride * std::max(1, widest)));
   }
 #undef TRY
@@ -830,6 +733,7 @@ int prepare_solve(pps_graph* g) {
   if (g->topo_dirty || !g->dev_ready || g->dev.n_scalars == 0) { rc = upload_all(g); if (rc != PPS_OK) return rc; }
   if (g->host_values_newer) { rc = upload_state(g); if (rc != PPS_OK) return rc; }
   if (g->meas_dirty) { rc = upload_measurements(g); if (rc != PPS_OK) return rc; }
+  HIP_TRY(g, ensure_k3_attrs());                                  // (once per device; the K3 launchers themselves check nothing)
   return PPS_OK;
 }
 
