@@ -75,6 +75,8 @@ struct DevGraph {
   int *frec = nullptr, *crec = nullptr, *srec = nullptr;   // packed metadata records (pps_symbolic.h)
   int* obs_dir = nullptr;                                   // direct (pose, plane) blocks: 3 ints per plane-observation slot (pps_symbolic.h)
   int* k3_flag = nullptr;                                   // hand-over flags between workgroups of the whole-tree launches (XGroup, pps_k3.hip): 4 x n_fronts ints
+  double* k3_xhand = nullptr;                               // ... and the local solutions that cross a group in the whole-tree back-substitution: 2 x n_fronts x kBandMaxRows
+                                                            // doubles (front, damping value); allocated where the plan's form is BandAll, else null
   int* nd_segs = nullptr; int n_nd_segs = 0;                // H segments that are not direct
   // K2 work lists (round 4): the non-direct segments of single-segment blocks (one wave each) and, per block of several
   // segments, its first segment (one workgroup each: the partial sums meet in LDS)

@@ -30,7 +30,17 @@ __device__ __forceinline__ int tri24(int i) { return __mul24(i, i + 1) >> 1; }
 // P: the panel buffer, 16 NT rows of kP8Stride doubles (at least 80 rows with STRIP).  Without STRIP, and with NT = 5, F is dead
 // once the tiles are loaded, and P may be F itself.
 // W: pivot columns per panel step, 8 or 4 (4 = the second pivot block never runs: the form up to round 3, kept for A/B).
-template <int NT, bool TR, bool STRIP, int W = 8, class G>
+// XH (whole-tree factor launch, without STRIP): a front whose parent another workgroup of the launch assembles (rec slot 13 >= 0) writes its
+// update matrix with agent-scope atomic stores (write-through: the hand-over of pps_k3.hip, XGroup); the elimination is the same code, only
+// the store loop exists twice.  The factor panel keeps plain stores: the next launch reads it.
+template <bool THROUGH>
+__device__ __forceinline__ void um_store(double* p, double v) {
+#ifndef PPS_WAVE_EMU
+  if constexpr (THROUGH) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
+#endif
+  *p = v;
+}
+template <int NT, bool TR, bool STRIP, int W = 8, bool XH = false, class G>
 __device__ __forceinline__ void front_reg_eliminate(const G& d, int rec, double* F, double* P) {      // (no __restrict__: P may be F)
   const int lane = threadIdx.x & 63;
   const int s = __builtin_amdgcn_readlane(rec, 0), p = __builtin_amdgcn_readlane(rec, 1), b = __builtin_amdgcn_readlane(rec, 2);
@@ -220,6 +230,36 @@ __device__ __forceinline__ void front_reg_eliminate(const G& d, int rec, double*
   // bases are computed once, and whole tiles left of the pivots or below the front are skipped by wave-uniform branches.
   double* __restrict__ Us = d.U + (((long long)__builtin_amdgcn_readlane(rec, 12) << 32) | (unsigned int)__builtin_amdgcn_readlane(rec, 11));
   const unsigned trash_u = (unsigned)(__mul24(b + 1, b + 1) - 1);
+  if constexpr (XH) {
+    // The stores below, once plain and once write-through, chosen per front.  (A block of its own: with the loop below put through such a
+    // lambda, the code objects of the kernels without XH come out different.)
+    static_assert(!STRIP && !TR, "the hand-over form holds neither strip nor trace");
+    auto out = [&](auto through) __attribute__((always_inline)) {
+      constexpr bool THROUGH = decltype(through)::value;
+#pragma unroll
+      for (int ti = 0; ti < NT; ti++) {
+        if (16 * ti >= mr) continue;                           // (wave-uniform)
+        int rbase[4]; bool rok[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) { const int row = 16 * ti + lq + 4 * q; rok[q] = row < mr; rbase[q] = tri24(row - p) - p; }
+#pragma unroll
+        for (int tj = 0; tj <= ti; tj++) {
+          if (16 * tj + 15 < p) continue;                      // (wave-uniform)
+          const int col = 16 * tj + l16;
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            const int row = 16 * ti + lq + 4 * q;
+            const bool ok = rok[q] && col <= row && col >= p;
+            um_store<THROUGH>(Us + (ok ? (unsigned)(rbase[q] + col) : trash_u), c[tile_id(ti, tj)][q]);
+          }
+        }
+      }
+      um_store<THROUGH>(Us + ((lane >= p && lane <= f) ? (unsigned)(tri24(b) + lane - p) : trash_u), lane < f ? y : 0.0);      // the rhs row
+    };
+    if (__builtin_amdgcn_readlane(rec, 13) >= 0) out(std::true_type{});      // (wave-uniform)
+    else out(std::false_type{});
+    return;
+  }
 #pragma unroll
   for (int ti = 0; ti < NT; ti++) {
     if (16 * ti >= mr) continue;                             // (wave-uniform)

@@ -444,16 +444,22 @@ __device__ __forceinline__ void wave_front_factor(const DevGraph& d, int s_in, d
 // scatter-add items per lane in flight in the extend-add.  Measured on C2 (us per LM iteration): 8 -> 78.9, 10 -> 77.6,
 // 12 -> 78.5, 16 -> 92.4 -- more loads in flight than about two dozen per lane cost more than the round trips they save
 constexpr int kEaDepth = 10;
+// a double that crosses workgroups inside a launch (XGroup below): agent-scope atomic access -- global_store / global_load ... sc1
+__device__ __forceinline__ void xg_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double xg_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 template <int N> struct ElBatch { int tg[N]; double v[N]; };
 // loads are issued unconditionally from clamped (always valid) addresses and masked by selects afterwards: predicated loads
 // become one exec-masked basic block each and serialise
-template <int N>
+// XH: the values are an update matrix that another workgroup of this launch wrote (xg_load; the targets are static)
+template <int N, bool XH = false>
 __device__ __forceinline__ void el_issue(const int* __restrict__ tgp, const double* __restrict__ val, int e, int e1, int lane, ElBatch<N>& q) {
   const int last = e1 > 0 ? e1 - 1 : 0;
 #pragma unroll
   for (int u = 0; u < N; u++) {
     const int x = e + lane + 64 * u, xc = x < e1 ? x : last;
-    const int t = tgp[xc]; const double v = val[xc];
+    const int t = tgp[xc];
+    double v;
+    if constexpr (XH) v = xg_load(val + xc); else v = val[xc];
     q.tg[u] = x < e1 ? t : -1; q.v[u] = x < e1 ? v : 0.0;
   }
 }
@@ -511,26 +517,44 @@ __device__ __forceinline__ void front_pre_finish(const DevGraph& d, int rec, int
 // extend-add of the children's packed update matrices, child by child, one batch of 512 entries in flight (more loads in
 // flight -- both children at once, two batches per child -- measured SLOWER on MI355X: DESIGN.md section 8)
 // Hand-over between WORKGROUPS of one launch (round 6: the whole tree in one factor launch and one back-substitution launch, XG = true
-// below).  A flag per front in global memory carries the number of the launch pair (the epoch: never reset).  Producer: the wave's stores,
-// an agent-scope release (on this chip: the wave's stores acknowledged + the XCD's L2 written back), the flag.  Consumer: polls the flag,
-// agent-scope acquire, then reads.  A workgroup only ever waits for workgroups with a LOWER block index -- children in the factor launch,
+// below).  A flag per front in global memory carries the number of the launch pair (the epoch: never reset).  No fence writes a cache
+// back: the bytes handed over leave the producer as write-through stores and reach the consumer by loads that bypass its L1.
+// Producer (ONE wave, for what it stored itself): the payload with agent-scope atomic stores (xg_store: global_store ... sc1), every store of
+// the wave acknowledged (s_waitcnt vmcnt(0)), then lane 0 stores the flag (xg_post).  Consumer (the wave that reads): polls the flag with
+// agent-scope loads (xg_wait) and reads the payload with agent-scope atomic loads (xg_load: global_load ... sc1) -- EVERY byte another
+// workgroup of the launch wrote is read that way, never by a plain load.  Factor launch: the update matrix of a group's top front, the only
+// wave of its workgroup that hands anything over; its reader passes no acquire (ACQ = false: a compiler barrier only).  That form holds with
+// ONE workgroup per CU (kXgLdsFloorBytes below) and hipMalloc memory.  Back-substitution launch: a front with children in another group
+// publishes its local solution [x_p | x_b] in XGroup::hand -- several waves of a workgroup do so, each for itself, which is not the form
+// measured without an acquire: the child keeps the agent-scope acquire (an L1 invalidate; no L2 write-back anywhere).
+// A workgroup only ever waits for workgroups with a LOWER block index -- children in the factor launch,
 // parents in the back-substitution launch, whose groups are numbered the other way round -- and the hardware starts workgroups in index
 // order: whatever a waiting workgroup waits for has been started and waits, if at all, for still lower indices.  No cycle, no dependence on
 // how many workgroups are resident, or on what else shares the device.  The spin is bounded like flow_wait's.
-struct XGroup { int* flag; int epoch; };          // flag: one int per front (of this damping value); epoch 0 / flag null: off
+// flag: one int per front (of this damping value); epoch 0 / flag null: off.  hand (back-substitution launch): kBandMaxRows doubles per front
+// (of this damping value), the local solutions of the fronts whose children another workgroup solves (DevGraph::k3_xhand)
+struct XGroup { int* flag; int epoch; double* hand; };
+// the dynamic LDS the two whole-tree launches ask for at least: more than half a CU's 160 KB, so that ONE workgroup is resident per CU -- a
+// precondition of the hand-over without an acquire, not a tuning
+constexpr size_t kXgLdsFloorBytes = 82 * 1024;
+// behind the wave's xg_store's: every store of the wave acknowledged, then the flag (no release fence: nothing of the payload sits in a cache)
 __device__ __forceinline__ void xg_post(const XGroup& x, int s) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if ((threadIdx.x & 63) == 0) __hip_atomic_store(x.flag + s, x.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// ACQ = false: the caller reads what the flag announces with xg_load only (the fence is no instruction: it keeps the compiler from moving those
+// loads in front of the poll)
+template <bool ACQ>
 __device__ __forceinline__ void xg_wait(const DevGraph& d, const XGroup& x, int s) {
   int spin = 0;
   while (__hip_atomic_load(x.flag + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != x.epoch) {
     if (++spin >= (1 << 21)) { if ((threadIdx.x & 63) == 0) raise_status(&d.result_dev[2], kStatusInternal); break; }
     __builtin_amdgcn_s_sleep(2);
   }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (ACQ) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-// XG: a child that another workgroup of this launch factors (child record slot 6) is waited for first (xg_wait)
+// XG: a child that another workgroup of this launch factors (child record slot 6) is waited for first (xg_wait, no acquire) and its update
+// matrix read with xg_load
 template <bool XG = false>
 __device__ __forceinline__ void front_extend_add(const DevGraph& d, int rec, int crv0, int lane, double* __restrict__ F, int tr, const XGroup* xg = nullptr) {
   const int cr0 = __builtin_amdgcn_readlane(rec, 5), nch = __builtin_amdgcn_readlane(rec, 6);
@@ -546,9 +570,12 @@ __device__ __forceinline__ void front_extend_add(const DevGraph& d, int rec, int
     for (; cj < 8 && cb + cj < nch; cj++) {
       int n; const double* Uc; const int* tgc;
       child(cj, n, Uc, tgc);
-      if (XG) { if (__builtin_amdgcn_readlane(crv, 8 * cj + 6)) xg_wait(d, *xg, __builtin_amdgcn_readlane(crv, 8 * cj + 5)); }
       // batches of kEaDepth x 64 = 640 entries: the update matrix of a separator front of a corridor tree (34 rows + rhs: 595
       // entries) is one memory round trip, not a full batch of 512 followed by a nearly empty one
+      if (XG && __builtin_amdgcn_readlane(crv, 8 * cj + 6)) {                                             // (wave-uniform)
+        xg_wait<false>(d, *xg, __builtin_amdgcn_readlane(crv, 8 * cj + 5));
+        for (int e = 0; e < n; e += 64 * kEaDepth) { ElBatch<kEaDepth> q; el_issue<kEaDepth, true>(tgc, Uc, e, n, lane, q); __builtin_amdgcn_wave_barrier(); el_apply<false>(q, 0.0, F, tr); }
+      } else
       for (int e = 0; e < n; e += 64 * kEaDepth) { ElBatch<kEaDepth> q; el_issue(tgc, Uc, e, n, lane, q); __builtin_amdgcn_wave_barrier(); el_apply<false>(q, 0.0, F, tr); }
       __builtin_amdgcn_wave_barrier();
     }
@@ -585,9 +612,9 @@ __device__ __forceinline__ void front_assemble(const DevGraph& d, int rec, doubl
   if (TR) PPS_TR(3);
 }
 // Second half: elimination in registers, factor panel and update matrix out.
-template <int NT, bool TR, bool STRIP = false, int W = kPanelWBand>
+template <int NT, bool TR, bool STRIP = false, int W = kPanelWBand, bool XH = false>
 __device__ __forceinline__ void front_eliminate_out(const DevGraph& d, int rec, double* F, double* P) {
-  front_reg_eliminate<NT, TR, STRIP, W>(d, rec, F, P);
+  front_reg_eliminate<NT, TR, STRIP, W, XH>(d, rec, F, P);
 }
 // One front from start to end (the level-per-launch kernels: one tile count per kernel)
 template <int NT, bool TR, bool STRIP = false, int W = kPanelWBand>
@@ -626,6 +653,20 @@ __device__ __forceinline__ void flow_post(const DevGraph& d, int* flow, int slot
     __hip_atomic_store(flow + slot, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// Back-substitution launch of the whole tree: does a child of this front belong to another group?  (crv: the records of its first eight
+// children, one field per lane; a front of more than eight children publishes in any case: harmless where nobody reads)
+__device__ __forceinline__ bool xg_has_external_child(int rec, int crv, int lane) {
+  const int nch = __builtin_amdgcn_readlane(rec, 6);
+  return nch > 8 || __ballot((lane & 7) == 6 && lane < 8 * nch && crv != 0) != 0;
+}
+// ... then its local solution [x_p | x_b] goes to XGroup::hand, where those children read it: this wave's stores, acknowledged, the flag
+__device__ __forceinline__ void xg_publish(const XGroup& x, int s, int p, int b, int lane, double tj, double g0, double g1) {
+  double* Xh = x.hand + (size_t)s * kBandMaxRows;
+  if (lane < p) xg_store(Xh + lane, tj);
+  if (lane < b) xg_store(Xh + p + lane, g0);
+  if (lane + 64 < b) xg_store(Xh + p + lane + 64, g1);
+  xg_post(x, s);
+}
 
 // The last sixteen pivots of a back-substitution (all of them for p <= 16), chain in registers: the scaling of the multipliers (does
 // not depend on the right-hand side) and the chain itself.
@@ -666,8 +707,9 @@ __device__ __forceinline__ void solve_pivot_chain(int p, double (&lk)[16], doubl
 // flow (band groups, body_band_solve_flow): every front of the group has been started at once; flow[q] != 0 <=> the local solution of the
 // group's front q is in X.  The front does everything that does not need its parent's solution, waits for the parent's flag right where
 // the boundary values are read, and raises its own flag behind its solution.
-// XG (with flow): the launch holds every band group (k_band_solve_all) -- a group's top front waits for its parent's flag before it gathers its
-// boundary values from delta, and every front with children raises its own flag behind its solution
+// XG (with flow): the launch holds every band group (k_band_solve_all) -- a front with a child in another group leaves its local solution
+// [x_p | x_b] in XGroup::hand (xg_store) and raises its flag behind it; a group's top front waits for its parent's flag and takes its boundary
+// values from the parent's vector there, through cmap like a child inside the group (xg_load).  Nothing crosses a group through delta.
 template <bool GROUP = true, bool TR = false, bool XG = false>
 __device__ __forceinline__ void wave_front_solve(const DevGraph& d, int rec, double* __restrict__ W, double* __restrict__ X, int slot, int* flow = nullptr, const XGroup* xg = nullptr) {
   const int lane = threadIdx.x & 63;
@@ -681,7 +723,16 @@ __device__ __forceinline__ void wave_front_solve(const DevGraph& d, int rec, dou
   // workgroup, else gathered from delta.  The index load does not depend on the parent and is issued first.
   // (unpredicated loads at clamped positions -- a predicated load is a basic block of its own that waits for its data, i.e. one more
   // memory round trip per index register in front of the panel's; the root has no list: any readable address does)
-  const int* __restrict__ ix = b == 0 ? d.frec : (pslot >= 0 ? d.cmap + __builtin_amdgcn_readlane(rec, 15) : d.bidx + __builtin_amdgcn_readlane(rec, 8));
+  const int xpar = XG ? __builtin_amdgcn_readlane(rec, 13) : -1;         // the parent's front when another workgroup of this launch solves it
+  // (XG) the records of the first eight children, requested first: whether one of them belongs to another group (slot 6) is known by the time
+  // the index lists have arrived, and no register holds the records any longer
+  int xcv = 0;
+  if (XG) {
+    const int nch = __builtin_amdgcn_readlane(rec, 6);
+    const int* __restrict__ cp = nch > 0 ? d.crec + (size_t)__builtin_amdgcn_readlane(rec, 5) * 8 : d.frec;
+    xcv = cp[lane < 8 * (nch < 8 ? nch : 8) ? lane : 0];
+  }
+  const int* __restrict__ ix = b == 0 ? d.frec : (pslot >= 0 || xpar >= 0 ? d.cmap + __builtin_amdgcn_readlane(rec, 15) : d.bidx + __builtin_amdgcn_readlane(rec, 8));
   double* xb = W;
   double* PL = W + kBandMaxRows;
   const int ix0r = ix[lane < b ? lane : 0], ix1r = ix[lane + 64 < b ? lane + 64 : 0];
@@ -710,15 +761,17 @@ __device__ __forceinline__ void wave_front_solve(const DevGraph& d, int rec, dou
     const double dg = Lp[lc * p + lc], yr = Lp[f * p + jc];
     const int ix0 = lane < b ? ix0r : 0, ix1 = lane + 64 < b ? ix1r : 0;
     double g0 = 0.0, g1 = 0.0;
-    const int xpar = XG ? __builtin_amdgcn_readlane(rec, 13) : -1;         // the parent's front when another workgroup of this launch solves it
+    const bool xpost = XG && xg_has_external_child(rec, xcv, lane);
     if (pslot < 0 && xpar < 0) { g0 = d.delta[ix0]; g1 = d.delta[ix1]; }
     if (flow) { dinv = 1.0 / dg; solve_pivot_scale(lk, dinv); }       // (all that can be done without the parent, before waiting for it)
     if (pslot >= 0) {
       if (flow) flow_wait(d, flow, pslot);
       const double* __restrict__ Xp = X + (size_t)pslot * kBandMaxRows; g0 = Xp[ix0]; g1 = Xp[ix1];
-    } else if (XG && xpar >= 0) {
-      xg_wait(d, *xg, xpar);
-      g0 = d.delta[ix0]; g1 = d.delta[ix1];
+    } else if constexpr (XG) {
+      if (xpar >= 0) {
+        xg_wait<true>(d, *xg, xpar);
+        const double* __restrict__ Xh = xg->hand + (size_t)xpar * kBandMaxRows; g0 = xg_load(Xh + ix0); g1 = xg_load(Xh + ix1);
+      }
     }
     if (TR) PPS_TR(1);
     if (lane < b) xb[lane] = g0;
@@ -750,7 +803,7 @@ __device__ __forceinline__ void wave_front_solve(const DevGraph& d, int rec, dou
     if (lane < b) Xs[p + lane] = g0;
     if (lane + 64 < b) Xs[p + lane + 64] = g1;
     if (flow) flow_post(d, flow, slot, pslot < 0);                       // (behind the solution)
-    if (XG) { if (__builtin_amdgcn_readlane(rec, 6) > 0) xg_post(*xg, s); }
+    if (XG) { if (xpost) xg_publish(*xg, s, p, b, lane, tj, g0, g1); }
     return;
   }
   // first batch of the panel (all of it for n <= 1024) issued right behind the index loads: the gather from delta below then waits
@@ -760,7 +813,7 @@ __device__ __forceinline__ void wave_front_solve(const DevGraph& d, int rec, dou
   for (int u = 0; u < 16; u++) { const int e = 64 * u + lane; v[u] = Lp[e < n ? e : n - 1]; }
   const int ix0 = lane < b ? ix0r : 0, ix1 = lane + 64 < b ? ix1r : 0;
   double g0 = 0.0, g1 = 0.0;
-  const int xpar = XG ? __builtin_amdgcn_readlane(rec, 13) : -1;
+  const bool xpost = XG && xg_has_external_child(rec, xcv, lane);
   if (pslot < 0 && xpar < 0) { g0 = d.delta[ix0]; g1 = d.delta[ix1]; }          // clamped index 0 when out of range: harmless
   // (entries past the end of the panel land in xb[127], which no front uses: b <= 126 -- unpredicated LDS writes)
 #pragma unroll
@@ -804,9 +857,11 @@ __device__ __forceinline__ void wave_front_solve(const DevGraph& d, int rec, dou
     if (flow) flow_wait(d, flow, pslot);
     const double* __restrict__ Xp = X + (size_t)pslot * kBandMaxRows;
     g0 = Xp[ix0]; g1 = Xp[ix1];
-  } else if (XG && xpar >= 0) {
-    xg_wait(d, *xg, xpar);
-    g0 = d.delta[ix0]; g1 = d.delta[ix1];
+  } else if constexpr (XG) {
+    if (xpar >= 0) {
+      xg_wait<true>(d, *xg, xpar);
+      const double* __restrict__ Xh = xg->hand + (size_t)xpar * kBandMaxRows; g0 = xg_load(Xh + ix0); g1 = xg_load(Xh + ix1);
+    }
   }
   if (lane < b) xb[lane] = g0;
   if (lane + 64 < b) xb[lane + 64] = g1;
@@ -876,7 +931,7 @@ __device__ __forceinline__ void wave_front_solve(const DevGraph& d, int rec, dou
   if (lane < b) Xs[p + lane] = g0;
   if (lane + 64 < b) Xs[p + lane + 64] = g1;
   if (flow) flow_post(d, flow, slot, pslot < 0);
-  if (XG) { if (__builtin_amdgcn_readlane(rec, 6) > 0) xg_post(*xg, s); }
+  if (XG) { if (xpost) xg_publish(*xg, s, p, b, lane, tj, g0, g1); }
 }
 
 // The back-substitution of a band group as a data flow: the group's fronts, top level first, are dealt to the waves round-robin and
@@ -1075,9 +1130,10 @@ __device__ __forceinline__ void body_band_factor_pre(const DevGraph& d, int g, d
       const int fa = __builtin_amdgcn_readlane(rec, 1) + __builtin_amdgcn_readlane(rec, 2) + 1;
       if (!mine_up) crv = front_orig_entries_sized(d, rec, lane, 1.0 + lambda, F, tr);
       front_extend_add<XG>(d, rec, crv, lane, F, tr, xg);
-      if (fa <= 33) front_eliminate_out<2, false, false, kPanelWBand>(d, rec, F, F);
-      else if (fa <= 49) front_eliminate_out<3, false, false, kPanelWBand>(d, rec, F, F);
-      else front_eliminate_out<4, false, false, kPanelWBand>(d, rec, F, F);
+      // (XG: the update matrix of a front whose parent another workgroup holds leaves as write-through stores -- front_reg_eliminate, XH)
+      if (fa <= 33) front_eliminate_out<2, false, false, kPanelWBand, XG>(d, rec, F, F);
+      else if (fa <= 49) front_eliminate_out<3, false, false, kPanelWBand, XG>(d, rec, F, F);
+      else front_eliminate_out<4, false, false, kPanelWBand, XG>(d, rec, F, F);
       // (slot 13: the parent's front when another group holds it; SW_DEBUG_DROP_XFLAG, tests only: the flag is withheld and the parent's workgroup runs into its time-out)
       if (XG) { if (__builtin_amdgcn_readlane(rec, 13) >= 0 && !(d.sw & SW_DEBUG_DROP_XFLAG)) xg_post(*xg, __builtin_amdgcn_readlane(rec, 0)); }
     } else if (ll == pre_at && up_ll > pre_at) {
@@ -1114,15 +1170,15 @@ __global__ __launch_bounds__(512) void k_band_root(DevGraph d, DualAlt alt, int 
 // cleared and receive their original entries while their children are still being eliminated.
 __global__ __launch_bounds__(512) void k_band_factor_all(DevGraph d, DualAlt alt, double lambda, int lds_doubles_per_wave, int epoch) {
   extern __shared__ double lds[];
-  XGroup xg{d.k3_flag, epoch};
+  XGroup xg{d.k3_flag, epoch, nullptr};
   if (blockIdx.y) { d.L = alt.L; d.U = alt.U; d.delta = alt.delta; d.result_dev = alt.result_dev; lambda = alt.lambda; xg.flag += d.n_fronts; }
   body_band_factor_pre<true>(d, blockIdx.x, lambda, lds_doubles_per_wave, lds, &xg);
 }
 // ... and the whole back-substitution in one: workgroup b = group n_groups - 1 - b, the top group first
 __global__ __launch_bounds__(768) void k_band_solve_all(DevGraph d, DualAlt alt, int n_groups, int lds_doubles_per_wave, int mg, int epoch) {
   extern __shared__ double lds[];
-  XGroup xg{d.k3_flag + 2 * d.n_fronts, epoch};
-  if (blockIdx.y) { d.L = alt.L; d.U = alt.U; d.delta = alt.delta; d.result_dev = alt.result_dev; xg.flag += d.n_fronts; }
+  XGroup xg{d.k3_flag + 2 * d.n_fronts, epoch, d.k3_xhand};
+  if (blockIdx.y) { d.L = alt.L; d.U = alt.U; d.delta = alt.delta; d.result_dev = alt.result_dev; xg.flag += d.n_fronts; xg.hand += (size_t)d.n_fronts * kBandMaxRows; }
   body_band_solve_flow<false, true>(d, n_groups - 1 - (int)blockIdx.x, lds_doubles_per_wave, lds, mg, &xg);
 }
 
@@ -1190,16 +1246,16 @@ hipError_t launch_band_root(const DevGraph& d, const DualAlt* alt, const K3Plan&
 }
 
 // the whole tree: one factor launch + one back-substitution launch (k_band_factor_all / k_band_solve_all); epoch: number of this launch
-// pair (> 0, never repeated)
+// pair (> 0, never repeated).  Both ask for kXgLdsFloorBytes of LDS at least: one workgroup per CU (XGroup)
 hipError_t launch_band_all_factor(const DevGraph& d, const DualAlt* alt, const K3Plan& p, double lambda, int epoch, hipStream_t st, hipEvent_t ev0,
                                   hipEvent_t ev1) {
   const K3AllPlan& a = p.all;
-  PPS_LAUNCH_EV(ev0, ev1, k_band_factor_all, dim3(a.n_groups, alt ? 2 : 1), dim3(64 * a.nw_factor), a.lds_factor, st, d, alt_arg(alt), lambda, a.pw_factor, epoch);
+  PPS_LAUNCH_EV(ev0, ev1, k_band_factor_all, dim3(a.n_groups, alt ? 2 : 1), dim3(64 * a.nw_factor), std::max(a.lds_factor, kXgLdsFloorBytes), st, d, alt_arg(alt), lambda, a.pw_factor, epoch);
   return hipGetLastError();
 }
 hipError_t launch_band_all_solve(const DevGraph& d, const DualAlt* alt, const K3Plan& p, int epoch, hipStream_t st) {
   const K3AllPlan& a = p.all;
-  PPS_LAUNCH(k_band_solve_all, dim3(a.n_groups, alt ? 2 : 1), dim3(64 * a.nw_solve), a.lds_solve, st, d, alt_arg(alt), a.n_groups, a.pw_solve, a.max_grp_fronts, epoch);
+  PPS_LAUNCH(k_band_solve_all, dim3(a.n_groups, alt ? 2 : 1), dim3(64 * a.nw_solve), std::max(a.lds_solve, kXgLdsFloorBytes), st, d, alt_arg(alt), a.n_groups, a.pw_solve, a.max_grp_fronts, epoch);
   return hipGetLastError();
 }
 

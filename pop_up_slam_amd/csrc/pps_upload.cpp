@@ -678,6 +678,9 @@ int upload_all(pps_graph* g) {
     d.result_dev = zb + n_dn + 2; g->spec_result = zb + n_dn + 6;
     g->status_clean = true;
   }
+  // the local solutions that cross a band group in the whole-tree back-substitution (XGroup::hand, pps_k3.hip): every value is written in the
+  // launch that reads it, behind its flag -- not zeroed
+  if (g->plan.form == K3Form::BandAll) TRY(dev_alloc(g, &d.k3_xhand, 2 * (size_t)A.n_fronts * kBandMaxRows));
   TRY(dev_alloc(g, &g->spec_pose, state_doubles + 1)); g->spec_plane = g->spec_pose + (size_t)7 * d.pose_ld;
   TRY(dev_alloc(g, &g->spec_chi2_partials, (size_t)std::max(1, d.chi2_blocks)));
   TRY(dev_alloc(g, &g->spec_dn_partials, (size_t)(d.n_pose + d.n_plane + 255) / 256 + 1));
