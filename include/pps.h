@@ -303,6 +303,53 @@ int pps_merge_gate_last(const pps_graph* g, double* kernel_sec, int* launches, i
  * before the first successful call of the handle, and after a call of more than 262144 pairs (the records of such a call are not kept). */
 int pps_debug_merge_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed);
 
+/* ---- Mahalanobis gate for loop-closure pose candidates, from the recovered covariances -------------------------
+ * The question the pose-graph side asks before it adds a loop closure: "is this relative-pose measurement between two existing poses
+ * consistent with the current estimate?" (the reference leaves it open: Mapping.cpp:658 always associates to the first frame).  Candidate k
+ * is the factor Pose3d_Pose3d_Factor(pose_a[k], pose_b[k], meas6[k], W_k) that pps_add_odometry would add; at the current ESTIMATE, in the
+ * handle's jacobian_mode and the column order of pps_eval_factor (columns of a, then of b):
+ *     r (6), Jw (6 x 12)   its whitened residual and Jacobian; the measurement is used as pps_add_odometry stores it (the six numbers as given)
+ *     Sigma (12 x 12)      the joint marginal of (a, b) from the current factor
+ *     S   = I + Jw Sigma Jw'
+ *     d2  = r' S^-1 r      (6 x 6 Cholesky solve); chi-square with 6 degrees of freedom for a correct closure: 12.592 is the 0.95 threshold
+ * Sigma is never formed and no covariance block goes to the host.
+ *   pose_a, pose_b  n node ids each; a pose may appear in any number of candidates and a pair may appear twice: every entry is answered on
+ *              its own, and its d2 and S are bit for bit independent of what else is in the call
+ *   meas6      n x 6 (x y z yaw pitch roll, as pps_add_odometry takes it);  sqrtinf_ut  n x 21, the packed upper triangle
+ *   d2         (may be NULL) n
+ *   S          (may be NULL) n x 36, row-major, EXACTLY symmetric: computed as the lower triangle and mirrored.  When NULL nothing n x 36
+ *              is copied to the host.
+ *   accepted, n_accepted  (may be NULL together) the indices INTO the list, ascending, of the entries with finite d2 < threshold; at most
+ *              cap_accepted are written, *n_accepted is always the full count (accepted may be NULL with cap_accepted == 0: the count alone)
+ * A candidate whose S is NOT positive definite (a pivot of its 6 x 6 factor not positive or not finite) gets d2 = NaN, is never accepted,
+ * and the call still returns PPS_OK; pps_loop_gate_last reports how many there were (the rule of pps_merge_gate: one bad candidate must not
+ * void the list).  Its S is still written, as computed.
+ * Everything is computed on the device: one upload, two launches (the root-path walks of pps_cov_block for the DISTINCT poses of the
+ * list, ONE candidate kernel: a wave per candidate, the common ancestors of its two poses found on the device from the tree), one copy.
+ * Nothing is added to the graph: the estimate, the linearisation point, the LM trace, the stats, both validity flags and the recovery stay
+ * untouched, and a pps_batch_optimize after the call is bit for bit the one without it.
+ *   PPS_EINVAL  (checked on the host before any launch, without a device) NULL handle or a NULL input array; negative n or cap_accepted;
+ *               d2, S and accepted / n_accepted all NULL; accepted without n_accepted, or n_accepted without accepted and
+ *               cap_accepted > 0; a threshold that is not finite while n_accepted is given; a non-finite measurement or weight; an
+ *               unknown, removed or non-pose id; pose_a[k] == pose_b[k]
+ *   PPS_OK      with the outputs untouched for n == 0 -- answered before the recovery is looked at
+ *   PPS_ESTATE  a robust cost function is set (the rule of pps_assoc_gate: a candidate measurement against a Gaussian innovation);
+ *               no valid factor: the text and the validity rules of pps_cov_block (either recovery provides the factor; a dense-front
+ *               graph has it after pps_cov_factor alone)
+ *   PPS_ENOMEM  a buffer of the call cannot be had
+ * Found by symbol lookup, like the pps_cov_* calls; PPS_VERSION was not bumped. */
+int pps_loop_gate(pps_graph* g, int n, const int* pose_a, const int* pose_b, const double* meas6 /* n x 6 */,
+                  const double* sqrtinf_ut /* n x 21 */, double threshold, double* d2 /* n */, double* S /* n x 36, may be NULL */,
+                  int cap_accepted, int* accepted, int* n_accepted);
+/* the last pps_loop_gate: device seconds (HIP events) around its two kernels, the kernel launches it made (2), and the number of its
+ * candidates whose S was not positive definite (each may be NULL) */
+int pps_loop_gate_last(const pps_graph* g, double* kernel_sec, int* launches, int* n_not_pd);
+/* diagnostics: Jw and r of every candidate of the last successful pps_loop_gate, as the kernel evaluated them: one slot of 78 doubles per
+ * entry, [Jw 6 x 12 row-major | r 6] -- the slot of pps_debug_factor_gate_records for an odometry factor --, so that a test can compare
+ * them with pps_eval_factor.  *needed = the number of doubles; nothing is copied when rec is NULL or cap is smaller.  PPS_ESTATE before
+ * the first successful call of the handle, and after a call of more than 65536 entries (the records of such a call are not kept). */
+int pps_debug_loop_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed);
+
 /* ---- leave-one-out chi-square test of every factor, from the recovered covariances ----------------------------
  * pps_assoc_gate and pps_merge_gate judge candidates; this call asks what a front end asks after a solve: "which factor already in the
  * graph is wrong?" (plane association is greedy and geometric, and one wrong pps_add_plane_obs bends the corridor).  For factor f, at

@@ -377,7 +377,7 @@ protected:
 // marginal() and access() keep that strict in-pattern contract (they read the selected inverse and throw for anything outside it).
 // block() and marginal_any() are the unrestricted forms: any nodes, by root-path solves on the same factor (pps_cov_block) -- what the
 // reference's marginal(node_list) / access(pairs) answer for nodes that share no front, e.g. the current pose against an old landmark.
-// They, gate() and merge_gate() need the factor alone: where pps_cov_recover refuses the graph (PPS_ESTATE: the dense-front form) they go on with
+// They, gate(), merge_gate() and loop_gate() need the factor alone: where pps_cov_recover refuses the graph (PPS_ESTATE: the dense-front form) they go on with
 // pps_cov_factor, so that they answer after a loop closure, too.  On every other graph they make the calls they always made.
 // select() computes the selected inverse in whatever form the graph is solved in (pps_cov_select): after it marginal() and access() answer on
 // a dense-front graph as well, until the next change of the graph ends the recovery; without it they throw there as they always did.
@@ -479,6 +479,37 @@ public:
                   "pps_merge_gate");
     for (int k = 0; k < count; k++) out.pairs.emplace_back(flat[2 * k], flat[2 * k + 1]);
     detail::check(pps_merge_gate_last(handle(), nullptr, nullptr, &out.n_not_pd), handle(), "pps_merge_gate_last");
+    return out;
+  }
+  // Mahalanobis gate for loop-closure candidates between poses (pps_loop_gate): may this relative-pose measurement be added as a loop
+  // closure?  Per candidate, d2 = r' (I + Jw Sigma Jw')^-1 r with r, Jw the whitened residual and Jacobian the
+  // Pose3d_Pose3d_Factor(a, b, measure, noise) would have at the estimate and Sigma the joint marginal of (a, b); chi-square with 6 degrees
+  // of freedom for a correct closure (12.592 at 0.95).  accepted = the indices into the list, ascending, of the candidates with finite
+  // d2 < threshold.  A pose may be in any number of candidates.  A candidate whose S is not positive definite has d2 = NaN and is never
+  // accepted; n_not_pd counts them.  Nothing is added to the graph: add_factor the accepted candidates, then solve.
+  struct LoopCandidate { Pose3d_Node* a; Pose3d_Node* b; Pose3d measure; Noise noise; };
+  struct LoopGate { std::vector<double> d2; std::vector<int> accepted; int n_not_pd = 0; };
+  LoopGate loop_gate(const std::vector<LoopCandidate>& candidates, double threshold = 12.592) const {
+    ensure_factor();
+    const int n = (int)candidates.size();
+    LoopGate out;
+    out.d2.assign((size_t)n, 0.0);
+    if (n == 0) return out;
+    std::vector<int> ia, ib, flat((size_t)n);
+    std::vector<double> m6, ut;
+    for (const LoopCandidate& c : candidates) {
+      if (!c.a || !c.b || c.a->backend_id() < 0 || c.b->backend_id() < 0) throw std::runtime_error("Covariances: node is not part of the graph");
+      if (c.noise.sqrtinf_ut().size() != 21) throw std::runtime_error("Covariances::loop_gate: a relative-pose measurement takes a 6 x 6 noise model");
+      ia.push_back(c.a->backend_id()); ib.push_back(c.b->backend_id());
+      const Vector6d v = c.measure.vector();
+      m6.insert(m6.end(), v.begin(), v.end());
+      ut.insert(ut.end(), c.noise.sqrtinf_ut().begin(), c.noise.sqrtinf_ut().end());
+    }
+    int count = 0;
+    detail::check(pps_loop_gate(handle(), n, ia.data(), ib.data(), m6.data(), ut.data(), threshold, out.d2.data(), nullptr, n, flat.data(), &count), handle(),
+                  "pps_loop_gate");
+    out.accepted.assign(flat.begin(), flat.begin() + count);
+    detail::check(pps_loop_gate_last(handle(), nullptr, nullptr, &out.n_not_pd), handle(), "pps_loop_gate_last");
     return out;
   }
   // Leave-one-out chi-square test of the graph's own factors (pps_factor_gate): which factor already in the graph is wrong?  Per entry of

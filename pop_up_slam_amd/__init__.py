@@ -136,6 +136,7 @@ SYMBOLS = [
     "pps_cov_block", "pps_cov_block_last", "pps_assoc_gate", "pps_assoc_gate_last", "pps_debug_assoc_gate_records",
     "pps_merge_gate", "pps_merge_gate_last", "pps_debug_merge_gate_records",
     "pps_factor_gate", "pps_factor_gate_last", "pps_debug_factor_gate_records",
+    "pps_loop_gate", "pps_loop_gate_last", "pps_debug_loop_gate_records",
     "pps_map_default_select", "pps_map_create", "pps_map_destroy", "pps_map_last_error", "pps_map_add_frame", "pps_map_redirect",
     "pps_map_info", "pps_map_chunks", "pps_map_built_chunks", "pps_map_select_host", "pps_map_build", "pps_map_download",
     "pps_map_last_times",
@@ -271,6 +272,9 @@ def lib():
         L.pps_merge_gate.argtypes = [C.c_void_p, C.c_int, _ip, C.c_double, C.c_double, _dp, _ip, C.c_int, _ip, _ip]
         L.pps_merge_gate_last.argtypes = [C.c_void_p, _dp, _ip, _ip]
         L.pps_debug_merge_gate_records.argtypes = [C.c_void_p, C.c_int64, _dp, C.POINTER(C.c_int64)]
+        L.pps_loop_gate.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _dp, _dp, C.c_double, _dp, _dp, C.c_int, _ip, _ip]
+        L.pps_loop_gate_last.argtypes = [C.c_void_p, _dp, _ip, _ip]
+        L.pps_debug_loop_gate_records.argtypes = [C.c_void_p, C.c_int64, _dp, C.POINTER(C.c_int64)]
         L.pps_factor_gate.argtypes = [C.c_void_p, C.c_int, _ip, C.c_double, C.c_double, _dp, _dp, C.c_int, _ip, _ip]
         L.pps_factor_gate_last.argtypes = [C.c_void_p, _dp, _ip, _ip]
         L.pps_debug_factor_gate_records.argtypes = [C.c_void_p, C.c_int64, _dp, C.POINTER(C.c_int64)]
@@ -584,6 +588,41 @@ class Graph:
         """(device seconds around the two kernels, kernel launches, pairs whose S was not positive definite) of the last merge_gate"""
         s = C.c_double(); n = C.c_int(); k = C.c_int()
         self._ck(self.L.pps_merge_gate_last(self.h, C.byref(s), C.byref(n), C.byref(k))); return s.value, n.value, k.value
+
+    def loop_gate(self, pose_a, pose_b, meas6, sqrtinf_ut, threshold=12.592, want_S=False):
+        """Mahalanobis gate for loop-closure candidates between poses (pps_loop_gate): may this relative-pose measurement be added as a
+        loop closure?  Candidate k is the factor add_odometry(pose_a[k], pose_b[k], meas6[k], sqrtinf_ut[k]) would add; meas6 (n x 6),
+        sqrtinf_ut (n x 21).  Returns (d2, S, accepted): d2 (n) = r' S^-1 r with S = I + Jw Sigma Jw', r and Jw the candidate's whitened
+        residual and Jacobian at the estimate in the handle's jacobian_mode, Sigma the joint marginal of its two poses from the last
+        recovery; S (n x 6 x 6, exactly symmetric; None without want_S -- nothing n x 36 is then copied from the device); accepted =
+        indices into the list, ascending, of the entries with finite d2 < threshold.  d2 is chi-square with 6 degrees of freedom for a
+        correct closure.  A pose may be in any number of candidates; every entry is answered on its own.  A candidate whose S is not
+        positive definite has d2 = NaN and is never accepted (loop_gate_last counts them).  Nothing is added to the graph."""
+        ia = np.ascontiguousarray(pose_a, dtype=np.int32).reshape(-1); ib = np.ascontiguousarray(pose_b, dtype=np.int32).reshape(-1)
+        n = len(ia)
+        m = np.ascontiguousarray(meas6, dtype=np.float64).reshape(-1, 6); w = np.ascontiguousarray(sqrtinf_ut, dtype=np.float64).reshape(-1, 21)
+        if len(ib) != n or len(m) != n or len(w) != n:
+            raise ValueError("loop_gate: pose_a, pose_b, meas6 and sqrtinf_ut must have one entry per candidate")
+        d2 = np.full(n, np.nan); S = np.zeros((n, 6, 6)) if want_S else None
+        acc = np.zeros(max(n, 1), dtype=np.int32); cnt = C.c_int(0)
+        self._ck(self.L.pps_loop_gate(self.h, n, ia.ctypes.data_as(_ip), ib.ctypes.data_as(_ip), m.ctypes.data_as(_dp), w.ctypes.data_as(_dp), float(threshold),
+                                      d2.ctypes.data_as(_dp), None if S is None else S.ctypes.data_as(_dp), n, acc.ctypes.data_as(_ip), C.byref(cnt)))
+        return d2, S, acc[:cnt.value].copy()
+
+    def loop_gate_records(self):
+        """diagnostics: (Jw, r) of every candidate of the last loop_gate as the kernel evaluated them -- (n, 6, 12) and (n, 6), columns of
+        pose a then of pose b: what pps_eval_factor gives for the candidate added as an odometry factor"""
+        n = C.c_int64(0)
+        self._ck(self.L.pps_debug_loop_gate_records(self.h, 0, None, C.byref(n)))
+        rec = np.zeros(n.value)
+        self._ck(self.L.pps_debug_loop_gate_records(self.h, n.value, rec.ctypes.data_as(_dp), C.byref(n)))
+        rec = rec.reshape(-1, 78)
+        return rec[:, :72].reshape(-1, 6, 12).copy(), rec[:, 72:].copy()
+
+    def loop_gate_last(self):
+        """(device seconds around the two kernels, kernel launches, candidates whose S was not positive definite) of the last loop_gate"""
+        s = C.c_double(); n = C.c_int(); k = C.c_int()
+        self._ck(self.L.pps_loop_gate_last(self.h, C.byref(s), C.byref(n), C.byref(k))); return s.value, n.value, k.value
 
     def factor_gate(self, fids=None, thr3=7.815, thr6=12.592):
         """Leave-one-out chi-square test of the graph's own factors (pps_factor_gate): which factor already in the graph is wrong?  fids:

@@ -37,6 +37,7 @@ void cov_release(pps_graph* g) {
   gate_release(g);
   merge_release(g);
   fgate_release(g);
+  loop_release(g);
   for (hipEvent_t& e : g->cov_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   for (hipEvent_t& e : g->cov_qev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   g->cov_cache = pps_graph::CovCache{};

@@ -1,7 +1,7 @@
-// pps_gate_dev.h -- what the Mahalanobis gate kernels share on the device (pps_gate.hip, pps_merge.hip, pps_fgate.hip): the lane
+// pps_gate_dev.h -- what the Mahalanobis gate kernels share on the device (pps_gate.hip, pps_merge.hip, pps_fgate.hip, pps_loop.hip): the lane
 // evaluations of a central difference, the strip products J Sigma J' from end-aligned strips, the small Cholesky solve behind d2, and the
-// best-candidate scan.  The three calls must agree bit for bit with pps_eval_factor and with each other, so every function states the
-// order of operations it promises; tests/test_host_gate_dev.py pins those orders on the host.  Compile the including file without
+// best-candidate scan, the common-ancestor walk.  The calls must agree bit for bit with pps_eval_factor and with each other, so every function states the
+// order of operations it promises; tests/test_host_gate_dev.py and tests/test_host_gate_dev_m6.py pin those orders on the host.  Compile the including file without
 // contraction (the Makefile does), like pps_k1_lanes.hip.
 #pragma once
 #include "pps_k1_body.h"
@@ -67,22 +67,27 @@ __device__ __forceinline__ void eval_pose_prior(const double pz[7], const double
 // is relative to |z_a|, multiplied out it would be relative to |z_a|^2 against a result of the size |z_a + z_b|^2.  Rows of fronts the
 // paths do not share keep their two squares apart: no cross term exists there, whatever sits at the same strip index -- which is also
 // why the strips are NOT added row by row ahead of the product (end-aligned strips put rows of two different fronts at one index).
-template <int DA, int DB>
-__device__ __forceinline__ void strip_gram3(const double* Ja, const double* Jb, const double* __restrict__ Ya, const double* __restrict__ Yb, int len_a,
-                                            int len_b, int common, int K, int lane, double s[6]) {
+// strip_gram<M, DA, DB> is that operation for M rows of J, with the M (M + 1) / 2 entries in the same row-major lower-triangle order
+// ((0,0) (1,0) (1,1) (2,0) ...) and the rows of Ja / Jb lda / ldb doubles apart (two halves of one wider J: pps_loop.hip reads its
+// 6 x 12 Jacobian from LDS, the same address in every lane).  strip_gram3 is its M = 3 case on packed Jacobians: the same statements.
+template <int M, int DA, int DB>
+__device__ __forceinline__ void strip_gram(const double* Ja, int lda, const double* Jb, int ldb, const double* __restrict__ Ya, const double* __restrict__ Yb,
+                                           int len_a, int len_b, int common, int K, int lane, double s[M * (M + 1) / 2]) {
   const int len = len_a > len_b ? len_a : len_b;
   for (int j = lane; j < len; j += 64) {
     const size_t k = (size_t)(K - 1 - j);
-    double za[3] = {0.0, 0.0, 0.0}, zb[3] = {0.0, 0.0, 0.0};
+    double za[M], zb[M], z[M];
+#pragma unroll
+    for (int i = 0; i < M; i++) za[i] = zb[i] = 0.0;
     if (j < len_a) {
       double y[DA];
 #pragma unroll
       for (int q = 0; q < DA; q++) y[q] = Ya[k * DA + q];
 #pragma unroll
-      for (int i = 0; i < 3; i++) {
+      for (int i = 0; i < M; i++) {
         double t = 0.0;
 #pragma unroll
-        for (int q = 0; q < DA; q++) t += Ja[i * DA + q] * y[q];
+        for (int q = 0; q < DA; q++) t += Ja[i * lda + q] * y[q];
         za[i] = t;
       }
     }
@@ -91,27 +96,53 @@ __device__ __forceinline__ void strip_gram3(const double* Ja, const double* Jb, 
 #pragma unroll
       for (int q = 0; q < DB; q++) y[q] = Yb[k * DB + q];
 #pragma unroll
-      for (int i = 0; i < 3; i++) {
+      for (int i = 0; i < M; i++) {
         double t = 0.0;
 #pragma unroll
-        for (int q = 0; q < DB; q++) t += Jb[i * DB + q] * y[q];
+        for (int q = 0; q < DB; q++) t += Jb[i * ldb + q] * y[q];
         zb[i] = t;
       }
     }
     const bool cross = j < common;
-    const double z[3] = {za[0] + zb[0], za[1] + zb[1], za[2] + zb[2]};
+#pragma unroll
+    for (int i = 0; i < M; i++) z[i] = za[i] + zb[i];
     int e = 0;
 #pragma unroll
-    for (int i = 0; i < 3; i++)
+    for (int i = 0; i < M; i++)
 #pragma unroll
       for (int jj = 0; jj <= i; jj++, e++) s[e] += cross ? z[i] * z[jj] : za[i] * za[jj] + zb[i] * zb[jj];
   }
+}
+template <int DA, int DB>
+__device__ __forceinline__ void strip_gram3(const double* Ja, const double* Jb, const double* __restrict__ Ya, const double* __restrict__ Yb, int len_a,
+                                            int len_b, int common, int K, int lane, double s[6]) {
+  strip_gram<3, DA, DB>(Ja, DA, Jb, DB, Ya, Yb, len_a, len_b, common, K, lane, s);
 }
 // the 64 partial sums of one entry, added in lane order from 0.0 by ONE lane: one fixed order of additions
 __device__ __forceinline__ double lane_order_sum(const double* part) {
   double t = 0.0;
   for (int k = 0; k < 64; k++) t += part[k];
   return t;
+}
+
+// ---- the pivots two root paths have in common (pps_merge.hip, pps_loop.hip) ----
+// parent: the parent front of every front (-1: a root); rootlen: per front the pivots of the front and of all its ancestors, which fall
+// strictly on the way up -- so the front with the longer path cannot be the meeting point and steps to its parent until the two meet (the
+// same front; one an ancestor of the other; disjoint subtrees) or both have left the tree (no common root: 0).  Every front the walk
+// reaches is checked against n_fronts and the hops are counted: false = an index outside the tables (common is then 0).
+__device__ __forceinline__ bool common_root_pivots(const int* __restrict__ parent, const int* __restrict__ rootlen, int n_fronts, int fa, int fb, int& common) {
+  common = 0;
+  int hops = 0;
+  while (fa != fb && fa >= 0 && fb >= 0) {
+    const int la = rootlen[fa], lb = rootlen[fb];
+    int na = fa, nb = fb;
+    if (la >= lb) na = parent[fa];
+    if (lb >= la) nb = parent[fb];
+    fa = na; fb = nb;
+    if (fa < -1 || fa >= n_fronts || fb < -1 || fb >= n_fronts || ++hops > 2 * n_fronts) return false;
+  }
+  common = (fa == fb && fa >= 0) ? rootlen[fa] : 0;
+  return true;
 }
 
 // ---- d2 = r' A^-1 r by the Cholesky factor of a symmetric M x M matrix ----

@@ -10,6 +10,7 @@
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
 //   pps_cov.cpp      marginal covariances from the factor (isam::Covariances): the recovery pipeline and the query scaffold (CovQuery); kernels in pps_cov*.hip
 //   pps_gate.cpp     pps_assoc_gate (measurement against landmark); pps_merge.cpp: pps_merge_gate (landmark against landmark): queries on the factor
+//   pps_loop.cpp     pps_loop_gate (a candidate loop closure between two poses): a query on the factor
 //   pps_fgate.cpp    pps_factor_gate (every factor of the graph against the rest of it): a query on the selected inverse
 //   pps_map.cpp      the dense map (pps_map: per-plane clouds of every frame, re-projected on the device); kernels in pps_map.hip
 #pragma once
@@ -233,7 +234,7 @@ struct pps_graph {
   std::vector<int> cov_epos, cov_front_of;               // delta index -> elimination-ordered scalar; that scalar -> front
   hipEvent_t cov_ev[3] = {nullptr, nullptr, nullptr};
   double cov_sec[2] = {0, 0};        // device seconds of the last recovery: whole call | root -> leaves pass alone
-  // the queries on the factor (CovQuery below: pps_cov_block, pps_assoc_gate, pps_merge_gate): per front the pivots of the front and all its
+  // the queries on the factor (CovQuery below: pps_cov_block, pps_assoc_gate, pps_merge_gate, pps_loop_gate): per front the pivots of the front and all its
   // ancestors; the request blob, the strips and the event pair of the query in flight (every query ends with a synchronisation)
   std::vector<int> cov_rootlen; int cov_max_p = 0, cov_max_rows = 0;
   pps_impl::DevBuf<char> cov_breq;
@@ -274,6 +275,11 @@ struct pps_graph {
   pps_impl::DevBuf<double> fgate_rec; size_t fgate_rec_n = 0;
   bool fgate_done = false;           // a call has succeeded on this handle
   double fgate_sec = 0; int fgate_launches = 0, fgate_untestable = 0;      // the kernel of the last call: device seconds, launches; its entries with d2 = NaN
+  // pps_loop_gate (pps_loop.cpp): result of a call on the device ([status | flags | d2 n | S n x 36], the status word zero between calls)
+  pps_impl::DevBuf<char> loop_out; bool loop_clean = false;
+  double loop_sec = 0; int loop_launches = 0, loop_not_pd = 0;         // the two kernels of the last call: device seconds, launches; its candidates without a positive definite S
+  pps_impl::DevBuf<double> loop_rec; size_t loop_rec_n = 0;     // [Jw 6 x 12 | r] per candidate of the last call (pps_debug_loop_gate_records)
+  bool loop_done = false;            // a call has succeeded on this handle
   // stats / trace
   pps_stats stats{};
   std::vector<double> tr_lambda, tr_chi2;
@@ -425,6 +431,8 @@ void gate_release(pps_graph* g);               // (from cov_release)
 void merge_release(pps_graph* g);              // (from cov_release)
 // ---- pps_fgate.cpp ----
 void fgate_release(pps_graph* g);              // (from cov_release)
+// ---- pps_loop.cpp ----
+void loop_release(pps_graph* g);               // (from cov_release)
 // ---- pps_api.cpp ----
 void report_front_trace(pps_graph* g);        // PPS_TRACE: the per-front cycle counters of the last solve -> stderr
 

@@ -73,19 +73,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_gate(DevGraph d, MergeA
     }
     if (ok) {
       // ---- 2. pivots of the common ancestors: a front's root length falls strictly on the way up, so the deeper front cannot be the meeting point ----
-      int fa = ca.front, fb = cb.front, hops = 0;
-      while (fa != fb && fa >= 0 && fb >= 0) {
-        const int la = a.rootlen[fa], lb = a.rootlen[fb];
-        int na = fa, nb = fb;
-        if (la >= lb) na = a.parent[fa];
-        if (lb >= la) nb = a.parent[fb];
-        fa = na; fb = nb;
-        if (fa < -1 || fa >= a.n_fronts || fb < -1 || fb >= a.n_fronts || ++hops > 2 * a.n_fronts) { ok = false; break; }
-      }
-      if (ok) {
-        common = (fa == fb && fa >= 0) ? a.rootlen[fa] : 0;
-        ok = common >= 0 && common <= (len_a < len_b ? len_a : len_b);
-      }
+      ok = common_root_pivots(a.parent, a.rootlen, a.n_fronts, ca.front, cb.front, common) && common >= 0 && common <= (len_a < len_b ? len_a : len_b);
     }
     if (!ok) { if (lane == 0) raise_status(a.status, kStatusInternal); valid = false; }
   }

@@ -66,7 +66,7 @@ def demangle(n):
 
 
 def short_name(mangled):
-    return re.sub(r"\(.*", "", demangle(mangled)).replace("pps::", "").replace("void ", "")
+    return re.sub(r"\(.*", "", demangle(mangled).replace("(anonymous namespace)::", "")).replace("pps::", "").replace("void ", "")
 
 
 # the kernels of DESIGN.md section 5's register table, in its order: (name as the tool prints it, what the row says in addition)
@@ -92,14 +92,15 @@ DESIGN_KERNELS = [
     ("k_linearize_repop_robust<1>", "... Factor2 edges, Huber"), ("k_chi2_robust<1>", "robust chi2 at the stored state"), ("k_chi2_trial_robust<1>", "... of the one-step loop's trial"),
     ("k_linearize_repop_robust<2>", "... Factor2 edges, pseudo-Huber"), ("k_chi2_robust<2>", "robust chi2 at the stored state"), ("k_chi2_trial_robust<2>", "... of the one-step loop's trial"),
     ("k_linearize_repop_robust<3>", "... Factor2 edges, Cauchy"), ("k_chi2_robust<3>", "robust chi2 at the stored state"), ("k_chi2_trial_robust<3>", "... of the one-step loop's trial"),
+    ("k_loop_gate", "pps_loop_gate: a wave per candidate loop closure, DESIGN.md section 5h"),
 ]
 TABLE_BEGIN, TABLE_END = "<!-- kernel-table:begin (tools/kernel_resources.py --update-design) -->", "<!-- kernel-table:end -->"
 
 
 def built_table():
-    """{name: dict} of every kernel of the solver objects the Makefile built"""
+    """{name: dict} of every kernel of the solver objects (and of pps_loop.hip) the Makefile built"""
     out = {}
-    for f in ("pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip", "pps_robust.hip"):
+    for f in ("pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip", "pps_robust.hip", "pps_loop.hip"):
         for r in resources(os.path.join(CSRC, f), [], built=True):
             v = int(r["vgpr_count"])
             out[short_name(r["name"])] = {"vgpr": v, "agpr": int(r["agpr_count"]), "waves": min(8, 512 // max(8, (v + 7) // 8 * 8)),
@@ -151,7 +152,7 @@ def main():
     for f in a.files:
         path = f if os.path.isabs(f) else os.path.join(CSRC, f)
         for r in sorted(resources(path, a.flags.split(), built=a.built), key=lambda r: r["name"]):
-            name = re.sub(r"\(.*", "", demangle(r["name"])).replace("pps::", "").replace("void ", "")
+            name = short_name(r["name"])
             if a.filter and not re.search(a.filter, name):
                 continue
             v, ag = int(r["vgpr_count"]), int(r["agpr_count"])
