@@ -215,7 +215,8 @@ int pps_debug_cov_select_form(pps_graph* g, int form);
  * again: the call reads the factor of the last pps_cov_recover or pps_cov_factor and falls under the same validity rules.
  *   PPS_EINVAL  NULL handle, rows or out; a negative count; an unknown or removed node id; a node twice in rows or twice in cols
  *   PPS_ESTATE  no valid factor (a dense-front graph has one after pps_cov_factor; pps_cov_recover has none to give there)
- *   PPS_ENOMEM  dense-front graphs: no device memory for the right-hand sides of the walks
+ *   PPS_ENOMEM  dense-front graphs: no device memory for the right-hand sides of the walks; any graph: no host memory for the request or
+ *               the result (never an abort)
  *   PPS_OK      with out untouched for nr == 0 or nc == 0
  * pps_cov_marginals / _access / _joint keep their in-pattern contract and their refusals.  Found by symbol lookup, like the calls above. */
 int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols, double* out);
@@ -244,6 +245,7 @@ int pps_cov_block_last(const pps_graph* g, double* kernel_sec, int* launches);
  *               is looked at (nothing is read from it), unlike pps_cov_block, which asks for the recovery first
  *   PPS_ESTATE  no valid factor: the text and the validity rules of pps_cov_block (a dense-front graph: after pps_cov_factor)
  *   PPS_ENOTPD  a pivot of a 3 x 3 factor was not positive or not finite (the outputs are untouched)
+ *   PPS_ENOMEM  as pps_cov_block: the right-hand sides of the walks on the device, the request or the result on the host
  * Mapper_mono::findClosestPlane's geometric gate (pps_find_closest_planes) is independent of this call and unchanged.
  * Found by symbol lookup, like the pps_cov_* calls; PPS_VERSION was not bumped. */
 int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, const double* sqrtinf_ut, int n_planes, const int* plane_ids,

@@ -503,6 +503,20 @@ class Graph:
         self._ck(self.L.pps_cov_joint(self.h, n, i.ctypes.data_as(_ip), out.ctypes.data_as(_dp)))
         return out
 
+    def _records(self, fn):
+        """the records of a query's last call (pps_debug_*_records): one call for the size, one for the doubles; the flat array"""
+        n = C.c_int64(0)
+        self._ck(fn(self.h, 0, None, C.byref(n)))
+        rec = np.zeros(n.value)
+        self._ck(fn(self.h, n.value, rec.ctypes.data_as(_dp), C.byref(n)))
+        return rec
+
+    def _last(self, fn, n_ints):
+        """the figures of a query's last call (pps_*_last): (device seconds, n_ints ints)"""
+        s = C.c_double(); k = [C.c_int() for _ in range(n_ints)]
+        self._ck(fn(self.h, C.byref(s), *[C.byref(i) for i in k]))
+        return (s.value,) + tuple(i.value for i in k)
+
     def cov_block(self, rows, cols=None):
         """Sigma(rows, cols) for ANY node ids, inside the pattern of the factor or not: a (sum dim(rows)) x (sum dim(cols)) array, nodes in
         the order given.  cols None: the joint marginal of rows (exactly symmetric).  One root-path solve per distinct node on the factor
@@ -518,7 +532,7 @@ class Graph:
 
     def cov_block_last(self):
         """(device seconds around the two kernels, kernel launches) of the last cov_block"""
-        s = C.c_double(); n = C.c_int(); self._ck(self.L.pps_cov_block_last(self.h, C.byref(s), C.byref(n))); return s.value, n.value
+        return self._last(self.L.pps_cov_block_last, 1)
 
     def assoc_gate(self, pose_id, meas4, sqrtinf_ut, plane_ids=None):
         """Mahalanobis gate of plane association (pps_assoc_gate): meas4 (M x 4) plane measurements of pose `pose_id` in its sensor frame,
@@ -540,16 +554,12 @@ class Graph:
     def assoc_gate_records(self):
         """diagnostics: (Jw, r) of every candidate of the last assoc_gate as the kernel evaluated them -- Jw (M*L, 3, 9) over pose 6 | plane 3,
         r (M*L, 3), candidates in row-major (measurement, plane) order; the values pps_eval_factor gives for the same factor"""
-        n = C.c_int64(0)
-        self._ck(self.L.pps_debug_assoc_gate_records(self.h, 0, None, C.byref(n)))
-        rec = np.zeros(n.value)
-        self._ck(self.L.pps_debug_assoc_gate_records(self.h, n.value, rec.ctypes.data_as(_dp), C.byref(n)))
-        rec = rec.reshape(-1, 30)
+        rec = self._records(self.L.pps_debug_assoc_gate_records).reshape(-1, 30)
         return np.concatenate([rec[:, :18].reshape(-1, 3, 6), rec[:, 18:27].reshape(-1, 3, 3)], axis=2), rec[:, 27:].copy()
 
     def assoc_gate_last(self):
         """(device seconds around the two kernels, kernel launches) of the last assoc_gate"""
-        s = C.c_double(); n = C.c_int(); self._ck(self.L.pps_assoc_gate_last(self.h, C.byref(s), C.byref(n))); return s.value, n.value
+        return self._last(self.L.pps_assoc_gate_last, 1)
 
     def merge_gate(self, plane_ids=None, floor_var=0.0, threshold=7.815, want_d2=True):
         """Mahalanobis merge gate between plane landmarks (pps_merge_gate): are two landmarks the same wall?  plane_ids: the n planes
@@ -577,17 +587,12 @@ class Graph:
         """diagnostics: (J_a, J_b, e) of every pair of the last merge_gate as the kernel evaluated them -- (P, 3, 3), (P, 3, 3), (P, 3), pair
         (i < j) at index i n - i (i + 1) / 2 + (j - i - 1); J_a and e are pps_eval_factor's of a plane prior on a with measurement pi_b,
         J_b the negated Jacobian of the mirrored prior"""
-        n = C.c_int64(0)
-        self._ck(self.L.pps_debug_merge_gate_records(self.h, 0, None, C.byref(n)))
-        rec = np.zeros(n.value)
-        self._ck(self.L.pps_debug_merge_gate_records(self.h, n.value, rec.ctypes.data_as(_dp), C.byref(n)))
-        rec = rec.reshape(-1, 21)
+        rec = self._records(self.L.pps_debug_merge_gate_records).reshape(-1, 21)
         return rec[:, :9].reshape(-1, 3, 3).copy(), rec[:, 9:18].reshape(-1, 3, 3).copy(), rec[:, 18:].copy()
 
     def merge_gate_last(self):
         """(device seconds around the two kernels, kernel launches, pairs whose S was not positive definite) of the last merge_gate"""
-        s = C.c_double(); n = C.c_int(); k = C.c_int()
-        self._ck(self.L.pps_merge_gate_last(self.h, C.byref(s), C.byref(n), C.byref(k))); return s.value, n.value, k.value
+        return self._last(self.L.pps_merge_gate_last, 2)
 
     def loop_gate(self, pose_a, pose_b, meas6, sqrtinf_ut, threshold=12.592, want_S=False):
         """Mahalanobis gate for loop-closure candidates between poses (pps_loop_gate): may this relative-pose measurement be added as a
@@ -612,17 +617,12 @@ class Graph:
     def loop_gate_records(self):
         """diagnostics: (Jw, r) of every candidate of the last loop_gate as the kernel evaluated them -- (n, 6, 12) and (n, 6), columns of
         pose a then of pose b: what pps_eval_factor gives for the candidate added as an odometry factor"""
-        n = C.c_int64(0)
-        self._ck(self.L.pps_debug_loop_gate_records(self.h, 0, None, C.byref(n)))
-        rec = np.zeros(n.value)
-        self._ck(self.L.pps_debug_loop_gate_records(self.h, n.value, rec.ctypes.data_as(_dp), C.byref(n)))
-        rec = rec.reshape(-1, 78)
+        rec = self._records(self.L.pps_debug_loop_gate_records).reshape(-1, 78)
         return rec[:, :72].reshape(-1, 6, 12).copy(), rec[:, 72:].copy()
 
     def loop_gate_last(self):
         """(device seconds around the two kernels, kernel launches, candidates whose S was not positive definite) of the last loop_gate"""
-        s = C.c_double(); n = C.c_int(); k = C.c_int()
-        self._ck(self.L.pps_loop_gate_last(self.h, C.byref(s), C.byref(n), C.byref(k))); return s.value, n.value, k.value
+        return self._last(self.L.pps_loop_gate_last, 2)
 
     def factor_gate(self, fids=None, thr3=7.815, thr6=12.592):
         """Leave-one-out chi-square test of the graph's own factors (pps_factor_gate): which factor already in the graph is wrong?  fids:
@@ -644,16 +644,11 @@ class Graph:
         """diagnostics: J and r of every entry of the last factor_gate as the kernel evaluated them -- (n, 78), one slot per entry holding
         [J m x c row-major, packed | r m] (the rest of the slot unspecified), columns of the factor's first node, then of its second:
         slot[:m * c].reshape(m, c) and slot[m * c:m * c + m] are what pps_eval_factor gives for the factor"""
-        n = C.c_int64(0)
-        self._ck(self.L.pps_debug_factor_gate_records(self.h, 0, None, C.byref(n)))
-        rec = np.zeros(n.value)
-        self._ck(self.L.pps_debug_factor_gate_records(self.h, n.value, rec.ctypes.data_as(_dp), C.byref(n)))
-        return rec.reshape(-1, 78)
+        return self._records(self.L.pps_debug_factor_gate_records).reshape(-1, 78)
 
     def factor_gate_last(self):
         """(device seconds around the kernel, kernel launches, untestable entries) of the last factor_gate"""
-        s = C.c_double(); n = C.c_int(); k = C.c_int()
-        self._ck(self.L.pps_factor_gate_last(self.h, C.byref(s), C.byref(n), C.byref(k))); return s.value, n.value, k.value
+        return self._last(self.L.pps_factor_gate_last, 2)
 
     def cov_last_times(self):
         """device seconds of the last cov_recover or cov_select: (whole call, root -> leaves pass alone); of the last cov_factor: (whole call, 0)"""

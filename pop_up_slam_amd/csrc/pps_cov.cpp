@@ -15,10 +15,9 @@
 // Every entry of Sigma inside the pattern of L is available: the diagonal block of every node and the cross block of every pair of nodes
 // that share a front (in particular every pair joined by a factor).  A recovery stays valid until the estimate, the measurements or the
 // topology change (cov_invalidate, pps_graph.h); the read calls then answer PPS_ESTATE.
-//   pps_cov_block      Sigma(rows, cols) for ANY nodes: (L^-1 E_rows)' (L^-1 E_cols) by one walk up the elimination tree per distinct node
-//                      and one Gram product over common ancestors (pps_cov.hip) -- one upload, two launches, one copy, whatever the query.
-//                      The walk half is CovQuery (pps_graph.h), which pps_assoc_gate and pps_merge_gate run with kernels of their own
-// pps_cov_block reads the lambda = 0 factor the recovery leaves in dev.L.  dev.L is written by the factorisations alone (pps_solve.cpp:
+// The five calls that question what a recovery leaves -- pps_cov_block and the gates -- are in pps_query.cpp and the gates' own files (the
+// protocol: pps_query.h).  All but pps_factor_gate read the lambda = 0 factor the recovery leaves in dev.L.
+// dev.L is written by the factorisations alone (pps_solve.cpp:
 // enqueue_factor_solve and do_solve, reached from pps_update, pps_batch_optimize and pps_debug_solve; the pps_multi launches), and each of those callers
 // ends the recovery.  What keeps it -- pps_chi2 (K4 reads the states), the getters and pps_save_state (state copies), pps_eval_factor and
 // pps_time_linearize (K1: J and the linearisation point), pps_get_stats / pps_get_trace (host fields), pps_analysis_dump, the
@@ -33,15 +32,13 @@ namespace pps_impl {
 
 void cov_release(pps_graph* g) {
   g->cov_S.release(); g->cov_parent.release(); g->cov_req.release(); g->cov_out.release(); g->cov_breq.release(); g->cov_strip.release();
-  g->cov_bout.release(); g->cov_zscr.release(); g->cov_G.release(); g->cov_dtab.release();
-  gate_release(g);
-  merge_release(g);
-  fgate_release(g);
-  loop_release(g);
+  g->cov_zscr.release(); g->cov_G.release(); g->cov_dtab.release();
+  for (QueryState* st : {&g->q_block, &g->q_assoc, &g->q_merge, &g->q_loop, &g->q_factor}) st->release();
+  g->fgate_tab.release(); g->fgate_list.release();
+  g->fgate_tab_version = -1; g->fgate_tab_n = 0;
   for (hipEvent_t& e : g->cov_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   for (hipEvent_t& e : g->cov_qev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
   g->cov_cache = pps_graph::CovCache{};
-  g->cov_bout_clean = false;
   g->cov_valid = g->cov_factor_valid = false;
 }
 
@@ -106,130 +103,6 @@ static int cov_fetch(pps_graph* g, const std::vector<CovReq>& req, size_t n_out,
   HIP_TRY(g, hipMemcpyAsync(g->cov_req.p, req.data(), req.size() * sizeof(CovReq), hipMemcpyHostToDevice, g->stream));
   HIP_TRY(g, launch_cov_gather(g->cov_S.p, reinterpret_cast<const CovReq*>(g->cov_req.p), (int)req.size(), g->cov_out.p, g->stream));
   HIP_TRY(g, hipMemcpyAsync(host, g->cov_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  return PPS_OK;
-}
-
-static bool cov_walk_wide(const pps_graph* g) {
-  return g->cov_path_form == 1 || cov_path_lds_bytes(g->cov_max_p, g->cov_max_rows) > (size_t)64 * 1024;
-}
-
-int CovQuery::build(const std::vector<int>& ids) {
-  const Analysis& A = g->an;
-  const int nw = (int)ids.size();
-  nd.assign((size_t)nw, CovNode{});
-  K = 0;
-  for (int w = 0; w < nw; w++) {
-    int rc = cov_node(g, ids[w], &nd[w]); if (rc != PPS_OK) return rc;
-    rc = cov_locate(g, ids[w], &nd[w]); if (rc != PPS_OK) return rc;
-    K = std::max(K, g->cov_rootlen[nd[w].front]);
-  }
-  walks.assign((size_t)nw, CovWalk{});
-  steps.clear();
-  step_end.assign((size_t)nw, 0);
-  n_strip = 0;
-  max_rows = 1;
-  for (int w = 0; w < nw; w++) {
-    walks[w] = CovWalk{n_strip, (int)steps.size(), 0, nd[w].local, nd[w].dim};
-    for (int s = nd[w].front; s >= 0; s = A.f_parent[s]) {
-      steps.push_back(CovStep{s, K - g->cov_rootlen[s]});
-      max_rows = std::max(max_rows, A.f_p[s] + A.f_b[s]);
-    }
-    walks[w].n_steps = (int)steps.size() - walks[w].step0;
-    step_end[w] = (int)steps.size();
-    n_strip += (long long)K * nd[w].dim;
-  }
-  o_steps = walks.size() * sizeof(CovWalk);
-  req.assign(o_steps + steps.size() * sizeof(CovStep), 0);
-  if (!walks.empty()) memcpy(req.data(), walks.data(), o_steps);
-  if (!steps.empty()) memcpy(req.data() + o_steps, steps.data(), steps.size() * sizeof(CovStep));
-  return PPS_OK;
-}
-
-// the pivots two paths have in common are a suffix of both
-int CovQuery::common_pivots(int a, int b) const {
-  int len = 0;
-  for (int i = step_end[a] - 1, j = step_end[b] - 1; i >= walks[a].step0 && j >= walks[b].step0 && steps[i].front == steps[j].front; i--, j--)
-    len += g->an.f_p[steps[i].front];
-  return len;
-}
-
-size_t CovQuery::add(const void* data, size_t bytes) {
-  const size_t off = up16(req.size());
-  req.resize(off + bytes, 0);
-  if (bytes) memcpy(req.data() + off, data, bytes);
-  return off;
-}
-
-// (cov_breq / cov_strip / cov_qev are shared by all queries: every one ends with a synchronisation, none is in flight here)
-int CovQuery::reserve(const char* who, const char* advice) {
-  HIP_TRY(g, hipSetDevice(g->props.device));
-  for (hipEvent_t& e : g->cov_qev) if (!e) HIP_TRY(g, hipEventCreate(&e));
-  int rc = g->cov_breq.reserve(g, req.size(), who, "the request", advice); if (rc != PPS_OK) return rc;
-  rc = g->cov_strip.reserve(g, (size_t)n_strip, who, "the strips", advice); if (rc != PPS_OK) return rc;
-  if (!cov_walk_wide(g) || walks.empty()) return PPS_OK;
-  // k_cov_path_wide: its right-hand sides, before the query's upload
-  const size_t want = walks.size() * cov_wide_scratch(max_rows);
-  if (want <= g->cov_zscr.cap && g->cov_zscr.p) return PPS_OK;
-  HIP_TRY(g, hipStreamSynchronize(g->stream));           // (so that what the reservation can still fail with is the allocation)
-  return g->cov_zscr.reserve(g, want, "covariance path solves: ", "the right-hand sides of " + std::to_string(walks.size()) + " walks through fronts of up to " +
-                                                                  std::to_string(max_rows) + " rows", ": ask for fewer nodes per call");
-}
-
-// k_cov_path where its LDS fits the graph's fronts, k_cov_path_wide otherwise (or when the handle asks for it)
-int CovQuery::walk(double* status) {
-  launches0 = launch_count();
-  HIP_TRY(g, hipMemcpyAsync(g->cov_breq.p, req.data(), req.size(), hipMemcpyHostToDevice, g->stream));
-  HIP_TRY(g, hipEventRecord(g->cov_qev[0], g->stream));
-  const int nw = (int)walks.size(), ns = (int)steps.size();
-  const CovWalk* w = dev<CovWalk>(0);
-  const CovStep* s = dev<CovStep>(o_steps);
-  if (cov_walk_wide(g))
-    HIP_TRY(g, launch_cov_path_wide(g->dev, w, nw, s, ns, K, max_rows, g->cov_zscr.p, (long long)g->cov_zscr.cap, g->cov_strip.p, n_strip, status, g->stream));
-  else
-    HIP_TRY(g, launch_cov_path(g->dev, w, nw, s, ns, K, g->cov_max_p, g->cov_max_rows, g->cov_strip.p, n_strip, status, g->stream));
-  return PPS_OK;
-}
-
-int CovQuery::finish(void* host, const void* dev_src, size_t bytes, double* sec, int* launches) {
-  HIP_TRY(g, hipEventRecord(g->cov_qev[1], g->stream));
-  HIP_TRY(g, hipMemcpyAsync(host, dev_src, bytes, hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  *launches = (int)(launch_count() - launches0);
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, g->cov_qev[0], g->cov_qev[1]) == hipSuccess) *sec = 1e-3 * ms;
-  return PPS_OK;
-}
-
-int plane_list(pps_graph* g, const char* prefix, const int** ids, int* n, std::vector<int>* all) {
-  if (!*ids) {
-    for (size_t i = 0; i < g->nodes.size(); i++) if (!g->nodes[i].deleted && g->nodes[i].type == NODE_PLANE) all->push_back((int)i);
-    *ids = all->data(); *n = (int)all->size();
-  }
-  std::vector<char> seen(g->nodes.size(), 0);
-  for (int i = 0; i < *n; i++) {
-    const int id = (*ids)[i];
-    if (!live_node(g, id, NODE_PLANE)) return fail(g, PPS_EINVAL, prefix + ("node " + std::to_string(id)) + " is not a live plane");
-    if (seen[id]) return fail(g, PPS_EINVAL, prefix + ("plane " + std::to_string(id)) + " is listed twice");
-    seen[id] = 1;
-  }
-  return PPS_OK;
-}
-
-int zero_between_calls(pps_graph* g, bool* clean, void* out, bool out_new, size_t status_bytes, DevBuf<unsigned int>* ticket, bool ticket_new) {
-  if (!*clean || out_new || ticket_new) {
-    HIP_TRY(g, hipMemsetAsync(out, 0, status_bytes, g->stream));
-    if (ticket) HIP_TRY(g, hipMemsetAsync(ticket->p, 0, ticket->cap * sizeof(unsigned int), g->stream));
-  }
-  *clean = false;
-  return PPS_OK;
-}
-
-int copy_records(pps_graph* g, const DevBuf<double>& rec, size_t n, int64_t cap, double* out, int64_t* needed) {
-  *needed = (int64_t)n;
-  if (!out || cap < *needed) return PPS_OK;
-  HIP_TRY(g, hipSetDevice(g->props.device));
-  HIP_TRY(g, hipMemcpyAsync(out, rec.p, n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
   HIP_TRY(g, hipStreamSynchronize(g->stream));
   return PPS_OK;
 }
@@ -461,13 +334,6 @@ int pps_cov_last_times(const pps_graph* g, double sec[2]) {
   return PPS_OK;
 }
 
-int pps_cov_block_last(const pps_graph* g, double* kernel_sec, int* launches) {
-  if (!g) return PPS_EINVAL;
-  if (kernel_sec) *kernel_sec = g->cov_block_sec;
-  if (launches) *launches = g->cov_block_launches;
-  return PPS_OK;
-}
-
 int pps_cov_marginals(pps_graph* g, int n, const int* ids, double* out, int64_t* offsets) {
   if (!g || !out || n < 0) return PPS_EINVAL;
   std::vector<int> all;
@@ -557,63 +423,6 @@ int pps_cov_joint(pps_graph* g, int n, const int* ids, double* out) {
         out[(size_t)(off[j] + c) * N + off[i] + a] = blk[a * nd[j].dim + c];
       }
   }
-  return PPS_OK;
-}
-
-int pps_cov_block(pps_graph* g, int nr, const int* rows, int nc, const int* cols, double* out) {
-  if (!g || !rows || !out || nr < 0 || (cols && nc < 0)) return PPS_EINVAL;
-  const bool joint = cols == nullptr;
-  if (joint) { cols = rows; nc = nr; }
-  // distinct nodes of the query: every one is walked once, however often it is asked for
-  std::vector<int> walk_of(g->nodes.size(), -1), ids, ri((size_t)nr), ci((size_t)nc);
-  for (int pass = 0; pass < (joint ? 1 : 2); pass++) {
-    const int n = pass ? nc : nr;
-    const int* list = pass ? cols : rows;
-    std::vector<char> seen(g->nodes.size(), 0);
-    for (int i = 0; i < n; i++) {
-      CovNode c;
-      const int rc = cov_node(g, list[i], &c); if (rc != PPS_OK) return rc;
-      if (seen[list[i]]) return fail(g, PPS_EINVAL, "covariance block: node " + std::to_string(list[i]) + " is listed twice among the " + (pass ? "columns" : "rows"));
-      seen[list[i]] = 1;
-      if (walk_of[list[i]] < 0) { walk_of[list[i]] = (int)ids.size(); ids.push_back(list[i]); }
-      (pass ? ci : ri)[i] = walk_of[list[i]];
-    }
-  }
-  if (joint) ci = ri;
-  if (!cov_factor_current(g)) return fail(g, PPS_ESTATE, kNoRecovery);
-  if (nr == 0 || nc == 0) return PPS_OK;
-  CovQuery q(g);
-  int rc = q.build(ids); if (rc != PPS_OK) return rc;
-  const std::vector<CovNode>& nd = q.nd;
-  std::vector<int> roff((size_t)nr + 1, 0), coff((size_t)nc + 1, 0);
-  for (int i = 0; i < nr; i++) roff[i + 1] = roff[i] + nd[ri[i]].dim;
-  for (int j = 0; j < nc; j++) coff[j + 1] = coff[j] + nd[ci[j]].dim;
-  const int ld = coff[nc];
-  const long long n_out = (long long)roff[nr] * ld;
-  std::vector<CovPair> pairs;
-  pairs.reserve(joint ? (size_t)nr * (nr + 1) / 2 : (size_t)nr * nc);
-  for (int i = 0; i < nr; i++)
-    for (int j = 0; j < (joint ? i + 1 : nc); j++) {
-      const int a = ri[i], b = ci[j], len = q.common_pivots(a, b);
-      CovPair pr;
-      pr.yi = q.walks[a].strip + (long long)(q.K - len) * nd[a].dim; pr.yj = q.walks[b].strip + (long long)(q.K - len) * nd[b].dim;
-      pr.dst = (long long)roff[i] * ld + coff[j];
-      pr.dst_t = joint ? (long long)roff[j] * ld + coff[i] : -1;          // (cols = rows: the lower triangle, mirrored)
-      pr.di = nd[a].dim; pr.dj = nd[b].dim; pr.len = len; pr.ld = ld;
-      pairs.push_back(pr);
-    }
-  const size_t o_pairs = q.add(pairs.data(), pairs.size() * sizeof(CovPair));
-  rc = q.reserve(); if (rc != PPS_OK) return rc;
-  const size_t bout_cap = g->cov_bout.cap;
-  rc = g->cov_bout.reserve(g, (size_t)n_out + 1); if (rc != PPS_OK) return rc;
-  rc = zero_between_calls(g, &g->cov_bout_clean, g->cov_bout.p, g->cov_bout.cap != bout_cap, sizeof(double), nullptr, false); if (rc != PPS_OK) return rc;
-  rc = q.walk(g->cov_bout.p); if (rc != PPS_OK) return rc;
-  HIP_TRY(g, launch_cov_gram(q.dev<CovPair>(o_pairs), (int)pairs.size(), g->cov_strip.p, q.n_strip, g->cov_bout.p, n_out, g->stream));
-  std::vector<double> host((size_t)n_out + 1);
-  rc = q.finish(host.data(), g->cov_bout.p, host.size() * sizeof(double), &g->cov_block_sec, &g->cov_block_launches); if (rc != PPS_OK) return rc;
-  if (host[0] != 0.0) return fail(g, PPS_EHIP, "internal error: a covariance path solve met an index outside its front or its strip");
-  g->cov_bout_clean = true;
-  memcpy(out, host.data() + 1, (size_t)n_out * sizeof(double));
   return PPS_OK;
 }
 

@@ -7,28 +7,22 @@
 // own.  Every pair joined by a factor lies in the pattern of L, so the three blocks of Sigma_ff are looked up like pps_cov_access looks its
 // blocks up (cov_locate, cov_request) -- once per analysis: the table of all factors stays on the device until the next upload, a second
 // call after the same recovery uploads the fid list alone.  ONE launch (pps_fgate.hip), one copy back ([d2 | lev | status]); the flagged
-// list and the count of untestable entries are made on the host from it.  Validity: that of pps_cov_marginals (cov_current: the selected
-// inverse of pps_cov_recover or pps_cov_select).
+// list and the count of untestable entries are made on the host from it.  The call state, the timed launch and the _last / _records entry points
+// are those of the queries on the factor (pps_query.h), without a walk; what is written here is the call's own: the argument checks, the table,
+// the kernel's arguments and the decoding of the result.  Validity: that of pps_cov_marginals (cov_current: the selected inverse of
+// pps_cov_recover or pps_cov_select).
 #include "pps_fgate.h"
-#include "pps_graph.h"
+#include "pps_query.h"
 
 using namespace pps;
 using namespace pps_impl;
-
-namespace pps_impl {
-
-void fgate_release(pps_graph* g) {
-  g->fgate_tab.release(); g->fgate_list.release(); g->fgate_out.release(); g->fgate_rec.release();
-  g->fgate_tab_version = -1; g->fgate_tab_n = 0; g->fgate_rec_n = 0;
-}
-
-}  // namespace pps_impl
 
 namespace {
 
 // records are kept for calls of at most this many entries (78 doubles each: 41 MB)
 constexpr int kFgateRecMaxEntries = 65536;
 
+const char* const kName = "factor gate";
 const char* const kWho = "factor gate: ";
 const char* const kAdvice = ": list fewer factors per call";
 
@@ -84,29 +78,20 @@ int table_current(pps_graph* g) {
 extern "C" {
 
 int pps_factor_gate_last(const pps_graph* g, double* kernel_sec, int* launches, int* n_untestable) {
-  if (!g) return PPS_EINVAL;
-  if (kernel_sec) *kernel_sec = g->fgate_sec;
-  if (launches) *launches = g->fgate_launches;
-  if (n_untestable) *n_untestable = g->fgate_untestable;
-  return PPS_OK;
+  return query_last(g, &pps_graph::q_factor, kernel_sec, launches, n_untestable);
 }
 
 int pps_debug_factor_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed) {
-  if (!g || !needed) return PPS_EINVAL;
-  if (!g->fgate_done) return fail(g, PPS_ESTATE, "no factor gate has been computed on this handle");
-  if (g->fgate_rec_n == 0 || !g->fgate_rec.p)
-    return fail(g, PPS_ESTATE, "factor gate: the records are kept for calls of at most " + std::to_string(kFgateRecMaxEntries) + " entries; the last call had more");
-  return copy_records(g, g->fgate_rec, g->fgate_rec_n * kFgateRecord, cap, rec, needed);
+  return query_records(g, &pps_graph::q_factor, kFgateRecord, kName, kFgateRecMaxEntries, "entries", cap, rec, needed);
 }
 
 int pps_factor_gate(pps_graph* g, int n, const int* fids, double thr3, double thr6, double* d2, double* leverage, int cap_flagged, int* flagged,
-                    int* n_flagged) {
+                    int* n_flagged) try {
   if (!g) return PPS_EINVAL;
   if (fids && n < 0) return fail(g, PPS_EINVAL, "factor gate: negative factor count");
   if (cap_flagged < 0) return fail(g, PPS_EINVAL, "factor gate: negative cap_flagged");
   if (!d2 && !leverage && !flagged && !n_flagged) return fail(g, PPS_EINVAL, "factor gate: no output asked for (d2, leverage and flagged / n_flagged are all NULL)");
-  if ((flagged && !n_flagged) || (!flagged && n_flagged && cap_flagged > 0))
-    return fail(g, PPS_EINVAL, "factor gate: flagged and n_flagged go together (flagged may be NULL with cap_flagged 0: the count alone)");
+  int rc = list_with_count(g, kWho, "flagged", flagged, n_flagged, cap_flagged); if (rc != PPS_OK) return rc;
   if (n_flagged && (!std::isfinite(thr3) || !std::isfinite(thr6))) return fail(g, PPS_EINVAL, "factor gate: the thresholds must be finite");
   std::vector<int> all;
   if (!fids) {
@@ -119,42 +104,33 @@ int pps_factor_gate(pps_graph* g, int n, const int* fids, double thr3, double th
   if (robust(g)) return fail(g, PPS_ESTATE, "factor gate: a robust cost function is set (pps_set_cost_function); the test has no robustified form -- set PPS_COST_NONE and recover again");
   if (n == 0) return PPS_OK;                               // nothing asked for: the outputs stay untouched, the recovery is not looked at
   if (!cov_current(g)) return fail(g, PPS_ESTATE, cov_factor_current(g) ? kFactorOnly : kNoRecovery);
-  HIP_TRY(g, hipSetDevice(g->props.device));
-  for (hipEvent_t& e : g->cov_qev) if (!e) HIP_TRY(g, hipEventCreate(&e));
-  int rc = table_current(g); if (rc != PPS_OK) return rc;
-  // the result: [d2 n | lev n | status: n ints]
+  rc = query_device(g); if (rc != PPS_OK) return rc;
+  rc = table_current(g); if (rc != PPS_OK) return rc;
+  // the result: [d2 n | lev n | status: n ints], doubles; no status word
   const size_t n_out = 2 * (size_t)n + ((size_t)n + 1) / 2;
   rc = g->fgate_list.reserve(g, (size_t)n, kWho, "the factor list", kAdvice); if (rc != PPS_OK) return rc;
-  rc = g->fgate_out.reserve(g, n_out, kWho, "the result", kAdvice); if (rc != PPS_OK) return rc;
-  g->fgate_rec_n = 0; g->fgate_done = false;
   const bool keep_rec = n <= kFgateRecMaxEntries;
-  if (keep_rec) { rc = g->fgate_rec.reserve(g, (size_t)n * kFgateRecord, kWho, "the records", kAdvice); if (rc != PPS_OK) return rc; }
-  std::vector<double> host;
-  try { host.resize(n_out); } catch (const std::bad_alloc&) { return fail(g, PPS_ENOMEM, "factor gate: no host memory for the result"); }
+  QueryState& st = g->q_factor;
+  rc = query_begin(g, &st, n_out * sizeof(double), 0, 0, keep_rec ? (size_t)n * kFgateRecord : kNoRecords, kWho, kAdvice); if (rc != PPS_OK) return rc;
+  double* const out = reinterpret_cast<double*>(st.out.p);
+  std::vector<double> host(n_out);
   FgateArgs fa;
   fa.factors = reinterpret_cast<const FgateFactor*>(g->fgate_tab.p); fa.n_factors = g->fgate_tab_n;
   fa.list = g->fgate_list.p; fa.n = n;
   fa.S = g->cov_S.p; fa.n_S = std::min<long long>((long long)g->an.L_size, (long long)g->cov_S.cap);
   fa.mode = g->props.jacobian_mode;
-  fa.d2 = g->fgate_out.p; fa.lev = g->fgate_out.p + n; fa.status = reinterpret_cast<int*>(g->fgate_out.p + 2 * (size_t)n);
-  fa.rec = keep_rec ? g->fgate_rec.p : nullptr;
-  const unsigned long long launches0 = launch_count();
+  fa.d2 = out; fa.lev = out + n; fa.status = reinterpret_cast<int*>(out + 2 * (size_t)n);
+  fa.rec = keep_rec ? st.rec.p : nullptr;
+  QueryTimer timer{g, 0};
   HIP_TRY(g, hipMemcpyAsync(g->fgate_list.p, fids, (size_t)n * sizeof(int), hipMemcpyHostToDevice, g->stream));
-  HIP_TRY(g, hipEventRecord(g->cov_qev[0], g->stream));
+  rc = timer.start(); if (rc != PPS_OK) return rc;
   HIP_TRY(g, launch_factor_gate(g->dev, fa, g->stream));
-  HIP_TRY(g, hipEventRecord(g->cov_qev[1], g->stream));
-  HIP_TRY(g, hipMemcpyAsync(host.data(), g->fgate_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  g->fgate_launches = (int)(launch_count() - launches0);
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, g->cov_qev[0], g->cov_qev[1]) == hipSuccess) g->fgate_sec = 1e-3 * ms;
+  rc = timer.stop(host.data(), n_out * sizeof(double), &st); if (rc != PPS_OK) return rc;
   const double* h_d2 = host.data();
   const double* h_lev = host.data() + n;
   const int* h_status = reinterpret_cast<const int*>(host.data() + 2 * (size_t)n);
   for (int i = 0; i < n; i++)
     if (h_status[i] != 0) return fail(g, PPS_EHIP, "internal error: the factor gate met an index outside its table, the state arrays or the selected inverse");
-  g->fgate_done = true;
-  g->fgate_rec_n = keep_rec ? (size_t)n : 0;
   int untestable = 0;
   long long over = 0;
   for (int i = 0; i < n; i++) {
@@ -164,11 +140,13 @@ int pps_factor_gate(pps_graph* g, int n, const int* fids, double thr3, double th
       over++;
     }
   }
-  g->fgate_untestable = untestable;
+  query_end(&st, keep_rec ? (size_t)n : 0, untestable);
   if (n_flagged) *n_flagged = (int)over;
   if (d2) memcpy(d2, h_d2, (size_t)n * sizeof(double));
   if (leverage) memcpy(leverage, h_lev, (size_t)n * sizeof(double));
   return PPS_OK;
+} catch (const std::bad_alloc&) {
+  return query_no_memory(g, kWho);
 }
 
 }  // extern "C"

@@ -5,49 +5,39 @@
 // a pairing is accepted when d2 is below a chi-square quantile (3 degrees of freedom: 7.815 at 0.95).
 //
 // The candidate factors are never added: the call reads the estimate and the lambda = 0 factor pps_cov_recover left in dev.L, and writes
-// buffers of its own.  A CovQuery (pps_graph.h) over the 1 + n_planes distinct nodes does the protocol -- one request upload, the walk launch of
-// pps_cov_block, the copy back ([status | d2 | best]) --; what is written here are the argument checks, the request's candidate and measurement
-// sections, the arguments of the gate launch (pps_gate.hip) and the decoding of the result.  Validity: that of pps_cov_block
-// (cov_factor_current: a factor of any of the three recovery calls).
+// buffers of its own.  A query on the factor by the protocol of pps_query.h, over the 1 + n_planes distinct nodes; what is written here is the call's
+// own: the argument checks, the request's candidate and measurement sections, the arguments of the gate launch (pps_gate.hip) and the decoding of
+// the result ([status | d2 | best]).  Validity: that of pps_cov_block (cov_factor_current: a factor of any of the three recovery calls).
 #include "pps_gate.h"
-#include "pps_graph.h"
+#include "pps_query.h"
 
 using namespace pps;
 using namespace pps_impl;
 
-namespace pps_impl {
+namespace {
 
-void gate_release(pps_graph* g) {
-  g->gate_out.release(); g->gate_ticket.release(); g->gate_rec.release();
-  g->gate_rec_n = 0; g->gate_clean = false;
-}
+const char* const kName = "association gate";
+const char* const kWho = "association gate: ";
 
-}  // namespace pps_impl
+}  // namespace
 
 extern "C" {
 
-int pps_assoc_gate_last(const pps_graph* g, double* kernel_sec, int* launches) {
-  if (!g) return PPS_EINVAL;
-  if (kernel_sec) *kernel_sec = g->gate_sec;
-  if (launches) *launches = g->gate_launches;
-  return PPS_OK;
-}
+int pps_assoc_gate_last(const pps_graph* g, double* kernel_sec, int* launches) { return query_last(g, &pps_graph::q_assoc, kernel_sec, launches, nullptr); }
 
 int pps_debug_assoc_gate_records(pps_graph* g, int64_t cap, double* rec, int64_t* needed) {
-  if (!g || !needed) return PPS_EINVAL;
-  if (g->gate_rec_n == 0 || !g->gate_rec.p) return fail(g, PPS_ESTATE, "no association gate has been computed on this handle");
-  return copy_records(g, g->gate_rec, g->gate_rec_n * 30, cap, rec, needed);
+  return query_records(g, &pps_graph::q_assoc, 30, kName, 0, "", cap, rec, needed);
 }
 
 int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, const double* sqrtinf_ut, int n_planes, const int* plane_ids,
-                   double* d2, int* best) {
+                   double* d2, int* best) try {
   if (!g || !meas4 || !sqrtinf_ut || !d2 || n_meas < 0 || (plane_ids && n_planes < 0)) return PPS_EINVAL;
   if (!live_node(g, pose_id, NODE_POSE)) return fail(g, PPS_EINVAL, "association gate: node " + std::to_string(pose_id) + " is not a live pose");
   if (n_meas > 65535) return fail(g, PPS_EINVAL, "association gate: more than 65535 measurements in one call");
   // the candidates' r and Jw are the squared-error ones; with a cost function the recovered covariance is that of the robustified system
   if (robust(g)) return fail(g, PPS_ESTATE, "association gate: a robust cost function is set (pps_set_cost_function); the gate has no robustified form -- set PPS_COST_NONE and recover again");
   std::vector<int> all;
-  { const int rc = plane_list(g, "association gate: ", &plane_ids, &n_planes, &all); if (rc != PPS_OK) return rc; }
+  { const int rc = plane_list(g, kWho, &plane_ids, &n_planes, &all); if (rc != PPS_OK) return rc; }
   // measurements: normalised like Plane3d(Vector4d), as pps_add_plane_obs stores them
   std::vector<double> meas((size_t)n_meas * 10);
   for (int i = 0; i < n_meas; i++) {
@@ -71,32 +61,29 @@ int pps_assoc_gate(pps_graph* g, int pose_id, int n_meas, const double* meas4, c
   const size_t o_cand = q.add(cand.data(), cand.size() * sizeof(GatePlane)), o_meas = q.add(meas.data(), meas.size() * sizeof(double));
   const size_t n_d2 = (size_t)n_meas * n_planes, n_out = 1 + n_d2 + ((size_t)n_meas + 1) / 2;      // doubles: status | d2 | best (ints)
   rc = q.reserve(); if (rc != PPS_OK) return rc;
-  const size_t out_cap = g->gate_out.cap, ticket_cap = g->gate_ticket.cap;
-  rc = g->gate_out.reserve(g, n_out); if (rc != PPS_OK) return rc;
-  rc = g->gate_ticket.reserve(g, (size_t)n_meas); if (rc != PPS_OK) return rc;
-  g->gate_rec_n = 0;
-  rc = g->gate_rec.reserve(g, n_d2 * 30); if (rc != PPS_OK) return rc;
-  rc = zero_between_calls(g, &g->gate_clean, g->gate_out.p, g->gate_out.cap != out_cap, sizeof(double), &g->gate_ticket, g->gate_ticket.cap != ticket_cap);
-  if (rc != PPS_OK) return rc;
+  QueryState& st = g->q_assoc;
+  rc = query_begin(g, &st, n_out * sizeof(double), sizeof(double), (size_t)n_meas, n_d2 * 30); if (rc != PPS_OK) return rc;
+  double* const out = reinterpret_cast<double*>(st.out.p);
   GateArgs ga;
   ga.planes = q.dev<GatePlane>(o_cand); ga.n_planes = n_planes;
   ga.meas = q.dev<double>(o_meas); ga.n_meas = n_meas;
   ga.strip_x = q.walks[0].strip; ga.pose_slot = g->nodes[pose_id].slot; ga.rootlen_x = g->cov_rootlen[q.nd[0].front];
   ga.K = q.K; ga.Y = g->cov_strip.p; ga.n_strip = q.n_strip;
   ga.mode = g->props.jacobian_mode;
-  ga.ticket = g->gate_ticket.p; ga.out = g->gate_out.p; ga.rec = g->gate_rec.p;
-  rc = q.walk(g->gate_out.p); if (rc != PPS_OK) return rc;
+  ga.ticket = st.ticket.p; ga.out = out; ga.rec = st.rec.p;
+  rc = q.walk(out); if (rc != PPS_OK) return rc;
   HIP_TRY(g, launch_assoc_gate(g->dev, ga, g->stream));
   std::vector<double> host(n_out);
-  rc = q.finish(host.data(), g->gate_out.p, n_out * sizeof(double), &g->gate_sec, &g->gate_launches); if (rc != PPS_OK) return rc;
+  rc = q.finish(host.data(), n_out * sizeof(double), &st); if (rc != PPS_OK) return rc;
   if (host[0] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: the association gate met an index outside its front, its strip or the state arrays");
   if (host[0] != 0.0)
     return fail(g, PPS_ENOTPD, "association gate: the innovation covariance of a candidate is not positive definite (a pivot of the 3 x 3 factor was not positive or not finite)");
-  g->gate_clean = true;
-  g->gate_rec_n = n_d2;
+  query_end(&st, n_d2, 0);
   memcpy(d2, host.data() + 1, n_d2 * sizeof(double));
   if (best) memcpy(best, host.data() + 1 + n_d2, (size_t)n_meas * sizeof(int));
   return PPS_OK;
+} catch (const std::bad_alloc&) {
+  return query_no_memory(g, kWho);
 }
 
 }  // extern "C"

@@ -8,7 +8,9 @@
 //   pps_lm.h         the LM rule the loops of pps_solve.cpp and pps_multi.cpp share (accept / reject / stop, lambda schedule, trace, counters): host only, no HIP
 //   pps_frames.cpp   registered frames (measurement refresh on the device), data association, point re-projection
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
-//   pps_cov.cpp      marginal covariances from the factor (isam::Covariances): the recovery pipeline and the query scaffold (CovQuery); kernels in pps_cov*.hip
+//   pps_cov.cpp      marginal covariances from the factor (isam::Covariances): the recovery pipeline and the reads of the selected inverse; kernels in pps_cov*.hip
+//   pps_query.cpp    the protocol of the five calls that question the factor a recovery leaves (pps_query.h: QueryState below, CovQuery, begin / end,
+//                    _last / _records), and the plainest of them, pps_cov_block
 //   pps_gate.cpp     pps_assoc_gate (measurement against landmark); pps_merge.cpp: pps_merge_gate (landmark against landmark): queries on the factor
 //   pps_loop.cpp     pps_loop_gate (a candidate loop closure between two poses): a query on the factor
 //   pps_fgate.cpp    pps_factor_gate (every factor of the graph against the rest of it): a query on the selected inverse
@@ -78,6 +80,19 @@ struct DevBuf {
   T* p = nullptr; size_t cap = 0;      // cap in elements
   int reserve(pps_graph* g, size_t count, const char* who = nullptr, const std::string& what = std::string(), const char* advice = "");
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// what one of the five query calls keeps on the handle between calls (the protocol that fills it: pps_query.h)
+struct QueryState {
+  DevBuf<char> out;                    // the result of a call on the device; where it has a status word, that comes first and is zero between calls
+  DevBuf<unsigned int> ticket;         // ... and its tickets, zero between calls
+  DevBuf<double> rec;                  // the records of the last call (pps_debug_*_records)
+  size_t rec_n = 0;                    // ... how many it kept (0: the call failed, or had more entries than records are kept for)
+  bool clean = false;                  // the status word and the tickets are zero
+  bool done = false;                   // the last call on this handle succeeded
+  double sec = 0; int launches = 0;    // its kernels: device seconds, launches
+  int count = 0;                       // its entries without an answer (S not positive definite / d2 = NaN)
+  void release() { out.release(); ticket.release(); rec.release(); rec_n = 0; clean = done = false; }
 };
 
 }  // namespace pps_impl
@@ -234,7 +249,7 @@ struct pps_graph {
   std::vector<int> cov_epos, cov_front_of;               // delta index -> elimination-ordered scalar; that scalar -> front
   hipEvent_t cov_ev[3] = {nullptr, nullptr, nullptr};
   double cov_sec[2] = {0, 0};        // device seconds of the last recovery: whole call | root -> leaves pass alone
-  // the queries on the factor (CovQuery below: pps_cov_block, pps_assoc_gate, pps_merge_gate, pps_loop_gate): per front the pivots of the front and all its
+  // the queries on the factor (CovQuery, pps_query.h: pps_cov_block, pps_assoc_gate, pps_merge_gate, pps_loop_gate): per front the pivots of the front and all its
   // ancestors; the request blob, the strips and the event pair of the query in flight (every query ends with a synchronisation)
   std::vector<int> cov_rootlen; int cov_max_p = 0, cov_max_rows = 0;
   pps_impl::DevBuf<char> cov_breq;
@@ -243,9 +258,6 @@ struct pps_graph {
   // the path walk for wide fronts (k_cov_path_wide): the right-hand sides of the walks of one query, sized by the widest front on its paths
   pps_impl::DevBuf<double> cov_zscr;
   int cov_path_form = 0;             // pps_debug_cov_path_form: 0 = k_cov_path where its LDS fits, 1 = always the wide kernel
-  // pps_cov_block: the result of a query on the device (the first double is the query's status word, zero between queries)
-  pps_impl::DevBuf<double> cov_bout; bool cov_bout_clean = false;
-  double cov_block_sec = 0; int cov_block_launches = 0;   // the two kernels of the last query: device seconds, launches
   // the dense-front pass (pps_cov_dense.hip): G = L_B L_A^-1 of every front in the panel layout of L, and the work-item prefix sums of its
   // launches -- [all fronts: G slabs | per level: gather pieces, Sigma_BA strips] -- on the device (cov_dtab) with their places
   pps_impl::DevBuf<double> cov_G;
@@ -253,33 +265,14 @@ struct pps_graph {
   int cov_dpre_items = 0;
   std::vector<int> cov_dlevel;       // per level, 4 ints: place of the gather sums in cov_dtab, their total, place of the strip sums, their total
   int cov_select_form = 0;           // pps_debug_cov_select_form: 1 = pps_cov_select takes the dense-front pass on a band graph too
-  // pps_assoc_gate (pps_gate.cpp): result of a call on the device ([status | d2 | best], the status word zero between calls) and one
-  // ticket per measurement (zero between calls)
-  pps_impl::DevBuf<double> gate_out; bool gate_clean = false;
-  pps_impl::DevBuf<unsigned int> gate_ticket;
-  double gate_sec = 0; int gate_launches = 0;             // the two kernels of the last call: device seconds, launches
-  pps_impl::DevBuf<double> gate_rec; size_t gate_rec_n = 0;   // [Jp | Jl | r] per candidate of the last call (pps_debug_assoc_gate_records)
-  // pps_merge_gate (pps_merge.cpp): result of a call on the device ([status | best | flags | d2 n x n], the status word zero between calls) and
-  // one ticket per listed plane (zero between calls)
-  pps_impl::DevBuf<char> merge_out; bool merge_clean = false;
-  pps_impl::DevBuf<unsigned int> merge_ticket;
-  double merge_sec = 0; int merge_launches = 0, merge_not_pd = 0;      // the two kernels of the last call: device seconds, launches; its pairs without a positive definite S
-  pps_impl::DevBuf<double> merge_rec; size_t merge_rec_n = 0;   // [J_a | J_b | e] per pair of the last call (pps_debug_merge_gate_records)
-  bool merge_done = false;           // a call has succeeded on this handle
+  // the five calls that question the factor (pps_query.h), one state each.  Result layouts: pps_cov_block [status | block] doubles; pps_assoc_gate
+  // [status | d2 | best] doubles, one ticket per measurement; pps_merge_gate [status (16 bytes) | best | flags | d2 n x n], one ticket per plane;
+  // pps_loop_gate [status (16 bytes) | flags | d2 n | S n x 36]; pps_factor_gate [d2 n | lev n | status: n ints], no status word
+  pps_impl::QueryState q_block, q_assoc, q_merge, q_loop, q_factor;
   // pps_factor_gate (pps_fgate.cpp): one FgateFactor per factor id on the device -- where the blocks of its joint marginal sit in cov_S --, built
-  // for the analysis of upload_version fgate_tab_version (like cov_cache); the fid list, the result ([d2 n | lev n | status: n ints]) and the
-  // records ([J m x c | r m] in slots of 78 doubles) of the last call
+  // for the analysis of upload_version fgate_tab_version (like cov_cache); the fid list of the last call
   pps_impl::DevBuf<char> fgate_tab; int fgate_tab_version = -1, fgate_tab_n = 0;
   pps_impl::DevBuf<int> fgate_list;
-  pps_impl::DevBuf<double> fgate_out;
-  pps_impl::DevBuf<double> fgate_rec; size_t fgate_rec_n = 0;
-  bool fgate_done = false;           // a call has succeeded on this handle
-  double fgate_sec = 0; int fgate_launches = 0, fgate_untestable = 0;      // the kernel of the last call: device seconds, launches; its entries with d2 = NaN
-  // pps_loop_gate (pps_loop.cpp): result of a call on the device ([status | flags | d2 n | S n x 36], the status word zero between calls)
-  pps_impl::DevBuf<char> loop_out; bool loop_clean = false;
-  double loop_sec = 0; int loop_launches = 0, loop_not_pd = 0;         // the two kernels of the last call: device seconds, launches; its candidates without a positive definite S
-  pps_impl::DevBuf<double> loop_rec; size_t loop_rec_n = 0;     // [Jw 6 x 12 | r] per candidate of the last call (pps_debug_loop_gate_records)
-  bool loop_done = false;            // a call has succeeded on this handle
   // stats / trace
   pps_stats stats{};
   std::vector<double> tr_lambda, tr_chi2;
@@ -301,9 +294,6 @@ inline int hip_fail(pps_graph* g, hipError_t e, const char* what) {
     hipError_t _e = (expr);                                \
     if (_e != hipSuccess) return hip_fail(g, _e, #expr);   \
   } while (0)
-
-
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }      // sections of a request or a result sit at multiples of 16 bytes
 
 inline bool live_node(const pps_graph* g, int id, int type) {
   return id >= 0 && id < (int)g->nodes.size() && !g->nodes[id].deleted && g->nodes[id].type == type;
@@ -396,43 +386,6 @@ int DevBuf<T>::reserve(pps_graph* g, size_t count, const char* who, const std::s
   (void)hipGetLastError();
   return fail(g, PPS_ENOMEM, std::string(who) + "no device memory for " + what + " (" + std::to_string(count * sizeof(T)) + " bytes)" + advice);
 }
-// A query on the factor: walks up the tree for a list of distinct, checked nodes (k_cov_path / k_cov_path_wide, pps_cov.h), then the caller's
-// own kernel over the strips the walks leave.  The order of a call: build -> add (its own sections) -> reserve -> its own buffers ->
-// walk -> its own launch -> finish.
-struct CovQuery {
-  pps_graph* g;
-  std::vector<CovNode> nd;                       // the nodes, located
-  std::vector<pps::CovWalk> walks; std::vector<pps::CovStep> steps; std::vector<int> step_end;
-  int K = 0;                                     // the longest path of the query in pivots
-  long long n_strip = 0;
-  int max_rows = 1;                              // the widest front (p + b) on the paths of this query
-  std::vector<char> req;                         // [walks | steps | the caller's sections ...], every section at a multiple of 16 bytes
-  size_t o_steps = 0;
-  unsigned long long launches0 = 0;
-  explicit CovQuery(pps_graph* g_) : g(g_) {}
-  int build(const std::vector<int>& ids);                      // id check (cov_node), cov_locate, paths leaf -> root; starts the request
-  int common_pivots(int a, int b) const;                       // walks a, b: pivots of their common ancestors
-  size_t add(const void* data, size_t bytes);                  // a section of the caller's; its offset in the request
-  template <class T> const T* dev(size_t off) const { return reinterpret_cast<const T*>(g->cov_breq.p + off); }   // (after reserve)
-  int reserve(const char* who = nullptr, const char* advice = "");   // device, events, cov_breq, cov_strip, the wide scratch (that one always PPS_ENOMEM)
-  int walk(double* status);                                    // upload -> event -> the walk launch; the caller's launch comes next
-  int finish(void* host, const void* dev_src, size_t bytes, double* sec, int* launches);      // event -> copy back -> synchronise -> the _last figures
-};
-// the default list (ids == NULL: all live planes) and the check of a given one: live planes, none listed twice
-int plane_list(pps_graph* g, const char* prefix, const int** ids, int* n, std::vector<int>* all);
-// the status word (the first status_bytes of `out`) and the tickets of a call are zero between calls: zeroed here after a call that failed
-// (!*clean) or when a buffer is new (its capacity is not what it was before the call reserved it); *clean is false until the call succeeds
-int zero_between_calls(pps_graph* g, bool* clean, void* out, bool out_new, size_t status_bytes, DevBuf<unsigned int>* ticket, bool ticket_new);
-// pps_debug_*_records: n doubles of the last call's records
-int copy_records(pps_graph* g, const DevBuf<double>& rec, size_t n, int64_t cap, double* out, int64_t* needed);
-// ---- pps_gate.cpp ----
-void gate_release(pps_graph* g);               // (from cov_release)
-// ---- pps_merge.cpp ----
-void merge_release(pps_graph* g);              // (from cov_release)
-// ---- pps_fgate.cpp ----
-void fgate_release(pps_graph* g);              // (from cov_release)
-// ---- pps_loop.cpp ----
-void loop_release(pps_graph* g);               // (from cov_release)
 // ---- pps_api.cpp ----
 void report_front_trace(pps_graph* g);        // PPS_TRACE: the per-front cycle counters of the last solve -> stderr
 

@@ -3,7 +3,7 @@
   emulate_block     the path walk and the suffix Gram product of csrc/pps_cov.hip (k_cov_path, k_cov_gram) in numpy, driven ONLY by the
                     arrays pps_analysis_dump exports (f_parent, f_p, f_b, f_poff, pidx, bidx, cmap).  The panels are cut out of one dense
                     Cholesky factor of the permuted H, like emulate_selected_inverse (tests/cov_helpers.py) cuts its own.
-  request_tables    the request of a query as csrc/pps_cov.cpp builds it (CovWalk / CovStep / CovPair of csrc/pps_cov.h), for the kernel
+  request_tables    the request of a query as csrc/pps_query.cpp builds it (CovWalk / CovStep / CovPair of csrc/pps_cov.h), for the kernel
                     source compiled for the host (tests/cpp/cov_block_emu.cpp)
   block_err         |M - M0|_F / sqrt(|S0(r, r)|_F |S0(c, c)|_F): a small cross block between distant nodes is measured against the
                     reference's diagonal blocks, not against its own near-zero norm

@@ -1,4 +1,4 @@
-"""CPU: the algorithm of pps_cov_block (csrc/pps_cov.hip: k_cov_path, k_cov_gram; csrc/pps_cov.cpp) before any kernel runs on a device.
+"""CPU: the algorithm of pps_cov_block (csrc/pps_cov.hip: k_cov_path, k_cov_gram; csrc/pps_query.cpp) before any kernel runs on a device.
 
 Sigma(R, C) = (L^-1 E_R)' (L^-1 E_C): one walk up the elimination tree per node, one Gram product over the pivots of common ancestors.
 A numpy restatement (tests/cov_block_helpers.py), driven only by what pps_analysis_dump exports, and the kernel source itself compiled
@@ -83,7 +83,7 @@ def test_path_walk_and_suffix_gram_reproduce_the_dense_inverse(built, case):
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_kernel_source_emulated_on_the_host_reproduces_the_dense_inverse(built, case, tmp_path):
     """k_cov_path / k_cov_gram themselves, one std::thread per GPU thread, on the panels of a dense Cholesky factor in the device layout
-    (above the diagonal of L_A, the rhs row and the strips before they are written: NaN), with the request tables of csrc/pps_cov.cpp
+    (above the diagonal of L_A, the rhs row and the strips before they are written: NaN), with the request tables of csrc/pps_query.cpp
     restated in tests/cov_block_helpers.py.  Same measure and bound; the joint is symmetric bit for bit, and Sigma(r, c) is the transpose
     of Sigma(c, r) bit for bit."""
     so = tmp_path / "libcovblockemu.so"
