@@ -447,21 +447,29 @@ constexpr int kEaDepth = 10;
 // a double that crosses workgroups inside a launch (XGroup below): agent-scope atomic access -- global_store / global_load ... sc1
 __device__ __forceinline__ void xg_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double xg_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <int N> struct ElBatch { int tg[N]; double v[N]; };
-// loads are issued unconditionally from clamped (always valid) addresses and masked by selects afterwards: predicated loads
-// become one exec-masked basic block each and serialise
+// a batch of N scatter-add items per lane: what the loads returned (tg, v) and how many of the lane's items exist.  Item u of a lane is
+// entry e + lane + 64 u of the source, so it exists iff 64 u < cnt = e1 - e - lane -- ONE integer per lane decides, and only in el_apply
+template <int N> struct ElBatch { int tg[N]; double v[N]; int cnt; };
+// Requesting: loads only, unconditional, from clamped (always valid) addresses.  Nothing is selected here: a per-item condition that
+// lives across the loads is what the scheduler put between them, a wait and a select behind every pair -- N dependent round trips (DESIGN.md
+// section 8, 1f); predicated loads become one exec-masked basic block each and serialise as well
 // XH: the values are an update matrix that another workgroup of this launch wrote (xg_load; the targets are static)
+__device__ __forceinline__ int el_clamp(int e, int e1, int lane, int u) { const int x = e + lane + 64 * u, last = e1 > 0 ? e1 - 1 : 0; return x < e1 ? x : last; }
+template <int N>
+__device__ __forceinline__ void el_issue_tgt(const int* __restrict__ tgp, int e, int e1, int lane, int (&tg)[N]) {
+#pragma unroll
+  for (int u = 0; u < N; u++) tg[u] = tgp[el_clamp(e, e1, lane, u)];
+}
+template <int N, bool XH = false>
+__device__ __forceinline__ void el_issue_val(const double* __restrict__ val, int e, int e1, int lane, ElBatch<N>& q) {
+#pragma unroll
+  for (int u = 0; u < N; u++) { const int xc = el_clamp(e, e1, lane, u); if constexpr (XH) q.v[u] = xg_load(val + xc); else q.v[u] = val[xc]; }
+  q.cnt = e1 - e - lane;
+}
 template <int N, bool XH = false>
 __device__ __forceinline__ void el_issue(const int* __restrict__ tgp, const double* __restrict__ val, int e, int e1, int lane, ElBatch<N>& q) {
-  const int last = e1 > 0 ? e1 - 1 : 0;
-#pragma unroll
-  for (int u = 0; u < N; u++) {
-    const int x = e + lane + 64 * u, xc = x < e1 ? x : last;
-    const int t = tgp[xc];
-    double v;
-    if constexpr (XH) v = xg_load(val + xc); else v = val[xc];
-    q.tg[u] = x < e1 ? t : -1; q.v[u] = x < e1 ? v : 0.0;
-  }
+  el_issue_tgt(tgp, e, e1, lane, q.tg);
+  el_issue_val<N, XH>(val, e, e1, lane, q);
 }
 // The N read-modify-writes of a batch as N reads, N adds, N writes -- one LDS round trip instead of N dependent ones.  Valid
 // because the targets of one source (the original entries of a front; one child's update matrix) are pairwise distinct;
@@ -473,16 +481,17 @@ __device__ __forceinline__ void el_apply(const ElBatch<N>& q, double damp, doubl
     // 0 + inc = inc (H entries are sums that start at +0: never -0): a plain store -- no LDS read, no add, one LDS round trip less per batch.
 #pragma unroll
     for (int u = 0; u < N; u++) {
-      const int t = q.tg[u] >= 0 ? (q.tg[u] & 0x3fffffff) : tr;
-      F[t] = (q.tg[u] & (1 << 30)) && q.tg[u] >= 0 ? q.v[u] * damp : q.v[u];        // (tg = -1: v = 0 into the spare double)
+      const bool ex = 64 * u < q.cnt;
+      const double v = (q.tg[u] & (1 << 30)) ? q.v[u] * damp : q.v[u];
+      F[ex ? (q.tg[u] & 0x3fffffff) : tr] = ex ? v : 0.0;                            // (missing: a zero into the spare double)
     }
     return;
   }
   int t[N]; double old[N];
 #pragma unroll
-  for (int u = 0; u < N; u++) { t[u] = q.tg[u] >= 0 ? q.tg[u] : tr; old[u] = F[t[u]]; }
+  for (int u = 0; u < N; u++) { t[u] = 64 * u < q.cnt ? q.tg[u] : tr; old[u] = F[t[u]]; }
 #pragma unroll
-  for (int u = 0; u < N; u++) F[t[u]] = old[u] + q.v[u];      // (tg = -1: v = 0)
+  for (int u = 0; u < N; u++) F[t[u]] = old[u] + (64 * u < q.cnt ? q.v[u] : 0.0);
 }
 // what a front needs before its children are complete: first batch of its original entries and its child records (requested),
 // the cleared triangle, the original entries added.  issue -> [anything] -> finish.  NPRE items per lane are requested ahead:
@@ -507,15 +516,17 @@ __device__ __forceinline__ void front_clear(int rec, int lane, double* __restric
   if (lane == 0) F[ntri - 1] = 0.0;
   __builtin_amdgcn_wave_barrier();
 }
-template <int NPRE>
+// TAIL: the front may have more than NPRE x 64 original entries (false where the caller has picked NPRE by the front's size: no loop is compiled in)
+template <int NPRE, bool TAIL = true>
 __device__ __forceinline__ void front_pre_finish(const DevGraph& d, int rec, int lane, const FrontPre<NPRE>& o, double damp, double* __restrict__ F, int tr) {
   const int e0 = __builtin_amdgcn_readlane(rec, 3), e1 = __builtin_amdgcn_readlane(rec, 4);
   el_apply<true>(o.q, damp, F, tr);
-  for (int e = e0 + 64 * NPRE; e < e1; e += 64 * 8) { ElBatch<8> q; el_issue(d.el_tgt, d.Hf, e, e1, lane, q); __builtin_amdgcn_wave_barrier(); el_apply<true>(q, damp, F, tr); }
+  if constexpr (TAIL)
+    for (int e = e0 + 64 * NPRE; e < e1; e += 64 * 8) { ElBatch<8> q; el_issue(d.el_tgt, d.Hf, e, e1, lane, q); __builtin_amdgcn_wave_barrier(); el_apply<true>(q, damp, F, tr); }
   __builtin_amdgcn_wave_barrier();
 }
-// extend-add of the children's packed update matrices, child by child, one batch of 512 entries in flight (more loads in
-// flight -- both children at once, two batches per child -- measured SLOWER on MI355X: DESIGN.md section 8)
+// (extend-add: front_extend_add below.  More than about two dozen loads in flight per lane -- both children's targets AND values at once,
+// two batches per child -- measured SLOWER on MI355X: DESIGN.md section 8)
 // Hand-over between WORKGROUPS of one launch (round 6: the whole tree in one factor launch and one back-substitution launch, XG = true
 // below).  A flag per front in global memory carries the number of the launch pair (the epoch: never reset).  No fence writes a cache
 // back: the bytes handed over leave the producer as write-through stores and reach the consumer by loads that bypass its L1.
@@ -553,30 +564,74 @@ __device__ __forceinline__ void xg_wait(const DevGraph& d, const XGroup& x, int 
   }
   if (ACQ) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// one child of a vector of child records (8 ints per child): entries of its packed update matrix, where that lies, its static targets
+struct EaChild { int n; const double* U; const int* tg; };
+__device__ __forceinline__ EaChild ea_child(const DevGraph& d, int crv, int cj) {
+  const long long uo = ((long long)__builtin_amdgcn_readlane(crv, 8 * cj + 2) << 32) | (unsigned int)__builtin_amdgcn_readlane(crv, 8 * cj + 1);
+  const long long eo = ((long long)__builtin_amdgcn_readlane(crv, 8 * cj + 4) << 32) | (unsigned int)__builtin_amdgcn_readlane(crv, 8 * cj + 3);
+  return {__builtin_amdgcn_readlane(crv, 8 * cj), d.U + uo, d.ea_tgt + eo};
+}
+// The first batch of the targets of a front's two children.  The targets are static, so a wave that is about to WAIT for its children --
+// at the workgroup barrier in front of its level, or at the flag of another workgroup -- requests them first: behind the wait only the
+// values are left to fetch, both children's in one round trip of 2 x kEaDepth loads (what one child's batch was)
+struct EaPre { int tg[2][kEaDepth]; };
+// (rec: the front's record, crv: its child records.  Both update matrices non-empty: the clamped loads of a batch need one valid entry)
+__device__ __forceinline__ bool ea_pairable(int rec, int crv) {
+  return __builtin_amdgcn_readlane(rec, 6) == 2 && __builtin_amdgcn_readlane(crv, 0) > 0 && __builtin_amdgcn_readlane(crv, 8) > 0;
+}
+__device__ __forceinline__ void ea_pre_issue(const DevGraph& d, int crv, int lane, EaPre& o) {
+#pragma unroll
+  for (int c = 0; c < 2; c++) { const EaChild ch = ea_child(d, crv, c); el_issue_tgt(ch.tg, 0, ch.n, lane, o.tg[c]); }
+}
+// Extend-add of the children's packed update matrices in child order, in batches of kEaDepth x 64 = 640 entries: the update matrix of a
+// separator front of a corridor tree (34 rows + rhs: 595 entries) is one memory round trip, not a full batch of 512 followed by a nearly
+// empty one.
 // XG: a child that another workgroup of this launch factors (child record slot 6) is waited for first (xg_wait, no acquire) and its update
 // matrix read with xg_load
-template <bool XG = false>
-__device__ __forceinline__ void front_extend_add(const DevGraph& d, int rec, int crv0, int lane, double* __restrict__ F, int tr, const XGroup* xg = nullptr) {
+// PAIR: a front with exactly two children whose wave waits for them (have_pre: it has requested the targets in front of the workgroup barrier; or a
+// child sits behind a flag) takes the paired form: targets, wait, the values of a child as soon as that child is complete, then the applies in
+// child order -- child 0 completely, its batches beyond the first included, then child 1: the sums are those of the sequential form.  Every
+// other front, and every wave that does not wait, goes child by child as before.
+template <bool XG = false, bool PAIR = false>
+__device__ __forceinline__ void front_extend_add(const DevGraph& d, int rec, int crv0, int lane, double* __restrict__ F, int tr, const XGroup* xg = nullptr,
+                                                 const EaPre* pre = nullptr, bool have_pre = false) {
   const int cr0 = __builtin_amdgcn_readlane(rec, 5), nch = __builtin_amdgcn_readlane(rec, 6);
+  // the batches of one child from entry e0 on, one round trip each
+  auto batches = [&](const EaChild& c, int e0, bool xh) {
+    if (XG && xh) for (int e = e0; e < c.n; e += 64 * kEaDepth) { ElBatch<kEaDepth> q; el_issue<kEaDepth, true>(c.tg, c.U, e, c.n, lane, q); __builtin_amdgcn_wave_barrier(); el_apply<false>(q, 0.0, F, tr); }
+    else for (int e = e0; e < c.n; e += 64 * kEaDepth) { ElBatch<kEaDepth> q; el_issue(c.tg, c.U, e, c.n, lane, q); __builtin_amdgcn_wave_barrier(); el_apply<false>(q, 0.0, F, tr); }
+  };
+  if constexpr (PAIR) {
+    const bool xh0 = XG && __builtin_amdgcn_readlane(crv0, 6), xh1 = XG && __builtin_amdgcn_readlane(crv0, 14);      // (wave-uniform)
+    if (ea_pairable(rec, crv0) && (have_pre || xh0 || xh1)) {
+      ElBatch<kEaDepth> q[2];
+      if (have_pre) {
+#pragma unroll
+        for (int u = 0; u < kEaDepth; u++) { q[0].tg[u] = pre->tg[0][u]; q[1].tg[u] = pre->tg[1][u]; }
+      }
+      const EaChild c0 = ea_child(d, crv0, 0), c1 = ea_child(d, crv0, 1);
+      if (!have_pre) { el_issue_tgt(c0.tg, 0, c0.n, lane, q[0].tg); el_issue_tgt(c1.tg, 0, c1.n, lane, q[1].tg); }
+      if (XG && xh0) { xg_wait<false>(d, *xg, __builtin_amdgcn_readlane(crv0, 5)); el_issue_val<kEaDepth, true>(c0.U, 0, c0.n, lane, q[0]); }
+      else el_issue_val(c0.U, 0, c0.n, lane, q[0]);
+      if (XG && xh1) { xg_wait<false>(d, *xg, __builtin_amdgcn_readlane(crv0, 13)); el_issue_val<kEaDepth, true>(c1.U, 0, c1.n, lane, q[1]); }
+      else el_issue_val(c1.U, 0, c1.n, lane, q[1]);
+      __builtin_amdgcn_wave_barrier();
+      el_apply<false>(q[0], 0.0, F, tr);
+      batches(c0, 64 * kEaDepth, xh0);
+      __builtin_amdgcn_wave_barrier();
+      el_apply<false>(q[1], 0.0, F, tr);
+      batches(c1, 64 * kEaDepth, xh1);
+      __builtin_amdgcn_wave_barrier();
+      return;
+    }
+  }
   for (int cb = 0; cb < nch; cb += 8) {
     const int crv = cb == 0 ? crv0 : ((lane < 8 * (nch - cb)) ? d.crec[(size_t)(cr0 + cb) * 8 + lane] : 0);      // (more than 8 children: rare)
-    auto child = [&](int cj, int& n, const double* __restrict__& Uc, const int* __restrict__& tgc) {
-      n = __builtin_amdgcn_readlane(crv, 8 * cj);
-      const long long uo = ((long long)__builtin_amdgcn_readlane(crv, 8 * cj + 2) << 32) | (unsigned int)__builtin_amdgcn_readlane(crv, 8 * cj + 1);
-      const long long eo = ((long long)__builtin_amdgcn_readlane(crv, 8 * cj + 4) << 32) | (unsigned int)__builtin_amdgcn_readlane(crv, 8 * cj + 3);
-      Uc = d.U + uo; tgc = d.ea_tgt + eo;
-    };
-    int cj = 0;
-    for (; cj < 8 && cb + cj < nch; cj++) {
-      int n; const double* Uc; const int* tgc;
-      child(cj, n, Uc, tgc);
-      // batches of kEaDepth x 64 = 640 entries: the update matrix of a separator front of a corridor tree (34 rows + rhs: 595
-      // entries) is one memory round trip, not a full batch of 512 followed by a nearly empty one
-      if (XG && __builtin_amdgcn_readlane(crv, 8 * cj + 6)) {                                             // (wave-uniform)
-        xg_wait<false>(d, *xg, __builtin_amdgcn_readlane(crv, 8 * cj + 5));
-        for (int e = 0; e < n; e += 64 * kEaDepth) { ElBatch<kEaDepth> q; el_issue<kEaDepth, true>(tgc, Uc, e, n, lane, q); __builtin_amdgcn_wave_barrier(); el_apply<false>(q, 0.0, F, tr); }
-      } else
-      for (int e = 0; e < n; e += 64 * kEaDepth) { ElBatch<kEaDepth> q; el_issue(tgc, Uc, e, n, lane, q); __builtin_amdgcn_wave_barrier(); el_apply<false>(q, 0.0, F, tr); }
+    for (int cj = 0; cj < 8 && cb + cj < nch; cj++) {
+      const EaChild c = ea_child(d, crv, cj);
+      const bool xh = XG && __builtin_amdgcn_readlane(crv, 8 * cj + 6);                                     // (wave-uniform)
+      if (XG && xh) xg_wait<false>(d, *xg, __builtin_amdgcn_readlane(crv, 8 * cj + 5));
+      batches(c, 0, xh);
       __builtin_amdgcn_wave_barrier();
     }
   }
@@ -1067,20 +1122,24 @@ __device__ __forceinline__ void body_band_factor(const DevGraph& d, int g, doubl
 
 // clear + original entries of a front, the first batch of NPRE x 64 entries requested before the clearing (front_pre_issue).  A
 // separator front of a corridor tree has 120 - 180 original entries, a leaf up to 650: three loads per lane cover the former -- eight
-// were five wasted load / read-modify-write pairs per lane (C2, same box, five runs each: 63.59 -> 63.33 us per LM iteration); eleven
-// for the leaves (one round trip instead of two for the largest) measured the same as eight.
-template <int NPRE>
+// were five wasted load / read-modify-write pairs per lane (C2, same box, five runs each: 63.59 -> 63.33 us per LM iteration).  Eleven
+// for the leaves measured the same as eight in round 5 -- on the per-band kernel k_band_factor_pre, whose tail loop was one pipelined
+// round trip; in the whole-tree kernel the tail was eight dependent ones.  The largest leaves (513 .. 704
+// entries) now take eleven: 22 loads in flight, within the two dozen of kEaDepth, one round trip; the tail loop is compiled into that class
+// alone (a larger front still goes on in batches of eight).
+template <int NPRE, bool TAIL>
 __device__ __forceinline__ int front_orig_entries(const DevGraph& d, int rec, int lane, double damp, double* F, int tr) {
   FrontPre<NPRE> pre;
   front_pre_issue(d, rec, lane, pre);
   front_clear(rec, lane, F);
-  front_pre_finish(d, rec, lane, pre, damp, F, tr);
+  front_pre_finish<NPRE, TAIL>(d, rec, lane, pre, damp, F, tr);
   return pre.crv;
 }
 __device__ __forceinline__ int front_orig_entries_sized(const DevGraph& d, int rec, int lane, double damp, double* F, int tr) {
   const int n_el = __builtin_amdgcn_readlane(rec, 4) - __builtin_amdgcn_readlane(rec, 3);
-  if (n_el <= 192) return front_orig_entries<3>(d, rec, lane, damp, F, tr);        // (wave-uniform)
-  return front_orig_entries<8>(d, rec, lane, damp, F, tr);
+  if (n_el <= 192) return front_orig_entries<3, false>(d, rec, lane, damp, F, tr);        // (wave-uniform)
+  if (n_el <= 512) return front_orig_entries<8, false>(d, rec, lane, damp, F, tr);
+  return front_orig_entries<11, true>(d, rec, lane, damp, F, tr);
 }
 
 // The register-only walk with the fronts of the upper local levels on waves of their own.  A band group of a dissection tree is a
@@ -1125,11 +1184,20 @@ __device__ __forceinline__ void body_band_factor_pre(const DevGraph& d, int g, d
     const int i0 = ll == 0 ? o0 : ll == 1 ? o1 : ll == 2 ? o2 : o3;
     const bool mine = wave >= lb && wave < lb + cnt;
     const bool mine_up = mine && up_ll == ll && ll > pre_at;    // (assembled ahead: starts with the extend-add)
+    // The barrier in front of a level: its children are complete and visible (same CU).  A wave whose upper front comes now requests the
+    // targets of that front's children (static) in front of the barrier and holds them across it -- requested and used inside ONE pass of
+    // this loop, so that they are dead while a front is eliminated: the register allocation of that part has no room for them
+    EaPre eat; bool have_pre = false;
+    if (ll > 0) {
+      have_pre = mine_up && ea_pairable(up_rec, crv);
+      if (have_pre) ea_pre_issue(d, crv, lane, eat);
+      __syncthreads();
+    }
     if (mine) {                                                 // (wave-uniform)
       const int rec = (up_ll == ll && ll > 0) ? up_rec : d.frec[(size_t)(i0 + wave - lb) * 16 + (threadIdx.x & 15)];
       const int fa = __builtin_amdgcn_readlane(rec, 1) + __builtin_amdgcn_readlane(rec, 2) + 1;
       if (!mine_up) crv = front_orig_entries_sized(d, rec, lane, 1.0 + lambda, F, tr);
-      front_extend_add<XG>(d, rec, crv, lane, F, tr, xg);
+      front_extend_add<XG, true>(d, rec, crv, lane, F, tr, xg, &eat, have_pre);
       // (XG: the update matrix of a front whose parent another workgroup holds leaves as write-through stores -- front_reg_eliminate, XH)
       if (fa <= 33) front_eliminate_out<2, false, false, kPanelWBand, XG>(d, rec, F, F);
       else if (fa <= 49) front_eliminate_out<3, false, false, kPanelWBand, XG>(d, rec, F, F);
@@ -1140,8 +1208,8 @@ __device__ __forceinline__ void body_band_factor_pre(const DevGraph& d, int g, d
       // nothing to eliminate on this level: the part of the upper front's assembly that needs no child
       crv = front_orig_entries_sized(d, up_rec, lane, 1.0 + lambda, F, tr);
     }
-    __syncthreads();   // children of the next local level are complete and visible (same CU)
   }
+  __syncthreads();     // (the top level is complete: k_band_root walks back down behind it)
 }
 
 template <bool REG_ONLY>
