@@ -537,6 +537,11 @@ int pps_bench_sweep(pps_graph* g, int mode, int replicas, int iters, double sec_
  * picks for a front of this size; strip != 0: rows 64 .. 79 as a strip of the LDS triangle under four tile rows (fronts of 65 .. 80
  * rows only).  not_pd: 1.0 when a pivot was not positive.  p <= 64, p + b + 1 <= 80.  Runs on the current device. */
 int pps_debug_front_factor(int tiles, int strip, int p, int b, const double* A, double* L, double* U, double* not_pd);
+/* The same with the panel width chosen: width 8 (two chained 4 x 4 pivot blocks per panel step: the level and wide kernels; what
+ * pps_debug_front_factor runs) or 4 (one pivot block per step, the tile column a compile-time constant: the register-only band kernels,
+ * fronts of at most 64 rows in 2 .. 4 tile rows -- width 4 with strip or five tile rows is PPS_EINVAL).  Found by symbol lookup, like the
+ * pps_cov_* calls; PPS_VERSION was not bumped. */
+int pps_debug_front_factor_w(int tiles, int strip, int p, int b, const double* A, double* L, double* U, double* not_pd, int width);
 
 /* ---- K4 diagnostic: the retraction of n nodes outside any graph ---- */
 /* kind 0: Pose3d::exmap (Pose3d.h:131-136: t += d[0:3], q <- q * Exp(d[3:6])); x n x 7 (tx ty tz qx qy qz qw), delta n x 6, out n x 7.

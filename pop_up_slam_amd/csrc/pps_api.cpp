@@ -539,6 +539,12 @@ int pps_debug_front_factor(int tiles, int strip, int p, int b, const double* A, 
   return rc == 0 ? PPS_OK : (rc < 0 ? PPS_EINVAL : PPS_EHIP);
 }
 
+int pps_debug_front_factor_w(int tiles, int strip, int p, int b, const double* A, double* L, double* U, double* not_pd, int width) {
+  if (!A || !L || !U) return PPS_EINVAL;
+  const int rc = pps::debug_front_factor_w(tiles, strip, p, b, A, L, U, not_pd, width);
+  return rc == 0 ? PPS_OK : (rc < 0 ? PPS_EINVAL : PPS_EHIP);
+}
+
 int pps_debug_exmap(int kind, int n, const double* x, const double* delta, double* out) {
   if (!x || !delta || !out) return PPS_EINVAL;
   const int rc = pps::debug_exmap(kind, n, x, delta, out);

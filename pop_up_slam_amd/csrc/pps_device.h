@@ -245,6 +245,7 @@ hipError_t launch_expand_el(const DevGraph& d, int n_asm, hipStream_t st);
 hipError_t launch_expand_lists(const DevGraph& d, int n_fronts, int n_asm, double* zero, size_t n_zero, hipStream_t st);   // both + the zero fill, one launch
 bool band_level_solve_direct_ok(int p, int b);   // a front whose level back-substitution may load L_B straight into registers (kb_level_solve)
 int debug_front_factor(int tiles, int strip, int p, int b, const double* A_host, double* L_host, double* U_host, double* not_pd);   // pps_debug_front_factor
+int debug_front_factor_w(int tiles, int strip, int p, int b, const double* A_host, double* L_host, double* U_host, double* not_pd, int width);   // pps_debug_front_factor_w
 int debug_exmap(int kind, int n, const double* x_host, const double* delta_host, double* out_host);   // pps_debug_exmap (pps_k4.hip)
 // est <- lin ; lin <- lin (+) delta          (LM trial: Optimizer.cpp:414-416)
 hipError_t launch_retract_trial(const DevGraph& d, hipStream_t st);

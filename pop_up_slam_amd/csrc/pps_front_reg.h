@@ -29,7 +29,9 @@ __device__ __forceinline__ int tri24(int i) { return __mul24(i, i + 1) >> 1; }
 // is a vector next to them.
 // P: the panel buffer, 16 NT rows of kP8Stride doubles (at least 80 rows with STRIP).  Without STRIP, and with NT = 5, F is dead
 // once the tiles are loaded, and P may be F itself.
-// W: pivot columns per panel step, 8 or 4 (4 = the second pivot block never runs: the form up to round 3, kept for A/B).
+// W: pivot columns per panel step, 8 or 4.  W = 4 without STRIP and with NT <= 4 (the register-only band kernels) is a loop
+// of its own, one per tile column with the column a template constant (column4 below, reg_trailing4); elsewhere W = 4 is the general
+// step whose second pivot block never runs.
 // XH (whole-tree factor launch, without STRIP): a front whose parent another workgroup of the launch assembles (rec slot 13 >= 0) writes its
 // update matrix with agent-scope atomic stores (write-through: the hand-over of pps_k3.hip, XGroup); the elimination is the same code, only
 // the store loop exists twice.  The factor panel keeps plain stores: the next launch reads it.
@@ -40,6 +42,13 @@ __device__ __forceinline__ void um_store(double* p, double v) {
 #endif
   *p = v;
 }
+// (4-column form, column4 below) kFlat4: how many leading steps of a tile column are straight-line code with K a literal -- every
+// v_readlane lane an immediate: such a step measured 0.1 .. 0.2 us shorter than a loop step, and the general loop had its first two
+// steps peeled that way by the compiler.  Column 0 is where every front starts and where a front of few pivots ends: the separators
+// of a C2 tree never leave it, the small fronts of a frame loop have one or two steps.  With loops there, fronts of two and four tile
+// rows measured slower than in the general loop; every column of every NT straight-line is another 1.0 us of k_band_factor_all for
+// 88 KB of it.  Measured in the one-front harness and on the graphs: DESIGN.md section 8 1g.
+template <int TJ> constexpr int kFlat4 = TJ == 0 ? 4 : 0;
 template <int NT, bool TR, bool STRIP, int W = 8, bool XH = false, class G>
 __device__ __forceinline__ void front_reg_eliminate(const G& d, int rec, double* F, double* P) {      // (no __restrict__: P may be F)
   const int lane = threadIdx.x & 63;
@@ -213,7 +222,60 @@ __device__ __forceinline__ void front_reg_eliminate(const G& d, int rec, double*
     __builtin_amdgcn_wave_barrier();
     if (TR && d.trace) { const long long tk2 = clock64(); cyc_panel += tk1 - tk0; cyc_trail += tk2 - tk1; }
   };
-  if constexpr (NT == 5) {
+  // The register-only 4-column form (the band kernels, kPanelWBand): one loop per TILE COLUMN, the column a template constant, and a
+  // trailing update that gives every tile of the columns >= TJ its one MFMA under no branch (reg_trailing4) -- the accumulator tiles
+  // have one definition per step and stay where they are.  Per entry the operations and their order are those of the general step
+  // above with W = 4: nb <= 4, no second pivot block; columns 4 .. 7 of the panel buffer are neither written nor read.  A column is a
+  // loop over its at most four steps, behind kFlat4 of them unrolled with K a literal.
+  auto column4 = [&](auto tjc) __attribute__((always_inline)) {
+    constexpr int TJ = decltype(tjc)::value;
+    auto step = [&](const int K) __attribute__((always_inline)) {
+      const long long tk0 = (TR && d.trace) ? clock64() : 0;
+      const int nb = p - K < 4 ? p - K : 4;
+      reg_extract_panel4<TJ, NT>(c, P, K - 16 * TJ, lane);
+      __builtin_amdgcn_wave_barrier();
+      // ---- panel: lane = row; the rhs row takes the idle lane f, its entries of columns K .. K+3 sit in lanes K .. K+3 of y ----
+      double r[4], x[4];
+#pragma unroll
+      for (int m = 0; m < 4; m++) r[m] = P[lane * kP8Stride + m];
+#pragma unroll
+      for (int m = 0; m < 4; m++) { const double q = readlane_d(y, K + m); r[m] = lane == f ? q : r[m]; }
+      const Chol4 c1 = chol4(readlane_d(r[0], K), readlane_d(r[0], K + 1), readlane_d(r[1], K + 1), readlane_d(r[0], K + 2), readlane_d(r[1], K + 2),
+                             readlane_d(r[2], K + 2), readlane_d(r[0], K + 3), readlane_d(r[1], K + 3), readlane_d(r[2], K + 3), readlane_d(r[3], K + 3), nb, bad);
+      trsm4(c1, r[0], r[1], r[2], r[3], x[0], x[1], x[2], x[3]);
+#pragma unroll
+      for (int m = 0; m < 4; m++) P[lane * kP8Stride + m] = x[m];
+      y = rank4(y, x[0], x[1], x[2], x[3], readlane_d(x[0], f), readlane_d(x[1], f), readlane_d(x[2], f), readlane_d(x[3], f));
+      if (lane < fa) {                                         // (rows above the diagonal: as in the general step)
+        double* __restrict__ lrow = Lp + (unsigned)(__mul24(lane, p) + K);
+        lrow[0] = x[0];
+        if (nb > 1) lrow[1] = x[1];
+        if (nb > 2) lrow[2] = x[2];
+        if (nb > 3) lrow[3] = x[3];
+      }
+      __builtin_amdgcn_wave_barrier();
+      const long long tk1 = (TR && d.trace) ? clock64() : 0;
+      reg_trailing4<TJ, NT>(c, P, nb, lane);
+      __builtin_amdgcn_wave_barrier();
+      if (TR && d.trace) { const long long tk2 = clock64(); cyc_panel += tk1 - tk0; cyc_trail += tk2 - tk1; }
+    };
+    const int kend = p < 16 * TJ + 16 ? p : 16 * TJ + 16;
+    constexpr int NF = kFlat4<TJ>;
+    bool more = true;
+#pragma unroll
+    for (int q = 0; q < NF; q++) {
+      if (16 * TJ + 4 * q >= kend) { more = false; break; }
+      step(16 * TJ + 4 * q);
+    }
+    if (NF < 4 && more)
+      for (int K = 16 * TJ + 4 * NF; K < kend; K += 4) step(K);
+  };
+  if constexpr (W == 4 && !STRIP && NT <= 4) {
+    column4(std::integral_constant<int, 0>{});
+    column4(std::integral_constant<int, 1>{});
+    if constexpr (NT > 2) column4(std::integral_constant<int, 2>{});
+    if constexpr (NT > 3) column4(std::integral_constant<int, 3>{});
+  } else if constexpr (NT == 5) {
     // (hipcc 7.2 miscompiled this loop with fifteen accumulator tiles once it peeled the first panel: rows 8 and up of every later
     // panel came out wrong, deterministically -- tests/test_gpu_fronts.py holds the case; without peeling the code is correct)
 #pragma clang loop unroll(disable)

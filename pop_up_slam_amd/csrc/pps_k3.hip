@@ -1637,7 +1637,7 @@ hipError_t launch_batch_solve(const BatchArgs& a, const BatchGeom& g, hipStream_
 
 // ---- diagnostic: one front through the register-tile elimination, outside any graph (pps_debug_front_factor) ----
 namespace pps {
-template <int NT, bool STRIP>
+template <int NT, bool STRIP, int W = 8>
 __global__ __launch_bounds__(64) void k_debug_front(DevGraph d, int p, int b, const double* A, int per_wave) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x;
@@ -1651,17 +1651,22 @@ __global__ __launch_bounds__(64) void k_debug_front(DevGraph d, int p, int b, co
   int rec = 0;                                    // (L and U of the front start at offset 0)
   if (lane == 1) rec = p;
   if (lane == 2) rec = b;
-  front_reg_eliminate<NT, false, STRIP>(d, rec, F, P);
+  front_reg_eliminate<NT, false, STRIP, W>(d, rec, F, P);
 }
 
 // tiles: 2 .. 5 tile rows; 0 = the choice the band kernels make for the front (by its row count); strip: rows 64 .. 79 as a strip of
-// the LDS triangle under four tile rows instead of a fifth tile row.  Returns a hipError_t (0 = ok), -1 for arguments no path takes.
+// the LDS triangle under four tile rows instead of a fifth tile row.  width: pivot columns per panel step, 8 (kPanelWLevel / kPanelWWide) or
+// 4 (kPanelWBand: the register-only form, no strip and at most four tile rows).  Returns a hipError_t (0 = ok), -1 for arguments no path takes.
 int debug_front_factor(int tiles, int strip, int p, int b, const double* A_host, double* L_host, double* U_host, double* not_pd) {
+  return debug_front_factor_w(tiles, strip, p, b, A_host, L_host, U_host, not_pd, 8);
+}
+int debug_front_factor_w(int tiles, int strip, int p, int b, const double* A_host, double* L_host, double* U_host, double* not_pd, int width) {
   const int f = p + b, fa = f + 1;
-  if (p < 1 || b < 0 || fa > kRegRowsMax || p > kRegRows) return -1;
+  if (p < 1 || b < 0 || fa > kRegRowsMax || p > kRegRows || (width != 8 && width != 4)) return -1;
   if (tiles == 0) tiles = fa <= 33 ? 2 : fa <= 49 ? 3 : fa <= kRegRows ? 4 : (strip ? 4 : 5);
   const bool wide = fa > kRegRows;
   if (tiles < 2 || tiles > 5 || (wide && tiles < 4) || (!wide && (tiles == 5 || strip)) || (tiles < 4 && f > 16 * tiles) || (wide && tiles == 4 && !strip)) return -1;
+  if (width == 4 && (strip || wide || tiles == 5)) return -1;
   const size_t ntri = (size_t)fa * (fa + 1) / 2, nL = (size_t)fa * p, nU = (size_t)(b + 1) * (b + 1);
   double *A = nullptr, *L = nullptr, *U = nullptr, *res = nullptr;
   hipError_t e = hipMalloc(&A, ntri * 8);
@@ -1676,16 +1681,19 @@ int debug_front_factor(int tiles, int strip, int p, int b, const double* A_host,
     DevGraph d{}; d.L = L; d.U = U; d.result_dev = res;
     const int per_wave = (int)(band_lds_bytes(fa - 1, !(tiles == 5 || wide)) / 8);
     const size_t bytes = (size_t)per_wave * 8;
-#define PPS_DBG_FRONT(NT_, STRIP_)                                                                                                      \
+#define PPS_DBG_FRONT(NT_, STRIP_, W_)                                                                                                   \
     do {                                                                                                                                \
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_debug_front<NT_, STRIP_>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLaunchCeilingBytes); \
-      if (e == hipSuccess) { hipLaunchKernelGGL((k_debug_front<NT_, STRIP_>), dim3(1), dim3(64), bytes, 0, d, p, b, A, per_wave); e = hipGetLastError(); } \
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_debug_front<NT_, STRIP_, W_>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLaunchCeilingBytes); \
+      if (e == hipSuccess) { hipLaunchKernelGGL((k_debug_front<NT_, STRIP_, W_>), dim3(1), dim3(64), bytes, 0, d, p, b, A, per_wave); e = hipGetLastError(); } \
     } while (0)
-    if (tiles == 5) PPS_DBG_FRONT(5, true);
-    else if (tiles == 4 && wide) PPS_DBG_FRONT(4, true);
-    else if (tiles == 4) PPS_DBG_FRONT(4, false);
-    else if (tiles == 3) PPS_DBG_FRONT(3, false);
-    else PPS_DBG_FRONT(2, false);
+    if (tiles == 5) PPS_DBG_FRONT(5, true, 8);
+    else if (tiles == 4 && wide) PPS_DBG_FRONT(4, true, 8);
+    else if (width == 4 && tiles == 4) PPS_DBG_FRONT(4, false, 4);
+    else if (width == 4 && tiles == 3) PPS_DBG_FRONT(3, false, 4);
+    else if (width == 4) PPS_DBG_FRONT(2, false, 4);
+    else if (tiles == 4) PPS_DBG_FRONT(4, false, 8);
+    else if (tiles == 3) PPS_DBG_FRONT(3, false, 8);
+    else PPS_DBG_FRONT(2, false, 8);
 #undef PPS_DBG_FRONT
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(L_host, L, nL * 8, hipMemcpyDeviceToHost);

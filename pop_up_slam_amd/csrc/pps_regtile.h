@@ -218,4 +218,41 @@ __device__ __forceinline__ void reg_trailing8(double4_t (&c)[NT * (NT + 1) / 2],
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// 4-column panels of the register-only kernels (front_reg_eliminate with W == 4, no strip, NT <= 4).  The tile column TJ is a
+// template constant and nothing but TJ and NT decides which MFMAs a step issues, so every accumulator tile has ONE definition per
+// step: with reg_trailing8's uniform branches (tjn == TJ, short_of_end, two) the tiles were phi values, and the register allocator
+// parked MFMA results in spare registers and copied whole tiles back.  Same panel layout (kP8Stride).
+// ------------------------------------------------------------------------------------------
+template <int TJ, int NT>
+__device__ __forceinline__ void reg_extract_panel4(const double4_t (&c)[NT * (NT + 1) / 2], double* P, int c0, int lane) {
+  const int l16 = lane & 15, lq = lane >> 4;
+  const int m = l16 - c0;                         // c0 = 0, 4, 8 or 12: a quarter of the lanes hold a panel column
+  if (m >= 0 && m < 4) {
+#pragma unroll
+    for (int ti = TJ; ti < NT; ti++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) P[(16 * ti + lq + 4 * r) * kP8Stride + m] = c[tile_id(ti, TJ)][r];
+  }
+}
+
+// Rank-nb update (nb <= 4): every tile of the columns >= TJ takes exactly one MFMA, under no branch.  A live tile got this MFMA,
+// with these operands, from reg_trailing8 as well.  The tiles that gain one are column TJ's on the step that ends the tile column:
+// they hold finished pivot columns, which nothing reads any more (the factor panel leaves through the panel buffer, the update-matrix
+// store skips col < p).
+// Order: column TJ, then column TJ + 1, then the rest.  Three steps out of four extract their next panel from column TJ, the
+// fourth from TJ + 1 (behind at most NT - TJ MFMAs of the dead column); the rest drains under the next step's pivot chain.
+template <int TJ, int NT>
+__device__ __forceinline__ void reg_trailing4(double4_t (&c)[NT * (NT + 1) / 2], const double* P, int nb, int lane) {
+  const int l16 = lane & 15, lq = lane >> 4;
+  const bool v0 = lq < nb;
+  double a0[NT];
+#pragma unroll
+  for (int t = TJ; t < NT; t++) { const double x = P[(16 * t + l16) * kP8Stride + lq]; a0[t] = v0 ? x : 0.0; }
+#pragma unroll
+  for (int tj = TJ; tj < NT; tj++)
+#pragma unroll
+    for (int ti = tj; ti < NT; ti++) c[tile_id(ti, tj)] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a0[ti], a0[tj], c[tile_id(ti, tj)], 0, 0, 0);
+}
+
 }  // namespace pps
