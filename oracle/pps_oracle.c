@@ -678,13 +678,17 @@ static void dplane_ddelta(const double p[4], double D[12]) {
   memcpy(D, m, sizeof m);
 }
 
-/* Euler-rate matrix: d(yaw,pitch,roll)/d(omega) for a right (body) perturbation R Exp(omega) */
-static void dypr_domega(double pitch, double roll, double E[9]) {
-  double sr = sin(roll), cr = cos(roll), cp = cos(pitch), tp = tan(pitch);
+/* Euler-rate matrix: d(yaw,pitch,roll)/d(omega) for a right (body) perturbation R Exp(omega) of the rotation q, from the arguments
+ * quat_to_euler hands to atan2 / asin (cp sr = R21, cp cr = R22, sin pitch = -R20): cos(asin(s)) would carry asin's conditioning,
+ * eps / cos^2 pitch of the entries near pitch = +-pi/2 (measured against tests/golden/mp_geometry_cases.json) */
+static void dypr_domega(const double q[4], double E[9]) {
+  const double q0 = q[3], q1 = q[0], q2 = q[1], q3 = q[2];
+  double a = 2.0 * (q0 * q1 + q2 * q3), b = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3, s = 2.0 * (q0 * q2 - q3 * q1);
+  double c2 = a * a + b * b, cp = sqrt(c2);
   double m[9] = {
-      0.0, sr / cp, cr / cp,   /* yaw   */
-      0.0, cr,      -sr,       /* pitch */
-      1.0, sr * tp, cr * tp};  /* roll  */
+      0.0, a / c2,     b / c2,       /* yaw   */
+      0.0, b / cp,     -a / cp,      /* pitch */
+      1.0, a * s / c2, b * s / c2};  /* roll  */
   memcpy(E, m, sizeof m);
 }
 
@@ -744,8 +748,7 @@ static void analytic_basic_jacobian(ora_graph* g, const factor_t* f, double* He,
     }
     case F_POSE_PRIOR: {
       pose_t p = g->nodes[f->n[0]].pose0;
-      double v[6]; pose_vector(&p, v);
-      double E[9]; dypr_domega(v[4], v[5], E);
+      double E[9]; dypr_domega(p.q, E);
       for (int i = 0; i < 3; i++) He[i * ncols + i] = 1.0;
       for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) He[(3 + i) * ncols + 3 + j] = E[i * 3 + j];
       break;
@@ -755,7 +758,7 @@ static void analytic_basic_jacobian(ora_graph* g, const factor_t* f, double* He,
       const pose_t* p2 = &g->nodes[f->n[1]].pose0;
       pose_t pred; pose_ominus(p2, p1, &pred);
       double v[6]; pose_vector(&pred, v);
-      double E[9]; dypr_domega(v[4], v[5], E);
+      double E[9]; dypr_domega(pred.q, E);
       double R1[9], R12[9];
       quat_to_R(p1->q, R1);
       quat_to_R(pred.q, R12);

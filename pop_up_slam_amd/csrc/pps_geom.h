@@ -467,12 +467,18 @@ PPS_HD void dlog_times_Q(const double DL[12], const double qm[4], double A[12]) 
     }
 }
 
-// d(yaw,pitch,roll)/d(omega) for a right (body-frame) perturbation R Exp(omega), ZYX Euler angles
-PPS_HD void dypr_domega(double pitch, double roll, double E[9]) {
-  const double sr = sin(roll), cr = cos(roll), cp = cos(pitch), tp = tan(pitch);
-  E[0] = 0.0; E[1] = sr / cp; E[2] = cr / cp;
-  E[3] = 0.0; E[4] = cr;      E[5] = -sr;
-  E[6] = 1.0; E[7] = sr * tp; E[8] = cr * tp;
+// d(yaw,pitch,roll)/d(omega) for a right (body-frame) perturbation R Exp(omega), ZYX Euler angles, of the rotation q:
+//   [0 sr/cp cr/cp ; 0 cr -sr ; 1 sr tp cr tp] with cp (sr, cr) = (R21, R22) and sin pitch = -R20 -- the arguments quat_to_euler hands to
+// atan2 and asin.  The angles themselves are not used: cos(asin(s)) carries asin's conditioning, eps / cos^2 pitch of the entries (4e-5 of
+// them at 1e-6 from pitch = +-pi/2, against the arbitrary-precision Jacobian of tests/golden/mp_geometry_cases.json), where R21 and R22 hold
+// cp to their own round-off, eps / cos pitch.
+PPS_HD void dypr_domega(const double q[4], double E[9]) {
+  const double q0 = q[3], q1 = q[0], q2 = q[1], q3 = q[2];
+  const double a = 2.0 * (q0 * q1 + q2 * q3), b = q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3, s = 2.0 * (q0 * q2 - q3 * q1);
+  const double c2 = a * a + b * b, cp = sqrt(c2);
+  E[0] = 0.0; E[1] = a / c2;     E[2] = b / c2;
+  E[3] = 0.0; E[4] = b / cp;     E[5] = -a / cp;
+  E[6] = 1.0; E[7] = a * s / c2; E[8] = b * s / c2;
 }
 
 // Pose-plane edge: residual e (3), Jp = de/d(pose tangent) 3x6, Jl = de/d(plane tangent) 3x3 (unwhitened)
@@ -550,7 +556,7 @@ PPS_HD void jac_pose_prior(const double pose[7], const double meas6[6], double e
   e[3] = standard_rad(ypr[0] - meas6[3]);
   e[4] = standard_rad(ypr[1] - meas6[4]);
   e[5] = standard_rad(ypr[2] - meas6[5]);
-  dypr_domega(ypr[1], ypr[2], E);
+  dypr_domega(pose + 3, E);
 #pragma unroll
   for (int i = 0; i < 36; i++) J[i] = 0.0;
   J[0] = J[7] = J[14] = 1.0;
@@ -571,7 +577,7 @@ PPS_HD void jac_odometry(const double p1[7], const double p2[7], const double me
   e[3] = standard_rad(ypr[0] - meas6[3]);
   e[4] = standard_rad(ypr[1] - meas6[4]);
   e[5] = standard_rad(ypr[2] - meas6[5]);
-  dypr_domega(ypr[1], ypr[2], E);
+  dypr_domega(q, E);
 #pragma unroll
   for (int i = 0; i < 36; i++) { J1[i] = 0.0; J2[i] = 0.0; }
 #pragma unroll
