@@ -341,6 +341,7 @@ int pps_remove_node(pps_graph* g, int nid) {
   }
   cov_invalidate(g);
   g->nodes[nid].deleted = true;
+  if (g->lm_of_plane.count(nid)) g->lms_dirty = true;   // its landmark record on the device still carries a live plane_slot
   g->n_removals++;
   g->grown_only = false; g->grown_only_upload = false;
   g->n_live_nodes--;
