@@ -5,7 +5,7 @@
 //   pps_solve.cpp    pps_update (Optimizer::relinearize), pps_batch_optimize (Optimizer::levenberg_marquardt), chi2
 //   pps_multi.cpp    pps_multi: G graphs per launch, lockstep LM rounds
 //   pps_k3_plan.h    how K3 is launched on an analysis (plan_k3 -> K3Plan: form, waves, LDS of every launch): host only, no HIP
-//   pps_lm.h         the LM rule the loops of pps_solve.cpp and pps_multi.cpp share (accept / reject / stop, lambda schedule, trace, counters): host only, no HIP
+//   pps_lm.h         the LM rule the loops of pps_solve.cpp and pps_multi.cpp share (accept / reject / stop, lambda schedule, trace, counters) and the dual-trial walk with the rotation of the three state copies: host only, no HIP
 //   pps_frames.cpp   registered frames (measurement refresh on the device), data association, point re-projection
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
 //   pps_cov.cpp      marginal covariances from the factor (isam::Covariances): the recovery pipeline and the reads of the selected inverse; kernels in pps_cov*.hip
@@ -340,6 +340,17 @@ struct NoSolveScope {
   }
 };
 inline LmSink lm_sink(pps_graph* g, bool verbose) { return LmSink{&g->props, &g->tr_lambda, &g->tr_chi2, &g->tr_acc, &g->stats, verbose}; }
+// the end of a dual-trial solve (LmDualWalk, pps_lm.h): of the three state copies, `fin` (LmDualWalk::final_copy) is the estimate; the other two,
+// dead now, are the linearisation point and the spare of the next solve
+inline void place_state_copies(pps_graph* g, double* const pose[3], double* const plane[3], int fin) {
+  g->dev.pose_est = pose[fin]; g->dev.plane_est = plane[fin];
+  g->dev.pose_lin = pose[(fin + 1) % 3]; g->dev.plane_lin = plane[(fin + 1) % 3];
+  g->spec_pose = pose[(fin + 2) % 3]; g->spec_plane = plane[(fin + 2) % 3];
+}
+// status word of a result record (rec[2]): 0 ok | 1 not positive definite | >= kStatusInternal an internal hand-over of a K3 launch timed out
+// (flow_wait, pps_k3.hip) -- the numbers of that record are not a solution, the call answers PPS_EHIP with this text
+constexpr const char* kHandoverMessage = "internal error: a hand-over flag between the waves or workgroups of a K3 launch never arrived (the step was discarded)";
+inline bool handover_timed_out(const double* rec) { return rec[2] >= pps::kStatusInternal; }
 // the one place where a handle's cost function chooses the kernels: K1 and the two chi2 sweeps (everything else consumes J, r and delta)
 inline bool robust(const pps_graph* g) { return g->cost.kind != COST_NONE; }
 inline hipError_t lin_launch(pps_graph* g, int mode, bool at_estimate, const LinGuard* guard = nullptr, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {

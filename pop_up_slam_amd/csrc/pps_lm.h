@@ -1,7 +1,9 @@
 // pps_lm.h -- the Levenberg-Marquardt rule of Optimizer::levenberg_marquardt (Thirdparty/isam/isamlib/Optimizer.cpp:371-467), once.
 // Host only, no HIP: the three host loops (lm_solve, lm_solve_dual: pps_solve.cpp; the rounds of pps_multi.cpp) decide WHEN a trial's
 // chi2 is on the host and what to launch next; what a chi2 means -- accept / reject / stop, the lambda schedule, the trace, the trial
-// counters, the not-PD report -- is here, and tests/test_host_lm.py replays recorded trajectories through it without a device.
+// counters, the not-PD report -- is here (LmControl), and so is the scheme lm_solve_dual and the batched rounds share (LmDualWalk): the walk
+// over the two records of a launch set that solved the step for lambda and for lambda * factor, and the rotation of the three state copies
+// that an accepted trial causes.  tests/test_host_lm.py replays recorded trajectories through both without a device.
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -86,6 +88,41 @@ struct LmControl {
     st.lm_trials_notpd = n_notpd;
     if (iterations) *iterations = num_iter;
     return last_notpd ? PPS_ENOTPD : PPS_OK;
+  }
+};
+
+// The dual-trial walk.  A launch set solves the step for lambda (record 0) and, when it carries two trials, for lambda * factor (record 1):
+// the step LM asks for next if it rejects the first.  One object per graph: the rule, which record is judged next, whether record 1 is such
+// a step, whether the solve ended on an accepted, converged trial -- and x, the place of the linearisation point among the three copies of
+// the state.  The copies rotate by index (the batch kernels read x: BatchArgs::xsel): trial k of a set is written to copy (x + 1 + k) % 3, an
+// accepted trial's copy is the next x.  What judge() says the caller owes:
+enum class LmNext {
+  Done,          // nothing: the solve is over (converged on this trial)
+  Second,        // the set's second record: once it is on the host, lm.take_step on it, then lm.running / judge again
+  Relaunch,      // both rejected: a new launch set (begin_set) on the same J and H
+  Relinearise    // accepted: x is that trial's copy now (cur still names the trial); relinearise there, then a new launch set
+};
+
+struct LmDualWalk {
+  LmControl lm;
+  int cur = 0, x = 0;              // record of the launch set that is judged next | copy that holds the linearisation point
+  bool have_next = false;          // record 1 of the set holds the step for the next lambda
+  bool trial_taken = false;        // ended on an accepted, converged trial: the estimate is that trial, not the linearisation point
+
+  explicit LmDualWalk(const pps_props& p) : lm(p) {}
+
+  // the copy trial k of a launch set goes to: (x + 1 + k) % 3, without the division (judge() rotates between a record and the launch it triggers)
+  int trial(int k) const { const int c = x + 1 + k; return c < 3 ? c : c - 3; }
+  int final_copy() const { return trial_taken ? trial(cur) : x; }    // linpoint_to_estimate (:466), or x when the pending step is dropped
+  void begin_set(bool two_trials) { cur = 0; have_next = two_trials; }
+  // the trial `cur` has chi2 error_new; *t is that trial for LmControl::note (at once, or behind the launch the answer asks for)
+  __attribute__((always_inline)) LmNext judge(const pps_props& p, double error_new, LmControl::Trial* t) {
+    const LmVerdict v = lm.decide(p, error_new, t);
+    if (v == LmVerdict::Converged) { trial_taken = true; return LmNext::Done; }
+    if (v == LmVerdict::Accepted) { x = trial(cur); return LmNext::Relinearise; }
+    if (!have_next) return LmNext::Relaunch;
+    cur = 1; have_next = false;
+    return LmNext::Second;
   }
 };
 

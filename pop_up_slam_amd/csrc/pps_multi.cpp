@@ -370,37 +370,29 @@ static bool plan_chunks(const std::vector<pps_graph*>& gs, int max_stages, int n
 }
 
 // ---- 4. the rounds: every graph walks lm_solve_dual's scheme, in lockstep rounds of one linearisation each ----
-// a graph's place in that scheme: the LM rule's state and what it writes, and which of its records / state copies the next verdict is about
+// a graph's place in that scheme (LmDualWalk, pps_lm.h), what the rule writes, and what the next round owes the graph
 struct GraphRun {
-  LmControl lm;
+  LmDualWalk walk;
   LmSink sink;                     // (no "LM Iteration" lines from a batch)
-  int cur = 0, xsel = 0;
-  bool done = false, have_next = true, relin = true, active = true, trial_taken = false;
+  bool done = false, relin = true, active = true;
 };
 
-// the part of lm_solve_dual's loop that needs no launch: consume the verdicts that are on the host (rec: the graph's 12 result doubles).
-// Returns with the graph done, or active (and possibly relin) for the next round.
+// consume the verdicts that are on the host (rec: the graph's 12 result doubles; chunk_done has seen both trial records, so the second one is
+// taken at once).  Returns with the graph done, or active (and possibly relin) for the next round, every set of which carries two trials.
 static void advance(GraphRun& q, pps_graph* g, const double* rec) {
   q.active = false; q.relin = false;
-  for (;;) {
-    if (!q.lm.running(g->props)) { q.done = true; return; }
-    const LmVerdict v = q.lm.judge(q.sink, rec[4 * (1 + q.cur)]);
-    if (v == LmVerdict::Converged) { q.trial_taken = true; q.done = true; return; }
-    if (v == LmVerdict::Accepted) {
-      q.xsel = (q.xsel + 1 + q.cur) % 3;                           // the accepted copy is the linearisation point now
-      q.relin = true; q.active = true; q.cur = 0; q.have_next = true;
-      g->stats.n_linearize++; g->stats.n_factorize += 2;
-      return;
-    }
-    if (q.have_next) {                                             // the step for this lambda was computed alongside
-      q.cur = 1; q.have_next = false;
-      q.lm.take_step(rec + 8);
-      continue;
-    }
-    q.active = true; q.cur = 0; q.have_next = true;               // both rejected: same J and H, two more damping values
-    g->stats.n_factorize += 2;
+  while (q.walk.lm.running(g->props)) {
+    LmControl::Trial t;
+    const LmNext next = q.walk.judge(g->props, rec[4 * (1 + q.walk.cur)], &t);
+    LmControl::note(q.sink, t);
+    if (next == LmNext::Second) { q.walk.lm.take_step(rec + 8); continue; }
+    if (next == LmNext::Done) break;
+    q.active = true; q.relin = next == LmNext::Relinearise;       // (else both rejected: same J and H, two more damping values)
+    q.walk.begin_set(true);
+    g->stats.n_linearize += q.relin ? 1 : 0; g->stats.n_factorize += 2;
     return;
   }
+  q.done = true;
 }
 
 struct RoundsHostTime { double launch = 0.0, book = 0.0; int n = 0; };   // host seconds inside run_round / between a chunk's records and its next launch
@@ -417,8 +409,8 @@ static int run_rounds(pps_multi* m, const ChunkPlan& plan, int mode, std::vector
     a.no_products = geom[c].lin_thread_form ? 1 : 0;
     for (int k = 0; k < a.n; k++) {
       const GraphRun& q = lm[a.b0 + k];
-      a.lambda[k] = q.lm.lambda; a.lambda2[k] = q.lm.lambda * m->gs[a.b0 + k]->props.lm_lambda_factor;
-      a.xsel[k] = (unsigned char)q.xsel;
+      a.lambda[k] = q.walk.lm.lambda; a.lambda2[k] = q.walk.lm.lambda * m->gs[a.b0 + k]->props.lm_lambda_factor;
+      a.xsel[k] = (unsigned char)q.walk.x;
       a.flags[k] = (unsigned char)((q.active ? BF_ACTIVE : 0) | (q.relin ? BF_RELIN : 0));
     }
     return a;
@@ -491,15 +483,13 @@ static int run_rounds(pps_multi* m, const ChunkPlan& plan, int mode, std::vector
         pps_graph* g = m->gs[i];
         const double* rr = m->results + 12 * (size_t)i;       // chi2 at x | trial 0 | trial 1: (chi2, |delta|^2, status word, seq) each
         if (cr[c].first) {
-          lm[i].lm.error = rr[0]; g->stats.chi2_initial = rr[0];
-          lm[i].lm.take_step(rr + 4);
+          lm[i].walk.lm.error = rr[0]; g->stats.chi2_initial = rr[0];
+          lm[i].walk.lm.take_step(rr + 4);
           g->stats.n_linearize = 1; g->stats.n_factorize = 2;
-        } else if (lm[i].active) lm[i].lm.take_step(rr + 4);
-        if (lm[i].active || cr[c].first) {                      // status words of this round's records (see wait_result, pps_solve.cpp)
-          if (rr[4 + 2] >= kStatusInternal || rr[8 + 2] >= kStatusInternal) {
-            drain();
-            return mfail(m, PPS_EHIP, "graph " + std::to_string(i) + ": internal error: a hand-over flag between the waves or workgroups of a K3 launch never arrived");
-          }
+        } else if (lm[i].active) lm[i].walk.lm.take_step(rr + 4);
+        if ((lm[i].active || cr[c].first) && (handover_timed_out(rr + 4) || handover_timed_out(rr + 8))) {      // this round's records (see wait_result, pps_solve.cpp)
+          drain();
+          return mfail(m, PPS_EHIP, "graph " + std::to_string(i) + ": " + kHandoverMessage);
         }
         if (!lm[i].done) advance(lm[i], g, rr); else { lm[i].active = false; lm[i].relin = false; }
         n_active += lm[i].active ? 1 : 0;
@@ -545,16 +535,10 @@ static int finish_graphs(pps_multi* m, const std::vector<BatchAlt>& ha, const st
   for (size_t i = 0; i < m->gs.size(); i++) {
     pps_graph* g = m->gs[i];
     const GraphRun& q = lm[i];
-    // linpoint_to_estimate (:466): the accepted, converged trial -- or the linearisation point when the pending step is dropped
-    const int fin = q.trial_taken ? (q.xsel + 1 + q.cur) % 3 : q.xsel;
-    double* const sp[3] = {ha[i].pose[0], ha[i].pose[1], ha[i].pose[2]};
-    double* const sl[3] = {ha[i].plane[0], ha[i].plane[1], ha[i].plane[2]};
-    g->dev.pose_est = sp[fin]; g->dev.plane_est = sl[fin];
-    g->dev.pose_lin = sp[(fin + 1) % 3]; g->dev.plane_lin = sl[(fin + 1) % 3];
-    g->spec_pose = sp[(fin + 2) % 3]; g->spec_plane = sl[(fin + 2) % 3];
+    place_state_copies(g, ha[i].pose, ha[i].plane, q.walk.final_copy());
     g->dev_values_newer = true; g->pin_holds_est = false;
     g->stats.t_total = m->t_total;
-    const int st_i = q.lm.finish(q.sink, iterations ? &iterations[i] : nullptr);
+    const int st_i = q.walk.lm.finish(q.sink, iterations ? &iterations[i] : nullptr);
     if (st_i != PPS_OK) g->err = kLmNotPdMessage;
     if (status) status[i] = st_i;
     if (st_i != PPS_OK && first_bad == PPS_OK) first_bad = st_i;
@@ -583,7 +567,7 @@ static int multi_optimize(pps_multi* m, int* iterations, int* status) {
   for (const BatchGeom& q : plan.geom) m->forms_last |= (q.lin_thread_form ? 1 : 0) | (q.level_form ? 2 : 0);
   std::vector<GraphRun> lm;
   lm.reserve(G);
-  for (int i = 0; i < G; i++) lm.push_back(GraphRun{LmControl(m->gs[i]->props), lm_sink(m->gs[i], false)});
+  for (int i = 0; i < G; i++) { lm.push_back(GraphRun{LmDualWalk(m->gs[i]->props), lm_sink(m->gs[i], false)}); lm.back().walk.begin_set(true); }
   RoundsHostTime ht;
   rc = run_rounds(m, plan, mode, lm, t0, &ht); if (rc != PPS_OK) return rc;
   m->t_total = now_s() - t0;

@@ -23,17 +23,32 @@ struct PhaseTimer {
   }
 };
 
+// the next start / stop pair of a launch's own events (profiling level 1), the vector grown by two when all are handed out; events = false: none
+static int take_event_pair(pps_graph* g, bool events, std::vector<hipEvent_t>& evs, int& used, hipEvent_t* e0, hipEvent_t* e1) {
+  *e0 = *e1 = nullptr;
+  if (!events) return PPS_OK;
+  if (used + 2 > (int)evs.size()) for (int k = 0; k < 2; k++) { hipEvent_t e; HIP_TRY(g, hipEventCreate(&e)); evs.push_back(e); }
+  *e0 = evs[used]; *e1 = evs[used + 1]; used += 2;
+  return PPS_OK;
+}
+// ... of a K1 sweep (resolve_k1_events sums them into t_linearize).  skip: not (yet) a linearisation that ran.  *pair: its index, -1 without profiling
+static int take_k1_events(pps_graph* g, char skip, hipEvent_t* e0, hipEvent_t* e1, int* pair = nullptr) {
+  const bool events = g->profiling == 1;
+  const int rc = take_event_pair(g, events, g->k1_events, g->k1_used, e0, e1); if (rc != PPS_OK) return rc;
+  if (pair) *pair = events ? g->k1_used / 2 - 1 : -1;
+  if (!events) return PPS_OK;
+  g->k1_skip.resize(g->k1_events.size() / 2, 0);
+  g->k1_skip[g->k1_used / 2 - 1] = skip;
+  return PPS_OK;
+}
+
 // linearise at `lin` (K1) and reduce the H blocks (K2)
 // guard: the launches are speculative (dual LM loop) -- the caller counts them once it knows they ran
 int do_linearize(pps_graph* g, const LinGuard* guard = nullptr) {
   if (g->profiling == 1) {
-    if (g->k1_used + 2 > (int)g->k1_events.size()) {
-      for (int k = 0; k < 2; k++) { hipEvent_t e; HIP_TRY(g, hipEventCreate(&e)); g->k1_events.push_back(e); }
-    }
-    g->k1_skip.resize(g->k1_events.size() / 2, 0);
-    g->k1_skip[g->k1_used / 2] = 0;
-    HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, false, guard, g->k1_events[g->k1_used], g->k1_events[g->k1_used + 1]));
-    g->k1_used += 2;
+    hipEvent_t e0, e1;
+    { const int rc = take_k1_events(g, 0, &e0, &e1); if (rc != PPS_OK) return rc; }
+    HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, false, guard, e0, e1));
   } else
   { PhaseTimer t(g, &g->stats.t_linearize); HIP_TRY(g, lin_launch(g, g->props.jacobian_mode, false, guard)); }
   { PhaseTimer t(g, &g->stats.t_assemble); HIP_TRY(g, launch_hblocks(g->dev, g->stream, guard, k1_products(g->dev, g->props.jacobian_mode))); }
@@ -44,16 +59,7 @@ int do_linearize(pps_graph* g, const LinGuard* guard = nullptr) {
 // delta = (J'J + lambda diag(J'J))^-1 J'b  (Optimizer::compute_gauss_newton_step, Optimizer.cpp:49-67)
 // Factor stages leaves -> root, back-substitution stages root -> leaves, for one damping value (alt == nullptr) or two.  The root stage
 // is one launch for both directions where its fronts allow it (K3Plan::root).  events: the factor launches carry their own start /
-// stop events (profiling level 1; the fused root launch's pair spans its back-substitution as well).
-// the start / stop events of a factor launch (profiling level 1: resolve_k1_events sums the pairs into t_factor)
-static int take_factor_events(pps_graph* g, bool events, hipEvent_t* e0, hipEvent_t* e1) {
-  *e0 = *e1 = nullptr;
-  if (!events) return PPS_OK;
-  if (g->fk_used + 2 > (int)g->fk_events.size()) for (int k = 0; k < 2; k++) { hipEvent_t e; HIP_TRY(g, hipEventCreate(&e)); g->fk_events.push_back(e); }
-  *e0 = g->fk_events[g->fk_used]; *e1 = g->fk_events[g->fk_used + 1]; g->fk_used += 2;
-  return PPS_OK;
-}
-
+// stop events (profiling level 1: resolve_k1_events sums the pairs into t_factor; the fused root launch's pair spans its back-substitution as well).
 // first_launched: called once, behind the first launch (the dual LM loop does there what it kept off the stretch in front of that launch)
 struct NoHook { void operator()() const {} };
 template <class Hook = NoHook>
@@ -61,7 +67,7 @@ static int enqueue_factor_solve(pps_graph* g, const DevGraph& dv, const DualAlt*
   const K3Plan& P = g->plan;
   hipEvent_t e0, e1;
   if (P.form == K3Form::BandAll) {                                 // the whole tree: two launches (pps_k3.hip, XGroup)
-    { const int rc = take_factor_events(g, events, &e0, &e1); if (rc != PPS_OK) return rc; }
+    { const int rc = take_event_pair(g, events, g->fk_events, g->fk_used, &e0, &e1); if (rc != PPS_OK) return rc; }
     g->k3_epoch = g->k3_epoch >= (1 << 30) ? 1 : g->k3_epoch + 1;
     HIP_TRY(g, launch_band_all_factor(dv, alt, P, lambda, g->k3_epoch, st_, e0, e1));
     first_launched();
@@ -71,7 +77,7 @@ static int enqueue_factor_solve(pps_graph* g, const DevGraph& dv, const DualAlt*
   const int top = (int)P.stages.size() - 1;
   const bool fuse = P.root.fusable;
   for (int st = 0; st <= top; st++) {
-    { const int rc = take_factor_events(g, events, &e0, &e1); if (rc != PPS_OK) return rc; }
+    { const int rc = take_event_pair(g, events, g->fk_events, g->fk_used, &e0, &e1); if (rc != PPS_OK) return rc; }
     if (fuse && st == top) HIP_TRY(g, launch_band_root(dv, alt, P, lambda, st_, e0, e1));
     else HIP_TRY(g, launch_band_factor(dv, alt, P.stages[st], lambda, st_, e0, e1));
     if (st == 0) first_launched();
@@ -80,10 +86,16 @@ static int enqueue_factor_solve(pps_graph* g, const DevGraph& dv, const DualAlt*
   return PPS_OK;
 }
 
+// the second factorisation of a handle (its spec_* buffers, pps_upload.cpp), for the damping value lambda2
+static DualAlt dual_alt(const pps_graph* g, double lambda2) {
+  return DualAlt{g->spec_L, g->spec_U, g->spec_delta, g->spec_result, g->spec_chi2_partials, g->spec_dn_partials, g->spec_ticket, lambda2};
+}
+
 int do_solve_on(pps_graph* g, const DevGraph& dv, double lambda, hipStream_t st_) { return enqueue_factor_solve(g, dv, nullptr, lambda, st_, false); }
 
 // The factorisation alone, every launch a plain one on g->stream: one launch per band stage, or -- dense fronts -- L zeroed, the H blocks
-// pushed, one launch per level.  The profiled forms of do_solve and the covariance recovery (pps_cov.cpp: lambda = 0) factor with it.
+// pushed, one launch per level, or one launch per level of the workgroup-per-front kernels.  The profiled forms of do_solve and the
+// covariance recovery (pps_cov.cpp: lambda = 0, band and dense fronts only) factor with it.
 int enqueue_plain_factor(pps_graph* g, double lambda) {
   const Analysis& A = g->an;
   const DevGraph& d = g->dev;
@@ -91,63 +103,48 @@ int enqueue_plain_factor(pps_graph* g, double lambda) {
     for (const K3StagePlan& sp : g->plan.stages) HIP_TRY(g, launch_band_factor(d, nullptr, sp, lambda, g->stream, nullptr, nullptr, false));
     return PPS_OK;
   }
-  HIP_TRY(g, hipMemsetAsync(d.L, 0, (size_t)A.L_size * 8, g->stream));
-  HIP_TRY(g, launch_dense_hpush(d, g->plan.max_el_per_front, lambda, g->stream));
+  if (g->use_dense()) {
+    HIP_TRY(g, hipMemsetAsync(d.L, 0, (size_t)A.L_size * 8, g->stream));
+    HIP_TRY(g, launch_dense_hpush(d, g->plan.max_el_per_front, lambda, g->stream));
+  }
   for (int l = 0; l < A.n_levels; l++) {
     const int base = A.level_off[l] + l, cnt = A.level_off[l + 1] - A.level_off[l];
-    HIP_TRY(g, launch_dense_factor_level(d, A.level_off[l], cnt, g->d_dw_asm + base, g->plan.dw_asm[base + cnt], g->d_dw_pan + base, g->plan.dw_pan[base + cnt],
-                                         g->d_dw_trl + base, g->plan.dw_trl[base + cnt], g->stream));
+    if (g->use_dense()) HIP_TRY(g, launch_dense_factor_level(d, A.level_off[l], cnt, g->d_dw_asm + base, g->plan.dw_asm[base + cnt], g->d_dw_pan + base, g->plan.dw_pan[base + cnt],
+                                                             g->d_dw_trl + base, g->plan.dw_trl[base + cnt], g->stream));
+    else HIP_TRY(g, launch_factor_level(d, A.level_off[l], cnt, g->plan.level_max_front[l], lambda, g->stream));
+  }
+  return PPS_OK;
+}
+
+// ... and its back-substitution: the stages, or the levels, from the root down
+static int enqueue_plain_backsolve(pps_graph* g) {
+  const Analysis& A = g->an;
+  const DevGraph& d = g->dev;
+  if (g->use_band()) {
+    for (int st = A.n_stages - 1; st >= 0; st--) HIP_TRY(g, launch_band_solve(d, nullptr, g->plan.stages[st], g->stream));
+    return PPS_OK;
+  }
+  for (int l = A.n_levels - 1; l >= 0; l--) {
+    const int cnt = A.level_off[l + 1] - A.level_off[l];
+    if (g->use_dense()) HIP_TRY(g, launch_dense_solve_level(d, A.level_off[l], cnt, g->plan.level_max_b[l], g->stream));
+    else HIP_TRY(g, launch_backsolve_level(d, A.level_off[l], cnt, g->stream));
   }
   return PPS_OK;
 }
 
 int do_solve(pps_graph* g, double lambda) {
-  const Analysis& A = g->an;
-  if (g->use_band()) {
-    if (g->profiling < 2) {            // no per-phase timing
-      int rc = do_solve_on(g, g->dev, lambda, g->stream);
-      if (rc != PPS_OK) return rc;
-      g->stats.n_factorize++;
-      return PPS_OK;
-    }
-    {
-      PhaseTimer t(g, &g->stats.t_factor);
-      const int rc = enqueue_plain_factor(g, lambda); if (rc != PPS_OK) return rc;
-    }
-    {
-      PhaseTimer t(g, &g->stats.t_backsolve);
-      for (int st = A.n_stages - 1; st >= 0; st--) HIP_TRY(g, launch_band_solve(g->dev, nullptr, g->plan.stages[st], g->stream));
-    }
-    g->stats.n_factorize++;
-    return PPS_OK;
-  }
-  if (g->use_dense()) {
-    {
-      PhaseTimer t(g, &g->stats.t_factor);
-      const int rc = enqueue_plain_factor(g, lambda); if (rc != PPS_OK) return rc;
-    }
-    {
-      PhaseTimer t(g, &g->stats.t_backsolve);
-      for (int l = A.n_levels - 1; l >= 0; l--)
-        HIP_TRY(g, launch_dense_solve_level(g->dev, A.level_off[l], A.level_off[l + 1] - A.level_off[l], g->plan.level_max_b[l], g->stream));
-    }
-    g->stats.n_factorize++;
-    return PPS_OK;
-  }
-  {
-    PhaseTimer t(g, &g->stats.t_factor);
-    for (int l = 0; l < A.n_levels; l++)
-      HIP_TRY(g, launch_factor_level(g->dev, A.level_off[l], A.level_off[l + 1] - A.level_off[l], g->plan.level_max_front[l], lambda,
-                                     g->stream));
-  }
-  {
-    PhaseTimer t(g, &g->stats.t_backsolve);
-    for (int l = A.n_levels - 1; l >= 0; l--)
-      HIP_TRY(g, launch_backsolve_level(g->dev, A.level_off[l], A.level_off[l + 1] - A.level_off[l], g->stream));
+  if (g->use_band() && g->profiling < 2) {            // no per-phase timing: the fused launches
+    const int rc = do_solve_on(g, g->dev, lambda, g->stream); if (rc != PPS_OK) return rc;
+  } else {
+    { PhaseTimer t(g, &g->stats.t_factor); const int rc = enqueue_plain_factor(g, lambda); if (rc != PPS_OK) return rc; }
+    { PhaseTimer t(g, &g->stats.t_backsolve); const int rc = enqueue_plain_backsolve(g); if (rc != PPS_OK) return rc; }
   }
   g->stats.n_factorize++;
   return PPS_OK;
 }
+
+// the status word of a record that has arrived (kHandoverMessage, pps_graph.h)
+static int check_handover(pps_graph* g, const double* rec) { return handover_timed_out(rec) ? fail(g, PPS_EHIP, kHandoverMessage) : PPS_OK; }
 
 // Wait for the result record with sequence number `seq`: spin on the pinned word the chi2 kernel writes
 // last (a few microseconds), falling back to a stream sync if it does not show up (launch failure).
@@ -162,10 +159,7 @@ int wait_result(pps_graph* g, volatile double* slot, double seq, hipStream_t pro
     }
   }
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  // status word of the solve that produced the record: 0 ok | 1 not positive definite | >= 64 an internal hand-over of the
-  // back-substitution timed out (flow_wait, pps_k3.hip) -- the numbers of this record are not a solution
-  if (slot[2] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: a hand-over flag between the waves or workgroups of a K3 launch never arrived (the step was discarded)");
-  return PPS_OK;
+  return check_handover(g, const_cast<const double*>(slot));
 }
 
 // est <-> lin by pointer: a rejected LM trial (estimate_to_linpoint, Optimizer.cpp:454) and the final
@@ -203,8 +197,7 @@ int read_result(pps_graph* g, bool at_estimate, double* chi2, double* dnorm, boo
   *chi2 = g->host_result[0];
   if (dnorm) *dnorm = std::sqrt(g->host_result[1]);
   if (notpd) *notpd = g->host_result[2] != 0.0;
-  if (g->host_result[2] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: a hand-over flag between the waves or workgroups of a K3 launch never arrived (the step was discarded)");
-  return PPS_OK;
+  return check_handover(g, g->host_result);
 }
 
 // after the final stream sync of a solve: fold the K1 event pairs into stats.t_linearize
@@ -232,6 +225,9 @@ static void reset_solve_stats(pps_graph* g) {
   g->launches0 = launch_count();
 }
 
+// a solve call ends: its wall time and the launches it issued
+static void end_solve_stats(pps_graph* g, double t0) { g->stats.t_total = now_s() - t0; g->stats.n_launches = (int)(launch_count() - g->launches0); }
+
 void begin_solve(pps_graph* g) {
   reset_solve_stats(g);
   g->tr_lambda.clear(); g->tr_chi2.clear(); g->tr_acc.clear();
@@ -240,6 +236,9 @@ void begin_solve(pps_graph* g) {
 // the device copy of a handle is given up after a failed solve: streams drained, nothing on the device is trusted any more --
 // the next upload sends the whole arena (up_unknown: the mirror says nothing about the device, measurements included) and the
 // estimate falls back to the host's node values
+// status_clean: both records' status words are zero since the upload, or the last call's chi2 kernels took them along.  The flag stands for BOTH
+// records: a one-step LM solve may have left a not-PD flag of a speculative factorisation that was never evaluated in the second one, and the
+// caller sets status_clean again at its end
 int clear_stale_status(pps_graph* g) {
   if (!g->status_clean) {
     HIP_TRY(g, launch_clear_status(g->dev, g->stream));
@@ -280,13 +279,7 @@ static int update_impl(pps_graph* g) {
   if (g->n_live_nodes > 0 && g->n_live_factors == 0) return PPS_OK;   // no factor, no step
   int rc = prepare_solve(g);
   if (rc != PPS_OK) return rc;
-  if (!g->status_clean) {                                              // (else: zero since the upload / the last chi2 kernel)
-    HIP_TRY(g, launch_clear_status(g->dev, g->stream));
-    // the flag stands for BOTH records: a one-step LM solve may have left a not-PD flag of a speculative factorisation that
-    // was never evaluated in the second one, and this call sets status_clean again at its end
-    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
-  }
-  g->status_clean = false;
+  rc = clear_stale_status(g); if (rc != PPS_OK) return rc;
   rc = copy_state(g, true); if (rc != PPS_OK) return rc;          // estimate_to_linpoint (Optimizer.cpp:116)
   rc = do_linearize(g); if (rc != PPS_OK) return rc;              // jacobian() (:119)
   rc = do_solve(g, 0.0); if (rc != PPS_OK) return rc;             // compute_gauss_newton_step, lambda = 0 (:122)
@@ -300,7 +293,7 @@ static int update_impl(pps_graph* g) {
     rc = enqueue_state_download(g); if (rc != PPS_OK) return rc;   // (arrives with the synchronisation below)
     HIP_TRY(g, hipStreamSynchronize(g->stream));
     chi2 = g->host_result[0]; dn = std::sqrt(g->host_result[1]); notpd = g->host_result[2] != 0.0;
-    if (g->host_result[2] >= kStatusInternal) return fail(g, PPS_EHIP, "internal error: a hand-over flag between the waves or workgroups of a K3 launch never arrived (the step was discarded)");
+    rc = check_handover(g, g->host_result); if (rc != PPS_OK) return rc;
   } else {
     { PhaseTimer t(g, &g->stats.t_retract_chi2); HIP_TRY(g, launch_retract_apply(g->dev, g->stream)); }
     rc = enqueue_state_download(g); if (rc != PPS_OK) return rc;
@@ -311,14 +304,14 @@ static int update_impl(pps_graph* g) {
     // the step is garbage: put the estimate back (lin still holds it) instead of handing NaNs to the caller
     rc = copy_state(g, false); if (rc != PPS_OK) return rc;
     HIP_TRY(g, hipStreamSynchronize(g->stream));
-    g->stats.t_total = now_s() - t0; g->stats.n_launches = (int)(launch_count() - g->launches0);
+    end_solve_stats(g, t0);
     return fail(g, PPS_ENOTPD, "normal equations not positive definite");
   }
   g->dev_values_newer = true;
   state_download_arrived(g);
   g->status_clean = true;                                         // the chi2 kernel took the flag with it
   g->stats.chi2_final = chi2; g->stats.last_delta_norm = dn; g->stats.lambda_final = 0;
-  g->stats.t_total = now_s() - t0; g->stats.n_launches = (int)(launch_count() - g->launches0);
+  end_solve_stats(g, t0);
   return PPS_OK;
 }
 
@@ -346,7 +339,7 @@ static int end_lm_solve(pps_graph* g, const LmControl& lm, const LmSink& sink, i
   state_download_arrived(g);
   g->status_clean = true;                // every solve was followed by its chi2 kernel (the dual loop: by both)
   resolve_k1_events(g);
-  g->stats.t_total = now_s() - t0; g->stats.n_launches = (int)(launch_count() - g->launches0);
+  end_solve_stats(g, t0);
   if (g->dev.trace) report_front_trace(g);
   if (lm.finish(sink, iterations) != PPS_OK) return fail(g, PPS_ENOTPD, kLmNotPdMessage);
   return PPS_OK;
@@ -356,32 +349,32 @@ static int end_lm_solve(pps_graph* g, const LmControl& lm, const LmSink& sink, i
 // A rejected trial only changes lambda (same J, same H), so every solve factors H for lambda AND for lambda * factor
 // (blockIdx.y of the band kernels, second L / U / delta set), applies both steps to two spare copies of the state and reduces
 // both chi2 values into two pinned records.  One stream, no events: 10 launches per linearisation instead of 21 on two streams.
-// The host walks the reference's lambda schedule over the records: an accepted step rotates its copy in as the new
-// linearisation point, a first rejection finds the next trial's verdict already on the host.  Arithmetic, lambda schedule and
-// LM trace are exactly those of the one-step-at-a-time loop below.
+// The host walks the reference's lambda schedule over the records (LmDualWalk, pps_lm.h): an accepted step rotates its copy in as the
+// new linearisation point, a first rejection finds the next trial's verdict already on the host.  Arithmetic, lambda schedule and
+// LM trace are exactly those of the one-step-at-a-time loop below.  This function owns what surrounds the walk: the launches, when a
+// record is on the host, whether the next set carries one trial or two, the two kinds of speculative linearisation and the profiling.
 static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
   const pps_props& prop = g->props;
   const Analysis& A = g->an;
-  if (!g->status_clean) {          // (else: both records are zero since the upload, or the last solve's chi2 kernels took the flags)
-    HIP_TRY(g, launch_clear_status(g->dev, g->stream));
-    HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
-  }
-  g->status_clean = false;
-  LmControl lm(prop);
+  int rc = clear_stale_status(g); if (rc != PPS_OK) return rc;
+  LmDualWalk walk(prop);
+  LmControl& lm = walk.lm;
   const LmSink sink = lm_sink(g, prop.verbose != 0);
   double* slot0 = g->host_result;                                   // chi2 at the linearisation point
   double* slot[2] = {g->host_result + 4, g->host_result + 8};       // trial for lambda / for lambda * factor
   DevGraph& d = g->dev;
-  int rc = copy_state(g, true); if (rc != PPS_OK) return rc;       // estimate_to_linpoint (Optimizer.cpp:376): est is dead from here on
-  // three state copies: x = the linearisation point (d.pose_lin), t[0] / t[1] = x (+) delta for the two damping values
-  double *t_pose[2] = {d.pose_est, g->spec_pose}, *t_plane[2] = {d.plane_est, g->spec_plane};
+  rc = copy_state(g, true); if (rc != PPS_OK) return rc;           // estimate_to_linpoint (Optimizer.cpp:376): est is dead from here on
+  // three state copies: walk.x = the linearisation point (d.pose_lin), trial k = x (+) delta of the k-th damping value -> copy walk.trial(k)
+  double* const c_pose[3] = {d.pose_lin, d.pose_est, g->spec_pose};
+  double* const c_plane[3] = {d.plane_lin, d.plane_est, g->spec_plane};
+  auto t_pose = [&](int k) { return c_pose[walk.trial(k)]; };
+  auto t_plane = [&](int k) { return c_plane[walk.trial(k)]; };
   double seqs[2] = {0, 0};
   // Speculation costs what it computes: on a graph whose lower tree levels fill the GPU by themselves (C3: 5 359 fronts) the second
   // factorisation + back-substitution of a launch set are extra time, not idle lanes -- and LM accepts most steps there.  Such a
   // graph factors the second damping value only while LM zig-zags (after a rejection); the trace is the same either way.
   const bool adaptive = A.n_fronts >= 2048;
   bool use_alt = !adaptive;
-  bool have_next = true;                 // trial 1 of the last launch is the step for the next lambda after a rejection
   // Round 6: the linearisation at the trial point LM is expected to accept rides in the trial launch, and K2 follows at once (SpecLin,
   // pps_device.h): when the host has seen the verdict and the prediction held, that point's J / H exist and become the current ones by
   // pointer; a wrong prediction launches the linearisation the plain way.  Graphs whose K1 is not the lane form over plain plane
@@ -396,24 +389,17 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
   auto enqueue_trial_lin = [&](const DualAlt& alt, double s0, double s1) -> int {
     pred_launched = use_alt ? pred : 0;
     const SpecLin sl{g->spec_J, g->spec_P, g->spec_H, g->spec_Hf, pred_launched};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    fused_pair = -1;
-    if (g->profiling == 1) {
-      if (g->k1_used + 2 > (int)g->k1_events.size()) for (int k = 0; k < 2; k++) { hipEvent_t e; HIP_TRY(g, hipEventCreate(&e)); g->k1_events.push_back(e); }
-      g->k1_skip.resize(g->k1_events.size() / 2, 0);
-      fused_pair = g->k1_used / 2;
-      g->k1_skip[fused_pair] = 1;          // (counted once the predicted trial is accepted: its sweep was a linearisation the solve asked for)
-      e0 = g->k1_events[g->k1_used]; e1 = g->k1_events[g->k1_used + 1]; g->k1_used += 2;
-    }
-    HIP_TRY(g, launch_trial_lin(d, alt, sl, d.pose_lin, d.plane_lin, t_pose[0], t_plane[0], t_pose[1], t_plane[1], slot[0], s0, slot[1], s1, g->stream, e0, e1));
+    hipEvent_t e0, e1;                     // (skipped until the predicted trial is accepted: then its sweep was a linearisation the solve asked for)
+    { const int rc2 = take_k1_events(g, 1, &e0, &e1, &fused_pair); if (rc2 != PPS_OK) return rc2; }
+    HIP_TRY(g, launch_trial_lin(d, alt, sl, d.pose_lin, d.plane_lin, t_pose(0), t_plane(0), t_pose(1), t_plane(1), slot[0], s0, slot[1], s1, g->stream, e0, e1));
     // (K2 of that linearisation leaves at once where the records say the prediction failed: 2 us instead of 7 in front of the plain sweep)
     const LinGuard gd{{d.result_dev, g->spec_result}, {nullptr, nullptr}, {nullptr, nullptr}, lm.error, error_known ? 1 : 0, use_alt ? 0 : 1, pred_launched};
     HIP_TRY(g, launch_hblocks_spec(d, sl, g->stream, &gd));
     return PPS_OK;
   };
   // The stretch between a trial record's arrival and the factor launch it triggers is on the solve's critical path -- the device has nothing
-  // queued behind K2 until that launch arrives -- so the host does there only what depends on the verdict: the rule (LmControl::decide), the
-  // pointer rotation, the launch.  The launch geometry of every form is worked out once per analysis (K3Plan), and what the trial leaves
+  // queued behind K2 until that launch arrives -- so the host does there only what depends on the verdict: the rule and the rotation
+  // (LmDualWalk::judge), the launch.  The launch geometry of every form is worked out once per analysis (K3Plan), and what the trial leaves
   // in the trace and the counters (LmControl::note) is written behind the launch.  PPS_LM_PLAIN_HOST: everything in its old place.
   const bool plain_host = g->sw.lm_plain_host;
   struct PendingNote {                   // the judged trial whose bookkeeping is still owed (written at the latest when the loop is left, however)
@@ -432,12 +418,11 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
     t_rec = 0.0; relin = false;
   };
   auto enqueue_dual = [&](double lam) -> int {
-    DualAlt alt{g->spec_L, g->spec_U, g->spec_delta, g->spec_result, g->spec_chi2_partials, g->spec_dn_partials, g->spec_ticket,
-                lam * prop.lm_lambda_factor};
-    have_next = use_alt;
+    const DualAlt alt = dual_alt(g, lam * prop.lm_lambda_factor);
+    walk.begin_set(use_alt);
     // one damping value (!use_alt): the single-lambda launches, and the trial kernel with ONE trial (round 6: it used to walk both copies, the
-    // second one with a stale delta that nothing read -- twice the retraction and chi2 work of a launch that C3 pays 22 us for; have_next is
-    // false, the second record is never waited for)
+    // second one with a stale delta that nothing read -- twice the retraction and chi2 work of a launch that C3 pays 22 us for; the walk never
+    // asks for the second record)
     const int n_trials = use_alt ? 2 : 1;
     const double t_pre = lm_timing ? now_s() : 0.0;
     {
@@ -449,7 +434,7 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
     g->seq += 1.0; seqs[0] = g->seq;
     g->seq2 += 1.0; seqs[1] = g->seq2;
     if (fuse_lin) return enqueue_trial_lin(alt, seqs[0], seqs[1]);
-    HIP_TRY(g, launch_trial_dual(d, alt, d.pose_lin, d.plane_lin, t_pose[0], t_plane[0], t_pose[1], t_plane[1], slot[0], seqs[0], slot[1], seqs[1],
+    HIP_TRY(g, launch_trial_dual(d, alt, d.pose_lin, d.plane_lin, t_pose(0), t_plane(0), t_pose(1), t_plane(1), slot[0], seqs[0], slot[1], seqs[1],
                                  g->stream, n_trials));
     return PPS_OK;
   };
@@ -466,7 +451,7 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
   int spec_pair = -1;                    // K1 event pair of the queued speculative linearisation
   auto enqueue_spec_lin = [&](double err) -> int {
     if (!spec_lin) return PPS_OK;
-    LinGuard gd{{d.result_dev, g->spec_result}, {t_pose[0], t_pose[1]}, {t_plane[0], t_plane[1]}, err, 1, have_next ? 0 : 1};
+    LinGuard gd{{d.result_dev, g->spec_result}, {t_pose(0), t_pose(1)}, {t_plane(0), t_plane(1)}, err, 1, walk.have_next ? 0 : 1};
     spec_pair = g->profiling == 1 ? g->k1_used / 2 : -1;
     return do_linearize(g, &gd);
   };
@@ -477,47 +462,38 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
   g->stats.chi2_initial = lm.error;
   rc = enqueue_spec_lin(lm.error); if (rc != PPS_OK) return rc;
   rc = wait_result(g, slot[0], seqs[0]); if (rc != PPS_OK) return rc;
-  int cur = 0;                           // which of the two trials the loop is looking at
   lm.take_step(slot[0]);
-  bool trial_taken = false;              // the loop ended on an accepted, converged step: the estimate is that trial
   while (lm.running(prop)) {
     if (lm_timing) t_rec = now_s();
-    LmVerdict v;
-    if (plain_host) v = lm.judge(sink, slot[cur][0]);
-    else { v = lm.decide(prop, slot[cur][0], &pending.t); pending.owed = true; }      // (its note: behind the launch, in enqueue_dual)
-    if (v == LmVerdict::Converged) { trial_taken = true; break; }
-    if (v == LmVerdict::Accepted) {
-      if (adaptive) use_alt = cur != 0;                           // (accepted at once: no speculation next time; after a rejection: keep it)
-      pred = cur;
-      // the accepted copy becomes the linearisation point; the old one is the spare now
-      std::swap(d.pose_lin, t_pose[cur]); std::swap(d.plane_lin, t_plane[cur]);
-      if (fuse_lin && cur == pred_launched) {                      // relinearise (:444): done beside the trials, at this very point
-        std::swap(d.J, g->spec_J); std::swap(d.P, g->spec_P); std::swap(d.H, g->spec_H); std::swap(d.Hf, g->spec_Hf);
-        g->stats.n_linearize++;
-        if (fused_pair >= 0 && (size_t)fused_pair < g->k1_skip.size()) g->k1_skip[fused_pair] = 0;
-      }
-      else if (fuse_lin) { relin = true; rc = do_linearize(g); if (rc != PPS_OK) return rc; }      // (the other trial was accepted: the plain way)
-      else if (spec_lin) { g->stats.n_linearize++; spec_pair = -1; }    // ... queued already, at this very copy
-      else { rc = do_linearize(g); if (rc != PPS_OK) return rc; }
-      rc = enqueue_dual(lm.lambda); if (rc != PPS_OK) return rc;   // (:458)
-      rc = enqueue_spec_lin(lm.error); if (rc != PPS_OK) return rc;
-      cur = 0;
-      rc = wait_result(g, slot[0], seqs[0]); if (rc != PPS_OK) return rc;
-    } else {                                                       // estimate_to_linpoint (:454): x was never overwritten
-      if (have_next) {                                             // computed alongside: nothing to launch
-        cur = 1; have_next = false; t_rec = 0.0;
-        pending.flush();
-        rc = wait_result(g, slot[1], seqs[1]); if (rc != PPS_OK) return rc;
-      } else {
+    const LmNext next = walk.judge(prop, slot[walk.cur][0], &pending.t);
+    if (plain_host) LmControl::note(sink, pending.t); else pending.owed = true;      // (its note: behind the launch, in enqueue_dual)
+    if (next == LmNext::Done) break;
+    if (next == LmNext::Second) {                                  // computed alongside: nothing to launch
+      t_rec = 0.0;
+      pending.flush();
+    } else {
+      if (next == LmNext::Relinearise) {                           // the accepted copy is the linearisation point; the old one is a trial's target now
+        const int acc = walk.cur;
+        if (adaptive) use_alt = acc != 0;                          // (accepted at once: no speculation next time; after a rejection: keep it)
+        pred = acc;
+        d.pose_lin = c_pose[walk.x]; d.plane_lin = c_plane[walk.x];
+        if (fuse_lin && acc == pred_launched) {                    // relinearise (:444): done beside the trials, at this very point
+          std::swap(d.J, g->spec_J); std::swap(d.P, g->spec_P); std::swap(d.H, g->spec_H); std::swap(d.Hf, g->spec_Hf);
+          g->stats.n_linearize++;
+          if (fused_pair >= 0 && (size_t)fused_pair < g->k1_skip.size()) g->k1_skip[fused_pair] = 0;
+        }
+        else if (fuse_lin) { relin = true; rc = do_linearize(g); if (rc != PPS_OK) return rc; }      // (the other trial was accepted: the plain way)
+        else if (spec_lin) { g->stats.n_linearize++; spec_pair = -1; }    // ... queued already, at this very copy
+        else { rc = do_linearize(g); if (rc != PPS_OK) return rc; }
+      } else {                                                     // estimate_to_linpoint (:454): x was never overwritten; same J and H
         drop_spec_lin();                                           // both trials rejected: its kernels left J and H alone
         if (adaptive) use_alt = true;                              // LM is zig-zagging: the next rejection should be free again
-        rc = enqueue_dual(lm.lambda); if (rc != PPS_OK) return rc; // (:458), same J and H
-        rc = enqueue_spec_lin(lm.error); if (rc != PPS_OK) return rc;
-        cur = 0;
-        rc = wait_result(g, slot[0], seqs[0]); if (rc != PPS_OK) return rc;
       }
+      rc = enqueue_dual(lm.lambda); if (rc != PPS_OK) return rc;   // (:458)
+      rc = enqueue_spec_lin(lm.error); if (rc != PPS_OK) return rc;
     }
-    lm.take_step(slot[cur]);
+    rc = wait_result(g, slot[walk.cur], seqs[walk.cur]); if (rc != PPS_OK) return rc;
+    lm.take_step(slot[walk.cur]);
   }
   // linpoint_to_estimate (:466): the estimate is the accepted trial, or the linearisation point when the pending step is dropped
   drop_spec_lin();                       // (a linearisation queued behind the last trials is not one the solve asked for)
@@ -525,10 +501,7 @@ static int lm_solve_dual(pps_graph* g, int* iterations, double t0) {
   if (lm_timing && rt_n > 0)
     fprintf(stderr, "[lm] record -> factor launch: %d launch sets, mean %.2f us before the launch call + %.2f us inside it; %d sets that relinearised first, mean %.2f us\n",
             rt_n, 1e6 * rt_pre / rt_n, 1e6 * rt_call / rt_n, rt_n_relin, rt_n_relin ? 1e6 * rt_relin / rt_n_relin : 0.0);
-  if (trial_taken) { std::swap(d.pose_lin, t_pose[cur]); std::swap(d.plane_lin, t_plane[cur]); }
-  d.pose_est = d.pose_lin; d.plane_est = d.plane_lin;
-  d.pose_lin = t_pose[0]; d.plane_lin = t_plane[0];
-  g->spec_pose = t_pose[1]; g->spec_plane = t_plane[1];
+  place_state_copies(g, c_pose, c_plane, walk.final_copy());
   return end_lm_solve(g, lm, sink, iterations, t0);
 }
 
@@ -539,8 +512,7 @@ static int lm_solve(pps_graph* g, int* iterations) {
   if (rc != PPS_OK) return rc;
   if (g->use_band() && g->profiling < 2 && !g->dev.trace && !g->sw.no_dual && !robust(g)) return lm_solve_dual(g, iterations, t0);      // (PPS_NO_DUAL: the loop-forms parity test; a cost function: the robust kernels exist for this loop only)
   const pps_props& prop = g->props;
-  if (!g->status_clean) HIP_TRY(g, launch_clear_status(g->dev, g->stream));
-  g->status_clean = false;
+  rc = clear_stale_status(g); if (rc != PPS_OK) return rc;
   LmControl lm(prop);
   const LmSink sink = lm_sink(g, prop.verbose != 0);
   double* slot0 = g->host_result;       // chi2 at the linearisation point
@@ -608,8 +580,7 @@ static int debug_solve_impl(pps_graph* g, double lambda, double lambda2, double*
   rc = linpoint_from_estimate(g); if (rc != PPS_OK) return rc;
   rc = do_linearize(g); if (rc != PPS_OK) return rc;
   if (dual) {
-    DualAlt alt{g->spec_L, g->spec_U, g->spec_delta, g->spec_result, g->spec_chi2_partials, g->spec_dn_partials, g->spec_ticket,
-                lambda2};
+    const DualAlt alt = dual_alt(g, lambda2);
     rc = enqueue_factor_solve(g, d, &alt, lambda, g->stream, false); if (rc != PPS_OK) return rc;
   } else {
     rc = do_solve(g, lambda); if (rc != PPS_OK) return rc;
@@ -621,9 +592,8 @@ static int debug_solve_impl(pps_graph* g, double lambda, double lambda2, double*
   HIP_TRY(g, hipMemcpyAsync(status, d.result_dev, 4 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
   if (dual) HIP_TRY(g, hipMemcpyAsync(status + 4, g->spec_result, 4 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
   HIP_TRY(g, hipStreamSynchronize(g->stream));
-  if (status[2] != 0.0 || status[6] != 0.0) {
-    HIP_TRY(g, launch_clear_status(d, g->stream));
-    if (g->spec_result) HIP_TRY(g, hipMemsetAsync(g->spec_result, 0, 4 * sizeof(double), g->stream));
+  if (status[2] != 0.0 || status[6] != 0.0) {                  // (status_clean is false since the clear above)
+    rc = clear_stale_status(g); if (rc != PPS_OK) return rc;
     HIP_TRY(g, hipStreamSynchronize(g->stream));
   }
   g->status_clean = true;
