@@ -180,6 +180,24 @@ int run_analysis(pps_graph* g) {
   if (rc != PPS_OK) { g->analyzed = false; g->analysis_stale = true; g->topo_dirty = true; g->cmp_valid = false; g->an_seq++; g->an_base_seq = -1; }
   return rc;
 }
+// host node i joins the compacted tables: the next compact id and the next slot of its type
+static void compact_node(pps_graph* g, size_t i) {
+  HostNode& n = g->nodes[i];
+  n.compact = (int)g->sym_nodes.size();
+  if (n.type == NODE_POSE) { n.slot = (int)g->pose_ids.size(); g->pose_ids.push_back((int)i); g->sym_nodes.push_back({NODE_POSE, 6, n.slot}); }
+  else { n.slot = (int)g->plane_ids.size(); g->plane_ids.push_back((int)i); g->sym_nodes.push_back({NODE_PLANE, 3, -1}); }
+}
+// the analysis' view of a live factor whose slot is assigned (base / pbase: j_bases / p_bases)
+static SymFactor sym_factor_of(const pps_graph* g, const HostFactor& f, const int64_t base[4], const int64_t pbase[4]) {
+  SymFactor q;
+  q.type = f.type;
+  q.a = g->nodes[f.a].compact;
+  q.b = f.b >= 0 ? g->nodes[f.b].compact : -1;
+  q.joff = (int)(base[f.type] + (int64_t)f.slot * kJSize[f.type]);
+  q.poff = (int)(pbase[f.type] + (int64_t)f.slot * kPSize[f.type]);
+  q.direct_ok = (f.type == F_PLANE_OBS && !f.repop) ? 1 : 0;
+  return q;
+}
 static int run_analysis_impl(pps_graph* g) {
   const double t0 = now_s();
   std::vector<SymNode>& sn = g->sym_nodes;
@@ -192,84 +210,52 @@ static int run_analysis_impl(pps_graph* g) {
     append = !g->factors[i].deleted && !(g->factors[i].type == F_PLANE_OBS && g->factors[i].repop);
   for (size_t i = g->cmp_nodes; append && i < g->nodes.size(); i++) append = !g->nodes[i].deleted;
   if (append) {
-    for (size_t i = g->cmp_nodes; i < g->nodes.size(); i++) {
-      HostNode& n = g->nodes[i];
-      n.compact = (int)sn.size();
-      if (n.type == NODE_POSE) { n.slot = (int)g->pose_ids.size(); g->pose_ids.push_back((int)i); sn.push_back({NODE_POSE, 6, n.slot}); }
-      else { n.slot = (int)g->plane_ids.size(); g->plane_ids.push_back((int)i); sn.push_back({NODE_PLANE, 3, -1}); }
-    }
+    for (size_t i = g->cmp_nodes; i < g->nodes.size(); i++) compact_node(g, i);
     for (size_t i = g->cmp_factors; i < g->factors.size(); i++) {
       HostFactor& f = g->factors[i];
       f.slot = (int)g->fslot_ids[f.type].size();
       g->fslot_ids[f.type].push_back((int)i);
     }
     g->n_obs_fixed = (int)g->fslot_ids[F_PLANE_OBS].size();
-    int64_t base[4], j_total = 0, pbase[4], p_total = 0;
-    j_bases(g, base, &j_total);
-    p_bases(g, pbase, &p_total);
-    if (j_total > 0x7fffffffLL || p_total > 0x7fffffffLL) return fail(g, PPS_ENOMEM, "graph too large for int32 J offsets");
-    if (memcmp(base, g->cmp_base, sizeof(base)) != 0) {          // a J slab outgrew its capacity: every offset moves
-      int cnt[4] = {0, 0, 0, 0};
-      for (SymFactor& q : sf) { const int k = cnt[q.type]++; q.joff = (int)(base[q.type] + (int64_t)k * kJSize[q.type]); q.poff = (int)(pbase[q.type] + (int64_t)k * kPSize[q.type]); }
-      memcpy(g->cmp_base, base, sizeof(base));
-    }
-    for (size_t i = g->cmp_factors; i < g->factors.size(); i++) {
-      const HostFactor& f = g->factors[i];
-      SymFactor q;
-      q.type = f.type;
-      q.a = g->nodes[f.a].compact;
-      q.b = f.b >= 0 ? g->nodes[f.b].compact : -1;
-      q.joff = (int)(base[f.type] + (int64_t)f.slot * kJSize[f.type]);
-      q.poff = (int)(pbase[f.type] + (int64_t)f.slot * kPSize[f.type]);
-      q.direct_ok = f.type == F_PLANE_OBS ? 1 : 0;
-      sf.push_back(q);
-    }
   } else {
-  g->pose_ids.clear(); g->plane_ids.clear();
-  for (int t = 0; t < 4; t++) g->fslot_ids[t].clear();
-  sn.clear(); sf.clear();
-  for (size_t i = 0; i < g->nodes.size(); i++) {
-    HostNode& n = g->nodes[i];
-    if (n.deleted) { n.compact = n.slot = -1; continue; }
-    n.compact = (int)sn.size();
-    if (n.type == NODE_POSE) { n.slot = (int)g->pose_ids.size(); g->pose_ids.push_back((int)i); sn.push_back({NODE_POSE, 6, n.slot}); }
-    else { n.slot = (int)g->plane_ids.size(); g->plane_ids.push_back((int)i); sn.push_back({NODE_PLANE, 3, -1}); }
-  }
-  // plane observations with a fixed measurement first, the re-popping ones (Factor2) behind them
-  g->cmp_has_repop = false;
-  for (int pass = 0; pass < 2; pass++)
-    for (size_t i = 0; i < g->factors.size(); i++) {
-      HostFactor& f = g->factors[i];
-      if (f.deleted) { f.slot = -1; continue; }
-      if ((f.type == F_PLANE_OBS && f.repop) != (pass == 1)) continue;
-      if (pass == 1) g->cmp_has_repop = true;
-      f.slot = (int)g->fslot_ids[f.type].size();
-      g->fslot_ids[f.type].push_back((int)i);
+    g->pose_ids.clear(); g->plane_ids.clear();
+    for (int t = 0; t < 4; t++) g->fslot_ids[t].clear();
+    sn.clear(); sf.clear();
+    for (size_t i = 0; i < g->nodes.size(); i++) {
+      if (g->nodes[i].deleted) g->nodes[i].compact = g->nodes[i].slot = -1;
+      else compact_node(g, i);
     }
-  g->n_obs_fixed = 0;
-  for (int id : g->fslot_ids[F_PLANE_OBS]) g->n_obs_fixed += g->factors[id].repop ? 0 : 1;
+    // plane observations with a fixed measurement first, the re-popping ones (Factor2) behind them
+    g->cmp_has_repop = false;
+    for (int pass = 0; pass < 2; pass++)
+      for (size_t i = 0; i < g->factors.size(); i++) {
+        HostFactor& f = g->factors[i];
+        if (f.deleted) { f.slot = -1; continue; }
+        if ((f.type == F_PLANE_OBS && f.repop) != (pass == 1)) continue;
+        if (pass == 1) g->cmp_has_repop = true;
+        f.slot = (int)g->fslot_ids[f.type].size();
+        g->fslot_ids[f.type].push_back((int)i);
+      }
+    g->n_obs_fixed = 0;
+    for (int id : g->fslot_ids[F_PLANE_OBS]) g->n_obs_fixed += g->factors[id].repop ? 0 : 1;
+    sf.reserve(g->factors.size());
+  }
   int64_t base[4], j_total = 0, pbase[4], p_total = 0;
   j_bases(g, base, &j_total);
   p_bases(g, pbase, &p_total);
   if (j_total > 0x7fffffffLL || p_total > 0x7fffffffLL) return fail(g, PPS_ENOMEM, "graph too large for int32 J offsets");
+  if (append && memcmp(base, g->cmp_base, sizeof(base)) != 0) {          // a J slab outgrew its capacity: every offset moves
+    int cnt[4] = {0, 0, 0, 0};
+    for (SymFactor& q : sf) { const int k = cnt[q.type]++; q.joff = (int)(base[q.type] + (int64_t)k * kJSize[q.type]); q.poff = (int)(pbase[q.type] + (int64_t)k * kPSize[q.type]); }
+  }
   memcpy(g->cmp_base, base, sizeof(base));
-  sf.reserve(g->factors.size());
   bool any_deleted = false;
-  for (size_t i = 0; i < g->factors.size(); i++) {
-    const HostFactor& f = g->factors[i];
-    if (f.deleted) { any_deleted = true; continue; }
-    SymFactor s;
-    s.type = f.type;
-    s.a = g->nodes[f.a].compact;
-    s.b = f.b >= 0 ? g->nodes[f.b].compact : -1;
-    s.joff = (int)(base[f.type] + (int64_t)f.slot * kJSize[f.type]);
-    s.poff = (int)(pbase[f.type] + (int64_t)f.slot * kPSize[f.type]);
-    s.direct_ok = (f.type == F_PLANE_OBS && !f.repop) ? 1 : 0;
-    sf.push_back(s);
+  for (size_t i = append ? g->cmp_factors : 0; i < g->factors.size(); i++) {
+    if (g->factors[i].deleted) any_deleted = true;
+    else sf.push_back(sym_factor_of(g, g->factors[i], base, pbase));
   }
   // the append path relies on: table index == host index order with nothing skipped
-  g->cmp_valid = !any_deleted && sn.size() == g->nodes.size();
-  }
+  if (!append) g->cmp_valid = !any_deleted && sn.size() == g->nodes.size();
   g->cmp_nodes = g->nodes.size(); g->cmp_factors = g->factors.size();
   // band depth: 3 levels per launch when the solve is latency bound, 2 when the lower levels are throughput bound (C3: 5 360 fronts;
   // 637 vs 710 us).  (Up to round 4: 4 levels, 113.3 vs 115.0 us per C2 LM iteration with 3.  Round 5: a group of 4 + 2 + 1 fronts on

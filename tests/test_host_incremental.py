@@ -138,6 +138,27 @@ def test_kept_parts_are_what_the_previous_analysis_held(built):
     assert moved >= 2                                              # ... including frames whose buffer offsets all moved
 
 
+def test_analysis_parameter_sets_the_c_abi_does_not_pass():
+    """tests/cpp/analysis_host.cpp links against csrc/pps_symbolic.cpp alone and grows graphs of its own, one pose (or a few) at a time:
+    ordering 0 / 1 / 2, a band_rows that brings in the minimum-degree comparison, arity 4, front_rows 0, leaf_poses 1 and 4, aligned and
+    quantile cuts, moved buffer offsets, an unchanged graph analysed twice.  After every step the incremental analysis must equal the one
+    from scratch word for word, every Analysis::Kept count must hold against the arrays of the step before, and the aligned-cut chain
+    sets must build on the previous analysis as often as they did before the analysis was split into phases."""
+    import os, subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "pop_up_slam_amd", "csrc")
+    srcs = [os.path.join(root, "tests", "cpp", "analysis_host.cpp"), os.path.join(csrc, "pps_symbolic.cpp")]
+    out = os.path.join(root, "tests", "cpp", "analysis_host")
+    deps = srcs + [os.path.join(csrc, "pps_symbolic.h")]
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I" + csrc] + srcs + ["-o", out])
+    r = subprocess.run([out], capture_output=True, text=True, timeout=120)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 14 and all(l.endswith(" ok") for l in lines), r.stdout
+
+
 def test_incremental_analysis_solves_the_normal_equations(built):
     """the arrays an incremental analysis leaves behind, replayed by the numpy emulation of the level and the band kernels"""
     from test_host_analysis import _dense_and_jbuf
