@@ -73,6 +73,7 @@ int pps_refresh_measurements(pps_graph* g) {
     if (first) { g->fr_hint_version = g->upload_version; g->fr_hint_cursor = c0; g->fr_hint_items = slot.size(); g->fr_hint_frames = pslot.size(); }
     rc = flush_uploads(g); if (rc != PPS_OK) return rc;
     rc = verify_uploads(g, "frames"); if (rc != PPS_OK) return rc;
+    rc = verify_frame_tables(g); if (rc != PPS_OK) return rc;
     g->up_inflight = true;                                  // (whoever writes the mirror next waits for this copy)
     g->frames_dirty = false;
   }

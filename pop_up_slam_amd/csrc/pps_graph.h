@@ -147,7 +147,10 @@ struct pps_graph {
   // place from one upload to the next (a slot with spare capacity per dev_upload call, in call order), the pinned mirror
   // knows what the device holds, and only the bytes that differ are sent -- gathered into one patch buffer, one copy, one
   // scatter kernel (dozens of small copies would cost more than they carry).
-  struct UpSlot { size_t off, cap; };
+  // owner: which array (the address of its device pointer) the slot received last.  Slots go by call order, and an array that is uploaded
+  // only on some graphs (obs_ray: re-popping edges) shifts every array behind it by one slot when it appears or goes: a claim about "what this
+  // slot received last time" (kept-prefix hints, rows sent by the previous upload) holds only while the owner is the same.
+  struct UpSlot { size_t off, cap; const void* owner = nullptr; };
   std::vector<UpSlot> up_slots;
   size_t up_cursor = 0, up_high = 0;
   bool up_unknown = true;              // the arena was (re)allocated: the mirror says nothing about the device
@@ -305,6 +308,7 @@ void release_arenas(pps_graph* g);
 void up_diff(pps_graph* g, size_t o, const char* src, size_t n, bool force, size_t same_prefix = 0);
 int flush_uploads(pps_graph* g);
 int verify_uploads(pps_graph* g, const char* where);
+int verify_frame_tables(pps_graph* g);         // PPS_DEBUG_VERIFY_UPLOAD: the frame tables against the factor / node records, host and device
 int ensure_device(pps_graph* g);
 int64_t j_capacity(int64_t n);
 void j_bases(const pps_graph* g, int64_t base[4], int64_t* total);
@@ -445,12 +449,16 @@ int dev_upload_impl(pps_graph* g, T** out, const std::vector<T>& v, size_t rows,
   size_t o = 0, fresh_cap = 0;
   bool placed = false;
   if (a.base && g->stage) {
-    if (k < g->up_slots.size() && bytes <= g->up_slots[k].cap) { o = g->up_slots[k].off; placed = true; }
+    if (k < g->up_slots.size() && bytes <= g->up_slots[k].cap) {
+      o = g->up_slots[k].off; placed = true;
+      if (g->up_slots[k].owner != out) same = 0;       // the slot held another array: its bytes are compared like any others
+      g->up_slots[k].owner = out;
+    }
     else {
       const size_t cap = (std::max<size_t>(256, bytes + bytes / 2) + 255) & ~size_t(255);
       o = (g->up_high + 255) & ~size_t(255);
       if (o + cap <= a.cap) {
-        if (k < g->up_slots.size()) g->up_slots[k] = pps_graph::UpSlot{o, cap}; else g->up_slots.push_back(pps_graph::UpSlot{o, cap});
+        if (k < g->up_slots.size()) g->up_slots[k] = pps_graph::UpSlot{o, cap, out}; else g->up_slots.push_back(pps_graph::UpSlot{o, cap, out});
         g->up_high = o + cap;
         placed = true;
         fresh_cap = cap;

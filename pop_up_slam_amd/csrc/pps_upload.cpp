@@ -51,8 +51,9 @@ void up_diff(pps_graph* g, size_t o, const char* src, size_t n, bool force, size
   char* mir = g->stage + o;
   g->up_bytes_total += n;
   if (g->up_unknown || force) { memcpy(mir, src, n); g->up_patches.push_back(pps_graph::UpPatch{o, n, false}); return; }
-  same_prefix = std::min(same_prefix, n) & ~size_t(63);
-  if (same_prefix && g->verify_hints && memcmp(mir, src, same_prefix) != 0) g->hint_violation = true;
+  same_prefix = std::min(same_prefix, n);
+  if (same_prefix && g->verify_hints && memcmp(mir, src, same_prefix) != 0) g->hint_violation = true;      // (the whole claim, not only the chunks it saves)
+  same_prefix &= ~size_t(63);
   // first and last 64-byte chunk that differs from what the device holds (4 KB strides first: most arrays of a frame loop
   // are unchanged from end to end, or up to a short tail)
   size_t lo = same_prefix, hi = n;
@@ -118,7 +119,7 @@ int flush_uploads(pps_graph* g) {
 
 // PPS_DEBUG_VERIFY_UPLOAD=1: after a flush, the arena on the device must equal the pinned mirror (except the observation
 // measurements, which kernels refresh behind the mirror's back) -- PPS_ESTATE if not.  tests/test_gpu_pipeline.py runs a frame
-// loop under it.
+// loop under it.  verify_packed / verify_expanded / verify_frame_tables below check the mirror's content itself.
 int verify_uploads(pps_graph* g, const char* where) {
   if (g->hint_violation) { g->hint_violation = false; return fail(g, PPS_ESTATE, std::string("upload verification (") + where + "): an array differs from the mirror inside the part the analysis reported as kept"); }
   if (!g->sw.verify_upload || g->up_high == 0 || g->up.spill) return PPS_OK;
@@ -135,6 +136,138 @@ int verify_uploads(pps_graph* g, const char* where) {
                                      std::to_string(g->up_slots[k].cap) + ") differs from the mirror at byte " + std::to_string(b));
     }
   }
+  return PPS_OK;
+}
+
+// ---- PPS_DEBUG_VERIFY_UPLOAD=1, beyond the mirror: what the device holds against what the host records say it should hold ----
+// The mirror check above passes when a shortcut (incr_pack, pk_meas_ok, a kept prefix) has packed the mirror wrongly: these start
+// from the host factor records and from the Analysis again.  tests/test_gpu_upload_states.py runs every upload path under them.
+static int verify_fail(pps_graph* g, const char* where, const char* array, const char* against, size_t index) {
+  return fail(g, PPS_ESTATE, std::string("upload verification (") + where + "): " + array + " differs from " + against + " at index " + std::to_string(index));
+}
+#define VTRY(x) do { rc = (x); if (rc != PPS_OK) return rc; } while (0)      // (the three verify_* functions below; undefined behind the last)
+// rows x [exempt, used) of an SoA array with leading dimension ld (rows == 1, ld == used: a plain array): `have` against `want`
+template <class T>
+static int verify_rows(pps_graph* g, const char* where, const char* array, const char* against, const T* have, const T* want, size_t rows, size_t ld,
+                       size_t used, size_t exempt = 0) {
+  for (size_t r = 0; r < rows; r++)
+    for (size_t s = exempt; s < used; s++)
+      if (memcmp(&have[r * ld + s], &want[r * ld + s], sizeof(T)) != 0) return verify_fail(g, where, array, against, r * ld + s);
+  return PPS_OK;
+}
+// ... the same with `have` on the device
+template <class T>
+static int verify_dev_rows(pps_graph* g, const char* where, const char* array, const char* against, const T* dev, const T* want, size_t rows, size_t ld,
+                           size_t used, size_t exempt = 0) {
+  if (rows * ld == 0 || used == 0) return PPS_OK;
+  std::vector<T> have(rows * ld);
+  HIP_TRY(g, hipMemcpy(have.data(), dev, have.size() * sizeof(T), hipMemcpyDeviceToHost));
+  return verify_rows(g, where, array, against, have.data(), want, rows, ld, used, exempt);
+}
+
+// a. The arrays upload_all maintains incrementally (pk_*: plane observations and odometry) packed again from the host factor records:
+// what was staged and what the device holds must both equal them.  kept_meas_rows: the leading rows of obs_meas that keep_meas left to the
+// device, where a refresh has written values the host does not have -- exactly those are exempt, and only on the device side.
+static int verify_packed(pps_graph* g, size_t kept_meas_rows) {
+  if (!g->sw.verify_upload) return PPS_OK;
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  const DevGraph& d = g->dev;
+  const char* where = "upload_all";
+  const char* scratch = "a pack from the host factor records";
+  struct Side { int type; size_t ld; int km, kw; const std::vector<int>*pa, *pb; const std::vector<double>*pm, *pw; const int *da, *db; const double *dm, *dw;
+                const char* names[4]; size_t exempt; };
+  const Side sides[2] = {
+      {F_PLANE_OBS, (size_t)d.obs_ld, 4, 6, &g->pk_obs_a, &g->pk_obs_b, &g->pk_obs_m, &g->pk_obs_w, d.obs_pose, d.obs_plane, d.obs_meas, d.obs_w,
+       {"obs_pose", "obs_plane", "obs_meas", "obs_w"}, kept_meas_rows},
+      {F_ODOMETRY, (size_t)d.odo_ld, 6, 21, &g->pk_odo_a, &g->pk_odo_b, &g->pk_odo_m, &g->pk_odo_w, d.odo_a, d.odo_b, d.odo_meas, d.odo_w,
+       {"odo_a", "odo_b", "odo_meas", "odo_w"}, 0}};
+  for (const Side& S : sides) {
+    const std::vector<int>& ids = g->fslot_ids[S.type];
+    const size_t n = ids.size(), ld = S.ld;
+    if (n == 0) continue;
+    if (S.pa->size() < n || S.pb->size() < n || S.pm->size() < (size_t)S.km * ld || S.pw->size() < (size_t)S.kw * ld) return verify_fail(g, where, S.names[0], "the slot count (staged arrays too short)", n);
+    std::vector<int> ia(n), ib(n);
+    std::vector<double> pm((size_t)S.km * ld, 0.0), pw((size_t)S.kw * ld, 0.0);
+    for (size_t s = 0; s < n; s++) {
+      const HostFactor& f = g->factors[ids[s]];
+      if (f.deleted || f.slot != (int)s) return verify_fail(g, where, S.names[0], "the slot table (deleted factor or wrong slot)", s);
+      ia[s] = g->nodes[f.a].slot; ib[s] = g->nodes[f.b].slot;
+      for (int k = 0; k < S.km; k++) pm[(size_t)k * ld + s] = f.meas[k];
+      for (int k = 0; k < S.kw; k++) pw[(size_t)k * ld + s] = f.w[k];
+    }
+    int rc;
+    VTRY(verify_rows(g, where, S.names[0], scratch, S.pa->data(), ia.data(), 1, n, n));
+    VTRY(verify_rows(g, where, S.names[1], scratch, S.pb->data(), ib.data(), 1, n, n));
+    VTRY(verify_rows(g, where, S.names[2], scratch, S.pm->data(), pm.data(), (size_t)S.km, ld, n));
+    VTRY(verify_rows(g, where, S.names[3], scratch, S.pw->data(), pw.data(), (size_t)S.kw, ld, n));
+    const char* scratch_dev = "a pack from the host factor records (device side)";
+    VTRY(verify_dev_rows(g, where, S.names[0], scratch_dev, S.da, ia.data(), 1, n, n));
+    VTRY(verify_dev_rows(g, where, S.names[1], scratch_dev, S.db, ib.data(), 1, n, n));
+    VTRY(verify_dev_rows(g, where, S.names[2], scratch_dev, S.dm, pm.data(), (size_t)S.km, ld, n, std::min(n, S.exempt)));
+    VTRY(verify_dev_rows(g, where, S.names[3], scratch_dev, S.dw, pw.data(), (size_t)S.kw, ld, n));
+  }
+  return PPS_OK;
+}
+
+// b. ea_tgt, el_tgt and blk_dst as the expansion launch left them (k_expand_lists, or k_expand_ea + fills + k_expand_el) against
+// expand_ea_tgt / expand_el_lists on a copy of the Analysis; blk_dst entries that no front gathers are -1 on both sides.
+// c. The block behind delta (dn partials, tickets, result records, both deltas, hand-over flags) reads back as zeros.
+static int verify_expanded(pps_graph* g, const double* zero_block, size_t zero_doubles) {
+  if (!g->sw.verify_upload) return PPS_OK;
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  const DevGraph& d = g->dev;
+  const char* where = "upload_all";
+  Analysis A = g->an;
+  expand_ea_tgt(A);
+  expand_el_lists(A);
+  int rc;
+  VTRY(verify_dev_rows(g, where, "ea_tgt", "expand_ea_tgt on the host", d.ea_tgt, A.ea_tgt.data(), 1, A.ea_tgt.size(), A.ea_tgt.size()));
+  if (!A.el_tgt.empty()) {
+    // (entry by entry of every assembled block: an element no block claims is written by nobody, on either side)
+    std::vector<int> have(A.el_tgt.size());
+    HIP_TRY(g, hipMemcpy(have.data(), d.el_tgt, have.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t a = 0; a < A.asm_blk.size(); a++) {
+      const int blk = A.asm_blk[a], rows = A.blk_rows[blk], cols = A.blk_cols[blk];
+      const size_t cnt = A.blk_size[blk] != rows * cols ? (size_t)rows * (rows + 1) / 2 + rows : (size_t)rows * cols, e0 = (size_t)A.asm_el0[a];
+      if (e0 + cnt > have.size()) return verify_fail(g, where, "asm_el0", "the length of el_tgt", a);
+      for (size_t e = e0; e < e0 + cnt; e++)
+        if (have[e] != A.el_tgt[e]) return verify_fail(g, where, "el_tgt", "expand_el_lists on the host", e);
+    }
+  }
+  VTRY(verify_dev_rows(g, where, "blk_dst", "expand_el_lists on the host", d.blk_dst, A.blk_dst.data(), 1, A.blk_dst.size(), A.blk_dst.size()));
+  const std::vector<double> zeros(zero_doubles, 0.0);
+  return verify_dev_rows(g, where, "the zeroed block behind delta", "zero", zero_block, zeros.data(), 1, zero_doubles, zero_doubles);
+}
+
+// The frame tables of pps_refresh_measurements after their flush: the cached slot tables (extended, not rebuilt, while nothing is removed)
+// against tables built from the factor and node records, and all six tables on the device against the host's.  The slot rule itself (a live,
+// fixed observation of a live pose, else -1) is restated from pps_frames.cpp, not checked: this pins the cache and the transfer, the rule is
+// pinned by the measurements the refresh then writes (tests/test_gpu_upload_states.py holds every one of them to the pop-up's statement).
+int verify_frame_tables(pps_graph* g) {
+  if (!g->sw.verify_upload) return PPS_OK;
+  HIP_TRY(g, hipStreamSynchronize(g->stream));
+  const char* where = "frames";
+  std::vector<int> slot(g->fr_item_fid.size()), pslot(g->fr_pose.size());
+  for (size_t i = 0; i < slot.size(); i++) {
+    const int fid = g->fr_item_fid[i];
+    slot[i] = (fid >= 0 && !g->factors[fid].deleted && !g->factors[fid].repop) ? g->factors[fid].slot : -1;
+    if (slot[i] >= 0 && g->nodes[g->fr_pose[g->fr_item_frame[i]]].deleted) slot[i] = -1;
+  }
+  for (size_t f = 0; f < pslot.size(); f++) pslot[f] = g->nodes[g->fr_pose[f]].deleted ? 0 : g->nodes[g->fr_pose[f]].slot;
+  if (g->fr_slot.size() != slot.size()) return verify_fail(g, where, "item_slot", "the number of registered items", std::min(slot.size(), g->fr_slot.size()));
+  if (g->fr_pslot.size() != pslot.size()) return verify_fail(g, where, "frame_pose_slot", "the number of registered frames", std::min(pslot.size(), g->fr_pslot.size()));
+  const char* scratch = "tables built from the factor and node records";
+  const char* host = "the host tables (device side)";
+  int rc;
+  VTRY(verify_rows(g, where, "item_slot", scratch, g->fr_slot.data(), slot.data(), 1, slot.size(), slot.size()));
+  VTRY(verify_rows(g, where, "frame_pose_slot", scratch, g->fr_pslot.data(), pslot.data(), 1, pslot.size(), pslot.size()));
+  VTRY(verify_dev_rows(g, where, "item_frame", host, g->d_item_frame, g->fr_item_frame.data(), 1, g->fr_item_frame.size(), g->fr_item_frame.size()));
+  VTRY(verify_dev_rows(g, where, "item_plane", host, g->d_item_plane, g->fr_item_plane.data(), 1, g->fr_item_plane.size(), g->fr_item_plane.size()));
+  VTRY(verify_dev_rows(g, where, "item_slot", host, g->d_item_slot, slot.data(), 1, slot.size(), slot.size()));
+  VTRY(verify_dev_rows(g, where, "frame_pose_slot", host, g->d_frame_pose_slot, pslot.data(), 1, pslot.size(), pslot.size()));
+  VTRY(verify_dev_rows(g, where, "frame_seg_off", host, g->d_frame_seg_off, g->fr_seg_off.data(), 1, g->fr_seg_off.size(), g->fr_seg_off.size()));
+  VTRY(verify_dev_rows(g, where, "fr_seg", host, g->d_fr_seg, g->fr_seg.data(), 1, g->fr_seg.size(), g->fr_seg.size()));
+#undef VTRY
   return PPS_OK;
 }
 
@@ -685,6 +818,7 @@ int upload_all(pps_graph* g) {
   lap("5 index arrays + diff");
   rc = flush_uploads(g); if (rc != PPS_OK) return rc;
   rc = verify_uploads(g, "upload_all"); if (rc != PPS_OK) return rc;
+  rc = verify_packed(g, keep_meas ? n_obs_on_device : 0); if (rc != PPS_OK) return rc;
   lap("6 flush");
   // one launch for both expansions when every H block is assembled by exactly one front (always, unless an analysis ever lists a block
   // twice or not at all: then the fill of blk_dst has to run first, in a launch of its own)
@@ -702,6 +836,7 @@ int upload_all(pps_graph* g) {
     }
     HIP_TRY(g, launch_expand_el(d, (int)A.asm_blk.size(), g->stream));
   }
+  rc = verify_expanded(g, zero_block, zero_doubles); if (rc != PPS_OK) return rc;
   g->topo_dirty = false;
   g->meas_dirty = false;
   g->grown_only_upload = true;
