@@ -803,6 +803,16 @@ const char* pps_map_last_error(const pps_map* m);
  *   PPS_EINVAL  NULL handle, nplanes outside 0 .. 65, an id that is not a live plane node of the graph, a context on another device
  *   PPS_ENOMEM  the frame's kept points exceed the remaining capacity; the map is unchanged */
 int pps_map_add_frame(pps_map* m, pps_popup* p, int frame_seq_id, int nplanes, const int* plane_node_ids, int* counts);
+/* Test hook: a frame of the map from HOST arrays -- cloud[npx] and plane_id[npx] in raster order, what pps_popup_download returns of a
+ * run -- so that a test chooses the pixel count, the plane count and the pattern of ids itself.  The two arrays are copied to scratch device
+ * buffers of the map on the graph's stream; from there on the call IS pps_map_add_frame (one function serves both: tiling, count, scan,
+ * totals, capacity check, scatter, chunk table, counts, pps_map_last_times), so what it stores is what a pop-up run with these pixels
+ * would have stored.  Only the upload is the hook's own.  A frame with nplanes = 0 reads no pixel and needs no device.
+ *   PPS_EINVAL  answered on the host before any device work, the map unchanged: NULL m / cloud / plane_id, npx outside 1 .. 2^30 (the
+ *               kernels index pixels with int), nplanes outside 0 .. 65, an id that is neither -1 nor a live plane node of the graph
+ *   PPS_ENOMEM  as pps_map_add_frame: the map is unchanged */
+int pps_debug_map_add_points(pps_map* m, const pps_point* cloud, const int* plane_id, int64_t npx, int frame_seq_id, int nplanes,
+                             const int* plane_node_ids, int* counts);
 /* loopclose_merge / copy_plane (Mapping.cpp:659-700, Map_plane.cpp:25): every chunk of from_plane belongs to to_plane from now on (and
  * counts towards its tracked times).  from_plane: a plane node id of the graph, live or removed; to_plane: a live one. */
 int pps_map_redirect(pps_map* m, int from_plane, int to_plane);

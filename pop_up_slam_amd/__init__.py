@@ -139,7 +139,7 @@ SYMBOLS = [
     "pps_loop_gate", "pps_loop_gate_last", "pps_debug_loop_gate_records",
     "pps_map_default_select", "pps_map_create", "pps_map_destroy", "pps_map_last_error", "pps_map_add_frame", "pps_map_redirect",
     "pps_map_info", "pps_map_chunks", "pps_map_built_chunks", "pps_map_select_host", "pps_map_build", "pps_map_download",
-    "pps_map_last_times",
+    "pps_map_last_times", "pps_debug_map_add_points",
     "pps_set_cost_function", "pps_get_cost_function",
 ]
 
@@ -288,6 +288,7 @@ def lib():
         L.pps_map_destroy.argtypes = [C.c_void_p]
         L.pps_map_last_error.argtypes = [C.c_void_p]; L.pps_map_last_error.restype = C.c_char_p
         L.pps_map_add_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _ip, _ip]
+        L.pps_debug_map_add_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, _ip, _ip]
         L.pps_map_redirect.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.pps_map_info.argtypes = [C.c_void_p, C.POINTER(PpsMapTotals)]
         L.pps_map_chunks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
@@ -1034,6 +1035,19 @@ class Map:
         cnt = np.zeros(max(len(ids), 1), dtype=np.int32)
         self._ck(self.L.pps_map_add_frame(self.h, popup.h if popup is not None else None, int(frame_seq_id), len(ids),
                                           ids.ctypes.data_as(_ip), cnt.ctypes.data_as(_ip)))
+        return cnt[:len(ids)].copy()
+
+    def debug_add_points(self, cloud, plane_id, frame_seq_id, plane_node_ids):
+        """pps_debug_map_add_points: add_frame fed host arrays (cloud: POINT_DTYPE, plane_id: int32, one record per pixel in raster
+        order -- what Popup.download returns) in place of a pop-up run; returns the points per plane"""
+        cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE).reshape(-1)
+        pid = np.ascontiguousarray(plane_id, dtype=np.int32).reshape(-1)
+        if len(cloud) != len(pid):
+            raise ValueError("debug_add_points: cloud and plane_id differ in length")
+        ids = np.ascontiguousarray(plane_node_ids, dtype=np.int32).reshape(-1)
+        cnt = np.zeros(max(len(ids), 1), dtype=np.int32)
+        self._ck(self.L.pps_debug_map_add_points(self.h, cloud.ctypes.data_as(C.c_void_p), pid.ctypes.data_as(C.c_void_p), len(cloud),
+                                                 int(frame_seq_id), len(ids), ids.ctypes.data_as(_ip), cnt.ctypes.data_as(_ip)))
         return cnt[:len(ids)].copy()
 
     def redirect(self, from_plane, to_plane):

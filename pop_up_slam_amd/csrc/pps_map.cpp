@@ -26,6 +26,7 @@ struct pps_map {
   int* d_table = nullptr; size_t table_cap = 0;       // planes x wave tiles of the last frame, then kMapPlanes totals
   int* h_totals = nullptr;                            // pinned, kMapPlanes
   char* d_sel = nullptr; size_t sel_cap = 0;          // offset table of a build: [out_off | src_off | slot]
+  MapPt* d_dbg_cloud = nullptr; int* d_dbg_pid = nullptr; size_t dbg_cap = 0;   // pixels uploaded by pps_debug_map_add_points
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   double sec[2] = {0, 0};
 };
@@ -96,10 +97,11 @@ int pps_map_create(pps_graph* g, int64_t capacity_points, pps_map** out) {
 
 int pps_map_destroy(pps_map* m) {
   if (!m) return PPS_EINVAL;
-  if (m->d_store || m->d_built || m->d_table || m->h_totals || m->d_sel || m->ev[0]) {
+  if (m->d_store || m->d_built || m->d_table || m->h_totals || m->d_sel || m->d_dbg_cloud || m->d_dbg_pid || m->ev[0]) {
     (void)hipSetDevice(m->g->props.device);
     if (m->g->stream) (void)hipStreamSynchronize(m->g->stream);
     (void)hipFree(m->d_store); (void)hipFree(m->d_built); (void)hipFree(m->d_table); (void)hipFree(m->d_sel);
+    (void)hipFree(m->d_dbg_cloud); (void)hipFree(m->d_dbg_pid);
     if (m->h_totals) (void)hipHostFree(m->h_totals);
     for (hipEvent_t e : m->ev) if (e) (void)hipEventDestroy(e);
   }
@@ -109,25 +111,31 @@ int pps_map_destroy(pps_map* m) {
 
 const char* pps_map_last_error(const pps_map* m) { return m ? m->err.c_str() : "null handle"; }
 
-int pps_map_add_frame(pps_map* m, pps_popup* p, int frame_seq_id, int nplanes, const int* plane_node_ids, int* counts) {
-  if (!m || !p) return mfail(m, PPS_EINVAL, "add_frame: null handle");
-  if (nplanes < 0 || nplanes > kMapPlanes || (nplanes > 0 && !plane_node_ids)) return mfail(m, PPS_EINVAL, "add_frame: nplanes outside 0 .. 65, or no ids");
-  pps_graph* g = m->g;
+}  // extern "C"
+
+namespace {
+
+// what both entry points of a frame ask of its plane list, answered on the host
+int frame_planes_valid(pps_map* m, const char* who, int nplanes, const int* plane_node_ids) {
+  if (nplanes < 0 || nplanes > kMapPlanes || (nplanes > 0 && !plane_node_ids)) return mfail(m, PPS_EINVAL, std::string(who) + ": nplanes outside 0 .. 65, or no ids");
   for (int k = 0; k < nplanes; k++)
-    if (plane_node_ids[k] != -1 && !live_node(g, plane_node_ids[k], NODE_PLANE))
-      return mfail(m, PPS_EINVAL, "add_frame: plane_node_ids[" + std::to_string(k) + "] is not a live plane node");
-  PopupRunView v{};
-  int rc = popup_last_run(p, &v);
-  if (rc != PPS_OK) return mfail(m, rc, std::string("add_frame: ") + pps_popup_last_error(p));
-  if (v.device != g->props.device) return mfail(m, PPS_EINVAL, "add_frame: the pop-up context lives on another device than the graph");
-  const int npx = v.width * v.height;
+    if (plane_node_ids[k] != -1 && !live_node(m->g, plane_node_ids[k], NODE_PLANE))
+      return mfail(m, PPS_EINVAL, std::string(who) + ": plane_node_ids[" + std::to_string(k) + "] is not a live plane node");
+  return PPS_OK;
+}
+
+// A frame from the point where its pixels are on the device (cloud, plane_id: npx records each, complete for the graph's stream): tiling,
+// table growth, count + scan, the totals read back, the capacity check, scatter, the chunk table, counts and sec[0].
+int add_points(pps_map* m, const char* who, const MapPt* cloud, const int* plane_id, int npx, int frame_seq_id, int nplanes,
+               const int* plane_node_ids, int* counts) {
+  pps_graph* g = m->g;
   std::vector<int> cnt((size_t)nplanes, 0);
   int64_t kept = 0;
   MapScatterBase base;
   for (int k = 0; k < kMapPlanes; k++) base.base[k] = -1;
   m->sec[0] = 0;
   if (nplanes > 0) {
-    rc = ensure_device(g);
+    int rc = ensure_device(g);
     if (rc != PPS_OK) return mfail(m, rc, g->err);
     MAP_TRY(m, hipSetDevice(g->props.device));
     rc = map_events(m);
@@ -143,21 +151,20 @@ int pps_map_add_frame(pps_map* m, pps_popup* p, int frame_seq_id, int nplanes, c
     if (!m->h_totals) MAP_TRY(m, hipHostMalloc(reinterpret_cast<void**>(&m->h_totals), kMapPlanes * sizeof(int), hipHostMallocDefault));
     if (!m->d_store && m->cap > 0) MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_store), (size_t)m->cap * sizeof(MapPt)));
     int* d_totals = m->d_table + (size_t)kMapPlanes * t.nT;
-    const MapPt* cloud = reinterpret_cast<const MapPt*>(v.cloud);
     MAP_TRY(m, hipEventRecord(m->ev[0], g->stream));
-    MAP_TRY(m, launch_map_count(cloud, v.plane_id, npx, nplanes, m->d_table, d_totals, g->stream));
+    MAP_TRY(m, launch_map_count(cloud, plane_id, npx, nplanes, m->d_table, d_totals, g->stream));
     MAP_TRY(m, hipEventRecord(m->ev[1], g->stream));
     MAP_TRY(m, hipMemcpyAsync(m->h_totals, d_totals, (size_t)nplanes * sizeof(int), hipMemcpyDeviceToHost, g->stream));
     MAP_TRY(m, hipStreamSynchronize(g->stream));
     for (int k = 0; k < nplanes; k++)
       if (plane_node_ids[k] >= 0) { cnt[k] = m->h_totals[k]; base.base[k] = m->used + kept; kept += cnt[k]; }
     if (kept > m->cap - m->used)
-      return mfail(m, PPS_ENOMEM, "add_frame: the frame keeps " + std::to_string(kept) + " points, the store has room for " + std::to_string(m->cap - m->used));
+      return mfail(m, PPS_ENOMEM, std::string(who) + ": the frame keeps " + std::to_string(kept) + " points, the store has room for " + std::to_string(m->cap - m->used));
     float ms0 = 0, ms1 = 0;
     (void)hipEventElapsedTime(&ms0, m->ev[0], m->ev[1]);
     if (kept > 0) {
       MAP_TRY(m, hipEventRecord(m->ev[2], g->stream));
-      MAP_TRY(m, launch_map_scatter(cloud, v.plane_id, npx, nplanes, m->d_table, base, m->d_store, g->stream));
+      MAP_TRY(m, launch_map_scatter(cloud, plane_id, npx, nplanes, m->d_table, base, m->d_store, g->stream));
       MAP_TRY(m, hipEventRecord(m->ev[3], g->stream));
       MAP_TRY(m, hipStreamSynchronize(g->stream));
       (void)hipEventElapsedTime(&ms1, m->ev[2], m->ev[3]);
@@ -172,6 +179,46 @@ int pps_map_add_frame(pps_map* m, pps_popup* p, int frame_seq_id, int nplanes, c
   m->n_frames++;
   if (counts) for (int k = 0; k < nplanes; k++) counts[k] = cnt[k];
   return PPS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pps_map_add_frame(pps_map* m, pps_popup* p, int frame_seq_id, int nplanes, const int* plane_node_ids, int* counts) {
+  if (!m || !p) return mfail(m, PPS_EINVAL, "add_frame: null handle");
+  int rc = frame_planes_valid(m, "add_frame", nplanes, plane_node_ids);
+  if (rc != PPS_OK) return rc;
+  PopupRunView v{};
+  rc = popup_last_run(p, &v);
+  if (rc != PPS_OK) return mfail(m, rc, std::string("add_frame: ") + pps_popup_last_error(p));
+  if (v.device != m->g->props.device) return mfail(m, PPS_EINVAL, "add_frame: the pop-up context lives on another device than the graph");
+  return add_points(m, "add_frame", reinterpret_cast<const MapPt*>(v.cloud), v.plane_id, v.width * v.height, frame_seq_id, nplanes,
+                    plane_node_ids, counts);
+}
+
+int pps_debug_map_add_points(pps_map* m, const pps_point* cloud, const int* plane_id, int64_t npx, int frame_seq_id, int nplanes,
+                             const int* plane_node_ids, int* counts) {
+  if (!m || !cloud || !plane_id) return mfail(m, PPS_EINVAL, "debug_add_points: null pointer");
+  if (npx < 1 || npx > kMapMaxPixels) return mfail(m, PPS_EINVAL, "debug_add_points: npx outside 1 .. 2^30");
+  int rc = frame_planes_valid(m, "debug_add_points", nplanes, plane_node_ids);
+  if (rc != PPS_OK) return rc;
+  if (nplanes > 0) {                                     // (a frame without planes reads no pixel, like add_frame)
+    pps_graph* g = m->g;
+    rc = ensure_device(g);
+    if (rc != PPS_OK) return mfail(m, rc, g->err);
+    MAP_TRY(m, hipSetDevice(g->props.device));
+    if ((size_t)npx > m->dbg_cap) {
+      MAP_TRY(m, hipStreamSynchronize(g->stream));
+      (void)hipFree(m->d_dbg_cloud); (void)hipFree(m->d_dbg_pid); m->d_dbg_cloud = nullptr; m->d_dbg_pid = nullptr; m->dbg_cap = 0;
+      MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_dbg_cloud), (size_t)npx * sizeof(MapPt)));
+      MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_dbg_pid), (size_t)npx * sizeof(int)));
+      m->dbg_cap = (size_t)npx;
+    }
+    MAP_TRY(m, hipMemcpyAsync(m->d_dbg_cloud, cloud, (size_t)npx * sizeof(MapPt), hipMemcpyHostToDevice, g->stream));
+    MAP_TRY(m, hipMemcpyAsync(m->d_dbg_pid, plane_id, (size_t)npx * sizeof(int), hipMemcpyHostToDevice, g->stream));
+  }
+  return add_points(m, "debug_add_points", m->d_dbg_cloud, m->d_dbg_pid, (int)npx, frame_seq_id, nplanes, plane_node_ids, counts);
 }
 
 int pps_map_redirect(pps_map* m, int from_plane, int to_plane) {

@@ -12,6 +12,7 @@ struct alignas(16) MapPt { float x, y, z; unsigned int rgba; };      // pps_poin
 
 // How a frame of npx pixels is cut: a wave owns `wt` consecutive pixels in raster order (a multiple of 64), nT such wave tiles cover the
 // frame.  256 pixels per wave until the count table (planes x nT) would pass 8192 columns, larger tiles beyond.
+constexpr int kMapMaxPixels = 1 << 30;   // what pps_debug_map_add_points accepts: the tiling and the kernels index pixels with int, tile ends included
 struct MapTiling { int wt, nT; };
 inline MapTiling map_tiling(int npx) {
   MapTiling t;

@@ -24,6 +24,7 @@ template <class K, class... A> void emu_launch(K k, dim3 grid, dim3 block, A... 
 using namespace pps;
 extern "C" {
 int emu_map_tiles(int npx) { return map_tiling(npx).nT; }
+int emu_map_wt(int npx) { return map_tiling(npx).wt; }
 // table: kMapPlanes * nT ints, totals: kMapPlanes
 int emu_map_count(const void* cloud, const int* pid, int npx, int nplanes, int* table, int* totals) {
   return launch_map_count((const MapPt*)cloud, pid, npx, nplanes, table, totals, nullptr);

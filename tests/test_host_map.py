@@ -4,7 +4,9 @@
   * the argument and state checks of every entry point, answered on the host (this suite runs without a device);
   * the kernels of csrc/pps_map.hip themselves, compiled for the host (tests/cpp/map_emu.cpp, one std::thread per GPU thread, barriers at
     the wave operations): the stable partition against numpy, the build against a numpy fp64 projection (1 fp32 ulp: the fp64 arithmetic
-    differs by rounding order only, which can move the final fp32 rounding by at most one ulp)."""
+    differs by rounding order only, which can move the final fp32 rounding by at most one ulp); the tiling arithmetic; two tiles per
+    scan thread, 64 distinct planes in one batch, a leader in lane 63, build windows of one-point chunks (the same frames run on the
+    device in tests/test_gpu_map_shapes.py)."""
 import ctypes as C
 import os
 import subprocess
@@ -13,7 +15,8 @@ import numpy as np
 import pytest
 
 import pop_up_slam_amd as P
-from map_helpers import assert_within_one_ulp, project_to_plane, ref_select
+from map_helpers import (assert_within_one_ulp, kept_key, project_to_plane, raw16, ref_select, split_flat, tiling, wave_pattern_frame,
+                         workgroup_windows)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -141,6 +144,41 @@ def test_every_refusal_is_answered_without_a_device(built):
     m.close(); g.close()
 
 
+def test_hook_refusals_are_answered_without_a_device(built):
+    """pps_debug_map_add_points checks everything pps_map_add_frame checks, and its own arrays, before it touches a device"""
+    L = P.lib()
+    g = P.Graph()
+    pose = g.add_pose([0, 0, 1, 0, 0, 0, 1]); a = g.add_plane([0, 0, 1, 0]); b = g.add_plane([1, 0, 0, -1])
+    m = P.Map(g, 1000)
+    cloud = np.zeros(8, dtype=P.POINT_DTYPE); cloud["rgba"] = 1 << 24
+    pid = np.zeros(8, dtype=np.int32)
+    ids = (C.c_int * 2)(a, b)
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)
+    assert L.pps_debug_map_add_points(None, vp(cloud), vp(pid), 8, 0, 2, ids, None) == P.PPS_EINVAL
+    for args in [(None, vp(pid), 8, 0, 2, ids, None), (vp(cloud), None, 8, 0, 2, ids, None), (vp(cloud), vp(pid), 8, 0, 2, None, None),
+                 (vp(cloud), vp(pid), 0, 0, 2, ids, None), (vp(cloud), vp(pid), -8, 0, 2, ids, None),
+                 (vp(cloud), vp(pid), 1 << 31, 0, 2, ids, None), (vp(cloud), vp(pid), (1 << 32) + 8, 0, 2, ids, None),
+                 (vp(cloud), vp(pid), (1 << 30) + 1, 0, 2, ids, None), (vp(cloud), vp(pid), 8, 0, -1, ids, None)]:
+        assert L.pps_debug_map_add_points(m.h, *args) == P.PPS_EINVAL, args
+        assert L.pps_map_last_error(m.h) != b""
+
+    def refused(fn):
+        with pytest.raises(P.PpsError) as e:
+            fn()
+        assert e.value.code == P.PPS_EINVAL, e.value
+
+    refused(lambda: m.debug_add_points(cloud, pid, 0, [a, pose]))        # a pose among the plane ids
+    refused(lambda: m.debug_add_points(cloud, pid, 0, [a, 99]))          # an unknown id
+    refused(lambda: m.debug_add_points(cloud, pid, 0, [a, -2]))          # only -1 skips
+    refused(lambda: m.debug_add_points(cloud, pid, 0, [a] * 66))         # more planes than a frame can hold
+    g.remove_node(b)
+    refused(lambda: m.debug_add_points(cloud, pid, 0, [a, b]))           # a node that left the graph
+    assert m.info() == dict(capacity=1000, n_points=0, built_points=0, n_frames=0, n_chunks=0, built_chunks=0)
+    assert len(m.debug_add_points(cloud, pid, 5, [])) == 0               # a frame without planes: no pixel is read, no device needed
+    assert m.info()["n_frames"] == 1 and m.info()["n_chunks"] == 0
+    m.close(); g.close()
+
+
 # ---- the kernels, compiled for the host ----------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def emu(built, tmp_path_factory):
@@ -211,10 +249,10 @@ def test_emulated_partition_is_stable_and_complete(emu, w, h, nplanes, p_valid, 
     assert len(store) == int(counts[take].sum())
 
 
-def test_emulated_build_projects_the_selected_chunks(emu):
-    rng = np.random.default_rng(9)
-    n_chunks, n_slots, ld = 700, 6, 11                                   # more chunks than one workgroup's window of 256
-    counts = rng.integers(1, 5, size=n_chunks); counts[rng.integers(0, n_chunks, 20)] = rng.integers(200, 900, 20)
+def emu_build_check(emu, rng, counts, sel, n_slots=6, ld=11):
+    """the build of the chunks `sel` (indices into a store of chunks with `counts` points) against the numpy fp64 projection; slots are
+    drawn from -1 .. n_slots-1; returns the chunks that passed through untouched"""
+    n_chunks = len(counts)
     src_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     store = np.zeros(int(src_off[-1]), dtype=P.POINT_DTYPE)
     for name in "xyz":
@@ -222,7 +260,7 @@ def test_emulated_build_projects_the_selected_chunks(emu):
     store["rgba"] = rng.integers(0, 1 << 32, size=len(store), dtype=np.uint32)
     planes = rng.normal(size=(n_slots, 4)); planes /= np.linalg.norm(planes, axis=1, keepdims=True)      # unit 4-vectors, like the state
     est = np.full((4, ld), np.nan); est[:, :n_slots] = planes.T
-    sel = np.sort(rng.choice(n_chunks, 500, replace=False))
+    assert np.all(counts[sel] > 0) and np.all(np.diff(sel) > 0) and sel[-1] < n_chunks
     slot = rng.integers(-1, n_slots, size=len(sel)).astype(np.int32)
     out_off = np.concatenate([[0], np.cumsum(counts[sel])]).astype(np.int64)
     built = np.zeros(int(out_off[-1]) + 3, dtype=P.POINT_DTYPE); built["rgba"] = 0xDEADBEEF
@@ -241,4 +279,85 @@ def test_emulated_build_projects_the_selected_chunks(emu):
             continue
         want = project_to_plane(planes[slot[j]], xyz)
         assert_within_one_ulp(gxyz, want)
-    assert n_through > 10
+    return n_through
+
+
+def test_emulated_build_projects_the_selected_chunks(emu):
+    rng = np.random.default_rng(9)
+    n_chunks = 700                                                       # more chunks than one workgroup's window of 256
+    counts = rng.integers(1, 5, size=n_chunks); counts[rng.integers(0, n_chunks, 20)] = rng.integers(200, 900, 20)
+    sel = np.sort(rng.choice(n_chunks, 500, replace=False))
+    assert emu_build_check(emu, rng, counts, sel) > 10
+
+
+# ---- what the random grids above do not reach ----------------------------------------------------------------------------------------
+BOUNDARIES = (65536, 65537, 307200, 2097152, 2097153)
+
+
+def test_tiling_arithmetic(emu):
+    """map_tiling (csrc/pps_map.h) over every small frame, the boundaries the device tests run at and random sizes up to 2^30: the tiles
+    are whole batches of 64, they cover the frame with no tile to spare, the count table stays within 8192 columns, and a wave keeps 256
+    pixels whenever that fits"""
+    rng = np.random.default_rng(77)
+    sizes = list(range(1, 301)) + list(BOUNDARIES) + [8192 * 320, 8192 * 320 + 1, 1 << 30] + [int(v) for v in rng.integers(1, 1 << 30, size=4000)]
+    grown = 0
+    for npx in sizes:
+        wt, nT = emu.emu_map_wt(npx), emu.emu_map_tiles(npx)
+        assert wt > 0 and wt % 64 == 0, npx
+        assert (nT - 1) * wt < npx <= nT * wt, npx
+        assert nT <= 8192, npx
+        if npx <= 8192 * 256:
+            assert wt == 256, npx
+        else:
+            grown += 1
+        assert (wt, nT) == tiling(npx)[:2], npx                          # the restatement the device tests assert their regime with
+    assert grown > 1000
+    assert [tiling(n) for n in BOUNDARIES] == [(256, 256, 1), (256, 257, 2), (256, 1200, 5), (256, 8192, 32), (320, 6554, 26)]
+
+
+def check_emulated_partition(emu, cloud, pid, nplanes, take):
+    """the emulated store against the numpy split of the same flat frame"""
+    counts, base, store = emu_partition(emu, cloud, pid, nplanes, take)
+    want = split_flat(cloud, pid, nplanes)
+    for k in range(nplanes):
+        assert counts[k] == len(want[k])
+        if take[k]:
+            np.testing.assert_array_equal(raw16(store[base[k]:base[k] + counts[k]]), raw16(want[k]))
+    assert len(store) == int(counts[take].sum())
+    return counts
+
+
+def test_emulated_scan_with_two_tiles_per_thread(emu):
+    """257 x 256: nT = 257, so the scan gives its threads seg = 2 tiles, thread 128 one tile and the threads above it none"""
+    w, h, nplanes = 257, 256, 7
+    assert tiling(w * h) == (256, 257, 2) and emu.emu_map_tiles(w * h) == 257
+    cloud, pid, valid = random_grid(np.random.default_rng(257), w, h, nplanes)
+    take = np.ones(nplanes, dtype=bool); take[1] = False
+    counts = check_emulated_partition(emu, cloud, pid, nplanes, take)
+    last_tile = kept_key(cloud, pid, nplanes)[256 * 256:]
+    assert np.all(counts > 0) and len(np.unique(last_tile[last_tile >= 0])) > 1     # the tile of thread 128 holds points of several planes
+
+
+def test_emulated_wave_patterns(emu):
+    """a batch of 64 distinct planes (64 turns of the loop), then a batch whose only kept pixel sits in lane 63: the leader is lane 63,
+    found in a mask whose only bit is bit 63, and its plane is the 65th"""
+    cloud, pid = wave_pattern_frame(np.random.default_rng(63))
+    take = np.ones(65, dtype=bool)
+    counts = check_emulated_partition(emu, cloud, pid, 65, take)
+    assert counts[64] >= 1
+
+
+def test_emulated_build_windows(emu):
+    """tiny chunks: a workgroup that starts on a chunk's first point and whose 256 points lie in 256 chunks, one that starts inside a chunk
+    and crosses more than 200, chunks dropped from the middle of both windows"""
+    rng = np.random.default_rng(256)
+    counts = np.array([512] + [1] * 300 + [220] + [1] * 300, dtype=np.int64)
+    every = np.arange(len(counts))
+    win = workgroup_windows(counts)
+    assert (False, 256) in win and any(mid and n >= 200 for mid, n in win)
+    emu_build_check(emu, rng, counts, every)
+    # the same after a selection: chunk 0 keeps the window's start on a chunk's first point, the dropped ones lie inside the windows
+    sel = np.sort(np.concatenate([[0], 1 + rng.choice(len(counts) - 1, 560, replace=False)]))
+    win = workgroup_windows(counts[sel])
+    assert (False, 256) in win
+    assert emu_build_check(emu, rng, counts, sel) > 10
