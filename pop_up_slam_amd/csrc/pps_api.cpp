@@ -148,6 +148,9 @@ int pps_graph_create(const pps_props* props, pps_graph** out) {
 int pps_graph_destroy(pps_graph* g) {
   if (!g) return PPS_EINVAL;
   if (!g->up_laps.empty()) {
+    const pps_impl::UploadMirror& m = g->mirror;      // (printed as ms: the counts)
+    g->up_laps["(bytes compared, count)"] = 1e-3 * (double)m.bytes_compared; g->up_laps["(bytes sent, count)"] = 1e-3 * (double)m.bytes_sent;
+    g->up_laps["(patches, count)"] = 1e-3 * (double)m.n_patches;
     std::vector<std::pair<std::string, double>> v(g->up_laps.begin(), g->up_laps.end());
     std::sort(v.begin(), v.end());
     for (auto& kv : v) fprintf(stderr, "[upload] %-34s %9.3f ms total\n", kv.first.c_str(), 1e3 * kv.second);

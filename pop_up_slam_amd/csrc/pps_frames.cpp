@@ -58,10 +58,10 @@ int pps_refresh_measurements(pps_graph* g) {
     if (g->up_inflight) { HIP_TRY(g, hipStreamSynchronize(g->stream)); g->up_inflight = false; }
     // The first table upload after an upload_all goes to the slots the previous layout's first table upload went to (same number of
     // uploads in front of it: same cursor), which nothing has written since: the entries it sent are in the mirror.
-    g->verify_hints = g->sw.verify_upload;
-    const size_t c0 = g->up_cursor;
+    g->mirror.verify_hints = g->sw.verify_upload;
+    const size_t c0 = g->mirror.cursor;
     const bool first = g->fr_hint_version != g->upload_version;
-    const bool hint = inc && first && !g->up_unknown && g->fr_hint_version + 1 == g->upload_version && g->fr_hint_cursor == c0 &&
+    const bool hint = inc && first && !g->mirror.unknown && g->fr_hint_version + 1 == g->upload_version && g->fr_hint_cursor == c0 &&
                       g->fr_hint_items <= slot.size() && g->fr_hint_frames <= pslot.size() && i0 >= g->fr_hint_items && f0 >= g->fr_hint_frames;
     const size_t hi = hint ? g->fr_hint_items : 0, hf = hint ? g->fr_hint_frames : 0;
     rc = dev_upload(g, &g->d_item_frame, g->fr_item_frame, hi); if (rc != PPS_OK) return rc;

@@ -6,6 +6,7 @@
 //   pps_multi.cpp    pps_multi: G graphs per launch, lockstep LM rounds
 //   pps_k3_plan.h    how K3 is launched on an analysis (plan_k3 -> K3Plan: form, waves, LDS of every launch): host only, no HIP
 //   pps_lm.h         the LM rule the loops of pps_solve.cpp and pps_multi.cpp share (accept / reject / stop, lambda schedule, trace, counters) and the dual-trial walk with the rotation of the three state copies: host only, no HIP
+//   pps_upmirror.h   the bookkeeping of the difference upload (UploadMirror: slots, owners, what differs, what a flush sends): host only, no HIP
 //   pps_frames.cpp   registered frames (measurement refresh on the device), data association, point re-projection
 //   pps_io.cpp       graph text format (Slam::save / Graph::write)
 //   pps_cov.cpp      marginal covariances from the factor (isam::Covariances): the recovery pipeline and the reads of the selected inverse; kernels in pps_cov*.hip
@@ -38,6 +39,7 @@
 #include "pps_lm.h"
 #include "pps_popup_dev.h"
 #include "pps_symbolic.h"
+#include "pps_upmirror.h"
 
 namespace pps_impl {
 
@@ -137,47 +139,32 @@ struct pps_graph {
   std::vector<void*> allocs;        // fallback allocations (arena full), freed at the next full upload
   // Device memory comes from two growable arenas that are re-used across uploads (a SLAM front end changes
   // the topology every frame; hipMalloc/hipFree per array per frame would dominate): `up` holds the arrays
-  // that are uploaded (mirrored in a host staging buffer and sent with ONE copy), `scr` the scratch arrays.
+  // that are uploaded (mirrored in a pinned host buffer; a flush sends what differs), `scr` the scratch arrays.
   struct Arena { char* base = nullptr; size_t cap = 0, off = 0, spill = 0; };
   Arena up, scr;
-  char* stage = nullptr;            // pinned host mirror of `up` (one H2D copy per upload, at link rate)
-  size_t stage_cap = 0;
-  size_t stage_lo = 0, stage_hi = 0;   // dirty range of the mirror
-  // Frame loops re-upload a topology that is the previous one plus a little: every array of the upload arena keeps its
-  // place from one upload to the next (a slot with spare capacity per dev_upload call, in call order), the pinned mirror
-  // knows what the device holds, and only the bytes that differ are sent -- gathered into one patch buffer, one copy, one
-  // scatter kernel (dozens of small copies would cost more than they carry).
-  // owner: which array (the address of its device pointer) the slot received last.  Slots go by call order, and an array that is uploaded
-  // only on some graphs (obs_ray: re-popping edges) shifts every array behind it by one slot when it appears or goes: a claim about "what this
-  // slot received last time" (kept-prefix hints, rows sent by the previous upload) holds only while the owner is the same.
-  struct UpSlot { size_t off, cap; const void* owner = nullptr; };
-  std::vector<UpSlot> up_slots;
-  size_t up_cursor = 0, up_high = 0;
-  bool up_unknown = true;              // the arena was (re)allocated: the mirror says nothing about the device
+  // the pinned host mirror of `up` (UploadMirror::mir: allocated and freed by free_device / release_arenas), what it knows about the device,
+  // where every upload of a layout goes, and which bytes the next flush sends (pps_upmirror.h)
+  pps_impl::UploadMirror mirror;
   // Which analysis the upload mirror holds: `an` (sequence number an_seq) was built upon the analysis an_base_seq; when that is the
   // one whose arrays were uploaded last (up_an_seq), the leading entries `an.kept` names are in the mirror already and are not
-  // compared again.  PPS_DEBUG_VERIFY_UPLOAD=1 checks every such claim (hint_violation -> PPS_ESTATE).
+  // compared again.  PPS_DEBUG_VERIFY_UPLOAD=1 checks every such claim (UploadMirror::hint_violation -> PPS_ESTATE).
   long an_seq = 0, an_base_seq = -1, up_an_seq = -1;
-  bool hint_violation = false;
-  bool verify_hints = false;           // PPS_DEBUG_VERIFY_UPLOAD, read once per upload
-  bool up_unknown_meas = false;        // ... only about the measurement arrays (written behind the mirror's back)
-  size_t slot_obs_meas = (size_t)-1;   // which upload slot holds obs_meas
-  size_t slot_lp_meas = (size_t)-1;    // ... and lp_meas (pps_set_measurement writes both arrays behind the mirror's back)
-  // packed factor arrays of the last upload: an upload that only appends fills in the new slots instead of packing every
-  // factor again (pk_n = slots that are current; pk_meas_ok: the measurement rows still match the host factors)
-  std::vector<int> pk_obs_a, pk_obs_b, pk_odo_a, pk_odo_b, pk_obs_ids, pk_odo_ids;
-  std::vector<double> pk_obs_m, pk_obs_w, pk_odo_m, pk_odo_w;
-  size_t pk_n_obs = 0, pk_n_odo = 0, pk_ld_obs = 0, pk_ld_odo = 0;
+  // packed factor arrays of the last upload, per side (plane observations, odometry): an upload that only appends fills in the new slots
+  // instead of packing every factor again (n = slots that are current; pk_meas_ok: the measurement rows of both sides still match the host factors)
+  struct PackedSide {
+    int type, km, kw;                  // factor type; rows of the measurement and of the weight array
+    std::vector<int> ids, a, b;        // slot -> factor id as packed; slot -> slot of the first / second node
+    std::vector<double> m, w;          // SoA with leading dimension ld
+    size_t n = 0, ld = 0;
+  };
+  PackedSide pk_obs{pps::F_PLANE_OBS, 4, 6}, pk_odo{pps::F_ODOMETRY, 6, 21};
   bool pk_meas_ok = false;
   bool status_clean = false;     // result_dev / spec_result are zero: upload_all zeroed them, or the last solve's chi2 kernels consumed the flags
   bool up_inflight = false;      // upload_all left copies from the pinned buffers in flight on `stream`
   double* state_pin = nullptr; size_t state_pin_cap = 0;     // pinned staging of upload_state / download_state
   bool pin_holds_est = false;                                // state_pin holds the device estimate as it is now (enqueue_state_download)
-  std::unordered_map<std::string, double> up_laps;         // PPS_UPLOAD_TIMING=1: seconds per phase of upload_all, summed; printed at destroy
-  struct UpPatch { size_t off, len; bool exact8 = false; };   // exact8: 8-byte granularity, nothing around the piece may be written
-  std::vector<UpPatch> up_patches;
+  std::unordered_map<std::string, double> up_laps;         // PPS_TIMING=2: seconds per phase of upload_all, summed; printed at destroy
   char* patch_host = nullptr; size_t patch_cap = 0;    // pinned: the table of k_scatter_patches (the pieces are read from the pinned mirror)
-  size_t up_bytes_sent = 0, up_bytes_total = 0;        // of the last flush (stats)
   double* host_result = nullptr;   // pinned, 12 doubles: chi2 at the linearisation point | trial | speculative trial
   double seq = 0.0;                // sequence number the chi2 kernel publishes last (host polls it)
   // the second damping value of a dual solve (lambda * factor): its own L / U / delta, a third copy of the state, its own
@@ -305,14 +292,14 @@ inline bool live_node(const pps_graph* g, int id, int type) {
 // ---- pps_upload.cpp ----
 void free_device(pps_graph* g);
 void release_arenas(pps_graph* g);
-void up_diff(pps_graph* g, size_t o, const char* src, size_t n, bool force, size_t same_prefix = 0);
 int flush_uploads(pps_graph* g);
 int verify_uploads(pps_graph* g, const char* where);
 int verify_frame_tables(pps_graph* g);         // PPS_DEBUG_VERIFY_UPLOAD: the frame tables against the factor / node records, host and device
 int ensure_device(pps_graph* g);
 int64_t j_capacity(int64_t n);
-void j_bases(const pps_graph* g, int64_t base[4], int64_t* total);
-void p_bases(const pps_graph* g, int64_t base[4], int64_t* total);      // product records (pps_symbolic.h: kPSize), same slab capacities
+void slab_bases(const pps_graph* g, const int size[4], int64_t base[4], int64_t* total);
+inline void j_bases(const pps_graph* g, int64_t base[4], int64_t* total) { slab_bases(g, pps::kJSize, base, total); }
+inline void p_bases(const pps_graph* g, int64_t base[4], int64_t* total) { slab_bases(g, pps::kPSize, base, total); }      // product records, same slab capacities
 int run_analysis(pps_graph* g);
 int state_pin_reserve(pps_graph* g, size_t doubles);
 int linpoint_from_estimate(pps_graph* g);
@@ -404,8 +391,10 @@ int DevBuf<T>::reserve(pps_graph* g, size_t count, const char* who, const std::s
 // ---- pps_api.cpp ----
 void report_front_trace(pps_graph* g);        // PPS_TRACE: the per-front cycle counters of the last solve -> stderr
 
+// `count` elements of scratch from the arena `scr`; when it is full (it is re-sized at the next upload), a plain allocation
 template <class T>
-int arena_alloc(pps_graph* g, pps_graph::Arena& a, T** out, size_t count) {
+int dev_alloc(pps_graph* g, T** out, size_t count) {
+  pps_graph::Arena& a = g->scr;
   *out = nullptr;
   if (count == 0) count = 1;
   const size_t bytes = count * sizeof(T);
@@ -420,91 +409,26 @@ int arena_alloc(pps_graph* g, pps_graph::Arena& a, T** out, size_t count) {
   return PPS_OK;
 }
 
-template <class T>
-int dev_alloc(pps_graph* g, T** out, size_t count) { return arena_alloc(g, g->scr, out, count); }
-
-
-// exact_from (rows of 8-byte values only): entries [0, exact_from) of every row are newer on the device than anywhere on the
-// host (measurements refreshed by k_refresh_measurements) -- exactly the entries [exact_from, used) are sent, byte for byte,
-// and nothing around them (a piece rounded to the 64-byte compare stride or to the 16-byte copy unit would put the mirror's
-// stale values over up to seven refreshed neighbours)
-constexpr size_t kNoExact = (size_t)-1;
-// same: leading ELEMENTS (of the array, or of every row) that the caller knows to be what this slot received last time
-template <class T>
-int dev_upload_impl(pps_graph* g, T** out, const std::vector<T>& v, size_t rows, size_t ld, size_t used, bool force, size_t exact_from, size_t same);
-template <class T>
-int dev_upload(pps_graph* g, T** out, const std::vector<T>& v, size_t same = 0) { return dev_upload_impl(g, out, v, 0, 0, 0, false, kNoExact, same); }
+// The next upload of the layout: the mirror places it (pps_upmirror.h) and records what differs; a flush sends that.  An array the arena has no
+// room for gets an allocation of its own and is copied at once (upload_spilled).
+// same: leading ELEMENTS (of the array, or of every row) that the caller knows to be what this slot received last time; exact_from: kNoExact
+int upload_spilled(pps_graph* g, void** out, const void* src, size_t n, size_t bytes);
 template <class T>
 int dev_upload_rows(pps_graph* g, T** out, const std::vector<T>& v, size_t rows, size_t ld, size_t used, bool force, size_t exact_from = kNoExact,
                     size_t same = 0) {
-  return dev_upload_impl(g, out, v, rows, ld, used, force, exact_from, same);
-}
-
-template <class T>
-int dev_upload_impl(pps_graph* g, T** out, const std::vector<T>& v, size_t rows, size_t ld, size_t used, bool force, size_t exact_from, size_t same) {
-  *out = nullptr;
-  pps_graph::Arena& a = g->up;
-  const size_t bytes = std::max<size_t>(1, v.size()) * sizeof(T);
-  const size_t k = g->up_cursor++;
-  size_t o = 0, fresh_cap = 0;
-  bool placed = false;
-  if (a.base && g->stage) {
-    if (k < g->up_slots.size() && bytes <= g->up_slots[k].cap) {
-      o = g->up_slots[k].off; placed = true;
-      if (g->up_slots[k].owner != out) same = 0;       // the slot held another array: its bytes are compared like any others
-      g->up_slots[k].owner = out;
-    }
-    else {
-      const size_t cap = (std::max<size_t>(256, bytes + bytes / 2) + 255) & ~size_t(255);
-      o = (g->up_high + 255) & ~size_t(255);
-      if (o + cap <= a.cap) {
-        if (k < g->up_slots.size()) g->up_slots[k] = pps_graph::UpSlot{o, cap, out}; else g->up_slots.push_back(pps_graph::UpSlot{o, cap, out});
-        g->up_high = o + cap;
-        placed = true;
-        fresh_cap = cap;
-      }
-    }
-  }
-  if (!placed) {                                     // arena exhausted (it is re-sized at the next upload): a plain allocation
-    a.spill += bytes + bytes / 2 + 512;
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) return hip_fail(g, e, "hipMalloc");
-    g->allocs.push_back(p);
-    *out = static_cast<T*>(p);
-    if (!v.empty()) HIP_TRY(g, hipMemcpy(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return PPS_OK;
-  }
-  *out = reinterpret_cast<T*>(a.base + o);
-  a.off = std::max(a.off, o + bytes);
-  if (fresh_cap) {
-    // A slot that has just been created (or moved behind the others because it outgrew its place) lies in a part of the arena
-    // the mirror says nothing about: neither side has ever been written there, and a diff against it may find the new bytes
-    // "already there" (zeros against a fresh pinned page, say) and leave the device with whatever it held.  Define the whole
-    // slot -- capacity, not just what is used today: later uploads grow into it -- and send it once.
-    memset(g->stage + o, 0, fresh_cap);
-    if (!v.empty()) memcpy(g->stage + o, v.data(), v.size() * sizeof(T));
-    g->up_bytes_total += fresh_cap;
-    g->up_patches.push_back(pps_graph::UpPatch{o, fresh_cap, false});
-    return PPS_OK;
-  }
-  if (v.empty()) return PPS_OK;
+  constexpr size_t E = sizeof(T);
+  const size_t n = v.size() * E, bytes = std::max<size_t>(1, v.size()) * E;
   const char* src = reinterpret_cast<const char*>(v.data());
-  if (rows == 0 || g->up_unknown) { up_diff(g, o, src, v.size() * sizeof(T), force, rows == 0 ? std::min(same, v.size()) * sizeof(T) : 0); return PPS_OK; }
-  const size_t keep = std::min(same, used);
-  if (exact_from != kNoExact && !force && sizeof(T) == 8) {
-    for (size_t r = 0; r < rows; r++) {
-      const size_t ro = r * ld * sizeof(T);
-      if (keep && g->verify_hints && memcmp(g->stage + o + ro, src + ro, keep * sizeof(T)) != 0) g->hint_violation = true;
-      memcpy(g->stage + o + ro + keep * sizeof(T), src + ro + keep * sizeof(T), (used - keep) * sizeof(T));   // the mirror keeps the host's view of the row
-      g->up_bytes_total += used * sizeof(T);
-      if (used > exact_from) g->up_patches.push_back(pps_graph::UpPatch{o + ro + exact_from * sizeof(T), (used - exact_from) * sizeof(T), true});
-    }
-    return PPS_OK;
-  }
-  for (size_t r = 0; r < rows; r++) up_diff(g, o + r * ld * sizeof(T), src + r * ld * sizeof(T), used * sizeof(T), force, keep * sizeof(T));
+  UploadMirror& m = g->mirror;
+  const UploadMirror::Place p = m.place(out, bytes);
+  if (!p.fits) return upload_spilled(g, reinterpret_cast<void**>(out), src, n, bytes);
+  *out = reinterpret_cast<T*>(g->up.base + p.off);
+  g->up.off = std::max(g->up.off, p.off + bytes);
+  if (rows == 0) m.put_array(p, src, n, same * E);
+  else m.put_rows(p, src, n, rows, ld * E, used * E, force, same * E, (exact_from != kNoExact && E == 8) ? exact_from * E : kNoExact);
   return PPS_OK;
 }
-
+template <class T>
+int dev_upload(pps_graph* g, T** out, const std::vector<T>& v, size_t same = 0) { return dev_upload_rows(g, out, v, 0, 0, 0, false, kNoExact, same); }
 
 }  // namespace pps_impl

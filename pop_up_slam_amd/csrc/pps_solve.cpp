@@ -234,7 +234,7 @@ void begin_solve(pps_graph* g) {
 }
 
 // the device copy of a handle is given up after a failed solve: streams drained, nothing on the device is trusted any more --
-// the next upload sends the whole arena (up_unknown: the mirror says nothing about the device, measurements included) and the
+// the next upload sends the whole arena (UploadMirror::unknown: the mirror says nothing about the device, measurements included) and the
 // estimate falls back to the host's node values
 // status_clean: both records' status words are zero since the upload, or the last call's chi2 kernels took them along.  The flag stands for BOTH
 // records: a one-step LM solve may have left a not-PD flag of a speculative factorisation that was never evaluated in the second one, and the
@@ -252,7 +252,7 @@ void abandon_device_copy(pps_graph* g) {
   if (!g->dev_ready) return;
   (void)hipStreamSynchronize(g->stream);
   g->topo_dirty = true; g->dev_values_newer = false; g->dev_meas_newer = false;
-  g->up_unknown = true; g->up_unknown_meas = true; g->pk_meas_ok = false; g->status_clean = false;
+  g->mirror.forget_device(); g->mirror.forget_measurements(); g->pk_meas_ok = false; g->status_clean = false;
 }
 
 // A failure in the middle of a solve (a HIP error: lost device, out of memory) leaves est / lin possibly exchanged and

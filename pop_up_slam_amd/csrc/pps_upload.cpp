@@ -1,5 +1,5 @@
 // pps_upload.cpp -- from the host tables to HBM: compaction + symbolic analysis (once per topology; incremental for frame
-// loops), the two device arenas, the difference upload (pinned mirror, patch buffer + scatter kernel), state and measurement
+// loops), the two device arenas, the difference upload (pinned mirror: pps_upmirror.h; scatter kernel), state and measurement
 // transfers.  pps_graph.h lists the other implementation files.
 #include "pps_graph.h"
 
@@ -8,93 +8,68 @@ using namespace pps_impl;
 
 namespace pps_impl {
 
+#define TRY(x) do { const int rc_ = (x); if (rc_ != PPS_OK) return rc_; } while (0)      // (in the functions of this file that answer with a PPS_* code)
+
 void free_device(pps_graph* g) {
   for (void* p : g->allocs) (void)hipFree(p);
   g->allocs.clear();
+  UploadMirror& m = g->mirror;
   // arenas are kept; grow them when the last layout spilled into fallback allocations
   for (pps_graph::Arena* a : {&g->up, &g->scr}) {
-    const size_t want = (a == &g->up ? std::max(a->off, g->up_high) : a->off) + a->spill;
+    const size_t want = (a == &g->up ? std::max(a->off, m.high) : a->off) + a->spill;
     if (a->spill > 0 || a->base == nullptr) {
       if (a->base) (void)hipFree(a->base);
-      a->cap = std::max<size_t>(size_t(1) << 20, 2 * want);
+      a->cap = UploadMirror::grown_capacity(want);
       if (hipMalloc(reinterpret_cast<void**>(&a->base), a->cap) != hipSuccess) { a->base = nullptr; a->cap = 0; }
-      if (a == &g->up) { g->up_slots.clear(); g->up_high = 0; g->up_unknown = true; }
+      if (a == &g->up) m.set_arena(a->cap);
     }
     a->off = 0; a->spill = 0;
   }
-  g->up_cursor = 0; g->up_patches.clear();
-  if (g->stage_cap < g->up.cap) {
-    if (g->stage) (void)hipHostFree(g->stage);
-    g->stage = nullptr; g->stage_cap = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&g->stage), g->up.cap, hipHostMallocDefault) == hipSuccess) g->stage_cap = g->up.cap;
-    g->up_unknown = true;
+  m.begin_layout();
+  if (m.mir_cap < g->up.cap) {                       // the pinned mirror: as large as the arena it describes
+    if (m.mir) (void)hipHostFree(m.mir);
+    char* p = nullptr;
+    const bool ok = hipHostMalloc(reinterpret_cast<void**>(&p), g->up.cap, hipHostMallocDefault) == hipSuccess;
+    m.set_mirror(ok ? p : nullptr, ok ? g->up.cap : 0);
   }
-  g->stage_lo = g->stage_hi = 0;
   g->dev = DevGraph();
 }
 
 void release_arenas(pps_graph* g) {
   for (pps_graph::Arena* a : {&g->up, &g->scr}) { if (a->base) (void)hipFree(a->base); a->base = nullptr; a->cap = a->off = a->spill = 0; }
-  if (g->stage) (void)hipHostFree(g->stage);
-  g->stage = nullptr; g->stage_cap = 0;
+  if (g->mirror.mir) (void)hipHostFree(g->mirror.mir);
   if (g->patch_host) (void)hipHostFree(g->patch_host);
   if (g->state_pin) (void)hipHostFree(g->state_pin);
   g->state_pin = nullptr; g->state_pin_cap = 0; g->pin_holds_est = false;
   g->patch_host = nullptr; g->patch_cap = 0;
-  g->up_slots.clear(); g->up_high = 0; g->up_unknown = true;
+  g->mirror.set_arena(0); g->mirror.set_mirror(nullptr, 0);
 }
 
-// bytes [0, n) of `src` against the mirror at offset o: record (and copy into the mirror) the range that differs
-// same_prefix: leading bytes the caller knows to be in the mirror already (pps_graph::an_seq): the comparison starts behind them
-void up_diff(pps_graph* g, size_t o, const char* src, size_t n, bool force, size_t same_prefix) {
-  if (n == 0) return;
-  char* mir = g->stage + o;
-  g->up_bytes_total += n;
-  if (g->up_unknown || force) { memcpy(mir, src, n); g->up_patches.push_back(pps_graph::UpPatch{o, n, false}); return; }
-  same_prefix = std::min(same_prefix, n);
-  if (same_prefix && g->verify_hints && memcmp(mir, src, same_prefix) != 0) g->hint_violation = true;      // (the whole claim, not only the chunks it saves)
-  same_prefix &= ~size_t(63);
-  // first and last 64-byte chunk that differs from what the device holds (4 KB strides first: most arrays of a frame loop
-  // are unchanged from end to end, or up to a short tail)
-  size_t lo = same_prefix, hi = n;
-  while (lo + 4096 <= hi && memcmp(mir + lo, src + lo, 4096) == 0) lo += 4096;
-  while (lo + 64 <= hi && memcmp(mir + lo, src + lo, 64) == 0) lo += 64;
-  if (lo + 64 > hi && memcmp(mir + lo, src + lo, hi - lo) == 0) return;      // identical
-  while (hi >= lo + 4096 && memcmp(mir + hi - 4096, src + hi - 4096, 4096) == 0) hi -= 4096;
-  while (hi >= lo + 64 && memcmp(mir + hi - 64, src + hi - 64, 64) == 0) hi -= 64;
-  lo &= ~size_t(15);
-  memcpy(mir + lo, src + lo, hi - lo);
-  g->up_patches.push_back(pps_graph::UpPatch{o + lo, hi - lo, false});
+// an upload the arena has no room for (it is re-sized at the next upload): a plain allocation, copied at once
+int upload_spilled(pps_graph* g, void** out, const void* src, size_t n, size_t bytes) {
+  *out = nullptr;
+  g->up.spill += bytes + bytes / 2 + 512;
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) return hip_fail(g, e, "hipMalloc");
+  g->allocs.push_back(p);
+  *out = p;
+  if (n) HIP_TRY(g, hipMemcpy(p, src, n, hipMemcpyHostToDevice));
+  return PPS_OK;
 }
 
-// The k-th upload of a layout goes where the k-th upload of the previous layout went, as long as it fits the slot.
-// rows > 0: an SoA array of `rows` rows with leading dimension ld of which the first `used` entries per row are live -- the
-// rows are compared one by one (appending a factor touches the end of every row, not the array from end to end).
-
-// send what differs: everything in one copy when the device content is unknown or most of it changed, else the patches
+// send what the mirror recorded: everything in one copy when the device content is unknown, else the pieces
 int flush_uploads(pps_graph* g) {
   // callers: upload_all (after its opening stream sync) and the frame tables of pps_refresh_measurements (which settles
-  // up_inflight first) -- the pinned mirror and the patch buffer are never rewritten under a copy that still reads them
-  size_t sent = 0;
-  for (const auto& pt : g->up_patches) sent += pt.len;
-  g->up_bytes_sent = sent;
-  if (g->up_patches.empty()) { g->up_bytes_total = 0; return PPS_OK; }
-  // One copy of the whole arena only when the device content is unknown.  Otherwise nothing but the changed pieces may be
-  // written: the span between two pieces can hold what kernels have refreshed behind the mirror's back (the observation
-  // measurements that stay on the device) -- a copy "from the first to the last change" would put stale values over them.
-  if (g->up_unknown) {
-    size_t lo = 0, hi = 0;
-    for (const auto& pt : g->up_patches) hi = std::max(hi, pt.off + pt.len);
-    hi = std::max(hi, g->up_high); hi = std::min(hi, g->stage_cap);
-    HIP_TRY(g, hipMemcpyAsync(g->up.base + lo, g->stage + lo, hi - lo, hipMemcpyHostToDevice, g->stream));
-    g->up_bytes_sent = hi - lo;
-  } else {
-    // A table of (destination, source, bytes, unit) records in pinned host memory; k_scatter_patches reads the table AND the pieces -- straight
-    // from the pinned mirror, whose offsets are the arena's -- over the bus (round 6: no patch buffer, no host copy of the pieces into it, no
-    // copy launch in front of the kernel: 1.7 copies of 63 KB per frame of the frame loop).  Piece lengths are rounded up to 16 bytes except
-    // where the bytes behind a piece may be newer on the device than in the mirror (exact8).
-    const size_t np = g->up_patches.size();
-    const size_t need = np * 32;
+  // up_inflight first) -- the pinned mirror and the patch table are never rewritten under a copy that still reads them
+  UploadMirror& m = g->mirror;
+  if (m.patches.empty()) return PPS_OK;
+  if (m.unknown) HIP_TRY(g, hipMemcpyAsync(g->up.base, m.mir, m.whole_span(), hipMemcpyHostToDevice, g->stream));
+  else {
+    // the table in pinned host memory; k_scatter_patches reads the table AND the pieces -- straight from the pinned mirror -- over the bus
+    // (round 6: no patch buffer, no host copy of the pieces into it, no copy launch in front of the kernel: 1.7 copies of 63 KB per frame of
+    // the frame loop)
+    const size_t need = m.patches.size() * 4 * sizeof(long long);
     if (need > g->patch_cap) {
       if (g->patch_host) (void)hipHostFree(g->patch_host);
       g->patch_host = nullptr; g->patch_cap = 0;
@@ -102,18 +77,11 @@ int flush_uploads(pps_graph* g) {
       HIP_TRY(g, hipHostMalloc(reinterpret_cast<void**>(&g->patch_host), cap, hipHostMallocDefault));
       g->patch_cap = cap;
     }
-    long long* tab = reinterpret_cast<long long*>(g->patch_host);
-    for (size_t i = 0; i < np; i++) {
-      const auto& pt = g->up_patches[i];
-      const size_t len = pt.exact8 ? pt.len : ((pt.len + 15) & ~size_t(15));      // (exact pieces are multiples of 8; the arena's capacity is a multiple of 16)
-      tab[4 * i + 0] = (long long)pt.off; tab[4 * i + 1] = (long long)pt.off; tab[4 * i + 2] = (long long)len; tab[4 * i + 3] = pt.exact8 ? 1 : 0;
-    }
-    HIP_TRY(g, launch_scatter_patches(g->patch_host, g->stage, (int)np, g->up.base, g->stream));
+    m.write_table(reinterpret_cast<long long*>(g->patch_host));
+    HIP_TRY(g, launch_scatter_patches(g->patch_host, m.mir, (int)m.patches.size(), g->up.base, g->stream));
     // (table and mirror are written again by the next upload_all / refresh, which wait for the stream first: up_inflight)
   }
-  g->up_unknown = false;
-  g->up_patches.clear();
-  g->stage_lo = g->stage_hi = 0;
+  m.mark_flushed();
   return PPS_OK;
 }
 
@@ -121,19 +89,20 @@ int flush_uploads(pps_graph* g) {
 // measurements, which kernels refresh behind the mirror's back) -- PPS_ESTATE if not.  tests/test_gpu_pipeline.py runs a frame
 // loop under it.  verify_packed / verify_expanded / verify_frame_tables below check the mirror's content itself.
 int verify_uploads(pps_graph* g, const char* where) {
-  if (g->hint_violation) { g->hint_violation = false; return fail(g, PPS_ESTATE, std::string("upload verification (") + where + "): an array differs from the mirror inside the part the analysis reported as kept"); }
-  if (!g->sw.verify_upload || g->up_high == 0 || g->up.spill) return PPS_OK;
+  const UploadMirror& m = g->mirror;
+  if (g->mirror.take_violation()) return fail(g, PPS_ESTATE, std::string("upload verification (") + where + "): an array differs from the mirror inside the part the analysis reported as kept");
+  if (!g->sw.verify_upload || m.high == 0 || g->up.spill) return PPS_OK;
   HIP_TRY(g, hipStreamSynchronize(g->stream));
-  std::vector<char> dev(g->up_high);
-  HIP_TRY(g, hipMemcpy(dev.data(), g->up.base, g->up_high, hipMemcpyDeviceToHost));
-  for (size_t k = 0; k < g->up_slots.size() && k < g->up_cursor; k++) {
-    if (k == g->slot_obs_meas || k == g->slot_lp_meas) continue;
-    const size_t o = g->up_slots[k].off, n = std::min(g->up_slots[k].cap, g->up_high - std::min(g->up_high, o));
-    if (o >= g->up_high) continue;
-    if (memcmp(dev.data() + o, g->stage + o, n) != 0) {
-      size_t b = 0; while (b < n && dev[o + b] == g->stage[o + b]) b++;
+  std::vector<char> dev(m.high);
+  HIP_TRY(g, hipMemcpy(dev.data(), g->up.base, m.high, hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < m.slots.size() && k < m.cursor; k++) {
+    const UploadMirror::Slot& sl = m.slots[k];
+    if (sl.owner == &g->dev.obs_meas || sl.owner == &g->dev.lp_meas || sl.off >= m.high) continue;
+    const size_t o = sl.off, n = std::min(sl.cap, m.high - o);
+    if (memcmp(dev.data() + o, m.mir + o, n) != 0) {
+      size_t b = 0; while (b < n && dev[o + b] == m.mir[o + b]) b++;
       return fail(g, PPS_ESTATE, std::string("upload verification (") + where + "): slot " + std::to_string(k) + " (offset " + std::to_string(o) + ", capacity " +
-                                     std::to_string(g->up_slots[k].cap) + ") differs from the mirror at byte " + std::to_string(b));
+                                     std::to_string(sl.cap) + ") differs from the mirror at byte " + std::to_string(b));
     }
   }
   return PPS_OK;
@@ -145,7 +114,6 @@ int verify_uploads(pps_graph* g, const char* where) {
 static int verify_fail(pps_graph* g, const char* where, const char* array, const char* against, size_t index) {
   return fail(g, PPS_ESTATE, std::string("upload verification (") + where + "): " + array + " differs from " + against + " at index " + std::to_string(index));
 }
-#define VTRY(x) do { rc = (x); if (rc != PPS_OK) return rc; } while (0)      // (the three verify_* functions below; undefined behind the last)
 // rows x [exempt, used) of an SoA array with leading dimension ld (rows == 1, ld == used: a plain array): `have` against `want`
 template <class T>
 static int verify_rows(pps_graph* g, const char* where, const char* array, const char* against, const T* have, const T* want, size_t rows, size_t ld,
@@ -168,51 +136,56 @@ static int verify_dev_rows(pps_graph* g, const char* where, const char* array, c
 // a. The arrays upload_all maintains incrementally (pk_*: plane observations and odometry) packed again from the host factor records:
 // what was staged and what the device holds must both equal them.  kept_meas_rows: the leading rows of obs_meas that keep_meas left to the
 // device, where a refresh has written values the host does not have -- exactly those are exempt, and only on the device side.
+struct SideOnDevice { size_t ld; const int *a, *b; const double *m, *w; const char* names[4]; size_t exempt; };
+static int verify_side(pps_graph* g, const pps_graph::PackedSide& S, const SideOnDevice& D) {
+  const char* where = "upload_all";
+  const char* scratch = "a pack from the host factor records";
+  const std::vector<int>& ids = g->fslot_ids[S.type];
+  const size_t n = ids.size(), ld = D.ld, km = (size_t)S.km, kw = (size_t)S.kw;
+  if (n == 0) return PPS_OK;
+  if (S.a.size() < n || S.b.size() < n || S.m.size() < km * ld || S.w.size() < kw * ld) return verify_fail(g, where, D.names[0], "the slot count (staged arrays too short)", n);
+  std::vector<int> ia(n), ib(n);
+  std::vector<double> pm(km * ld, 0.0), pw(kw * ld, 0.0);
+  for (size_t s = 0; s < n; s++) {
+    const HostFactor& f = g->factors[ids[s]];
+    if (f.deleted || f.slot != (int)s) return verify_fail(g, where, D.names[0], "the slot table (deleted factor or wrong slot)", s);
+    ia[s] = g->nodes[f.a].slot; ib[s] = g->nodes[f.b].slot;
+    for (size_t k = 0; k < km; k++) pm[k * ld + s] = f.meas[k];
+    for (size_t k = 0; k < kw; k++) pw[k * ld + s] = f.w[k];
+  }
+  TRY(verify_rows(g, where, D.names[0], scratch, S.a.data(), ia.data(), 1, n, n));
+  TRY(verify_rows(g, where, D.names[1], scratch, S.b.data(), ib.data(), 1, n, n));
+  TRY(verify_rows(g, where, D.names[2], scratch, S.m.data(), pm.data(), km, ld, n));
+  TRY(verify_rows(g, where, D.names[3], scratch, S.w.data(), pw.data(), kw, ld, n));
+  const char* scratch_dev = "a pack from the host factor records (device side)";
+  TRY(verify_dev_rows(g, where, D.names[0], scratch_dev, D.a, ia.data(), 1, n, n));
+  TRY(verify_dev_rows(g, where, D.names[1], scratch_dev, D.b, ib.data(), 1, n, n));
+  TRY(verify_dev_rows(g, where, D.names[2], scratch_dev, D.m, pm.data(), km, ld, n, std::min(n, D.exempt)));
+  return verify_dev_rows(g, where, D.names[3], scratch_dev, D.w, pw.data(), kw, ld, n);
+}
 static int verify_packed(pps_graph* g, size_t kept_meas_rows) {
   if (!g->sw.verify_upload) return PPS_OK;
   HIP_TRY(g, hipStreamSynchronize(g->stream));
   const DevGraph& d = g->dev;
-  const char* where = "upload_all";
-  const char* scratch = "a pack from the host factor records";
-  struct Side { int type; size_t ld; int km, kw; const std::vector<int>*pa, *pb; const std::vector<double>*pm, *pw; const int *da, *db; const double *dm, *dw;
-                const char* names[4]; size_t exempt; };
-  const Side sides[2] = {
-      {F_PLANE_OBS, (size_t)d.obs_ld, 4, 6, &g->pk_obs_a, &g->pk_obs_b, &g->pk_obs_m, &g->pk_obs_w, d.obs_pose, d.obs_plane, d.obs_meas, d.obs_w,
-       {"obs_pose", "obs_plane", "obs_meas", "obs_w"}, kept_meas_rows},
-      {F_ODOMETRY, (size_t)d.odo_ld, 6, 21, &g->pk_odo_a, &g->pk_odo_b, &g->pk_odo_m, &g->pk_odo_w, d.odo_a, d.odo_b, d.odo_meas, d.odo_w,
-       {"odo_a", "odo_b", "odo_meas", "odo_w"}, 0}};
-  for (const Side& S : sides) {
-    const std::vector<int>& ids = g->fslot_ids[S.type];
-    const size_t n = ids.size(), ld = S.ld;
-    if (n == 0) continue;
-    if (S.pa->size() < n || S.pb->size() < n || S.pm->size() < (size_t)S.km * ld || S.pw->size() < (size_t)S.kw * ld) return verify_fail(g, where, S.names[0], "the slot count (staged arrays too short)", n);
-    std::vector<int> ia(n), ib(n);
-    std::vector<double> pm((size_t)S.km * ld, 0.0), pw((size_t)S.kw * ld, 0.0);
-    for (size_t s = 0; s < n; s++) {
-      const HostFactor& f = g->factors[ids[s]];
-      if (f.deleted || f.slot != (int)s) return verify_fail(g, where, S.names[0], "the slot table (deleted factor or wrong slot)", s);
-      ia[s] = g->nodes[f.a].slot; ib[s] = g->nodes[f.b].slot;
-      for (int k = 0; k < S.km; k++) pm[(size_t)k * ld + s] = f.meas[k];
-      for (int k = 0; k < S.kw; k++) pw[(size_t)k * ld + s] = f.w[k];
-    }
-    int rc;
-    VTRY(verify_rows(g, where, S.names[0], scratch, S.pa->data(), ia.data(), 1, n, n));
-    VTRY(verify_rows(g, where, S.names[1], scratch, S.pb->data(), ib.data(), 1, n, n));
-    VTRY(verify_rows(g, where, S.names[2], scratch, S.pm->data(), pm.data(), (size_t)S.km, ld, n));
-    VTRY(verify_rows(g, where, S.names[3], scratch, S.pw->data(), pw.data(), (size_t)S.kw, ld, n));
-    const char* scratch_dev = "a pack from the host factor records (device side)";
-    VTRY(verify_dev_rows(g, where, S.names[0], scratch_dev, S.da, ia.data(), 1, n, n));
-    VTRY(verify_dev_rows(g, where, S.names[1], scratch_dev, S.db, ib.data(), 1, n, n));
-    VTRY(verify_dev_rows(g, where, S.names[2], scratch_dev, S.dm, pm.data(), (size_t)S.km, ld, n, std::min(n, S.exempt)));
-    VTRY(verify_dev_rows(g, where, S.names[3], scratch_dev, S.dw, pw.data(), (size_t)S.kw, ld, n));
-  }
-  return PPS_OK;
+  const int rc = verify_side(g, g->pk_obs, {(size_t)d.obs_ld, d.obs_pose, d.obs_plane, d.obs_meas, d.obs_w, {"obs_pose", "obs_plane", "obs_meas", "obs_w"}, kept_meas_rows});
+  return rc != PPS_OK ? rc : verify_side(g, g->pk_odo, {(size_t)d.odo_ld, d.odo_a, d.odo_b, d.odo_meas, d.odo_w, {"odo_a", "odo_b", "odo_meas", "odo_w"}, 0});
 }
 
 // b. ea_tgt, el_tgt and blk_dst as the expansion launch left them (k_expand_lists, or k_expand_ea + fills + k_expand_el) against
 // expand_ea_tgt / expand_el_lists on a copy of the Analysis; blk_dst entries that no front gathers are -1 on both sides.
 // c. The block behind delta (dn partials, tickets, result records, both deltas, hand-over flags) reads back as zeros.
-static int verify_expanded(pps_graph* g, const double* zero_block, size_t zero_doubles) {
+// The zeroed block behind delta, in doubles from its start: [dn_partials | ticket | spec ticket | result record | the second factorisation's
+// result record | delta | the second delta | the hand-over flags of the whole-tree launches: 4 ints per front].  Cleared by the expansion
+// launch of upload_all (or by a memset when that launch has nothing to expand).
+struct ZeroBlock {
+  size_t n_dn, dn_partials = 0, ticket, spec_ticket, result, spec_result, delta, spec_delta, flags, total;
+  ZeroBlock(int n_nodes, int n_scalars, int n_fronts) : n_dn((size_t)(n_nodes + 255) / 256 + 1) {
+    const size_t delta_doubles = (size_t)std::max(1, n_scalars);
+    ticket = n_dn; spec_ticket = ticket + 1; result = spec_ticket + 1; spec_result = result + 4; delta = spec_result + 4;
+    spec_delta = delta + delta_doubles; flags = spec_delta + delta_doubles; total = flags + 2 * (size_t)std::max(1, n_fronts) + 1;
+  }
+};
+static int verify_expanded(pps_graph* g, const double* zero_block, const ZeroBlock& Z) {
   if (!g->sw.verify_upload) return PPS_OK;
   HIP_TRY(g, hipStreamSynchronize(g->stream));
   const DevGraph& d = g->dev;
@@ -220,8 +193,7 @@ static int verify_expanded(pps_graph* g, const double* zero_block, size_t zero_d
   Analysis A = g->an;
   expand_ea_tgt(A);
   expand_el_lists(A);
-  int rc;
-  VTRY(verify_dev_rows(g, where, "ea_tgt", "expand_ea_tgt on the host", d.ea_tgt, A.ea_tgt.data(), 1, A.ea_tgt.size(), A.ea_tgt.size()));
+  TRY(verify_dev_rows(g, where, "ea_tgt", "expand_ea_tgt on the host", d.ea_tgt, A.ea_tgt.data(), 1, A.ea_tgt.size(), A.ea_tgt.size()));
   if (!A.el_tgt.empty()) {
     // (entry by entry of every assembled block: an element no block claims is written by nobody, on either side)
     std::vector<int> have(A.el_tgt.size());
@@ -234,9 +206,9 @@ static int verify_expanded(pps_graph* g, const double* zero_block, size_t zero_d
         if (have[e] != A.el_tgt[e]) return verify_fail(g, where, "el_tgt", "expand_el_lists on the host", e);
     }
   }
-  VTRY(verify_dev_rows(g, where, "blk_dst", "expand_el_lists on the host", d.blk_dst, A.blk_dst.data(), 1, A.blk_dst.size(), A.blk_dst.size()));
-  const std::vector<double> zeros(zero_doubles, 0.0);
-  return verify_dev_rows(g, where, "the zeroed block behind delta", "zero", zero_block, zeros.data(), 1, zero_doubles, zero_doubles);
+  TRY(verify_dev_rows(g, where, "blk_dst", "expand_el_lists on the host", d.blk_dst, A.blk_dst.data(), 1, A.blk_dst.size(), A.blk_dst.size()));
+  const std::vector<double> zeros(Z.total, 0.0);
+  return verify_dev_rows(g, where, "the zeroed block behind delta", "zero", zero_block, zeros.data(), 1, Z.total, Z.total);
 }
 
 // The frame tables of pps_refresh_measurements after their flush: the cached slot tables (extended, not rebuilt, while nothing is removed)
@@ -258,16 +230,14 @@ int verify_frame_tables(pps_graph* g) {
   if (g->fr_pslot.size() != pslot.size()) return verify_fail(g, where, "frame_pose_slot", "the number of registered frames", std::min(pslot.size(), g->fr_pslot.size()));
   const char* scratch = "tables built from the factor and node records";
   const char* host = "the host tables (device side)";
-  int rc;
-  VTRY(verify_rows(g, where, "item_slot", scratch, g->fr_slot.data(), slot.data(), 1, slot.size(), slot.size()));
-  VTRY(verify_rows(g, where, "frame_pose_slot", scratch, g->fr_pslot.data(), pslot.data(), 1, pslot.size(), pslot.size()));
-  VTRY(verify_dev_rows(g, where, "item_frame", host, g->d_item_frame, g->fr_item_frame.data(), 1, g->fr_item_frame.size(), g->fr_item_frame.size()));
-  VTRY(verify_dev_rows(g, where, "item_plane", host, g->d_item_plane, g->fr_item_plane.data(), 1, g->fr_item_plane.size(), g->fr_item_plane.size()));
-  VTRY(verify_dev_rows(g, where, "item_slot", host, g->d_item_slot, slot.data(), 1, slot.size(), slot.size()));
-  VTRY(verify_dev_rows(g, where, "frame_pose_slot", host, g->d_frame_pose_slot, pslot.data(), 1, pslot.size(), pslot.size()));
-  VTRY(verify_dev_rows(g, where, "frame_seg_off", host, g->d_frame_seg_off, g->fr_seg_off.data(), 1, g->fr_seg_off.size(), g->fr_seg_off.size()));
-  VTRY(verify_dev_rows(g, where, "fr_seg", host, g->d_fr_seg, g->fr_seg.data(), 1, g->fr_seg.size(), g->fr_seg.size()));
-#undef VTRY
+  TRY(verify_rows(g, where, "item_slot", scratch, g->fr_slot.data(), slot.data(), 1, slot.size(), slot.size()));
+  TRY(verify_rows(g, where, "frame_pose_slot", scratch, g->fr_pslot.data(), pslot.data(), 1, pslot.size(), pslot.size()));
+  TRY(verify_dev_rows(g, where, "item_frame", host, g->d_item_frame, g->fr_item_frame.data(), 1, g->fr_item_frame.size(), g->fr_item_frame.size()));
+  TRY(verify_dev_rows(g, where, "item_plane", host, g->d_item_plane, g->fr_item_plane.data(), 1, g->fr_item_plane.size(), g->fr_item_plane.size()));
+  TRY(verify_dev_rows(g, where, "item_slot", host, g->d_item_slot, slot.data(), 1, slot.size(), slot.size()));
+  TRY(verify_dev_rows(g, where, "frame_pose_slot", host, g->d_frame_pose_slot, pslot.data(), 1, pslot.size(), pslot.size()));
+  TRY(verify_dev_rows(g, where, "frame_seg_off", host, g->d_frame_seg_off, g->fr_seg_off.data(), 1, g->fr_seg_off.size(), g->fr_seg_off.size()));
+  TRY(verify_dev_rows(g, where, "fr_seg", host, g->d_fr_seg, g->fr_seg.data(), 1, g->fr_seg.size(), g->fr_seg.size()));
   return PPS_OK;
 }
 
@@ -286,22 +256,11 @@ int ensure_device(pps_graph* g) {
 // sized for a capacity that grows in powers of two, so that a graph that gains a few factors per frame keeps all of its J
 // offsets -- and with them the whole contribution list of the H-block kernel -- from one frame to the next.
 int64_t j_capacity(int64_t n) { int64_t c = 16; while (c < n) c <<= 1; return c; }
-void j_bases(const pps_graph* g, int64_t base[4], int64_t* total) {
-  const int64_t n_pp = g->fslot_ids[F_POSE_PRIOR].size(), n_odo = g->fslot_ids[F_ODOMETRY].size(),
-                n_obs = g->fslot_ids[F_PLANE_OBS].size(), n_lp = g->fslot_ids[F_PLANE_PRIOR].size();
-  const int64_t joff_obs = 0, joff_odo = j_capacity(n_obs) * 30, joff_pp = joff_odo + j_capacity(n_odo) * 78,
-                joff_lp = joff_pp + j_capacity(n_pp) * 42;
-  base[F_POSE_PRIOR] = joff_pp; base[F_ODOMETRY] = joff_odo; base[F_PLANE_OBS] = joff_obs; base[F_PLANE_PRIOR] = joff_lp;
-  if (total) *total = joff_lp + j_capacity(n_lp) * 12;
-}
-// the product records (pps_symbolic.h: kPSize) in slabs of the same capacities: a product offset moves exactly when the J offset does
-void p_bases(const pps_graph* g, int64_t base[4], int64_t* total) {
-  const int64_t n_pp = g->fslot_ids[F_POSE_PRIOR].size(), n_odo = g->fslot_ids[F_ODOMETRY].size(),
-                n_obs = g->fslot_ids[F_PLANE_OBS].size(), n_lp = g->fslot_ids[F_PLANE_PRIOR].size();
-  const int64_t p_obs = 0, p_odo = j_capacity(n_obs) * kPSize[F_PLANE_OBS], p_pp = p_odo + j_capacity(n_odo) * kPSize[F_ODOMETRY],
-                p_lp = p_pp + j_capacity(n_pp) * kPSize[F_POSE_PRIOR];
-  base[F_POSE_PRIOR] = p_pp; base[F_ODOMETRY] = p_odo; base[F_PLANE_OBS] = p_obs; base[F_PLANE_PRIOR] = p_lp;
-  if (total) *total = p_lp + j_capacity(n_lp) * kPSize[F_PLANE_PRIOR];
+// (size: kJSize, or kPSize for the product records, in slabs of the same capacities: a product offset moves exactly when the J offset does)
+void slab_bases(const pps_graph* g, const int size[4], int64_t base[4], int64_t* total) {
+  int64_t off = 0;
+  for (int t : {F_PLANE_OBS, F_ODOMETRY, F_POSE_PRIOR, F_PLANE_PRIOR}) { base[t] = off; off += j_capacity((int64_t)g->fslot_ids[t].size()) * size[t]; }
+  if (total) *total = off;
 }
 
 // ---- compaction + symbolic analysis (host only) -------------------------------------------
@@ -473,15 +432,13 @@ int download_state(pps_graph* g) {
   if (!g->dev_values_newer) return PPS_OK;
   HIP_TRY(g, hipSetDevice(g->props.device));
   const DevGraph& d = g->dev;
-  const size_t np = (size_t)7 * d.pose_ld, nl = (size_t)4 * d.plane_ld;
   if (!g->pin_holds_est) {
-    int rc = state_pin_reserve(g, np + nl);
+    int rc = enqueue_state_download(g);
     if (rc != PPS_OK) return rc;
-    HIP_TRY(g, hipMemcpyAsync(g->state_pin, d.pose_est, (np + nl) * 8, hipMemcpyDeviceToHost, g->stream));   // [poses | planes], one block
     HIP_TRY(g, hipStreamSynchronize(g->stream));
   }
   g->pin_holds_est = false;
-  double* bp = g->state_pin; double* bl = g->state_pin + np;
+  double* bp = g->state_pin; double* bl = g->state_pin + (size_t)7 * d.pose_ld;
   for (int s = 0; s < d.n_pose; s++) for (int k = 0; k < 7; k++) g->nodes[g->pose_ids[s]].v[k] = bp[(size_t)k * d.pose_ld + s];
   for (int s = 0; s < d.n_plane; s++) for (int k = 0; k < 4; k++) g->nodes[g->plane_ids[s]].v[k] = bl[(size_t)k * d.plane_ld + s];
   g->dev_values_newer = false;
@@ -510,8 +467,7 @@ int upload_state(pps_graph* g, bool sync) {
 
 // SoA with leading dimension ld (>= count): value k of slot s at [k * ld + s]
 template <int K>
-void pack_soa(const pps_graph* g, int type, const double HostFactor::*dummy, bool weights, std::vector<double>& out, size_t ld) {
-  (void)dummy;
+void pack_soa(const pps_graph* g, int type, bool weights, std::vector<double>& out, size_t ld) {
   const std::vector<int>& ids = g->fslot_ids[type];
   const size_t n = ids.size();
   out.assign((size_t)K * ld, 0.0);
@@ -543,310 +499,304 @@ int download_measurements(pps_graph* g) {
 int upload_measurements(pps_graph* g) {
   DevGraph& d = g->dev;
   std::vector<double> m;
-  pack_soa<4>(g, F_PLANE_OBS, nullptr, false, m, (size_t)d.obs_ld);
+  pack_soa<4>(g, F_PLANE_OBS, false, m, (size_t)d.obs_ld);
   if (d.n_obs) HIP_TRY(g, hipMemcpyAsync(d.obs_meas, m.data(), m.size() * 8, hipMemcpyHostToDevice, g->stream));
   std::vector<double> m2;
-  pack_soa<4>(g, F_PLANE_PRIOR, nullptr, false, m2, (size_t)d.lp_ld);
+  pack_soa<4>(g, F_PLANE_PRIOR, false, m2, (size_t)d.lp_ld);
   if (d.n_lp) HIP_TRY(g, hipMemcpyAsync(d.lp_meas, m2.data(), m2.size() * 8, hipMemcpyHostToDevice, g->stream));
   // (the upload mirror no longer describes these arrays: the next topology upload sends them whole)
-  g->up_unknown_meas = true;
+  g->mirror.forget_measurements();
   HIP_TRY(g, hipStreamSynchronize(g->stream));
   g->meas_dirty = false;
   return PPS_OK;
 }
 
-int upload_all(pps_graph* g) {
-  const double t0 = now_s();
-  const bool was_grown_only = g->grown_only_upload;
-  const bool tm = g->sw.upload_timing;
-  g->verify_hints = g->sw.verify_upload;
-  double tl = t0;
-  auto lap = [&](const char* what) { if (!tm) return; const double t = now_s(); g->up_laps[what] += t - tl; tl = t; };
-  int rc = ensure_device(g);
-  if (rc != PPS_OK) return rc;
-  lap("0 ensure_device");
-  if (g->dev_values_newer) { rc = download_state(g); if (rc != PPS_OK) return rc; }
-  lap("1a state download");
-  // Refreshed measurements may stay on the device across an upload that only appends (see the obs_meas upload below): same
-  // arena, same slot with room for the new rows, same leading dimension, no re-popping edges (their slots sit behind the
-  // fixed ones and would move).
-  bool keep_meas = false;
-  const size_t n_obs_on_device = (size_t)g->dev.n_obs;         // (free_device below resets g->dev)
-  if (g->dev_meas_newer) {
-    // (live counts kept by the add / remove calls: a walk over the 300-byte factor records here was 30 us per frame at 7 600 factors)
-    const size_t n_obs_new = (size_t)g->n_live_type[F_PLANE_OBS], n_lp_new = (size_t)g->n_live_type[F_PLANE_PRIOR];
-    const bool any_repop = g->n_live_repop > 0;
-    keep_meas = g->grown_only_upload && !g->up_unknown && !g->up_unknown_meas && g->up.spill == 0 && !any_repop && g->dev.n_obs == g->dev.n_obs_fixed &&
-                j_capacity((int64_t)n_obs_new) == g->dev.obs_ld && j_capacity((int64_t)n_lp_new) == g->dev.lp_ld && g->slot_obs_meas < g->up_slots.size() &&
-                true;
-    if (!keep_meas) {
-      if (tm) g->up_laps["(measurement downloads, count)"] += 1e-3;      // (printed as ms: the count)
-      rc = download_measurements(g); if (rc != PPS_OK) return rc;
-    }
+// the appended slots of one packed side (every slot unless the id list of the last pack is a prefix of today's and the leading dimension is
+// unchanged); repack_meas: the host's measurements changed since, the rows of the old slots again.  Returns the first slot it packed.
+// (One pass over the factors: a HostFactor is 300 bytes, a pass per array was four times the memory traffic.)
+static size_t pack_side(const pps_graph* g, pps_graph::PackedSide& S, size_t ld, bool incr, bool repack_meas) {
+  const std::vector<int>& ids = g->fslot_ids[S.type];
+  const size_t n = ids.size(), km = (size_t)S.km, kw = (size_t)S.kw;
+  size_t s_begin = 0;
+  if (incr && S.ld == ld && S.n <= n && S.m.size() == km * ld && S.ids.size() == S.n && std::equal(S.ids.begin(), S.ids.end(), ids.begin()))
+    s_begin = S.n;                                     // (re-popping edges sit behind the fixed ones: their slots move)
+  S.a.resize(n); S.b.resize(n); S.m.resize(km * ld); S.w.resize(kw * ld);
+  for (size_t s = s_begin; s < n; s++) {
+    const HostFactor& f = g->factors[ids[s]];
+    S.a[s] = g->nodes[f.a].slot; S.b[s] = g->nodes[f.b].slot;
+    for (size_t k = 0; k < km; k++) S.m[k * ld + s] = f.meas[k];
+    for (size_t k = 0; k < kw; k++) S.w[k * ld + s] = f.w[k];
   }
-  lap("1b measurements");
-  // the analysis is host work on host tables: it runs while the device finishes what the last frame left on the stream (the measurement
-  // refresh of a frame loop: the opening sync below waited 10 us per frame for it)
-  if (!g->analyzed || g->analysis_stale) { rc = run_analysis(g); if (rc != PPS_OK) return rc; }
-  lap("3 analysis");
-  HIP_TRY(g, hipStreamSynchronize(g->stream));
-  g->up_inflight = false;
-  lap("1c opening stream sync");
-  free_device(g);
-  g->spec_L = g->spec_U = g->spec_delta = nullptr; g->spec_result = nullptr;
-  g->spec_pose = g->spec_plane = g->spec_chi2_partials = g->spec_dn_partials = nullptr; g->spec_ticket = nullptr;
-  g->spec_J = g->spec_P = g->spec_H = g->spec_Hf = nullptr;
-  g->d_item_frame = g->d_item_plane = g->d_item_slot = g->d_frame_pose_slot = g->d_frame_seg_off = nullptr; g->d_fr_seg = nullptr;
-  g->frames_dirty = true;
-  g->snap_pose = g->snap_plane = nullptr; g->upload_version++;
-  lap("2 free_device");
+  for (size_t s = 0; repack_meas && s < s_begin; s++) { const HostFactor& f = g->factors[ids[s]]; for (size_t k = 0; k < km; k++) S.m[k * ld + s] = f.meas[k]; }
+  S.n = n; S.ld = ld; S.ids.resize(s_begin); S.ids.insert(S.ids.end(), ids.begin() + (std::ptrdiff_t)s_begin, ids.end());
+  return s_begin;
+}
+
+// One topology upload: the phases of upload_all in the order it runs them, and what one hands to the next.  The sequence of dev_upload* calls
+// is the layout of the upload arena (slots go by call order, hints hold per owner): it does not change from one upload to the next.
+struct UploadPass {
+  pps_graph* const g;
   const Analysis& A = g->an;
   DevGraph& d = g->dev;
-  // the mirror holds the arrays of the analysis this one was built upon: its kept parts are not compared again
-  const bool hints = was_grown_only && !g->up_unknown && g->up_an_seq >= 0 && g->an_base_seq == g->up_an_seq;
-  const Analysis::Kept K = hints ? A.kept : Analysis::Kept();
-  const size_t kF = (size_t)K.fronts, kFl = (size_t)K.fronts_lists, kB = (size_t)K.blocks, kS = (size_t)K.segs;
-  auto at = [](const auto& v, size_t i) -> size_t { return i < v.size() ? (size_t)v[i] : 0; };     // (0 = no claim)
-  double* zero_block = nullptr; size_t zero_doubles = 0;
-  d.n_pose = (int)g->pose_ids.size(); d.n_plane = (int)g->plane_ids.size();
-  d.no_strip = g->sw.no_strip ? 1 : 0;
-  d.sw = g->sw.dev_bits();
-  HIP_TRY(g, step_constants(d.step_ac));
-  d.pose_ld = std::max(1, (d.n_pose + 63) / 64 * 64); d.plane_ld = std::max(1, (d.n_plane + 63) / 64 * 64);
-#define TRY(x) do { rc = (x); if (rc != PPS_OK) return rc; } while (0)
-  // every copy of the state is one block [poses | planes]: one transfer moves it (copies rotate by pointer pairs, so a
-  // plane array always sits behind its pose array)
-  const size_t state_doubles = (size_t)7 * d.pose_ld + (size_t)4 * d.plane_ld;
-  TRY(dev_alloc(g, &d.pose_est, state_doubles)); d.plane_est = d.pose_est + (size_t)7 * d.pose_ld;
-  TRY(dev_alloc(g, &d.pose_lin, state_doubles)); d.plane_lin = d.pose_lin + (size_t)7 * d.pose_ld;
-  std::vector<int> pv(d.n_pose), lv(d.n_plane);
-  for (int s = 0; s < d.n_pose; s++) pv[s] = A.node_voff[g->nodes[g->pose_ids[s]].compact];
-  for (int s = 0; s < d.n_plane; s++) lv[s] = A.node_voff[g->nodes[g->plane_ids[s]].compact];
-  TRY(dev_upload(g, &d.pose_voff, pv)); TRY(dev_upload(g, &d.plane_voff, lv));
-  // factors
-  d.n_obs = (int)g->fslot_ids[F_PLANE_OBS].size(); d.n_odo = (int)g->fslot_ids[F_ODOMETRY].size();
-  d.n_pp = (int)g->fslot_ids[F_POSE_PRIOR].size(); d.n_lp = (int)g->fslot_ids[F_PLANE_PRIOR].size();
-  { int64_t base[4]; j_bases(g, base, nullptr); d.joff_obs = base[F_PLANE_OBS]; d.joff_odo = base[F_ODOMETRY]; d.joff_pp = base[F_POSE_PRIOR]; d.joff_lp = base[F_PLANE_PRIOR]; }
-  auto idx_of = [&](int type, bool second) {
-    std::vector<int> v(g->fslot_ids[type].size());
-    for (size_t s = 0; s < v.size(); s++) {
-      const HostFactor& f = g->factors[g->fslot_ids[type][s]];
-      v[s] = g->nodes[second ? f.b : f.a].slot;
+  const double t0 = now_s();
+  double tl = t0;
+  // Refreshed measurements may stay on the device across an upload that only appends (see the obs_meas upload): same arena, same slot with
+  // room for the new rows, same leading dimension, no re-popping edges (their slots sit behind the fixed ones and would move).
+  bool keep_meas = false;
+  const size_t n_obs_on_device = (size_t)g->dev.n_obs;         // (reset() clears g->dev)
+  bool hints = false;                  // the mirror holds the arrays of the analysis this one was built upon: its kept parts are not compared again
+  Analysis::Kept K;
+  ZeroBlock Z{0, 0, 0};
+  double* zero_block = nullptr;
+
+  void lap(const char* what) { if (!g->sw.upload_timing) return; const double t = now_s(); g->up_laps[what] += t - tl; tl = t; }
+  size_t state_doubles() const { return (size_t)7 * g->dev.pose_ld + (size_t)4 * g->dev.plane_ld; }
+
+  // what only the device has: the estimate, and the refreshed measurements unless they can stay there
+  int bring_home() {
+    if (g->dev_values_newer) TRY(download_state(g));
+    lap("1a state download");
+    if (g->dev_meas_newer) {
+      // (live counts kept by the add / remove calls: a walk over the 300-byte factor records here was 30 us per frame at 7 600 factors)
+      keep_meas = g->grown_only_upload && !g->mirror.unknown && !g->mirror.unknown_meas && g->up.spill == 0 && g->n_live_repop == 0 && d.n_obs == d.n_obs_fixed &&
+                  j_capacity(g->n_live_type[F_PLANE_OBS]) == d.obs_ld && j_capacity(g->n_live_type[F_PLANE_PRIOR]) == d.lp_ld &&
+                  g->mirror.slot_of(&d.obs_meas) != UploadMirror::npos;
+      if (!keep_meas) {
+        if (g->sw.upload_timing) g->up_laps["(measurement downloads, count)"] += 1e-3;      // (printed as ms: the count)
+        TRY(download_measurements(g));
+      }
     }
-    return v;
-  };
-  std::vector<double> tmp;
-  // the previous upload's packed arrays are still right for the old factors when nothing was removed since (slots only append)
-  const bool incr_pack = was_grown_only;
-  d.obs_ld = (int)j_capacity(d.n_obs); d.odo_ld = (int)j_capacity(d.n_odo); d.pp_ld = (int)j_capacity(d.n_pp); d.lp_ld = (int)j_capacity(d.n_lp);
-  {
-    // one pass over the plane observations (a HostFactor is 300 bytes: four passes were four times the memory traffic), and
-    // only over the new ones when the graph has just grown
-    const std::vector<int>& ids = g->fslot_ids[F_PLANE_OBS];
-    const size_t n = ids.size(), ld = (size_t)d.obs_ld;
-    std::vector<int>& ia = g->pk_obs_a; std::vector<int>& ib = g->pk_obs_b;
-    std::vector<double>& pm = g->pk_obs_m; std::vector<double>& pw = g->pk_obs_w;
-    size_t s_begin = 0;
-    if (incr_pack && g->pk_ld_obs == ld && g->pk_n_obs <= n && pm.size() == 4 * ld && g->pk_obs_ids.size() == g->pk_n_obs &&
-        std::equal(g->pk_obs_ids.begin(), g->pk_obs_ids.end(), ids.begin())) s_begin = g->pk_n_obs;   // (re-popping edges sit behind the fixed ones: their slots move)
-    ia.resize(n); ib.resize(n); pm.resize(4 * ld); pw.resize(6 * ld);
-    for (size_t s2 = s_begin; s2 < n; s2++) {
-      const HostFactor& f = g->factors[ids[s2]];
-      ia[s2] = g->nodes[f.a].slot; ib[s2] = g->nodes[f.b].slot;
-      for (int k = 0; k < 4; k++) pm[(size_t)k * ld + s2] = f.meas[k];
-      for (int k = 0; k < 6; k++) pw[(size_t)k * ld + s2] = f.w[k];
-    }
-    if (s_begin > 0 && !g->pk_meas_ok)                                 // the host's measurements changed: those rows again
-      for (size_t s2 = 0; s2 < s_begin; s2++) { const HostFactor& f = g->factors[ids[s2]]; for (int k = 0; k < 4; k++) pm[(size_t)k * ld + s2] = f.meas[k]; }
-    g->pk_n_obs = n; g->pk_ld_obs = ld; g->pk_obs_ids.resize(s_begin); g->pk_obs_ids.insert(g->pk_obs_ids.end(), ids.begin() + (std::ptrdiff_t)s_begin, ids.end());
-    const size_t same_idx = hints ? s_begin : 0, same_meas = (hints && g->pk_meas_ok) ? s_begin : 0;       // (rows packed and sent by the previous upload)
-    TRY(dev_upload(g, &d.obs_pose, ia, same_idx)); TRY(dev_upload(g, &d.obs_plane, ib, same_idx));
+    lap("1b measurements");
+    return PPS_OK;
+  }
+  // the stream drained, the last layout given up, every pointer into it forgotten
+  int reset() {
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+    g->up_inflight = false;
+    lap("1c opening stream sync");
+    free_device(g);
+    g->spec_L = g->spec_U = g->spec_delta = nullptr; g->spec_result = nullptr;
+    g->spec_pose = g->spec_plane = g->spec_chi2_partials = g->spec_dn_partials = nullptr; g->spec_ticket = nullptr;
+    g->spec_J = g->spec_P = g->spec_H = g->spec_Hf = nullptr;
+    g->d_item_frame = g->d_item_plane = g->d_item_slot = g->d_frame_pose_slot = g->d_frame_seg_off = nullptr; g->d_fr_seg = nullptr;
+    g->frames_dirty = true;
+    g->snap_pose = g->snap_plane = nullptr; g->upload_version++;
+    lap("2 free_device");
+    hints = g->grown_only_upload && !g->mirror.unknown && g->up_an_seq >= 0 && g->an_base_seq == g->up_an_seq;
+    if (hints) K = g->an.kept;
+    return PPS_OK;
+  }
+  // One packed side, packed (pack_side; the previous upload's arrays are still right for the old factors when nothing was removed since: slots
+  // only append) and uploaded: [first index | second index | measurements | weights].  same: rows packed and sent by the previous upload
+  int put_side(pps_graph::PackedSide& S, int** da, int** db, double** dm, double** dw, size_t n, size_t ld, bool repack_meas, bool force_meas, size_t exact_from) {
+    const size_t s_begin = pack_side(g, S, ld, g->grown_only_upload, repack_meas);
+    const size_t same_idx = hints ? s_begin : 0, same_meas = (hints && g->pk_meas_ok) ? s_begin : 0;
+    TRY(dev_upload(g, da, S.a, same_idx)); TRY(dev_upload(g, db, S.b, same_idx));
+    TRY(dev_upload_rows(g, dm, S.m, (size_t)S.km, ld, n, force_meas, exact_from, same_meas));
+    return dev_upload_rows(g, dw, S.w, (size_t)S.kw, ld, n, false, kNoExact, same_idx);
+  }
+  // the state copies, the value offsets and the arrays of the four factor types
+  int factor_arrays() {
+    d.n_pose = (int)g->pose_ids.size(); d.n_plane = (int)g->plane_ids.size();
+    d.no_strip = g->sw.no_strip ? 1 : 0;
+    d.sw = g->sw.dev_bits();
+    HIP_TRY(g, step_constants(d.step_ac));
+    d.pose_ld = std::max(1, (d.n_pose + 63) / 64 * 64); d.plane_ld = std::max(1, (d.n_plane + 63) / 64 * 64);
+    // every copy of the state is one block [poses | planes]: one transfer moves it (copies rotate by pointer pairs, so a
+    // plane array always sits behind its pose array)
+    TRY(dev_alloc(g, &d.pose_est, state_doubles())); d.plane_est = d.pose_est + (size_t)7 * d.pose_ld;
+    TRY(dev_alloc(g, &d.pose_lin, state_doubles())); d.plane_lin = d.pose_lin + (size_t)7 * d.pose_ld;
+    std::vector<int> pv(d.n_pose), lv(d.n_plane);
+    for (int s = 0; s < d.n_pose; s++) pv[s] = A.node_voff[g->nodes[g->pose_ids[s]].compact];
+    for (int s = 0; s < d.n_plane; s++) lv[s] = A.node_voff[g->nodes[g->plane_ids[s]].compact];
+    TRY(dev_upload(g, &d.pose_voff, pv)); TRY(dev_upload(g, &d.plane_voff, lv));
+    d.n_obs = (int)g->fslot_ids[F_PLANE_OBS].size(); d.n_odo = (int)g->fslot_ids[F_ODOMETRY].size();
+    d.n_pp = (int)g->fslot_ids[F_POSE_PRIOR].size(); d.n_lp = (int)g->fslot_ids[F_PLANE_PRIOR].size();
+    { int64_t base[4]; j_bases(g, base, nullptr); d.joff_obs = base[F_PLANE_OBS]; d.joff_odo = base[F_ODOMETRY]; d.joff_pp = base[F_POSE_PRIOR]; d.joff_lp = base[F_PLANE_PRIOR]; }
+    auto idx_of = [&](int type) {
+      std::vector<int> v(g->fslot_ids[type].size());
+      for (size_t s = 0; s < v.size(); s++) v[s] = g->nodes[g->factors[g->fslot_ids[type][s]].a].slot;
+      return v;
+    };
+    std::vector<double> tmp;
+    d.obs_ld = (int)j_capacity(d.n_obs); d.odo_ld = (int)j_capacity(d.n_odo); d.pp_ld = (int)j_capacity(d.n_pp); d.lp_ld = (int)j_capacity(d.n_lp);
+    UploadMirror& m = g->mirror;
     // Measurements that a device-side refresh has rewritten (pps_refresh_measurements) stay where they are when this upload
     // only appends: the host packs its (older) copies, the mirror holds the same bytes, so nothing is sent for them and the
     // device keeps the refreshed values; only the new observations travel.  dev_meas_newer stays set.
-    g->slot_obs_meas = g->up_cursor;
-    TRY(dev_upload_rows(g, &d.obs_meas, pm, 4, ld, n, g->up_unknown_meas, keep_meas ? std::min(n, n_obs_on_device) : kNoExact, same_meas));
-    TRY(dev_upload_rows(g, &d.obs_w, pw, 6, ld, n, false, kNoExact, same_idx));
-  }
-  d.n_obs_fixed = g->n_obs_fixed;
-  {
-    const std::vector<int>& ids = g->fslot_ids[F_PLANE_OBS];
-    const size_t n2 = ids.size() - (size_t)g->n_obs_fixed;
-    if (n2 > 0) {
+    TRY(put_side(g->pk_obs, &d.obs_pose, &d.obs_plane, &d.obs_meas, &d.obs_w, (size_t)d.n_obs, (size_t)d.obs_ld, !g->pk_meas_ok, m.unknown_meas,
+                 keep_meas ? std::min((size_t)d.n_obs, n_obs_on_device) : kNoExact));
+    d.n_obs_fixed = g->n_obs_fixed;
+    if (const size_t n2 = (size_t)(d.n_obs - d.n_obs_fixed)) {      // the re-popping observations' rays
       tmp.assign(6 * n2, 0.0);
       for (size_t k = 0; k < n2; k++)
-        for (int c = 0; c < 6; c++) tmp[(size_t)c * n2 + k] = g->factors[ids[g->n_obs_fixed + k]].ray[c];
+        for (int c = 0; c < 6; c++) tmp[(size_t)c * n2 + k] = g->factors[g->fslot_ids[F_PLANE_OBS][d.n_obs_fixed + k]].ray[c];
       TRY(dev_upload(g, &d.obs_ray, tmp));
     }
+    TRY(put_side(g->pk_odo, &d.odo_a, &d.odo_b, &d.odo_meas, &d.odo_w, (size_t)d.n_odo, (size_t)d.odo_ld, false, false, kNoExact));      // (only the observations re-pack old measurement rows)
+    TRY(dev_upload(g, &d.pp_pose, idx_of(F_POSE_PRIOR)));
+    pack_soa<6>(g, F_POSE_PRIOR, false, tmp, (size_t)d.pp_ld); TRY(dev_upload_rows(g, &d.pp_meas, tmp, 6, (size_t)d.pp_ld, (size_t)d.n_pp, false));
+    pack_soa<21>(g, F_POSE_PRIOR, true, tmp, (size_t)d.pp_ld); TRY(dev_upload_rows(g, &d.pp_w, tmp, 21, (size_t)d.pp_ld, (size_t)d.n_pp, false));
+    TRY(dev_upload(g, &d.lp_plane, idx_of(F_PLANE_PRIOR)));
+    pack_soa<4>(g, F_PLANE_PRIOR, false, tmp, (size_t)d.lp_ld); TRY(dev_upload_rows(g, &d.lp_meas, tmp, 4, (size_t)d.lp_ld, (size_t)d.n_lp, m.unknown_meas));
+    pack_soa<6>(g, F_PLANE_PRIOR, true, tmp, (size_t)d.lp_ld); TRY(dev_upload_rows(g, &d.lp_w, tmp, 6, (size_t)d.lp_ld, (size_t)d.n_lp, false));
+    m.unknown_meas = false;
+    g->pk_meas_ok = true;
+    lap("4 factor packing + diff");
+    return PPS_OK;
   }
-  {
-    const std::vector<int>& ids = g->fslot_ids[F_ODOMETRY];
-    const size_t n = ids.size(), ld = (size_t)d.odo_ld;
-    std::vector<int>& ia = g->pk_odo_a; std::vector<int>& ib = g->pk_odo_b;
-    std::vector<double>& pm = g->pk_odo_m; std::vector<double>& pw = g->pk_odo_w;
-    size_t s_begin = 0;
-    if (incr_pack && g->pk_ld_odo == ld && g->pk_n_odo <= n && pm.size() == 6 * ld && g->pk_odo_ids.size() == g->pk_n_odo &&
-        std::equal(g->pk_odo_ids.begin(), g->pk_odo_ids.end(), ids.begin())) s_begin = g->pk_n_odo;
-    ia.resize(n); ib.resize(n); pm.resize(6 * ld); pw.resize(21 * ld);
-    for (size_t s2 = s_begin; s2 < n; s2++) {
-      const HostFactor& f = g->factors[ids[s2]];
-      ia[s2] = g->nodes[f.a].slot; ib[s2] = g->nodes[f.b].slot;
-      for (int k = 0; k < 6; k++) pm[(size_t)k * ld + s2] = f.meas[k];
-      for (int k = 0; k < 21; k++) pw[(size_t)k * ld + s2] = f.w[k];
+  // the linear system's storage, the analysis' index arrays, the scratch of the solves
+  int index_arrays() {
+    const size_t kF = (size_t)K.fronts, kFl = (size_t)K.fronts_lists, kB = (size_t)K.blocks, kS = (size_t)K.segs;
+    // (the device array of the analysis array of the same name)
+#define UPA(name, same) TRY(dev_upload(g, &d.name, A.name, same))
+    auto at = [](const auto& v, size_t i) -> size_t { return i < v.size() ? (size_t)v[i] : 0; };     // (0 = no claim)
+    TRY(dev_alloc(g, &d.J, (size_t)A.J_size)); TRY(dev_alloc(g, &d.H, (size_t)A.H_size));
+    TRY(dev_alloc(g, &d.P, (size_t)std::max<int64_t>(1, A.P_size)));
+    { int64_t pb[4]; p_bases(g, pb, nullptr); d.poff_obs = pb[F_PLANE_OBS]; }
+    TRY(dev_alloc(g, &d.L, (size_t)A.L_size)); TRY(dev_alloc(g, &d.U, (size_t)A.U_size));
+    TRY(dev_alloc(g, &g->spec_L, (size_t)A.L_size)); TRY(dev_alloc(g, &g->spec_U, (size_t)A.U_size));
+    d.n_scalars = A.n_scalars;
+    d.n_fronts = A.n_fronts; d.n_levels = A.n_levels; d.max_front = A.max_front; d.n_segs = A.n_segs; d.n_blocks = A.n_blocks;
+    UPA(f_p, kF); UPA(f_b, kF); UPA(f_poff, kF); UPA(pidx, kF ? at(A.f_poff, kF) : 0); UPA(f_Loff, kF); UPA(f_Uoff, kF);
+    UPA(f_bidx_off, kF ? kF + 1 : 0); UPA(bidx, kF ? at(A.f_bidx_off, kF) : 0); UPA(f_child_off, kF ? kF + 1 : 0); UPA(child, kF ? at(A.f_child_off, kF) : 0);
+    UPA(f_cmap_off, kF ? kF + 1 : 0); UPA(cmap, 0); UPA(level_fronts, 0);      // (cmap: kept fronts below a redone parent are rewritten)
+    const size_t kA = kFl ? at(A.f_asm_off, kFl) : 0;
+    UPA(f_asm_off, kFl ? kFl + 1 : 0); UPA(asm_blk, kA); UPA(asm_lrow, kA); UPA(asm_lcol, kA);
+    UPA(blk_rows, kB); UPA(blk_cols, kB); UPA(blk_size, kB); UPA(blk_nseg, kB); UPA(blk_hoff, kB);
+    UPA(seg_blk, kS); UPA(seg_c0, kS); UPA(seg_cnt, kS); UPA(seg_hoff, kS); UPA(contrib, 4 * (size_t)K.contribs);
+    {
+      std::vector<int> mseg;
+      for (int bk = 0; bk < A.n_blocks; bk++) if (A.blk_nseg[bk] > 1) mseg.push_back(bk);
+      d.n_mseg = (int)mseg.size();
+      TRY(dev_upload(g, &d.mseg_blk, mseg));
+      // K2's two work lists: segments of single-segment blocks that K1 does not write itself; first segment of every other block
+      std::vector<int> k2s, k2m, k2f;
+      for (int sg : A.nd_segs) if (A.blk_nseg[A.seg_blk[sg]] == 1) k2s.push_back(sg);
+      for (int sg = 0; sg < A.n_segs; sg++) {
+        const int ns = A.blk_nseg[A.seg_blk[sg]];
+        if (ns <= 1 || (sg > 0 && A.seg_blk[sg - 1] == A.seg_blk[sg])) continue;      // (first segment of a block of several)
+        for (int c0 = 0; c0 < ns; c0 += 16) { k2m.push_back(sg + c0); k2m.push_back(std::min(16, ns - c0) | (ns <= 16 ? 1 << 16 : 0)); }
+        if (ns > 16) k2f.push_back(sg);
+      }
+      d.n_k2_single = (int)k2s.size(); d.n_k2_multi = (int)k2m.size() / 2; d.n_k2_finish = (int)k2f.size();
+      TRY(dev_upload(g, &d.k2_single, k2s)); TRY(dev_upload(g, &d.k2_multi, k2m)); TRY(dev_upload(g, &d.k2_finish, k2f));
     }
-    g->pk_n_odo = n; g->pk_ld_odo = ld; g->pk_odo_ids.resize(s_begin); g->pk_odo_ids.insert(g->pk_odo_ids.end(), ids.begin() + (std::ptrdiff_t)s_begin, ids.end());
-    const size_t same_idx = hints ? s_begin : 0;
-    TRY(dev_upload(g, &d.odo_a, ia, same_idx)); TRY(dev_upload(g, &d.odo_b, ib, same_idx));
-    TRY(dev_upload_rows(g, &d.odo_meas, pm, 6, ld, n, false, kNoExact, (hints && g->pk_meas_ok) ? s_begin : 0));
-    TRY(dev_upload_rows(g, &d.odo_w, pw, 21, ld, n, false, kNoExact, same_idx));
-  }
-  TRY(dev_upload(g, &d.pp_pose, idx_of(F_POSE_PRIOR, false)));
-  pack_soa<6>(g, F_POSE_PRIOR, nullptr, false, tmp, (size_t)d.pp_ld); TRY(dev_upload_rows(g, &d.pp_meas, tmp, 6, (size_t)d.pp_ld, (size_t)d.n_pp, false));
-  pack_soa<21>(g, F_POSE_PRIOR, nullptr, true, tmp, (size_t)d.pp_ld); TRY(dev_upload_rows(g, &d.pp_w, tmp, 21, (size_t)d.pp_ld, (size_t)d.n_pp, false));
-  TRY(dev_upload(g, &d.lp_plane, idx_of(F_PLANE_PRIOR, false)));
-  pack_soa<4>(g, F_PLANE_PRIOR, nullptr, false, tmp, (size_t)d.lp_ld); g->slot_lp_meas = g->up_cursor; TRY(dev_upload_rows(g, &d.lp_meas, tmp, 4, (size_t)d.lp_ld, (size_t)d.n_lp, g->up_unknown_meas));
-  pack_soa<6>(g, F_PLANE_PRIOR, nullptr, true, tmp, (size_t)d.lp_ld); TRY(dev_upload_rows(g, &d.lp_w, tmp, 6, (size_t)d.lp_ld, (size_t)d.n_lp, false));
-  g->up_unknown_meas = false;
-  g->pk_meas_ok = true;
-  lap("4 factor packing + diff");
-  // linear system storage
-  TRY(dev_alloc(g, &d.J, (size_t)A.J_size)); TRY(dev_alloc(g, &d.H, (size_t)A.H_size));
-  TRY(dev_alloc(g, &d.P, (size_t)std::max<int64_t>(1, A.P_size)));
-  { int64_t pb[4]; p_bases(g, pb, nullptr); d.poff_obs = pb[F_PLANE_OBS]; }
-  TRY(dev_alloc(g, &d.L, (size_t)A.L_size)); TRY(dev_alloc(g, &d.U, (size_t)A.U_size));
-  TRY(dev_alloc(g, &g->spec_L, (size_t)A.L_size)); TRY(dev_alloc(g, &g->spec_U, (size_t)A.U_size));
-  const size_t delta_doubles = (size_t)std::max(1, A.n_scalars);   // (delta and the second delta sit in the zeroed block below)
-  d.n_scalars = A.n_scalars;
-  d.n_fronts = A.n_fronts; d.n_levels = A.n_levels; d.max_front = A.max_front; d.n_segs = A.n_segs; d.n_blocks = A.n_blocks;
-  TRY(dev_upload(g, &d.f_p, A.f_p, kF)); TRY(dev_upload(g, &d.f_b, A.f_b, kF)); TRY(dev_upload(g, &d.f_poff, A.f_poff, kF)); TRY(dev_upload(g, &d.pidx, A.pidx, kF ? at(A.f_poff, kF) : 0));
-  TRY(dev_upload(g, &d.f_Loff, A.f_Loff, kF)); TRY(dev_upload(g, &d.f_Uoff, A.f_Uoff, kF));
-  TRY(dev_upload(g, &d.f_bidx_off, A.f_bidx_off, kF ? kF + 1 : 0)); TRY(dev_upload(g, &d.bidx, A.bidx, kF ? at(A.f_bidx_off, kF) : 0));
-  TRY(dev_upload(g, &d.f_child_off, A.f_child_off, kF ? kF + 1 : 0)); TRY(dev_upload(g, &d.child, A.child, kF ? at(A.f_child_off, kF) : 0));
-  TRY(dev_upload(g, &d.f_cmap_off, A.f_cmap_off, kF ? kF + 1 : 0)); TRY(dev_upload(g, &d.cmap, A.cmap));      // (cmap: kept fronts below a redone parent are rewritten)
-  TRY(dev_upload(g, &d.level_fronts, A.level_fronts));
-  const size_t kA = kFl ? at(A.f_asm_off, kFl) : 0;
-  TRY(dev_upload(g, &d.f_asm_off, A.f_asm_off, kFl ? kFl + 1 : 0)); TRY(dev_upload(g, &d.asm_blk, A.asm_blk, kA));
-  TRY(dev_upload(g, &d.asm_lrow, A.asm_lrow, kA)); TRY(dev_upload(g, &d.asm_lcol, A.asm_lcol, kA));
-  TRY(dev_upload(g, &d.blk_rows, A.blk_rows, kB)); TRY(dev_upload(g, &d.blk_cols, A.blk_cols, kB));
-  TRY(dev_upload(g, &d.blk_size, A.blk_size, kB)); TRY(dev_upload(g, &d.blk_nseg, A.blk_nseg, kB));
-  TRY(dev_upload(g, &d.blk_hoff, A.blk_hoff, kB));
-  TRY(dev_upload(g, &d.seg_blk, A.seg_blk, kS)); TRY(dev_upload(g, &d.seg_c0, A.seg_c0, kS)); TRY(dev_upload(g, &d.seg_cnt, A.seg_cnt, kS));
-  TRY(dev_upload(g, &d.seg_hoff, A.seg_hoff, kS));
-  TRY(dev_upload(g, &d.contrib, A.contrib, 4 * (size_t)K.contribs));
-  {
-    std::vector<int> mseg;
-    for (int bk = 0; bk < A.n_blocks; bk++) if (A.blk_nseg[bk] > 1) mseg.push_back(bk);
-    d.n_mseg = (int)mseg.size();
-    TRY(dev_upload(g, &d.mseg_blk, mseg));
-    // K2's two work lists: segments of single-segment blocks that K1 does not write itself; first segment of every other block
-    std::vector<int> k2s, k2m, k2f;
-    for (int sg : A.nd_segs) if (A.blk_nseg[A.seg_blk[sg]] == 1) k2s.push_back(sg);
-    for (int sg = 0; sg < A.n_segs; sg++) {
-      const int ns = A.blk_nseg[A.seg_blk[sg]];
-      if (ns <= 1 || (sg > 0 && A.seg_blk[sg - 1] == A.seg_blk[sg])) continue;      // (first segment of a block of several)
-      for (int c0 = 0; c0 < ns; c0 += 16) { k2m.push_back(sg + c0); k2m.push_back(std::min(16, ns - c0) | (ns <= 16 ? 1 << 16 : 0)); }
-      if (ns > 16) k2f.push_back(sg);
+    UPA(f_el_off, kFl ? kFl + 1 : 0); TRY(dev_alloc(g, &d.el_tgt, (size_t)std::max<int64_t>(1, A.el_total)));   // filled by k_expand_el (expand)
+    UPA(asm_el0, kA); UPA(asm_fsz, kA);
+    UPA(f_ea_off, kF ? kF + 1 : 0); TRY(dev_alloc(g, &d.ea_tgt, (size_t)std::max<int64_t>(1, A.ea_total)));   // filled by k_expand_ea (expand)
+    UPA(blk_doff, kB ? kB + 1 : 0); TRY(dev_alloc(g, &d.blk_dst, (size_t)std::max(1, A.blk_doff[A.n_blocks])));
+    TRY(dev_alloc(g, &d.Hf, (size_t)A.el_total));
+    if (g->use_band() && !g->sw.no_spec_lin) {                        // the spare set of the fused trial + linearisation launch (lm_solve_dual)
+      TRY(dev_alloc(g, &g->spec_J, (size_t)A.J_size)); TRY(dev_alloc(g, &g->spec_P, (size_t)std::max<int64_t>(1, A.P_size)));
+      TRY(dev_alloc(g, &g->spec_H, (size_t)A.H_size)); TRY(dev_alloc(g, &g->spec_Hf, (size_t)A.el_total));
     }
-    d.n_k2_single = (int)k2s.size(); d.n_k2_multi = (int)k2m.size() / 2; d.n_k2_finish = (int)k2f.size();
-    TRY(dev_upload(g, &d.k2_single, k2s)); TRY(dev_upload(g, &d.k2_multi, k2m)); TRY(dev_upload(g, &d.k2_finish, k2f));
-  }
-  TRY(dev_upload(g, &d.f_el_off, A.f_el_off, kFl ? kFl + 1 : 0)); TRY(dev_alloc(g, &d.el_tgt, (size_t)std::max<int64_t>(1, A.el_total)));   // filled by k_expand_el below
-  TRY(dev_upload(g, &d.asm_el0, A.asm_el0, kA)); TRY(dev_upload(g, &d.asm_fsz, A.asm_fsz, kA));
-  TRY(dev_upload(g, &d.f_ea_off, A.f_ea_off, kF ? kF + 1 : 0)); TRY(dev_alloc(g, &d.ea_tgt, (size_t)std::max<int64_t>(1, A.ea_total)));   // filled by k_expand_ea below
-  TRY(dev_upload(g, &d.blk_doff, A.blk_doff, kB ? kB + 1 : 0)); TRY(dev_alloc(g, &d.blk_dst, (size_t)std::max(1, A.blk_doff[A.n_blocks])));
-  TRY(dev_alloc(g, &d.Hf, (size_t)A.el_total));
-  if (g->use_band() && !g->sw.no_spec_lin) {                        // the spare set of the fused trial + linearisation launch (lm_solve_dual)
-    TRY(dev_alloc(g, &g->spec_J, (size_t)A.J_size)); TRY(dev_alloc(g, &g->spec_P, (size_t)std::max<int64_t>(1, A.P_size)));
-    TRY(dev_alloc(g, &g->spec_H, (size_t)A.H_size)); TRY(dev_alloc(g, &g->spec_Hf, (size_t)A.el_total));
-  }
-  TRY(dev_upload(g, &d.grp_lvl_off, A.grp_lvl_off)); TRY(dev_upload(g, &d.glvl_front_off, A.glvl_front_off));
-  {
-    // per group, one 32-byte record: first position, fronts, local levels, first position of local levels 1 .. 4 (the last one
-    // repeated), 0 -- what the band kernels would otherwise fetch with two dependent look-ups (levels of the group, their offsets)
-    std::vector<int> span(8 * (size_t)std::max(1, A.n_groups), 0);
-    for (int gi = 0; gi < A.n_groups; gi++) {
-      const int l0 = A.grp_lvl_off[gi], nl = A.grp_lvl_off[gi + 1] - l0;
-      int* r = &span[8 * (size_t)gi];
-      r[0] = A.glvl_front_off[l0]; r[1] = A.glvl_front_off[l0 + nl] - r[0]; r[2] = nl;
-      for (int k = 1; k <= 4; k++) r[2 + k] = A.glvl_front_off[l0 + std::min(k, nl)];
+    UPA(grp_lvl_off, 0); UPA(glvl_front_off, 0);
+    {
+      // per group, one 32-byte record: first position, fronts, local levels, first position of local levels 1 .. 4 (the last one
+      // repeated), 0 -- what the band kernels would otherwise fetch with two dependent look-ups (levels of the group, their offsets)
+      std::vector<int> span(8 * (size_t)std::max(1, A.n_groups), 0);
+      for (int gi = 0; gi < A.n_groups; gi++) {
+        const int l0 = A.grp_lvl_off[gi], nl = A.grp_lvl_off[gi + 1] - l0;
+        int* r = &span[8 * (size_t)gi];
+        r[0] = A.glvl_front_off[l0]; r[1] = A.glvl_front_off[l0 + nl] - r[0]; r[2] = nl;
+        for (int k = 1; k <= 4; k++) r[2 + k] = A.glvl_front_off[l0 + std::min(k, nl)];
+      }
+      TRY(dev_upload(g, &d.grp_span, span));
     }
-    TRY(dev_upload(g, &d.grp_span, span));
-  }
-  TRY(dev_upload(g, &d.glvl_fronts, A.glvl_fronts));
-  TRY(dev_upload(g, &d.frec, A.frec)); TRY(dev_upload(g, &d.crec, A.crec)); TRY(dev_upload(g, &d.srec, A.srec, 8 * kS));
-  TRY(dev_upload(g, &d.obs_dir, A.obs_dir)); TRY(dev_upload(g, &d.nd_segs, A.nd_segs, (size_t)K.nd_segs)); d.n_nd_segs = (int)A.nd_segs.size();
-  TRY(dev_upload(g, &d.cls_off, A.cls_off)); TRY(dev_upload(g, &d.cls_fronts, A.cls_fronts));
-  if (g->use_dense()) { TRY(dev_upload(g, &g->d_dw_asm, g->plan.dw_asm)); TRY(dev_upload(g, &g->d_dw_pan, g->plan.dw_pan)); TRY(dev_upload(g, &g->d_dw_trl, g->plan.dw_trl)); }
-  d.chi2_blocks = (d.n_obs + 255) / 256 + (d.n_odo + 255) / 256 + (d.n_pp + 255) / 256 + (d.n_lp + 255) / 256;
-  TRY(dev_alloc(g, &d.chi2_partials, (size_t)std::max(1, d.chi2_blocks)));
+    UPA(glvl_fronts, 0); UPA(frec, 0); UPA(crec, 0); UPA(srec, 8 * kS);
+    UPA(obs_dir, 0); UPA(nd_segs, (size_t)K.nd_segs); d.n_nd_segs = (int)A.nd_segs.size();
+    UPA(cls_off, 0); UPA(cls_fronts, 0);
+    if (g->use_dense()) { TRY(dev_upload(g, &g->d_dw_asm, g->plan.dw_asm)); TRY(dev_upload(g, &g->d_dw_pan, g->plan.dw_pan)); TRY(dev_upload(g, &g->d_dw_trl, g->plan.dw_trl)); }
+    d.chi2_blocks = (d.n_obs + 255) / 256 + (d.n_odo + 255) / 256 + (d.n_pp + 255) / 256 + (d.n_lp + 255) / 256;
+    TRY(dev_alloc(g, &d.chi2_partials, (size_t)std::max(1, d.chi2_blocks)));
 
-  {
-    // one zeroed block: [dn_partials | ticket | spec ticket | result record | the second factorisation's result record |
-    // delta | the second delta | the hand-over flags of the whole-tree launches: 4 ints per front]
-    const size_t n_dn = (size_t)(d.n_pose + d.n_plane + 255) / 256 + 1;
-    const size_t flag_doubles = 2 * (size_t)std::max(1, A.n_fronts) + 1;
-    double* zb = nullptr;
-    TRY(dev_alloc(g, &zb, n_dn + 2 + 8 + 2 * delta_doubles + flag_doubles));
-    zero_block = zb; zero_doubles = n_dn + 2 + 8 + 2 * delta_doubles + flag_doubles;     // (cleared by k_expand_ea below, or by a memset when that launch has nothing to expand)
-    d.k3_flag = reinterpret_cast<int*>(zb + n_dn + 2 + 8 + 2 * delta_doubles);
+    Z = ZeroBlock(d.n_pose + d.n_plane, A.n_scalars, A.n_fronts);
+    TRY(dev_alloc(g, &zero_block, Z.total));
+    double* const zb = zero_block;
+    d.dn_partials = zb + Z.dn_partials;
+    d.ticket = reinterpret_cast<unsigned int*>(zb + Z.ticket); g->spec_ticket = reinterpret_cast<unsigned int*>(zb + Z.spec_ticket);
+    d.result_dev = zb + Z.result; g->spec_result = zb + Z.spec_result;
+    d.delta = zb + Z.delta; g->spec_delta = zb + Z.spec_delta;
+    d.k3_flag = reinterpret_cast<int*>(zb + Z.flags);
     g->k3_epoch = 0;
-    d.delta = zb + n_dn + 10; g->spec_delta = d.delta + delta_doubles;
-    d.dn_partials = zb;
-    d.ticket = reinterpret_cast<unsigned int*>(zb + n_dn);
-    g->spec_ticket = reinterpret_cast<unsigned int*>(zb + n_dn + 1);
-    d.result_dev = zb + n_dn + 2; g->spec_result = zb + n_dn + 6;
     g->status_clean = true;
-  }
-  // the local solutions that cross a band group in the whole-tree back-substitution (XGroup::hand, pps_k3.hip): every value is written in the
-  // launch that reads it, behind its flag -- not zeroed
-  if (g->plan.form == K3Form::BandAll) TRY(dev_alloc(g, &d.k3_xhand, 2 * (size_t)A.n_fronts * kBandMaxRows));
-  TRY(dev_alloc(g, &g->spec_pose, state_doubles + 1)); g->spec_plane = g->spec_pose + (size_t)7 * d.pose_ld;
-  TRY(dev_alloc(g, &g->spec_chi2_partials, (size_t)std::max(1, d.chi2_blocks)));
-  TRY(dev_alloc(g, &g->spec_dn_partials, (size_t)(d.n_pose + d.n_plane + 255) / 256 + 1));
-  d.trace_solve = g->sw.trace >= 2 ? 1 : 0;
-  if (g->sw.trace) { TRY(dev_alloc(g, &d.trace, (size_t)A.n_fronts * 8)); HIP_TRY(g, hipMemset(d.trace, 0, (size_t)A.n_fronts * 64)); }
-  // fronts that exceed the LDS limit run from a global workspace (one slab per front of the widest level)
-  if (!g->use_band() && !g->use_dense() && A.max_front > lds_front_limit()) {
-    const int fa = A.max_front + 1;
-    d.gwork_stride = (int64_t)fa * (fa | 1);
-    int widest = 0;
-    for (int l = 0; l < A.n_levels; l++)
-      if (g->plan.level_max_front[l] > lds_front_limit()) widest = std::max(widest, A.level_off[l + 1] - A.level_off[l]);
-    TRY(dev_alloc(g, &d.gwork, (size_t)d.gwork_stride * std::max(1, widest)));
-  }
-#undef TRY
-  lap("5 index arrays + diff");
-  rc = flush_uploads(g); if (rc != PPS_OK) return rc;
-  rc = verify_uploads(g, "upload_all"); if (rc != PPS_OK) return rc;
-  rc = verify_packed(g, keep_meas ? n_obs_on_device : 0); if (rc != PPS_OK) return rc;
-  lap("6 flush");
-  // one launch for both expansions when every H block is assembled by exactly one front (always, unless an analysis ever lists a block
-  // twice or not at all: then the fill of blk_dst has to run first, in a launch of its own)
-  const bool one_launch = A.ea_total > 0 && zero_doubles < (size_t)1 << 30 && (int)A.asm_blk.size() == A.n_blocks && A.n_fronts > 0 &&
-                          !g->sw.split_expand;
-  if (one_launch) HIP_TRY(g, launch_expand_lists(d, A.n_fronts, (int)A.asm_blk.size(), zero_block, zero_doubles, g->stream));
-  else {
-    const size_t n_dst = (size_t)std::max(1, A.blk_doff[A.n_blocks]);
-    if (A.ea_total > 0 && zero_doubles < (size_t)1 << 30 && n_dst < (size_t)1 << 30)
-      HIP_TRY(g, launch_expand_ea(d, A.n_fronts, zero_block, zero_doubles, d.blk_dst, n_dst, g->stream));
-    else {
-      if (A.ea_total > 0) HIP_TRY(g, launch_expand_ea(d, A.n_fronts, nullptr, 0, nullptr, 0, g->stream));
-      HIP_TRY(g, hipMemsetAsync(zero_block, 0, zero_doubles * 8, g->stream));
-      HIP_TRY(g, hipMemsetAsync(d.blk_dst, 0xff, sizeof(int) * n_dst, g->stream));
+    // the local solutions that cross a band group in the whole-tree back-substitution (XGroup::hand, pps_k3.hip): every value is written in the
+    // launch that reads it, behind its flag -- not zeroed
+    if (g->plan.form == K3Form::BandAll) TRY(dev_alloc(g, &d.k3_xhand, 2 * (size_t)A.n_fronts * kBandMaxRows));
+    TRY(dev_alloc(g, &g->spec_pose, state_doubles() + 1)); g->spec_plane = g->spec_pose + (size_t)7 * d.pose_ld;
+    TRY(dev_alloc(g, &g->spec_chi2_partials, (size_t)std::max(1, d.chi2_blocks)));
+    TRY(dev_alloc(g, &g->spec_dn_partials, Z.n_dn));
+    d.trace_solve = g->sw.trace >= 2 ? 1 : 0;
+    if (g->sw.trace) { TRY(dev_alloc(g, &d.trace, (size_t)A.n_fronts * 8)); HIP_TRY(g, hipMemset(d.trace, 0, (size_t)A.n_fronts * 64)); }
+    // fronts that exceed the LDS limit run from a global workspace (one slab per front of the widest level)
+    if (!g->use_band() && !g->use_dense() && A.max_front > lds_front_limit()) {
+      const int fa = A.max_front + 1;
+      d.gwork_stride = (int64_t)fa * (fa | 1);
+      int widest = 0;
+      for (int l = 0; l < A.n_levels; l++)
+        if (g->plan.level_max_front[l] > lds_front_limit()) widest = std::max(widest, A.level_off[l + 1] - A.level_off[l]);
+      TRY(dev_alloc(g, &d.gwork, (size_t)d.gwork_stride * std::max(1, widest)));
     }
-    HIP_TRY(g, launch_expand_el(d, (int)A.asm_blk.size(), g->stream));
+#undef UPA
+    lap("5 index arrays + diff");
+    return PPS_OK;
   }
-  rc = verify_expanded(g, zero_block, zero_doubles); if (rc != PPS_OK) return rc;
-  g->topo_dirty = false;
-  g->meas_dirty = false;
-  g->grown_only_upload = true;
-  g->up_an_seq = g->an_seq;
-  lap("7 expand kernels + sync");
+  int flush_and_verify() {
+    TRY(flush_uploads(g));
+    TRY(verify_uploads(g, "upload_all"));
+    TRY(verify_packed(g, keep_meas ? n_obs_on_device : 0));
+    lap("6 flush");
+    return PPS_OK;
+  }
+  // ea_tgt, el_tgt and blk_dst filled on the device, the zeroed block cleared
+  int expand() {
+    // one launch for both expansions when every H block is assembled by exactly one front (always, unless an analysis ever lists a block
+    // twice or not at all: then the fill of blk_dst has to run first, in a launch of its own)
+    const bool one_launch = A.ea_total > 0 && Z.total < (size_t)1 << 30 && (int)A.asm_blk.size() == A.n_blocks && A.n_fronts > 0 &&
+                            !g->sw.split_expand;
+    if (one_launch) HIP_TRY(g, launch_expand_lists(d, A.n_fronts, (int)A.asm_blk.size(), zero_block, Z.total, g->stream));
+    else {
+      const size_t n_dst = (size_t)std::max(1, A.blk_doff[A.n_blocks]);
+      if (A.ea_total > 0 && Z.total < (size_t)1 << 30 && n_dst < (size_t)1 << 30)
+        HIP_TRY(g, launch_expand_ea(d, A.n_fronts, zero_block, Z.total, d.blk_dst, n_dst, g->stream));
+      else {
+        if (A.ea_total > 0) HIP_TRY(g, launch_expand_ea(d, A.n_fronts, nullptr, 0, nullptr, 0, g->stream));
+        HIP_TRY(g, hipMemsetAsync(zero_block, 0, Z.total * 8, g->stream));
+        HIP_TRY(g, hipMemsetAsync(d.blk_dst, 0xff, sizeof(int) * n_dst, g->stream));
+      }
+      HIP_TRY(g, launch_expand_el(d, (int)A.asm_blk.size(), g->stream));
+    }
+    TRY(verify_expanded(g, zero_block, Z));
+    g->topo_dirty = false;
+    g->meas_dirty = false;
+    g->grown_only_upload = true;
+    g->up_an_seq = g->an_seq;
+    lap("7 expand kernels + sync");
+    return PPS_OK;
+  }
+};
+
+int upload_all(pps_graph* g) {
+  UploadPass P{g};
+  g->mirror.verify_hints = g->sw.verify_upload;
+  TRY(ensure_device(g));
+  P.lap("0 ensure_device");
+  TRY(P.bring_home());
+  // the analysis is host work on host tables: it runs while the device finishes what the last frame left on the stream (the measurement
+  // refresh of a frame loop: the opening sync of reset() waited 10 us per frame for it)
+  if (!g->analyzed || g->analysis_stale) TRY(run_analysis(g));
+  P.lap("3 analysis");
+  TRY(P.reset());
+  TRY(P.factor_arrays());
+  TRY(P.index_arrays());
+  TRY(P.flush_and_verify());
+  TRY(P.expand());
   // no sync: the solve that follows runs on the same stream (and ends with one); whatever writes the pinned buffers
   // again checks up_inflight or follows upload_all's opening sync
-  rc = upload_state(g, false);
-  lap("8 upload_state");
-  g->stats.t_upload = now_s() - t0 - g->stats.t_analysis;
+  const int rc = upload_state(g, false);
+  P.lap("8 upload_state");
+  g->stats.t_upload = now_s() - P.t0 - g->stats.t_analysis;
   return rc;
 }
 
@@ -861,4 +811,5 @@ int prepare_solve(pps_graph* g) {
   return PPS_OK;
 }
 
+#undef TRY
 }  // namespace pps_impl

@@ -91,7 +91,7 @@ def c5(n):
         lm += max(pl.process(fr), 0)
     pipeline.gpu_pipeline_finish(pp, st5)
     e = time.perf_counter() - t1
-    out = {"frames": n, "frames_per_s": n / e, "lm_iterations": lm, "chi2": g.chi2(), "popup_us": 1e6 * st5["popup_kernel_s"] / n}
+    out = {"frames": n, "frames_per_s": n / e, "lm_iterations": lm, "chi2": g.chi2(), "trace": trace_hash(g), "popup_us": 1e6 * st5["popup_kernel_s"] / n}
     g.close(); pp.close()
     return out
 
