@@ -833,6 +833,69 @@ int pps_map_download(pps_map* m, int which, int64_t first, int64_t n, pps_point*
 /* device seconds (HIP events): sec[0] the kernels of the last pps_map_add_frame, sec[1] the kernel of the last pps_map_build */
 int pps_map_last_times(const pps_map* m, double sec[2]);
 
+/* ---- grid map: one point per cell of every landmark plane ----------------------------------------------------------
+ * pps_map_build writes every kept point of every selected chunk: the map grows with the length of the run although the walls do not.
+ * A landmark is a plane, so its points live on a 2-D lattice in that plane; pps_map_build_grid keeps ONE point per lattice cell.
+ *
+ * Let B be the map pps_map_build(m, sel, ..) would write at the current estimate.  The grid map is a subset of B's records, bit for bit.
+ *   taking part   the points of B whose chunk belongs to a live plane node.  Points of a landmark that was removed and not redirected
+ *                 take no part (n_passed_through counts them; the grid has no cells for them).
+ *   frame         per landmark, on the host in fp64 from the four doubles p[0..3] of the estimate the device projects with:
+ *                 l = sqrt(p0^2 + p1^2 + p2^2), n = (p0, p1, p2) / l, a = (0,0,1) if |n_z| <= 0.7 else (1,0,0), e1 = (a x n) / |a x n|,
+ *                 e2 = n x e1.  Anchored at the foot of the world origin: a point's plane coordinates are u = p . e1, v = p . e2.
+ *   cell          with x, y, z the fp32 coordinates B holds, converted to double: u = (x*e1[0] + y*e1[1]) + z*e1[2] (every product and sum
+ *                 rounded once, never fused), i = floor(u * inv_cell) with inv_cell = 1.0 / cell; j likewise from e2.  A point whose u or
+ *                 v is not finite, or whose |i| or |j| is 2^30 or more, is dropped (n_dropped).
+ *   winner        of a cell: the point with the greatest (PPS_GRID_NEWEST) or smallest (PPS_GRID_OLDEST) index in B.  A cell is emitted
+ *                 if at least min_count points fell into it; it carries that count.
+ *   order         landmarks by ascending plane node id; inside a landmark the cells of its bounding box (i0, j0, ni, nj: the extent of
+ *                 the points that voted) in raster order, j ascending, then i.  Nothing depends on the order waves run in: two calls on
+ *                 the same state give the same bytes.
+ *   limit         the boxes of all landmarks together hold at most max_cells cells, else PPS_ENOMEM before anything of that size is
+ *                 allocated; the text names the landmark with the largest box (one far outlier makes such a box).
+ * The grid has device buffers of its own; the store, the result of the last pps_map_build, the chunk tables and the graph are not touched.
+ * A call that fails leaves no grid (pps_map_grid_info reports zeros); the map stays usable.  Found by symbol lookup, like pps_map_create;
+ * PPS_VERSION was not bumped. */
+enum pps_grid_rule { PPS_GRID_NEWEST = 0, PPS_GRID_OLDEST = 1 };
+typedef struct pps_map_grid_params {
+  double cell;                     /* edge of a cell in metres */
+  int32_t rule, min_count;
+  int64_t max_cells;
+} pps_map_grid_params;
+void pps_map_grid_default_params(pps_map_grid_params* p);          /* 0.02 m, NEWEST, 1, 1 << 26 */
+typedef struct pps_map_grid_plane {
+  int32_t plane_id, n_chunks;      /* selected chunks that belong to it now, empty ones included */
+  int32_t i0, j0, ni, nj;          /* bounding box of its cells (all 0 if no point of it voted) */
+  int64_t offset, count;           /* its cells in the grid map */
+  int64_t n_in;                    /* points that took part and were not dropped */
+  double  n[3], e1[3], e2[3];
+} pps_map_grid_plane;
+typedef struct pps_map_grid_totals {
+  int64_t n_points;                /* points of B = n_in + n_dropped + n_passed_through */
+  int64_t n_cells;                 /* cells emitted: the points of the grid map */
+  int64_t n_in, n_dropped, n_passed_through;
+  int32_t n_planes, launches;
+  double  cell, inv_cell;
+  double  sec[4];                  /* device seconds (HIP events): extent pass | vote pass | emission | whole call */
+} pps_map_grid_totals;
+/* n_points (may be NULL): cells emitted; n_planes (may be NULL): rows of the plane table = live landmarks with a selected chunk.
+ *   PPS_EINVAL  answered on the host without a device: NULL m, cell not finite or <= 0 or so small that 1.0 / cell is not finite, an
+ *               unknown rule, min_count < 1, max_cells < 1, an invalid sel (the rule of pps_map_build).  prm == NULL: the defaults.
+ *   PPS_ENOMEM  more than max_cells cells, or the device has no room for the grid's buffers
+ * A selection without a point that takes part returns PPS_OK with zero points and needs no device. */
+int pps_map_build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params* prm, int64_t* n_points, int* n_planes);
+/* the plane table of the last grid: *n = rows in all, the first min(cap, *n) are copied */
+int pps_map_grid_planes(const pps_map* m, int cap, pps_map_grid_plane* out, int* n);
+int pps_map_grid_info(const pps_map* m, pps_map_grid_totals* out);
+/* cells [first, first + n) of the last grid; every output may be NULL: the point, the points that fell into the cell, (i, j),
+ * and the winner's index in the map pps_map_build writes for the same selection.  PPS_EINVAL: a range outside the grid. */
+int pps_map_grid_download(pps_map* m, int64_t first, int64_t n, pps_point* pts, uint32_t* counts, int32_t* ij, int64_t* src);
+/* host only, no device: the frame and the cell arithmetic as stated above, compiled from the header the kernels include.
+ * frame: PPS_EINVAL if abc has no finite positive length.  cell: *cell = floor(u * inv_cell) for one axis e, *dropped = 1 if the point
+ * is dropped on that axis (*cell is then 0). */
+int pps_map_grid_frame_host(const double abcd[4], double n[3], double e1[3], double e2[3]);
+int pps_map_grid_cell_host(const double e[3], double inv_cell, const float xyz[3], int64_t* cell, int* dropped);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,30 @@ CHUNK_DTYPE = np.dtype([("frame", "<i4"), ("frame_seq_id", "<i4"), ("frame_plane
                         ("offset", "<i8"), ("count", "<i8")])
 
 
+GRID_NEWEST, GRID_OLDEST = 0, 1                                       # enum pps_grid_rule
+
+
+class PpsMapGridParams(C.Structure):
+    """pps_map_grid_params (include/pps.h); defaults via pps_map_grid_default_params."""
+    _fields_ = [("cell", C.c_double), ("rule", C.c_int32), ("min_count", C.c_int32), ("max_cells", C.c_int64)]
+
+
+class PpsMapGridPlane(C.Structure):
+    """pps_map_grid_plane (include/pps.h): one landmark of the grid map."""
+    _fields_ = [("plane_id", C.c_int32), ("n_chunks", C.c_int32), ("i0", C.c_int32), ("j0", C.c_int32), ("ni", C.c_int32), ("nj", C.c_int32),
+                ("offset", C.c_int64), ("count", C.c_int64), ("n_in", C.c_int64),
+                ("n", C.c_double * 3), ("e1", C.c_double * 3), ("e2", C.c_double * 3)]
+
+
+class PpsMapGridTotals(C.Structure):
+    _fields_ = [("n_points", C.c_int64), ("n_cells", C.c_int64), ("n_in", C.c_int64), ("n_dropped", C.c_int64), ("n_passed_through", C.c_int64),
+                ("n_planes", C.c_int32), ("launches", C.c_int32), ("cell", C.c_double), ("inv_cell", C.c_double), ("sec", C.c_double * 4)]
+
+
+GRID_PLANE_DTYPE = np.dtype([("plane_id", "<i4"), ("n_chunks", "<i4"), ("i0", "<i4"), ("j0", "<i4"), ("ni", "<i4"), ("nj", "<i4"),
+                             ("offset", "<i8"), ("count", "<i8"), ("n_in", "<i8"), ("n", "<f8", 3), ("e1", "<f8", 3), ("e2", "<f8", 3)])
+
+
 SYMBOLS = [
     "pps_default_props", "pps_version", "pps_last_error", "pps_graph_create", "pps_graph_destroy",
     "pps_get_props", "pps_set_props", "pps_add_pose", "pps_add_plane", "pps_add_pose_prior",
@@ -140,6 +164,8 @@ SYMBOLS = [
     "pps_map_default_select", "pps_map_create", "pps_map_destroy", "pps_map_last_error", "pps_map_add_frame", "pps_map_redirect",
     "pps_map_info", "pps_map_chunks", "pps_map_built_chunks", "pps_map_select_host", "pps_map_build", "pps_map_download",
     "pps_map_last_times", "pps_debug_map_add_points",
+    "pps_map_grid_default_params", "pps_map_build_grid", "pps_map_grid_planes", "pps_map_grid_info", "pps_map_grid_download",
+    "pps_map_grid_frame_host", "pps_map_grid_cell_host",
     "pps_set_cost_function", "pps_get_cost_function",
 ]
 
@@ -297,6 +323,13 @@ def lib():
         L.pps_map_build.argtypes = [C.c_void_p, C.POINTER(PpsMapSelect), _i64p, _ip]
         L.pps_map_download.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
         L.pps_map_last_times.argtypes = [C.c_void_p, _dp]
+        L.pps_map_grid_default_params.argtypes = [C.POINTER(PpsMapGridParams)]; L.pps_map_grid_default_params.restype = None
+        L.pps_map_build_grid.argtypes = [C.c_void_p, C.POINTER(PpsMapSelect), C.POINTER(PpsMapGridParams), _i64p, _ip]
+        L.pps_map_grid_planes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
+        L.pps_map_grid_info.argtypes = [C.c_void_p, C.POINTER(PpsMapGridTotals)]
+        L.pps_map_grid_download.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pps_map_grid_frame_host.argtypes = [_dp, _dp, _dp, _dp]
+        L.pps_map_grid_cell_host.argtypes = [_dp, C.c_double, _fp, _i64p, _ip]
         _LIB = L
     return _LIB
 
@@ -1089,6 +1122,60 @@ class Map:
     def last_times(self):
         """device seconds: (kernels of the last add_frame, kernel of the last build)"""
         s = (C.c_double * 2)(); self._ck(self.L.pps_map_last_times(self.h, s)); return float(s[0]), float(s[1])
+
+    def build_grid(self, sel=None, cell=0.02, rule=GRID_NEWEST, min_count=1, max_cells=1 << 26):
+        """pps_map_build_grid: one point per cell (edge `cell` metres) of every landmark plane, of the map build(sel) would write;
+        -> (cells emitted, rows of the plane table)"""
+        prm = PpsMapGridParams(float(cell), int(rule), int(min_count), int(max_cells))
+        npt = C.c_int64(); npl = C.c_int()
+        self._ck(self.L.pps_map_build_grid(self.h, C.byref(sel) if sel is not None else None, C.byref(prm), C.byref(npt), C.byref(npl)))
+        return npt.value, npl.value
+
+    def grid_planes(self):
+        """plane table of the last grid (GRID_PLANE_DTYPE rows, ascending plane node id)"""
+        n = C.c_int(); self._ck(self.L.pps_map_grid_planes(self.h, 0, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=GRID_PLANE_DTYPE)
+        if n.value:
+            self._ck(self.L.pps_map_grid_planes(self.h, n.value, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out
+
+    def grid_info(self):
+        """pps_map_grid_totals of the last grid as a dict (sec: 4-tuple); all zeros after a call that failed"""
+        t = PpsMapGridTotals(); self._ck(self.L.pps_map_grid_info(self.h, C.byref(t)))
+        d = {k: getattr(t, k) for k, _ in t._fields_ if k != "sec"}
+        d["sec"] = tuple(float(v) for v in t.sec)
+        return d
+
+    def grid_download(self, first=0, n=None):
+        """cells [first, first + n) of the last grid -> (points POINT_DTYPE, counts uint32, ij int32 (n, 2), src int64: the winner's index
+        in the map build() writes for the same selection)"""
+        if n is None:
+            n = self.grid_info()["n_cells"] - first
+        k = max(int(n), 0)
+        pts = np.zeros(k, dtype=POINT_DTYPE); cnt = np.zeros(k, dtype=np.uint32); ij = np.zeros((k, 2), dtype=np.int32); src = np.zeros(k, dtype=np.int64)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._ck(self.L.pps_map_grid_download(self.h, int(first), int(n), vp(pts), vp(cnt), vp(ij), vp(src)))
+        return pts, cnt, ij, src
+
+
+def map_grid_frame_host(abcd):
+    """pps_map_grid_frame_host: (n, e1, e2) of a plane's four doubles, the frame its grid cells are counted in.  No device needed."""
+    p = np.ascontiguousarray(abcd, dtype=np.float64).reshape(4)
+    n, e1, e2 = np.zeros(3), np.zeros(3), np.zeros(3)
+    rc = lib().pps_map_grid_frame_host(p.ctypes.data_as(_dp), n.ctypes.data_as(_dp), e1.ctypes.data_as(_dp), e2.ctypes.data_as(_dp))
+    if rc != PPS_OK:
+        raise PpsError(rc, "pps_map_grid_frame_host")
+    return n, e1, e2
+
+
+def map_grid_cell_host(e, inv_cell, xyz):
+    """pps_map_grid_cell_host: (cell index along the axis e, dropped flag) of one fp32 point.  No device needed."""
+    ax = np.ascontiguousarray(e, dtype=np.float64).reshape(3); p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(3)
+    cell = C.c_int64(); dropped = C.c_int()
+    rc = lib().pps_map_grid_cell_host(ax.ctypes.data_as(_dp), float(inv_cell), p.ctypes.data_as(_fp), C.byref(cell), C.byref(dropped))
+    if rc != PPS_OK:
+        raise PpsError(rc, "pps_map_grid_cell_host")
+    return cell.value, bool(dropped.value)
 
 
 class Multi:

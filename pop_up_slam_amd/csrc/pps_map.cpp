@@ -6,8 +6,7 @@
 // count kernel is enqueued on the graph's stream; it returns after a synchronisation of that stream, so the context's next run cannot
 // overwrite a cloud that is still being read.  pps_map_build follows prepare_solve on the same stream: the solver's estimate, the store's
 // last writes and the build are ordered by the stream itself.
-#include "pps_graph.h"
-#include "pps_map.h"
+#include "pps_map_host.h"
 #include "pps_popup_host.h"
 
 using namespace pps;
@@ -15,30 +14,7 @@ using namespace pps_impl;
 
 static_assert(sizeof(MapPt) == sizeof(pps_point), "MapPt is pps_point");
 
-struct pps_map {
-  pps_graph* g = nullptr;
-  std::string err;
-  int64_t cap = 0, used = 0;
-  int n_frames = 0;
-  std::vector<pps_map_chunk> chunks, built;
-  int64_t built_points = 0;
-  MapPt *d_store = nullptr, *d_built = nullptr;
-  int* d_table = nullptr; size_t table_cap = 0;       // planes x wave tiles of the last frame, then kMapPlanes totals
-  int* h_totals = nullptr;                            // pinned, kMapPlanes
-  char* d_sel = nullptr; size_t sel_cap = 0;          // offset table of a build: [out_off | src_off | slot]
-  MapPt* d_dbg_cloud = nullptr; int* d_dbg_pid = nullptr; size_t dbg_cap = 0;   // pixels uploaded by pps_debug_map_add_points
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  double sec[2] = {0, 0};
-};
-
 namespace {
-
-int mfail(pps_map* m, int code, const std::string& msg) { if (m) m->err = msg; return code; }
-#define MAP_TRY(m, expr)                                                                                        \
-  do {                                                                                                          \
-    hipError_t _e = (expr);                                                                                     \
-    if (_e != hipSuccess) return mfail(m, _e == hipErrorOutOfMemory ? PPS_ENOMEM : PPS_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 bool select_valid(const pps_map_select* s) { return !s || (s->old_every > 0 && s->new_every > 0); }
 
@@ -75,6 +51,11 @@ int map_events(pps_map* m) {
 
 }  // namespace
 
+namespace pps_impl {
+bool map_select_valid(const pps_map_select* s) { return select_valid(s); }
+void map_select_chunks(const pps_map_chunk* c, int n, const pps_map_select* s, int32_t* keep) { select_chunks(c, n, s, keep); }
+}  // namespace pps_impl
+
 extern "C" {
 
 void pps_map_default_select(pps_map_select* s, int counter) {
@@ -105,6 +86,7 @@ int pps_map_destroy(pps_map* m) {
     if (m->h_totals) (void)hipHostFree(m->h_totals);
     for (hipEvent_t e : m->ev) if (e) (void)hipEventDestroy(e);
   }
+  map_grid_release(m);
   delete m;
   return PPS_OK;
 }
