@@ -896,6 +896,60 @@ int pps_map_grid_download(pps_map* m, int64_t first, int64_t n, pps_point* pts, 
 int pps_map_grid_frame_host(const double abcd[4], double n[3], double e1[3], double e2[3]);
 int pps_map_grid_cell_host(const double e[3], double inv_cell, const float xyz[3], int64_t* cell, int* dropped);
 
+/* ---- posed map: stored points follow their frame's pose estimate -----------------------------------------------------
+ * The store holds every frame's points in world coordinates, made with the T_wc its pop-up run was given -- the pose predicted from
+ * odometry (main_3d.cpp:426-431).  pps_map_build repairs a point along the normal of its landmark only; when the optimiser moves the
+ * frame's pose (a loop closure moves it by metres), the point stays where the old pose put it inside the plane.  A posed build first moves
+ * every stored point rigidly with the correction of its frame's pose and then projects it as pps_map_build does.
+ *
+ * All arithmetic is fp64 in the order written, nothing is fused.
+ *   frame record  a frame may carry T0 (row-major 4x4 fp32, sensor -> world, as given to the pop-up run) and the id of a pose node.
+ *                 R0 = T0[0:3,0:3], t0 = T0[0:3,3], converted to double.  T0 must be rigid to fp32: every entry finite, last row
+ *                 (0,0,0,1), max |R0^T R0 - I| <= 1e-4.
+ *   motion        D = (R_D, t_D), 12 doubles (R_D row-major, then t_D).  With (t, q) the current estimate of the pose node and R the
+ *                 rotation matrix of q as the solver forms it (Eigen::Matrix3d(q), no renormalisation): R_D = R R0^T, every entry
+ *                 (a*b + c*d) + e*f; t_D = t - R_D t0, the product summed the same way, then one subtraction.  Computed on the device
+ *                 from the estimate in place, one thread per frame; no pose is downloaded.  A frame without a record, or whose pose node
+ *                 is not live any more, has no motion: its points are not moved (n_unposed_frames counts such frames).
+ *   point         (x, y, z) the fp32 store coordinates converted to double; x' = ((R_D[0]*x + R_D[1]*y) + R_D[2]*z) + t_D[0], y' and z'
+ *                 likewise.  If the chunk's landmark is live, Plane3d::project_to_plane on the DOUBLES (x', y', z') with the arithmetic
+ *                 of pps_map_build (no cast to fp32 in between); if it is gone and was not redirected, (x', y', z') itself.  One cast to
+ *                 fp32; rgba copied.  A point that is not moved is pps_map_build's point, bit for bit: a posed build of a map without
+ *                 any frame record IS pps_map_build's map.
+ *   order, selection, chunk tables: pps_map_build's.  The result replaces the built map (pps_map_download(which = 1), pps_map_built_chunks).
+ * Rigid motion plus projection is exact to first order in the plane's correction; it does not re-intersect the pixel's ray with the moved
+ * plane.  Found by symbol lookup, like pps_map_create; PPS_VERSION was not bumped. */
+typedef struct pps_map_frame {
+  int32_t frame, frame_seq_id;     /* insertion index (pps_map_chunk.frame), tracking_frame::frame_seq_id */
+  int32_t pose_id, reserved;       /* pose node of the record, -1: none */
+  float   T_wc[16];                /* T0 of the record (zeros without one) */
+} pps_map_frame;
+/* The record of `frame` (its insertion index).  T_wc == NULL: the T_wc of the pop-up run the frame was added from (pps_map_add_frame
+ * remembers it).  pose_node_id = -1 clears the record.  Needs no device.
+ *   PPS_EINVAL  NULL m, an unknown frame, an id that is not a live pose node of the graph, a T_wc that is not rigid (above), T_wc == NULL
+ *               for a frame added with pps_debug_map_add_points.  The record is unchanged. */
+int pps_map_set_frame_pose(pps_map* m, int frame, int pose_node_id, const float T_wc[16]);
+/* the frame table: *n = frames in all, the first min(cap, *n) are copied.  Needs no device. */
+int pps_map_frames(const pps_map* m, int cap, pps_map_frame* out, int* n);
+/* pps_map_build with every point moved as stated above; arguments and errors of pps_map_build. */
+int pps_map_build_posed(pps_map* m, const pps_map_select* sel, int64_t* n_points, int* n_chunks);
+/* pps_map_build_grid with B replaced by the map pps_map_build_posed writes for the same selection and state: every sentence of the grid
+ * statement holds with that B (subset bit for bit, src indexes it); pps_map_grid_* read the result like any grid.  The built map itself
+ * is not touched. */
+int pps_map_build_grid_posed(pps_map* m, const pps_map_select* sel, const pps_map_grid_params* prm, int64_t* n_points, int* n_planes);
+/* The motion table of the last posed build or posed grid that ran on the device, copied from it: one row per frame that has a point in the
+ * selection, in frame order (the distinct `frame` values of the selected non-empty chunks, ascending).  *n = rows in all; the first
+ * min(cap, *n) rows go to D (cap x 12, may be NULL) and moved (may be NULL; 0: the frame has no motion, its row is the identity).
+ * For callers that move polygons the same way. */
+int pps_map_frame_motions(pps_map* m, int cap, double* D, int32_t* moved, int* n);
+/* of the last posed call (each output may be NULL): device seconds (HIP events) of the motion kernel and of the posed build kernel (0
+ * after a posed grid: pps_map_grid_info has its passes); kernels launched outside the grid passes; frames of the motion table without a motion */
+int pps_map_posed_last(const pps_map* m, double sec[2], int* launches, int* n_unposed_frames);
+/* host only, no device: the statement above, compiled from the header the kernels include.  motion: tq in the layout of pps_get_pose;
+ * PPS_EINVAL if T_wc is not rigid.  move_point: D == NULL leaves the point unmoved, abcd == NULL unprojected. */
+int pps_map_motion_host(const float T_wc[16], const double tq[7], double D[12]);
+int pps_map_move_point_host(const double* D, const double* abcd, const float xyz[3], float out[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,7 +112,10 @@ CHUNK_DTYPE = np.dtype([("frame", "<i4"), ("frame_seq_id", "<i4"), ("frame_plane
                         ("offset", "<i8"), ("count", "<i8")])
 
 
-GRID_NEWEST, GRID_OLDEST = 0, 1                                       # enum pps_grid_rule
+FRAME_DTYPE = np.dtype([("frame", "<i4"), ("frame_seq_id", "<i4"), ("pose_id", "<i4"), ("reserved", "<i4"), ("T_wc", "<f4", (4, 4))])   # pps_map_frame
+
+
+GRID_NEWEST, GRID_OLDEST = 0, 1                                      # enum pps_grid_rule
 
 
 class PpsMapGridParams(C.Structure):
@@ -166,6 +169,8 @@ SYMBOLS = [
     "pps_map_last_times", "pps_debug_map_add_points",
     "pps_map_grid_default_params", "pps_map_build_grid", "pps_map_grid_planes", "pps_map_grid_info", "pps_map_grid_download",
     "pps_map_grid_frame_host", "pps_map_grid_cell_host",
+    "pps_map_set_frame_pose", "pps_map_frames", "pps_map_build_posed", "pps_map_build_grid_posed", "pps_map_frame_motions",
+    "pps_map_posed_last", "pps_map_motion_host", "pps_map_move_point_host",
     "pps_set_cost_function", "pps_get_cost_function",
 ]
 
@@ -330,6 +335,14 @@ def lib():
         L.pps_map_grid_download.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pps_map_grid_frame_host.argtypes = [_dp, _dp, _dp, _dp]
         L.pps_map_grid_cell_host.argtypes = [_dp, C.c_double, _fp, _i64p, _ip]
+        L.pps_map_set_frame_pose.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp]
+        L.pps_map_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
+        L.pps_map_build_posed.argtypes = [C.c_void_p, C.POINTER(PpsMapSelect), _i64p, _ip]
+        L.pps_map_build_grid_posed.argtypes = [C.c_void_p, C.POINTER(PpsMapSelect), C.POINTER(PpsMapGridParams), _i64p, _ip]
+        L.pps_map_frame_motions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _ip]
+        L.pps_map_posed_last.argtypes = [C.c_void_p, _dp, _ip, _ip]
+        L.pps_map_motion_host.argtypes = [_fp, _dp, _dp]
+        L.pps_map_move_point_host.argtypes = [_dp, _dp, _fp, _fp]
         _LIB = L
     return _LIB
 
@@ -1105,11 +1118,44 @@ class Map:
         """chunk table of the last build: offsets into the built map"""
         return self._table(self.L.pps_map_built_chunks)
 
-    def build(self, sel=None):
-        """-> (points, chunks) of the map just built; sel: a PpsMapSelect (map_select) or None = every chunk"""
+    def build(self, sel=None, posed=False):
+        """-> (points, chunks) of the map just built; sel: a PpsMapSelect (map_select) or None = every chunk.  posed: pps_map_build_posed,
+        every point first moved with the correction of its frame's pose (set_frame_pose)"""
         npt = C.c_int64(); nch = C.c_int()
-        self._ck(self.L.pps_map_build(self.h, C.byref(sel) if sel is not None else None, C.byref(npt), C.byref(nch)))
+        fn = self.L.pps_map_build_posed if posed else self.L.pps_map_build
+        self._ck(fn(self.h, C.byref(sel) if sel is not None else None, C.byref(npt), C.byref(nch)))
         return npt.value, nch.value
+
+    def set_frame_pose(self, frame, pose_node_id, T_wc=None):
+        """pps_map_set_frame_pose: frame (insertion index) was captured at T_wc (4x4 fp32; None: the T_wc of the pop-up run it was added
+        from) and follows the estimate of pose_node_id from now on; pose_node_id = -1 clears the record.  No device needed."""
+        T = None
+        if T_wc is not None:
+            T = np.ascontiguousarray(T_wc, dtype=np.float32).reshape(16)
+        self._ck(self.L.pps_map_set_frame_pose(self.h, int(frame), int(pose_node_id), T.ctypes.data_as(_fp) if T is not None else None))
+
+    def frames(self):
+        """the frame table (FRAME_DTYPE rows: frame, frame_seq_id, pose_id (-1: no record), T_wc).  No device needed."""
+        n = C.c_int(); self._ck(self.L.pps_map_frames(self.h, 0, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=FRAME_DTYPE)
+        if n.value:
+            self._ck(self.L.pps_map_frames(self.h, n.value, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out
+
+    def frame_motions(self):
+        """motion table of the last posed build / posed grid, read from the device -> (D (n, 12): R_D row-major then t_D, moved (n,) int32),
+        one row per frame with a point in the selection, in frame order"""
+        n = C.c_int(); self._ck(self.L.pps_map_frame_motions(self.h, 0, None, None, C.byref(n)))
+        D = np.zeros((n.value, 12)); moved = np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            self._ck(self.L.pps_map_frame_motions(self.h, n.value, D.ctypes.data_as(C.c_void_p), moved.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return D, moved
+
+    def posed_last(self):
+        """of the last posed call: dict(sec=(motion kernel, posed build kernel) device seconds, launches, n_unposed_frames)"""
+        s = (C.c_double * 2)(); nl = C.c_int(); nu = C.c_int()
+        self._ck(self.L.pps_map_posed_last(self.h, s, C.byref(nl), C.byref(nu)))
+        return dict(sec=(float(s[0]), float(s[1])), launches=nl.value, n_unposed_frames=nu.value)
 
     def download(self, which=0, first=0, n=None):
         """points [first, first + n) of the store (which = 0) or the built map (which = 1) as a POINT_DTYPE array"""
@@ -1123,12 +1169,13 @@ class Map:
         """device seconds: (kernels of the last add_frame, kernel of the last build)"""
         s = (C.c_double * 2)(); self._ck(self.L.pps_map_last_times(self.h, s)); return float(s[0]), float(s[1])
 
-    def build_grid(self, sel=None, cell=0.02, rule=GRID_NEWEST, min_count=1, max_cells=1 << 26):
-        """pps_map_build_grid: one point per cell (edge `cell` metres) of every landmark plane, of the map build(sel) would write;
-        -> (cells emitted, rows of the plane table)"""
+    def build_grid(self, sel=None, cell=0.02, rule=GRID_NEWEST, min_count=1, max_cells=1 << 26, posed=False):
+        """pps_map_build_grid: one point per cell (edge `cell` metres) of every landmark plane, of the map build(sel) would write
+        (posed: pps_map_build_grid_posed, of the map build(sel, posed=True) would write); -> (cells emitted, rows of the plane table)"""
         prm = PpsMapGridParams(float(cell), int(rule), int(min_count), int(max_cells))
         npt = C.c_int64(); npl = C.c_int()
-        self._ck(self.L.pps_map_build_grid(self.h, C.byref(sel) if sel is not None else None, C.byref(prm), C.byref(npt), C.byref(npl)))
+        fn = self.L.pps_map_build_grid_posed if posed else self.L.pps_map_build_grid
+        self._ck(fn(self.h, C.byref(sel) if sel is not None else None, C.byref(prm), C.byref(npt), C.byref(npl)))
         return npt.value, npl.value
 
     def grid_planes(self):
@@ -1176,6 +1223,30 @@ def map_grid_cell_host(e, inv_cell, xyz):
     if rc != PPS_OK:
         raise PpsError(rc, "pps_map_grid_cell_host")
     return cell.value, bool(dropped.value)
+
+
+def map_motion_host(T_wc, tq):
+    """pps_map_motion_host: the 12 doubles (R_D row-major, t_D) that carry points captured at T_wc (4x4 fp32) to the pose tq (layout of
+    Graph.get_pose).  No device needed."""
+    T = np.ascontiguousarray(T_wc, dtype=np.float32).reshape(16); p = np.ascontiguousarray(tq, dtype=np.float64).reshape(7)
+    D = np.zeros(12)
+    rc = lib().pps_map_motion_host(T.ctypes.data_as(_fp), p.ctypes.data_as(_dp), D.ctypes.data_as(_dp))
+    if rc != PPS_OK:
+        raise PpsError(rc, "pps_map_motion_host")
+    return D
+
+
+def map_move_point_host(D, abcd, xyz):
+    """pps_map_move_point_host: one fp32 point of the posed map -- moved by D (None: not moved), projected onto abcd (None: not
+    projected), cast to fp32 once.  No device needed."""
+    d = np.ascontiguousarray(D, dtype=np.float64).reshape(12) if D is not None else None
+    pl = np.ascontiguousarray(abcd, dtype=np.float64).reshape(4) if abcd is not None else None
+    p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(3); out = np.zeros(3, dtype=np.float32)
+    rc = lib().pps_map_move_point_host(d.ctypes.data_as(_dp) if d is not None else None, pl.ctypes.data_as(_dp) if pl is not None else None,
+                                       p.ctypes.data_as(_fp), out.ctypes.data_as(_fp))
+    if rc != PPS_OK:
+        raise PpsError(rc, "pps_map_move_point_host")
+    return out
 
 
 class Multi:

@@ -35,10 +35,13 @@ struct GridSelArgs {
   double inv_cell;
 };
 
+// The kernels that form a point of B take a motion table beside the selection: mt.motion == nullptr (the default), B is pps_map_build's;
+// otherwise B is the posed map (pps_map_build_grid_posed) and mt.fidx has n_sel rows.
 // pass 1: per landmark the extent of (i, j) and the points that voted; *n_dropped += the dropped ones
-hipError_t launch_grid_extent(const GridSelArgs& a, GridExtent* ext, unsigned long long* n_dropped, hipStream_t st);
+hipError_t launch_grid_extent(const GridSelArgs& a, GridExtent* ext, unsigned long long* n_dropped, hipStream_t st, const MapMotionTable& mt = MapMotionTable{});
 // pass 2: key[c] = max over the cell's points of the rule's key, cnt[c] += 1.  combine: one atomic pair per distinct cell and wave
-hipError_t launch_grid_vote(const GridSelArgs& a, int oldest, bool combine, unsigned long long* key, unsigned int* cnt, hipStream_t st);
+hipError_t launch_grid_vote(const GridSelArgs& a, int oldest, bool combine, unsigned long long* key, unsigned int* cnt, hipStream_t st,
+                            const MapMotionTable& mt = MapMotionTable{});
 
 // pass 3.  A workgroup owns `cpw` consecutive cells (a multiple of 256); nT such tiles cover the n cells.
 struct GridTiling { long long cpw; int nT; };
@@ -64,6 +67,6 @@ struct GridEmitArgs {
 // count per tile, scan over the tiles, emitted cells before every landmark (three launches)
 hipError_t launch_grid_count(const GridEmitArgs& e, int n_planes, hipStream_t st);
 // the stable compaction: cell c with cnt[c] >= min_count goes to tile_prefix[T] + its rank inside the tile
-hipError_t launch_grid_emit(const GridSelArgs& a, const GridEmitArgs& e, hipStream_t st);
+hipError_t launch_grid_emit(const GridSelArgs& a, const GridEmitArgs& e, hipStream_t st, const MapMotionTable& mt = MapMotionTable{});
 
 }  // namespace pps

@@ -14,6 +14,9 @@
 //                   the stable compaction of the cells with count >= min_count in cell order -- count per tile, scan over the tiles,
 //                   write at tile prefix + rank; no atomic cursor --, and the emitted cells before every landmark.
 //
+// pps_map_build_grid_posed: the same passes with B the posed map.  The three kernels that form a point of B (extent, vote, emit) do so
+// through grid_b_point, which moves the point with its frame's motion first when it is given a motion table (pps_map_move.h).
+//
 // Max, min and add of integers do not depend on the order they arrive in: two runs give the same bytes.
 // Compiled without contraction (Makefile), like pps_map.hip.
 #include <hip/hip_runtime.h>
@@ -22,6 +25,7 @@
 
 #include "pps_grid.h"
 #include "pps_grid_cell.h"
+#include "pps_map_move.h"
 #include "pps_project.h"
 
 namespace pps {
@@ -57,8 +61,31 @@ __device__ __forceinline__ void grid_stage_window(const GridSelArgs& a, long lon
   __syncthreads();
 }
 
+// The point B holds for the stored point *pt of chunk c (a row of the selection; sl: its landmark's slot, -1: gone).  Without a motion
+// table B is pps_map_build's: project_to_plane_f32 of the raw point.  With one B is the posed map (pps_map_build_grid_posed): a point of
+// a frame that has a motion is moved and then projected (map_move_point, pps_map_move.h), every other point is formed as before.
+__device__ __forceinline__ void grid_b_point(const GridSelArgs& a, const MapMotionTable& mt, int c, int sl, MapPt* pt) {
+  double p[4] = {0.0, 0.0, 1.0, 0.0};
+  if (sl >= 0)
+    for (int k = 0; k < 4; k++) p[k] = a.plane_est[(size_t)k * a.plane_ld + sl];
+  if (mt.motion) {
+    const int f = mt.fidx[c];
+    if (mt.moved[f]) {
+      double D[12];
+      for (int k = 0; k < 12; k++) D[k] = mt.motion[12 * (size_t)f + k];
+      double x = (double)pt->x, y = (double)pt->y, z = (double)pt->z;
+      map_move_xyz(D, &x, &y, &z);
+      if (sl >= 0) project_to_plane_f64(p, x, y, z, &pt->x, &pt->y, &pt->z);
+      else { pt->x = (float)x; pt->y = (float)y; pt->z = (float)z; }
+      return;
+    }
+  }
+  if (sl >= 0) project_to_plane_f32(p, pt->x, pt->y, pt->z, &pt->x, &pt->y, &pt->z);
+}
+
 // point i of B (i < n_out): its landmark row (-1: it passes through) and, for a landmark's point, its cell; false if it is dropped
-__device__ __forceinline__ bool grid_point_cell(const GridSelArgs& a, const GridWindow& w, long long i, int* lm, long long* ci, long long* cj) {
+__device__ __forceinline__ bool grid_point_cell(const GridSelArgs& a, const MapMotionTable& mt, const GridWindow& w, long long i, int* lm, long long* ci,
+                                                long long* cj) {
   int lo = 0, hi = kMapThreads;                                  // off[lo] <= i < off[hi]
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
@@ -68,17 +95,14 @@ __device__ __forceinline__ bool grid_point_cell(const GridSelArgs& a, const Grid
   *lm = L;
   if (L < 0) return true;
   MapPt pt = a.store[w.src[lo] + (i - w.off[lo])];
-  const int sl = w.slot[lo];
-  double p[4];
-  for (int k = 0; k < 4; k++) p[k] = a.plane_est[(size_t)k * a.plane_ld + sl];
-  project_to_plane_f32(p, pt.x, pt.y, pt.z, &pt.x, &pt.y, &pt.z);
+  grid_b_point(a, mt, w.c0 + lo, w.slot[lo], &pt);
   const GridPlaneDev& pl = a.planes[L];
   const bool oi = grid_cell(pl.e1, a.inv_cell, pt.x, pt.y, pt.z, ci);
   const bool oj = grid_cell(pl.e2, a.inv_cell, pt.x, pt.y, pt.z, cj);
   return oi && oj;
 }
 
-__global__ __launch_bounds__(kMapThreads) void k_grid_extent(GridSelArgs a, GridExtent* __restrict__ ext, unsigned long long* __restrict__ n_dropped) {
+__global__ __launch_bounds__(kMapThreads) void k_grid_extent(GridSelArgs a, MapMotionTable mt, GridExtent* __restrict__ ext, unsigned long long* __restrict__ n_dropped) {
   __shared__ GridWindow w;
   const int lane = threadIdx.x & 63;
   const long long first = (long long)blockIdx.x * kMapThreads;
@@ -87,7 +111,7 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_extent(GridSelArgs a, Grid
   int lm = -1;
   long long ci = 0, cj = 0;
   bool dropped = false;
-  if (i < a.n_out && !grid_point_cell(a, w, i, &lm, &ci, &cj)) { dropped = true; lm = -1; }
+  if (i < a.n_out && !grid_point_cell(a, mt, w, i, &lm, &ci, &cj)) { dropped = true; lm = -1; }
   const unsigned long long dm = __ballot(dropped);
   if (dm && lane == 0) atomicAdd(n_dropped, (unsigned long long)__popcll(dm));
   const int vi = (int)ci, vj = (int)cj;                          // (|i|, |j| < 2^30)
@@ -124,7 +148,7 @@ __device__ __forceinline__ long long grid_key_index(unsigned long long key, int 
 }
 
 template <bool COMBINE>
-__global__ __launch_bounds__(kMapThreads) void k_grid_vote(GridSelArgs a, int oldest, unsigned long long* __restrict__ key, unsigned int* __restrict__ cnt) {
+__global__ __launch_bounds__(kMapThreads) void k_grid_vote(GridSelArgs a, MapMotionTable mt, int oldest, unsigned long long* __restrict__ key, unsigned int* __restrict__ cnt) {
   __shared__ GridWindow w;
   const int lane = threadIdx.x & 63;
   const long long first = (long long)blockIdx.x * kMapThreads;
@@ -133,7 +157,7 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_vote(GridSelArgs a, int ol
   long long c = -1;                                              // the point's cell in the arrays, -1: it does not vote
   if (i < a.n_out) {
     int lm; long long ci, cj;
-    if (grid_point_cell(a, w, i, &lm, &ci, &cj) && lm >= 0) {
+    if (grid_point_cell(a, mt, w, i, &lm, &ci, &cj) && lm >= 0) {
       const GridPlaneDev& pl = a.planes[lm];
       const long long di = ci - pl.i0, dj = cj - pl.j0;
       if (di >= 0 && di < pl.ni && dj >= 0 && dj < pl.nj) c = pl.base + dj * pl.ni + di;      // (always, after the extent pass; the arrays end at the boxes)
@@ -212,7 +236,7 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_plane_off(GridEmitArgs e, 
   if (tid == 0) e.plane_off[blockIdx.x] = e.tile_prefix[T] + s_sum[0];
 }
 
-__global__ __launch_bounds__(kMapThreads) void k_grid_emit(GridSelArgs a, GridEmitArgs e, long long cpw) {
+__global__ __launch_bounds__(kMapThreads) void k_grid_emit(GridSelArgs a, MapMotionTable mt, GridEmitArgs e, long long cpw) {
   __shared__ int s_wave[kMapWaves];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const long long c0 = (long long)blockIdx.x * cpw, c1 = min(e.n_cells_all, c0 + cpw);
@@ -247,12 +271,7 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_emit(GridSelArgs a, GridEm
       MapPt pt = {0.f, 0.f, 0.f, 0u};
       if (idx >= 0 && idx < a.n_out) {                           // (always: the key of a counted cell is a point's)
         pt = a.store[a.src_off[lo] + (idx - a.out_off[lo])];
-        const int sl = a.slot[lo];
-        if (sl >= 0) {
-          double p[4];
-          for (int k = 0; k < 4; k++) p[k] = a.plane_est[(size_t)k * a.plane_ld + sl];
-          project_to_plane_f32(p, pt.x, pt.y, pt.z, &pt.x, &pt.y, &pt.z);
-        }
+        grid_b_point(a, mt, lo, a.slot[lo], &pt);
       }
       e.pts[pos] = pt;
       e.counts[pos] = n;
@@ -265,20 +284,21 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_emit(GridSelArgs a, GridEm
 
 }  // namespace
 
-hipError_t launch_grid_extent(const GridSelArgs& a, GridExtent* ext, unsigned long long* n_dropped, hipStream_t st) {
+hipError_t launch_grid_extent(const GridSelArgs& a, GridExtent* ext, unsigned long long* n_dropped, hipStream_t st, const MapMotionTable& mt) {
   if (a.n_out <= 0 || a.n_sel <= 0) return hipSuccess;
   const long long nwg = (a.n_out + kMapThreads - 1) / kMapThreads;
   if (nwg > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_grid_extent, dim3((unsigned int)nwg), dim3(kMapThreads), 0, st, a, ext, n_dropped);
+  hipLaunchKernelGGL(k_grid_extent, dim3((unsigned int)nwg), dim3(kMapThreads), 0, st, a, mt, ext, n_dropped);
   return hipGetLastError();
 }
 
-hipError_t launch_grid_vote(const GridSelArgs& a, int oldest, bool combine, unsigned long long* key, unsigned int* cnt, hipStream_t st) {
+hipError_t launch_grid_vote(const GridSelArgs& a, int oldest, bool combine, unsigned long long* key, unsigned int* cnt, hipStream_t st,
+                            const MapMotionTable& mt) {
   if (a.n_out <= 0 || a.n_sel <= 0) return hipSuccess;
   const long long nwg = (a.n_out + kMapThreads - 1) / kMapThreads;
   if (nwg > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (combine) hipLaunchKernelGGL(k_grid_vote<true>, dim3((unsigned int)nwg), dim3(kMapThreads), 0, st, a, oldest, key, cnt);
-  else hipLaunchKernelGGL(k_grid_vote<false>, dim3((unsigned int)nwg), dim3(kMapThreads), 0, st, a, oldest, key, cnt);
+  if (combine) hipLaunchKernelGGL(k_grid_vote<true>, dim3((unsigned int)nwg), dim3(kMapThreads), 0, st, a, mt, oldest, key, cnt);
+  else hipLaunchKernelGGL(k_grid_vote<false>, dim3((unsigned int)nwg), dim3(kMapThreads), 0, st, a, mt, oldest, key, cnt);
   return hipGetLastError();
 }
 
@@ -291,10 +311,10 @@ hipError_t launch_grid_count(const GridEmitArgs& e, int n_planes, hipStream_t st
   return hipGetLastError();
 }
 
-hipError_t launch_grid_emit(const GridSelArgs& a, const GridEmitArgs& e, hipStream_t st) {
+hipError_t launch_grid_emit(const GridSelArgs& a, const GridEmitArgs& e, hipStream_t st, const MapMotionTable& mt) {
   if (e.n_cells_all <= 0) return hipSuccess;
   const GridTiling t = grid_tiling(e.n_cells_all);
-  hipLaunchKernelGGL(k_grid_emit, dim3(t.nT), dim3(kMapThreads), 0, st, a, e, t.cpw);
+  hipLaunchKernelGGL(k_grid_emit, dim3(t.nT), dim3(kMapThreads), 0, st, a, mt, e, t.cpw);
   return hipGetLastError();
 }
 

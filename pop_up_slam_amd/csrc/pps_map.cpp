@@ -7,6 +7,7 @@
 // overwrite a cloud that is still being read.  pps_map_build follows prepare_solve on the same stream: the solver's estimate, the store's
 // last writes and the build are ordered by the stream itself.
 #include "pps_map_host.h"
+#include "pps_map_move.h"
 #include "pps_popup_host.h"
 
 using namespace pps;
@@ -54,6 +55,54 @@ int map_events(pps_map* m) {
 namespace pps_impl {
 bool map_select_valid(const pps_map_select* s) { return select_valid(s); }
 void map_select_chunks(const pps_map_chunk* c, int n, const pps_map_select* s, int32_t* keep) { select_chunks(c, n, s, keep); }
+
+void map_motion_plan(const pps_map* m, const std::vector<int>& src, MapMotionPlan* p) {
+  const pps_graph* g = m->g;
+  p->fidx.resize(src.size()); p->recs.clear(); p->n_unposed = 0;
+  int last = -1;                                         // (chunks are in insertion order: the frames of src ascend)
+  for (size_t j = 0; j < src.size(); j++) {
+    const int f = m->chunks[src[j]].frame;
+    if (f != last) {
+      const MapFrameRec& r = m->frames[f];
+      MapFrameDev d{};
+      d.pose_slot = r.pose_id >= 0 && live_node(g, r.pose_id, NODE_POSE) ? g->nodes[r.pose_id].slot : -1;
+      if (d.pose_slot >= 0) memcpy(d.T, r.T, sizeof d.T); else p->n_unposed++;
+      p->recs.push_back(d);
+      last = f;
+    }
+    p->fidx[j] = (int)p->recs.size() - 1;
+  }
+}
+
+int map_motion_launch(pps_map* m, const MapMotionPlan& p, const MapFrameDev* d_recs, const int* d_fidx, MapMotionTable* t) {
+  pps_graph* g = m->g;
+  const size_t nf = p.recs.size(), bytes = nf * (12 * sizeof(double) + sizeof(int));
+  for (hipEvent_t& e : m->ev_posed)
+    if (!e) MAP_TRY(m, hipEventCreate(&e));
+  if (bytes > m->motion_cap) {
+    MAP_TRY(m, hipStreamSynchronize(g->stream));
+    (void)hipFree(m->d_motion); m->d_motion = nullptr; m->motion_cap = 0;
+    MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_motion), 2 * bytes));
+    m->motion_cap = 2 * bytes;
+  }
+  MapMotionArgs a{};
+  a.n_frames = (int)nf; a.recs = d_recs;
+  a.pose_est = g->dev.pose_est; a.pose_ld = g->dev.pose_ld;
+  a.motion = reinterpret_cast<double*>(m->d_motion);
+  a.moved = reinterpret_cast<int*>(m->d_motion + nf * 12 * sizeof(double));
+  MAP_TRY(m, hipEventRecord(m->ev_posed[0], g->stream));
+  MAP_TRY(m, launch_map_motion(a, g->stream));
+  MAP_TRY(m, hipEventRecord(m->ev_posed[1], g->stream));
+  m->n_motion = (int)nf; m->n_unposed = p.n_unposed;
+  t->fidx = d_fidx; t->motion = a.motion; t->moved = a.moved;
+  return PPS_OK;
+}
+
+void map_motion_done(pps_map* m) {
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, m->ev_posed[0], m->ev_posed[1]);
+  m->posed_sec[0] = 1e-3 * ms;
+}
 }  // namespace pps_impl
 
 extern "C" {
@@ -86,6 +135,12 @@ int pps_map_destroy(pps_map* m) {
     if (m->h_totals) (void)hipHostFree(m->h_totals);
     for (hipEvent_t e : m->ev) if (e) (void)hipEventDestroy(e);
   }
+  if (m->d_motion || m->ev_posed[0]) {
+    (void)hipSetDevice(m->g->props.device);
+    if (m->g->stream) (void)hipStreamSynchronize(m->g->stream);
+    (void)hipFree(m->d_motion);
+    for (hipEvent_t e : m->ev_posed) if (e) (void)hipEventDestroy(e);
+  }
   map_grid_release(m);
   delete m;
   return PPS_OK;
@@ -109,7 +164,7 @@ int frame_planes_valid(pps_map* m, const char* who, int nplanes, const int* plan
 // A frame from the point where its pixels are on the device (cloud, plane_id: npx records each, complete for the graph's stream): tiling,
 // table growth, count + scan, the totals read back, the capacity check, scatter, the chunk table, counts and sec[0].
 int add_points(pps_map* m, const char* who, const MapPt* cloud, const int* plane_id, int npx, int frame_seq_id, int nplanes,
-               const int* plane_node_ids, int* counts) {
+               const int* plane_node_ids, int* counts, const float* run_T) {
   pps_graph* g = m->g;
   std::vector<int> cnt((size_t)nplanes, 0);
   int64_t kept = 0;
@@ -158,6 +213,10 @@ int add_points(pps_map* m, const char* who, const MapPt* cloud, const int* plane
     m->chunks.push_back(pps_map_chunk{m->n_frames, frame_seq_id, k, plane_node_ids[k], base.base[k], cnt[k]});
   }
   m->used += kept;
+  MapFrameRec rec;                                       // (what pps_map_set_frame_pose with T_wc == NULL will use)
+  rec.frame_seq_id = frame_seq_id;
+  if (run_T) { rec.has_run_T = true; memcpy(rec.run_T, run_T, sizeof rec.run_T); }
+  m->frames.push_back(rec);
   m->n_frames++;
   if (counts) for (int k = 0; k < nplanes; k++) counts[k] = cnt[k];
   return PPS_OK;
@@ -176,7 +235,7 @@ int pps_map_add_frame(pps_map* m, pps_popup* p, int frame_seq_id, int nplanes, c
   if (rc != PPS_OK) return mfail(m, rc, std::string("add_frame: ") + pps_popup_last_error(p));
   if (v.device != m->g->props.device) return mfail(m, PPS_EINVAL, "add_frame: the pop-up context lives on another device than the graph");
   return add_points(m, "add_frame", reinterpret_cast<const MapPt*>(v.cloud), v.plane_id, v.width * v.height, frame_seq_id, nplanes,
-                    plane_node_ids, counts);
+                    plane_node_ids, counts, v.T_wc);
 }
 
 int pps_debug_map_add_points(pps_map* m, const pps_point* cloud, const int* plane_id, int64_t npx, int frame_seq_id, int nplanes,
@@ -200,7 +259,7 @@ int pps_debug_map_add_points(pps_map* m, const pps_point* cloud, const int* plan
     MAP_TRY(m, hipMemcpyAsync(m->d_dbg_cloud, cloud, (size_t)npx * sizeof(MapPt), hipMemcpyHostToDevice, g->stream));
     MAP_TRY(m, hipMemcpyAsync(m->d_dbg_pid, plane_id, (size_t)npx * sizeof(int), hipMemcpyHostToDevice, g->stream));
   }
-  return add_points(m, "debug_add_points", m->d_dbg_cloud, m->d_dbg_pid, (int)npx, frame_seq_id, nplanes, plane_node_ids, counts);
+  return add_points(m, "debug_add_points", m->d_dbg_cloud, m->d_dbg_pid, (int)npx, frame_seq_id, nplanes, plane_node_ids, counts, nullptr);
 }
 
 int pps_map_redirect(pps_map* m, int from_plane, int to_plane) {
@@ -231,9 +290,12 @@ int pps_map_select_host(const pps_map_chunk* chunks, int n, const pps_map_select
   return PPS_OK;
 }
 
-int pps_map_build(pps_map* m, const pps_map_select* sel, int64_t* n_points, int* n_chunks) {
+// pps_map_build and pps_map_build_posed: the selection, the tables of the device and their one upload are the same; the posed build adds
+// the per-chunk frame rows and the frame records to that upload, runs k_map_motion and the posed sibling of k_map_build.
+static int build_common(pps_map* m, const pps_map_select* sel, bool posed, int64_t* n_points, int* n_chunks) {
   if (!m) return PPS_EINVAL;
-  if (!select_valid(sel)) return mfail(m, PPS_EINVAL, "build: old_every and new_every must be positive");
+  const char* who = posed ? "build_posed" : "build";
+  if (!select_valid(sel)) return mfail(m, PPS_EINVAL, std::string(who) + ": old_every and new_every must be positive");
   pps_graph* g = m->g;
   const int n = (int)m->chunks.size();
   std::vector<int32_t> keep((size_t)n);
@@ -248,7 +310,8 @@ int pps_map_build(pps_map* m, const pps_map_select* sel, int64_t* n_points, int*
     c.offset = total; total += c.count;
     built.push_back(c);
   }
-  m->sec[1] = 0;
+  if (posed) { m->posed_sec[0] = m->posed_sec[1] = 0; m->n_motion = 0; m->n_unposed = 0; m->posed_launches = 0; }
+  else m->sec[1] = 0;
   if (total > 0) {
     int rc = prepare_solve(g);
     if (rc != PPS_OK) return mfail(m, rc, g->err);
@@ -257,7 +320,12 @@ int pps_map_build(pps_map* m, const pps_map_select* sel, int64_t* n_points, int*
     if (rc != PPS_OK) return rc;
     if (!m->d_built) MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_built), (size_t)m->cap * sizeof(MapPt)));
     const size_t ns = src.size();
-    const size_t off_src = (ns + 1) * sizeof(long long), off_slot = off_src + ns * sizeof(long long), bytes = off_slot + ns * sizeof(int);
+    MapMotionPlan plan;
+    if (posed) map_motion_plan(m, src, &plan);
+    const size_t nf = plan.recs.size();
+    const size_t off_src = (ns + 1) * sizeof(long long), off_slot = off_src + ns * sizeof(long long), plain = off_slot + ns * sizeof(int);
+    const size_t off_fidx = plain, off_recs = (off_fidx + ns * sizeof(int) + 7) / 8 * 8;
+    const size_t bytes = posed ? off_recs + nf * sizeof(MapFrameDev) : plain;
     std::vector<char> host(bytes);
     long long* out_off = reinterpret_cast<long long*>(host.data());
     long long* src_off = reinterpret_cast<long long*>(host.data() + off_src);
@@ -270,6 +338,10 @@ int pps_map_build(pps_map* m, const pps_map_select* sel, int64_t* n_points, int*
       slot[j] = live_node(g, c.plane_id, NODE_PLANE) ? g->nodes[c.plane_id].slot : -1;
     }
     out_off[ns] = o;
+    if (posed) {
+      memcpy(host.data() + off_fidx, plan.fidx.data(), ns * sizeof(int));
+      memcpy(host.data() + off_recs, plan.recs.data(), nf * sizeof(MapFrameDev));
+    }
     if (bytes > m->sel_cap) {
       MAP_TRY(m, hipStreamSynchronize(g->stream));
       (void)hipFree(m->d_sel); m->d_sel = nullptr; m->sel_cap = 0;
@@ -284,18 +356,96 @@ int pps_map_build(pps_map* m, const pps_map_select* sel, int64_t* n_points, int*
     a.slot = reinterpret_cast<const int*>(m->d_sel + off_slot);
     a.plane_est = g->dev.plane_est; a.plane_ld = g->dev.plane_ld;
     a.store = m->d_store; a.built = m->d_built;
-    MAP_TRY(m, hipEventRecord(m->ev[0], g->stream));
-    MAP_TRY(m, launch_map_build(a, g->stream));
-    MAP_TRY(m, hipEventRecord(m->ev[4], g->stream));
-    MAP_TRY(m, hipStreamSynchronize(g->stream));            // (`host` leaves scope; the result is complete on return)
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, m->ev[0], m->ev[4]);
-    m->sec[1] = 1e-3 * ms;
+    if (posed) {
+      MapMotionTable t{};
+      rc = map_motion_launch(m, plan, reinterpret_cast<const MapFrameDev*>(m->d_sel + off_recs), reinterpret_cast<const int*>(m->d_sel + off_fidx), &t);
+      if (rc != PPS_OK) return rc;
+      MAP_TRY(m, hipEventRecord(m->ev_posed[2], g->stream));
+      MAP_TRY(m, launch_map_build_posed(a, t, g->stream));
+      MAP_TRY(m, hipEventRecord(m->ev_posed[3], g->stream));
+      MAP_TRY(m, hipStreamSynchronize(g->stream));
+      map_motion_done(m);
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, m->ev_posed[2], m->ev_posed[3]);
+      m->posed_sec[1] = 1e-3 * ms;
+      m->posed_launches = 2;
+    } else {
+      MAP_TRY(m, hipEventRecord(m->ev[0], g->stream));
+      MAP_TRY(m, launch_map_build(a, g->stream));
+      MAP_TRY(m, hipEventRecord(m->ev[4], g->stream));
+      MAP_TRY(m, hipStreamSynchronize(g->stream));            // (`host` leaves scope; the result is complete on return)
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, m->ev[0], m->ev[4]);
+      m->sec[1] = 1e-3 * ms;
+    }
   }
   m->built.swap(built);
   m->built_points = total;
   if (n_points) *n_points = total;
   if (n_chunks) *n_chunks = (int)m->built.size();
+  return PPS_OK;
+}
+
+int pps_map_build(pps_map* m, const pps_map_select* sel, int64_t* n_points, int* n_chunks) { return build_common(m, sel, false, n_points, n_chunks); }
+int pps_map_build_posed(pps_map* m, const pps_map_select* sel, int64_t* n_points, int* n_chunks) { return build_common(m, sel, true, n_points, n_chunks); }
+
+int pps_map_set_frame_pose(pps_map* m, int frame, int pose_node_id, const float T_wc[16]) {
+  if (!m) return PPS_EINVAL;
+  if (frame < 0 || frame >= (int)m->frames.size()) return mfail(m, PPS_EINVAL, "set_frame_pose: unknown frame");
+  MapFrameRec& r = m->frames[frame];
+  if (pose_node_id == -1) { r.pose_id = -1; memset(r.T, 0, sizeof r.T); return PPS_OK; }
+  if (!live_node(m->g, pose_node_id, NODE_POSE)) return mfail(m, PPS_EINVAL, "set_frame_pose: pose_node_id is not a live pose node");
+  if (!T_wc && !r.has_run_T) return mfail(m, PPS_EINVAL, "set_frame_pose: the frame was not added from a pop-up run, T_wc must be given");
+  const float* T = T_wc ? T_wc : r.run_T;
+  if (!map_rigid(T)) return mfail(m, PPS_EINVAL, "set_frame_pose: T_wc is not a rigid transform (finite, last row 0 0 0 1, R^T R = I to 1e-4)");
+  r.pose_id = pose_node_id;
+  memcpy(r.T, T, sizeof r.T);
+  return PPS_OK;
+}
+
+int pps_map_frames(const pps_map* m, int cap, pps_map_frame* out, int* n) {
+  if (!m || !n || cap < 0 || (cap > 0 && !out)) return PPS_EINVAL;
+  *n = (int)m->frames.size();
+  const size_t k = std::min<size_t>((size_t)cap, m->frames.size());
+  for (size_t f = 0; f < k; f++) {
+    const MapFrameRec& r = m->frames[f];
+    out[f].frame = (int32_t)f; out[f].frame_seq_id = r.frame_seq_id; out[f].pose_id = r.pose_id; out[f].reserved = 0;
+    memcpy(out[f].T_wc, r.T, sizeof r.T);
+  }
+  return PPS_OK;
+}
+
+int pps_map_frame_motions(pps_map* m, int cap, double* D, int32_t* moved, int* n) {
+  if (!m || !n || cap < 0) return PPS_EINVAL;
+  *n = m->n_motion;
+  const size_t k = std::min<size_t>((size_t)cap, (size_t)m->n_motion);
+  if (k == 0 || (!D && !moved)) return PPS_OK;
+  MAP_TRY(m, hipSetDevice(m->g->props.device));
+  static_assert(sizeof(int32_t) == sizeof(int), "moved flags are int32");
+  if (D) MAP_TRY(m, hipMemcpyAsync(D, m->d_motion, k * 12 * sizeof(double), hipMemcpyDeviceToHost, m->g->stream));
+  if (moved) MAP_TRY(m, hipMemcpyAsync(moved, m->d_motion + (size_t)m->n_motion * 12 * sizeof(double), k * sizeof(int), hipMemcpyDeviceToHost, m->g->stream));
+  MAP_TRY(m, hipStreamSynchronize(m->g->stream));
+  return PPS_OK;
+}
+
+int pps_map_posed_last(const pps_map* m, double sec[2], int* launches, int* n_unposed_frames) {
+  if (!m) return PPS_EINVAL;
+  if (sec) { sec[0] = m->posed_sec[0]; sec[1] = m->posed_sec[1]; }
+  if (launches) *launches = m->posed_launches;
+  if (n_unposed_frames) *n_unposed_frames = m->n_unposed;
+  return PPS_OK;
+}
+
+int pps_map_motion_host(const float T_wc[16], const double tq[7], double D[12]) {
+  if (!T_wc || !tq || !D) return PPS_EINVAL;
+  if (!map_rigid(T_wc)) return PPS_EINVAL;
+  map_motion(T_wc, tq, D);
+  return PPS_OK;
+}
+
+int pps_map_move_point_host(const double* D, const double* abcd, const float xyz[3], float out[3]) {
+  if (!xyz || !out) return PPS_EINVAL;
+  map_move_point(D, abcd, xyz[0], xyz[1], xyz[2], &out[0], &out[1], &out[2]);
   return PPS_OK;
 }
 

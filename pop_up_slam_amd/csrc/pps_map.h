@@ -45,4 +45,23 @@ struct MapBuildArgs {
 };
 hipError_t launch_map_build(const MapBuildArgs& a, hipStream_t st);
 
+// The posed build (include/pps.h: pps_map_build_posed).  One record per frame of the selection: the capture pose and the slot of the
+// frame's pose node in pose_est (-1: the frame has no motion).  k_map_motion writes the motion table from them -- motion[12 * f ..] =
+// (R_D | t_D), moved[f] = 1, or the identity and 0 --, the build reads it through fidx[c], the row of chunk c's frame.
+struct MapFrameDev { float T[16]; int pose_slot; int pad; };
+struct MapMotionArgs {
+  int n_frames;
+  const MapFrameDev* recs;
+  const double* pose_est; int pose_ld;
+  double* motion;                      // [12 * n_frames]
+  int* moved;                          // [n_frames]
+};
+hipError_t launch_map_motion(const MapMotionArgs& a, hipStream_t st);
+struct MapMotionTable {                // what a kernel reads of the table; motion == nullptr: no point is moved
+  const int* fidx;                     // [n_sel]
+  const double* motion;
+  const int* moved;
+};
+hipError_t launch_map_build_posed(const MapBuildArgs& a, const MapMotionTable& t, hipStream_t st);
+
 }  // namespace pps

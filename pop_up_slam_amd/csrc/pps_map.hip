@@ -14,9 +14,14 @@
 // alone (LDS operations of one wave execute in order), so there is no workgroup barrier in pass 1 and 3.
 //
 // Compiled without contraction (Makefile): k_map_build gives the bits of k_reproject (pps_project.h).
+//
+// The posed build (pps_map_build_posed) moves every point rigidly with the correction of its frame's pose before it is projected:
+// k_map_motion computes one motion per frame of the selection from pose_est in place (pps_map_move.h: the text the host entry points are
+// compiled from), k_map_build_posed is k_map_build with the motion of the point's frame applied.
 #include <hip/hip_runtime.h>
 
 #include "pps_map.h"
+#include "pps_map_move.h"
 #include "pps_project.h"
 
 namespace pps {
@@ -148,6 +153,85 @@ __global__ __launch_bounds__(kMapThreads) void k_map_build(MapBuildArgs a) {
   a.built[i] = pt;
 }
 
+// One thread per frame of the selection: D = (R R0^T | t - R_D t0) from the frame's capture pose and the estimate of its pose node.
+__global__ __launch_bounds__(kMapThreads) void k_map_motion(MapMotionArgs a) {
+  const int f = blockIdx.x * kMapThreads + threadIdx.x;
+  if (f >= a.n_frames) return;
+  const MapFrameDev r = a.recs[f];
+  double D[12] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+  int mv = 0;
+  if (r.pose_slot >= 0) {
+    double tq[7];
+    for (int k = 0; k < 7; k++) tq[k] = a.pose_est[(size_t)k * a.pose_ld + r.pose_slot];
+    map_motion(r.T, tq, D);
+    mv = 1;
+  }
+  for (int k = 0; k < 12; k++) a.motion[12 * (size_t)f + k] = D[k];
+  a.moved[f] = mv;
+}
+
+// k_map_build with the motion of the point's frame: the window in LDS also holds the row of every chunk's frame in the motion table.
+// The 256 points of a workgroup belong to few frames (a chunk is one plane of one frame), so a motion is not loaded per point: the lanes
+// of a wave that share a frame find each other with a ballot, the 96 bytes of that frame's motion are read at a wave-uniform address
+// (scalar loads, one turn per distinct frame of the wave), and the lanes of that frame move their point.  16 B in, 16 B out.
+__global__ __launch_bounds__(kMapThreads) void k_map_build_posed(MapBuildArgs a, const int* __restrict__ fidx, const double* __restrict__ motion,
+                                                                 const int* __restrict__ moved) {
+  __shared__ long long s_off[kMapThreads + 1], s_src[kMapThreads];
+  __shared__ int s_slot[kMapThreads], s_fidx[kMapThreads];
+  __shared__ int s_c0;
+  const int tid = threadIdx.x;
+  const long long first = (long long)blockIdx.x * kMapThreads;
+  if (tid == 0) {
+    int lo = 0, hi = a.n_sel;                                    // out_off[lo] <= first < out_off[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (a.out_off[mid] <= first) lo = mid; else hi = mid;
+    }
+    s_c0 = lo;
+  }
+  __syncthreads();
+  const int c0 = s_c0;
+  for (int j = tid; j <= kMapThreads; j += kMapThreads) s_off[j] = c0 + j <= a.n_sel ? a.out_off[c0 + j] : 0x7fffffffffffffffLL;
+  if (c0 + tid < a.n_sel) { s_src[tid] = a.src_off[c0 + tid]; s_slot[tid] = a.slot[c0 + tid]; s_fidx[tid] = fidx[c0 + tid]; }
+  __syncthreads();
+  const long long i = first + tid;
+  const bool in = i < a.n_out;                                   // (no early return: the ballots below are the whole wave's)
+  MapPt pt = {0.f, 0.f, 0.f, 0u};
+  int sl = -1, f = -1;
+  if (in) {
+    int lo = 0, hi = kMapThreads;                                // s_off[lo] <= i < s_off[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (s_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    pt = a.store[s_src[lo] + (i - s_off[lo])];
+    sl = s_slot[lo]; f = s_fidx[lo];
+  }
+  double p[4] = {0.0, 0.0, 1.0, 0.0};
+  if (sl >= 0)
+    for (int k = 0; k < 4; k++) p[k] = a.plane_est[(size_t)k * a.plane_ld + sl];
+  unsigned long long rem = __ballot(f >= 0);
+  while (rem) {                                                  // one turn per distinct frame among the 64 points (wave-uniform)
+    const int leader = __ffsll((long long)rem) - 1;
+    const int F = __builtin_amdgcn_readlane(f, leader);
+    const unsigned long long mk = __ballot(f == F);
+    if (moved[F]) {
+      double D[12];
+      for (int k = 0; k < 12; k++) D[k] = motion[12 * (size_t)F + k];
+      if (f == F) {
+        double x = (double)pt.x, y = (double)pt.y, z = (double)pt.z;
+        map_move_xyz(D, &x, &y, &z);
+        if (sl >= 0) project_to_plane_f64(p, x, y, z, &pt.x, &pt.y, &pt.z);
+        else { pt.x = (float)x; pt.y = (float)y; pt.z = (float)z; }          // (the landmark is gone: moved, not projected)
+      }
+    } else if (f == F && sl >= 0) {                              // a frame without motion: k_map_build's point
+      project_to_plane_f32(p, pt.x, pt.y, pt.z, &pt.x, &pt.y, &pt.z);
+    }
+    rem &= ~mk;
+  }
+  if (in) a.built[i] = pt;
+}
+
 }  // namespace
 
 hipError_t launch_map_count(const MapPt* cloud, const int* plane_id, int npx, int nplanes, int* table, int* totals, hipStream_t st) {
@@ -172,6 +256,20 @@ hipError_t launch_map_build(const MapBuildArgs& a, hipStream_t st) {
   const long long nwg = (a.n_out + kMapThreads - 1) / kMapThreads;
   if (nwg > 0x7fffffffLL) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_map_build, dim3((unsigned int)nwg), dim3(kMapThreads), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_motion(const MapMotionArgs& a, hipStream_t st) {
+  if (a.n_frames <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_map_motion, dim3((a.n_frames + kMapThreads - 1) / kMapThreads), dim3(kMapThreads), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_map_build_posed(const MapBuildArgs& a, const MapMotionTable& t, hipStream_t st) {
+  if (a.n_out <= 0 || a.n_sel <= 0) return hipSuccess;
+  const long long nwg = (a.n_out + kMapThreads - 1) / kMapThreads;
+  if (nwg > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_map_build_posed, dim3((unsigned int)nwg), dim3(kMapThreads), 0, st, a, t.fidx, t.motion, t.moved);
   return hipGetLastError();
 }
 

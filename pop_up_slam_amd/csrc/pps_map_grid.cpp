@@ -76,7 +76,7 @@ bool vote_combines() {
   return !(v && std::string(v) == "direct");
 }
 
-int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params& prm, int64_t* n_points, int* n_planes) {
+int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params& prm, bool posed, int64_t* n_points, int* n_planes) {
   pps_graph* g = m->g;
   MapGrid& G = *m->grid;
   const double inv_cell = 1.0 / prm.cell;
@@ -123,8 +123,12 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
       if (!e) MAP_TRY(m, hipEventCreate(&e));
     // ---- tables of the selection
     const size_t ns = src.size();
+    MapMotionPlan plan;                                              // posed: the frame rows and records ride in the same upload
+    if (posed) map_motion_plan(m, src, &plan);
+    const size_t nf = plan.recs.size();
     const size_t off_src = (ns + 1) * sizeof(long long), off_slot = off_src + ns * sizeof(long long), off_lm = off_slot + ns * sizeof(int),
-                 bytes = off_lm + ns * sizeof(int);
+                 off_fidx = off_lm + ns * sizeof(int), off_recs = (off_fidx + ns * sizeof(int) + 7) / 8 * 8,
+                 bytes = posed ? off_recs + nf * sizeof(MapFrameDev) : off_fidx;
     std::vector<char> host(bytes);
     long long* out_off = reinterpret_cast<long long*>(host.data());
     long long* src_off = reinterpret_cast<long long*>(host.data() + off_src);
@@ -140,6 +144,10 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
       lm[j] = live ? row_of[c.plane_id] : -1;
     }
     out_off[ns] = o;
+    if (posed) {
+      memcpy(host.data() + off_fidx, plan.fidx.data(), ns * sizeof(int));
+      memcpy(host.data() + off_recs, plan.recs.data(), nf * sizeof(MapFrameDev));
+    }
     std::vector<GridPlaneDev> pd((size_t)nL);
     for (int L = 0; L < nL; L++) {
       pd[L] = GridPlaneDev{};
@@ -168,15 +176,21 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
     a.store = m->d_store;
     a.planes = G.d_planes.p; a.n_planes = nL;
     a.inv_cell = inv_cell;
+    MapMotionTable mt{};                                             // (all null: B is pps_map_build's)
+    if (posed) {
+      const int rc = map_motion_launch(m, plan, reinterpret_cast<const MapFrameDev*>(G.sel.p + off_recs), reinterpret_cast<const int*>(G.sel.p + off_fidx), &mt);
+      if (rc != PPS_OK) return rc;
+    }
     // ---- pass 1: extents
     GridExtent* d_ext = reinterpret_cast<GridExtent*>(G.small.p);
     unsigned long long* d_dropped = reinterpret_cast<unsigned long long*>(G.small.p + (size_t)nL * sizeof(GridExtent));
     MAP_TRY(m, hipEventRecord(G.ev[1], g->stream));
-    MAP_TRY(m, launch_grid_extent(a, d_ext, d_dropped, g->stream));
+    MAP_TRY(m, launch_grid_extent(a, d_ext, d_dropped, g->stream, mt));
     MAP_TRY(m, hipEventRecord(G.ev[2], g->stream));
     MAP_TRY(m, hipMemcpyAsync(small.data(), G.small.p, small_bytes, hipMemcpyDeviceToHost, g->stream));
     MAP_TRY(m, hipStreamSynchronize(g->stream));
     tot.launches = 1;
+    if (posed) { map_motion_done(m); m->posed_launches = 1; }        // (k_map_motion: counted by pps_map_posed_last)
     ext = reinterpret_cast<GridExtent*>(small.data());
     tot.n_dropped = (int64_t) * reinterpret_cast<unsigned long long*>(small.data() + (size_t)nL * sizeof(GridExtent));
     // ---- the boxes and the layout of the cell arrays
@@ -214,7 +228,7 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
       MAP_TRY(m, hipEventRecord(G.ev[3], g->stream));
       MAP_TRY(m, hipMemsetAsync(G.key.p, 0, (size_t)all * sizeof(unsigned long long), g->stream));
       MAP_TRY(m, hipMemsetAsync(G.cnt.p, 0, (size_t)all * sizeof(unsigned int), g->stream));
-      MAP_TRY(m, launch_grid_vote(a, prm.rule == PPS_GRID_OLDEST, vote_combines(), G.key.p, G.cnt.p, g->stream));
+      MAP_TRY(m, launch_grid_vote(a, prm.rule == PPS_GRID_OLDEST, vote_combines(), G.key.p, G.cnt.p, g->stream, mt));
       MAP_TRY(m, hipEventRecord(G.ev[4], g->stream));
       // ---- pass 3: emission
       GridEmitArgs e{};
@@ -235,7 +249,7 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
         MAP_TRY(m, G.out_pts.reserve(nc)); MAP_TRY(m, G.out_cnt.reserve(nc)); MAP_TRY(m, G.out_ij.reserve(2 * nc)); MAP_TRY(m, G.out_src.reserve(nc));
         e.pts = G.out_pts.p; e.counts = G.out_cnt.p; e.ij = G.out_ij.p; e.src = G.out_src.p;
         MAP_TRY(m, hipEventRecord(G.ev[6], g->stream));
-        MAP_TRY(m, launch_grid_emit(a, e, g->stream));
+        MAP_TRY(m, launch_grid_emit(a, e, g->stream, mt));
         MAP_TRY(m, hipEventRecord(G.ev[7], g->stream));
         tot.launches += 1;
       }
@@ -272,8 +286,9 @@ void pps_map_grid_default_params(pps_map_grid_params* p) {
   p->cell = 0.02; p->rule = PPS_GRID_NEWEST; p->min_count = 1; p->max_cells = (int64_t)1 << 26;
 }
 
-int pps_map_build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params* prm, int64_t* n_points, int* n_planes) {
+static int build_grid_checked(pps_map* m, const pps_map_select* sel, const pps_map_grid_params* prm, bool posed, int64_t* n_points, int* n_planes) {
   if (!m) return PPS_EINVAL;
+  if (posed) { m->posed_sec[0] = m->posed_sec[1] = 0; m->n_motion = 0; m->n_unposed = 0; m->posed_launches = 0; }
   if (m->grid) { m->grid->valid = false; m->grid->planes.clear(); m->grid->tot = pps_map_grid_totals{}; }      // a call that fails leaves no grid
   pps_map_grid_params p;
   pps_map_grid_default_params(&p);
@@ -287,9 +302,16 @@ int pps_map_build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid
     m->grid = new (std::nothrow) MapGrid();
     if (!m->grid) return mfail(m, PPS_ENOMEM, "build_grid: out of host memory");
   }
-  const int rc = build_grid(m, sel, p, n_points, n_planes);
+  const int rc = build_grid(m, sel, p, posed, n_points, n_planes);
   if (rc != PPS_OK) { m->grid->valid = false; m->grid->planes.clear(); m->grid->tot = pps_map_grid_totals{}; }
   return rc;
+}
+
+int pps_map_build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params* prm, int64_t* n_points, int* n_planes) {
+  return build_grid_checked(m, sel, prm, false, n_points, n_planes);
+}
+int pps_map_build_grid_posed(pps_map* m, const pps_map_select* sel, const pps_map_grid_params* prm, int64_t* n_points, int* n_planes) {
+  return build_grid_checked(m, sel, prm, true, n_points, n_planes);
 }
 
 int pps_map_grid_planes(const pps_map* m, int cap, pps_map_grid_plane* out, int* n) {

@@ -611,7 +611,7 @@ int pps::popup_last_run(pps_popup* p, PopupRunView* v) {
   const int rc = popup_settle(p);
   if (rc != PPS_OK) return rc;
   v->device = p->device; v->width = p->width; v->height = p->height; v->step = p->last_step;
-  v->cloud = p->d_cloud; v->plane_id = p->d_pid;
+  v->cloud = p->d_cloud; v->plane_id = p->d_pid; v->T_wc = p->last_T;
   return PPS_OK;
 }
 extern "C" {

@@ -9,6 +9,7 @@ struct PopupRunView {
   int device, width, height, step;
   const pps_point* cloud;      // width * height, every pixel written (valid bit = bit 24 of rgba)
   const int* plane_id;         // width * height, -1 = none
+  const float* T_wc;           // the 16 floats the run was given (row-major, sensor -> world)
 };
 // PPS_ESTATE (answered on the host, before anything is waited for): no run yet, or the run had the plane-id output switched off.
 // A run in flight is waited for, like every reader of a run does.  The message goes to pps_popup_last_error(p).

@@ -121,6 +121,7 @@ class PopupSlamPipeline:
         self.pose_nodes, self.landmarks = [], {}
         self.frames = []          # (pose node, seg2d, fids)
         self.assoc_log = []       # per frame: landmark key chosen for every plane (association mode)
+        self.last_planes = []     # plane node of every plane of the frame being processed, ground first (what a dense map files its chunks under)
         self.k = 0
 
     def _associate(self, est, fr, planes, seg3d):
@@ -190,6 +191,7 @@ class PopupSlamPipeline:
                 fids.append(-1)
             else:
                 fids.append(g.add_plane_obs(p, self.landmarks[key], m, synth._ut_diag([1.0 / sig] * 3)))
+        self.last_planes = [self.landmarks[key] for key in keys]
         self.frames.append((p, fr.seg2d, fids))
         if self.k % 5 == 0:                                                      # Mapping.cpp:551-554
             it = g.batch_optimize()
@@ -230,6 +232,7 @@ class PopupSlamPipeline:
             self.landmark_fn(node, j, self.k, seg2d[j], seg3d_xy[j])              # copy_plane (:526)
             chosen.append(node)
         self.assoc_log.append(chosen)
+        self.last_planes = list(chosen)
         self.frames.append((p, fr.seg2d, fids))
         if self.k % 5 == 0:
             it = g.batch_optimize()
@@ -248,18 +251,24 @@ def gpu_pipeline_finish(pp, stats):
 
 
 def gpu_pipeline(width=640, height=480, K=synth.K_TUM, jacobian_mode=0, step=2, with_image=True, seed=0, associate=False,
-                 assoc_params=None, repop=False, async_popup=False):
-    """Product pipeline: Graph + Popup on the GPU; pop-up results stay on the device."""
+                 assoc_params=None, repop=False, async_popup=False, map_points=0):
+    """Product pipeline: Graph + Popup on the GPU; pop-up results stay on the device.  map_points > 0: the pipeline keeps a dense map of
+    that capacity (stats["map"]); every frame is added to it after its graph update and registered with its pose node, so that
+    Map.build(posed=True) follows the optimised trajectory."""
     import pop_up_slam_amd as P
+    if map_points > 0 and async_popup:
+        raise ValueError("gpu_pipeline: a kept map reads every frame's pixels before the next run starts; use async_popup=False with map_points")
     invK = np.linalg.inv(K).astype(np.float32)
     g = P.Graph(jacobian_mode=jacobian_mode)
     g.frames_set_calibration(invK)
     pp = P.Popup(width, height, invK)
-    pp.set_outputs(depth=False, plane_id=False)      # the frame loop consumes the planes and the cloud only
+    pp.set_outputs(depth=False, plane_id=map_points > 0)      # the frame loop consumes the planes and the cloud only; a map also the plane ids
     if with_image:
         rng = np.random.default_rng(seed)
         pp.set_image(rng.integers(0, 256, size=(height, width, 3), dtype=np.uint8))
     stats = {"popup_kernel_s": 0.0, "points": 0}
+    if map_points > 0:
+        stats["map"] = P.Map(g, map_points)
 
     def popup_fn(seg, T32, polys):
         if async_popup and not associate:
@@ -282,6 +291,10 @@ def gpu_pipeline(width=640, height=480, K=synth.K_TUM, jacobian_mode=0, step=2, 
     def refresh_fn(pl, pose_node, seg, fids):
         g.frames_add(pose_node, seg, fids)
         g.refresh_measurements()
+        if map_points > 0:                               # (a run in flight is waited for; T_wc: the pose this frame's run was given)
+            dense = stats["map"]
+            dense.add_frame(pp, pl.k, pl.last_planes)
+            dense.set_frame_pose(dense.info()["n_frames"] - 1, pose_node)
 
     assoc_fn = landmark_fn = None
     if associate:

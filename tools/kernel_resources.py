@@ -93,14 +93,17 @@ DESIGN_KERNELS = [
     ("k_linearize_repop_robust<2>", "... Factor2 edges, pseudo-Huber"), ("k_chi2_robust<2>", "robust chi2 at the stored state"), ("k_chi2_trial_robust<2>", "... of the one-step loop's trial"),
     ("k_linearize_repop_robust<3>", "... Factor2 edges, Cauchy"), ("k_chi2_robust<3>", "robust chi2 at the stored state"), ("k_chi2_trial_robust<3>", "... of the one-step loop's trial"),
     ("k_loop_gate", "pps_loop_gate: a wave per candidate loop closure, DESIGN.md section 5h"),
+    # the dense map's builds (pps_map.hip): the plain one as the yardstick of its posed sibling
+    ("k_map_build", "pps_map_build: 16 B in, 16 B out per point"), ("k_map_build_posed", "pps_map_build_posed: ... with the frame's motion from scalar loads"),
+    ("k_map_motion", "one thread per frame of the selection"),
 ]
 TABLE_BEGIN, TABLE_END = "<!-- kernel-table:begin (tools/kernel_resources.py --update-design) -->", "<!-- kernel-table:end -->"
 
 
 def built_table():
-    """{name: dict} of every kernel of the solver objects (and of pps_loop.hip) the Makefile built"""
+    """{name: dict} of every kernel of the solver objects (and of pps_loop.hip, pps_map.hip) the Makefile built"""
     out = {}
-    for f in ("pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip", "pps_robust.hip", "pps_loop.hip"):
+    for f in ("pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip", "pps_robust.hip", "pps_loop.hip", "pps_map.hip"):
         for r in resources(os.path.join(CSRC, f), [], built=True):
             v = int(r["vgpr_count"])
             out[short_name(r["name"])] = {"vgpr": v, "agpr": int(r["agpr_count"]), "waves": min(8, 512 // max(8, (v + 7) // 8 * 8)),
