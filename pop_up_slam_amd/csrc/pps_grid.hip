@@ -1,7 +1,7 @@
 // pps_grid.hip -- the grid map on the device: one point per lattice cell of every landmark plane (include/pps.h: pps_map_build_grid).
 //
-// B, the map k_map_build would write for the selection, is never materialised: each pass walks B's indices, finds a point's chunk the way
-// k_map_build does (offset table, window of 256 chunks in LDS), projects the raw point with project_to_plane_f32 -- B's bits -- and
+// B, the map k_map_build would write for the selection, is never materialised: each pass walks B's indices, finds a point's chunk in
+// k_map_build's chunk window (pps_map_window.h), projects the raw point with project_to_plane_f32 -- B's bits -- and
 // computes its cell with grid_cell (pps_grid_cell.h), the text the host entry points are compiled from.
 //
 //   k_grid_extent   per landmark min / max of i and j, and the points that voted.  Integer atomics after a reduction inside the wave.
@@ -26,6 +26,7 @@
 #include "pps_grid.h"
 #include "pps_grid_cell.h"
 #include "pps_map_move.h"
+#include "pps_map_window.h"
 #include "pps_project.h"
 
 namespace pps {
@@ -33,37 +34,11 @@ namespace {
 
 constexpr int kGridExtentTurns = 4;     // landmarks reduced inside a wave before the rest of its lanes send their own atomics
 
-__device__ __forceinline__ int grid_lanes_below(unsigned long long m) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
-}
-
-// the chunk window of a workgroup of 256 consecutive points of B (k_map_build's scheme)
-struct GridWindow {
-  long long off[kMapThreads + 1], src[kMapThreads];
-  int slot[kMapThreads], lm[kMapThreads];
-  int c0;
-};
-
-__device__ __forceinline__ void grid_stage_window(const GridSelArgs& a, long long first, GridWindow& w) {
-  const int tid = threadIdx.x;
-  if (tid == 0) {
-    int lo = 0, hi = a.n_sel;                                    // out_off[lo] <= first < out_off[hi]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (a.out_off[mid] <= first) lo = mid; else hi = mid;
-    }
-    w.c0 = lo;
-  }
-  __syncthreads();
-  const int c0 = w.c0;
-  for (int j = tid; j <= kMapThreads; j += kMapThreads) w.off[j] = c0 + j <= a.n_sel ? a.out_off[c0 + j] : 0x7fffffffffffffffLL;
-  if (c0 + tid < a.n_sel) { w.src[tid] = a.src_off[c0 + tid]; w.slot[tid] = a.slot[c0 + tid]; w.lm[tid] = a.lm[c0 + tid]; }
-  __syncthreads();
-}
+typedef MapWindow<true> GridWindow;       // the chunk window of 256 consecutive points of B; its fourth row: the landmark of every chunk
 
 // The point B holds for the stored point *pt of chunk c (a row of the selection; sl: its landmark's slot, -1: gone).  Without a motion
 // table B is pps_map_build's: project_to_plane_f32 of the raw point.  With one B is the posed map (pps_map_build_grid_posed): a point of
-// a frame that has a motion is moved and then projected (map_move_point, pps_map_move.h), every other point is formed as before.
+// a frame that has a motion is moved and then projected (map_moved_point, pps_map_move.h), every other point is formed as before.
 __device__ __forceinline__ void grid_b_point(const GridSelArgs& a, const MapMotionTable& mt, int c, int sl, MapPt* pt) {
   double p[4] = {0.0, 0.0, 1.0, 0.0};
   if (sl >= 0)
@@ -73,10 +48,7 @@ __device__ __forceinline__ void grid_b_point(const GridSelArgs& a, const MapMoti
     if (mt.moved[f]) {
       double D[12];
       for (int k = 0; k < 12; k++) D[k] = mt.motion[12 * (size_t)f + k];
-      double x = (double)pt->x, y = (double)pt->y, z = (double)pt->z;
-      map_move_xyz(D, &x, &y, &z);
-      if (sl >= 0) project_to_plane_f64(p, x, y, z, &pt->x, &pt->y, &pt->z);
-      else { pt->x = (float)x; pt->y = (float)y; pt->z = (float)z; }
+      map_moved_point(D, p, sl >= 0, &pt->x, &pt->y, &pt->z);
       return;
     }
   }
@@ -86,12 +58,8 @@ __device__ __forceinline__ void grid_b_point(const GridSelArgs& a, const MapMoti
 // point i of B (i < n_out): its landmark row (-1: it passes through) and, for a landmark's point, its cell; false if it is dropped
 __device__ __forceinline__ bool grid_point_cell(const GridSelArgs& a, const MapMotionTable& mt, const GridWindow& w, long long i, int* lm, long long* ci,
                                                 long long* cj) {
-  int lo = 0, hi = kMapThreads;                                  // off[lo] <= i < off[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (w.off[mid] <= i) lo = mid; else hi = mid;
-  }
-  const int L = w.lm[lo];
+  const int lo = map_window_find(w, i);
+  const int L = w.aux[lo];
   *lm = L;
   if (L < 0) return true;
   MapPt pt = a.store[w.src[lo] + (i - w.off[lo])];
@@ -106,7 +74,7 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_extent(GridSelArgs a, MapM
   __shared__ GridWindow w;
   const int lane = threadIdx.x & 63;
   const long long first = (long long)blockIdx.x * kMapThreads;
-  grid_stage_window(a, first, w);
+  map_stage_window(w, a.out_off, a.src_off, a.slot, a.lm, a.n_sel, first);
   const long long i = first + threadIdx.x;
   int lm = -1;
   long long ci = 0, cj = 0;
@@ -152,7 +120,7 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_vote(GridSelArgs a, MapMot
   __shared__ GridWindow w;
   const int lane = threadIdx.x & 63;
   const long long first = (long long)blockIdx.x * kMapThreads;
-  grid_stage_window(a, first, w);
+  map_stage_window(w, a.out_off, a.src_off, a.slot, a.lm, a.n_sel, first);
   const long long i = first + threadIdx.x;
   long long c = -1;                                              // the point's cell in the arrays, -1: it does not vote
   if (i < a.n_out) {
@@ -189,13 +157,8 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_count(GridEmitArgs e, long
   const long long c0 = (long long)blockIdx.x * cpw, c1 = min(e.n_cells_all, c0 + cpw);
   int n = 0;
   for (long long c = c0 + tid; c < c1; c += kMapThreads) n += e.cnt[c] >= e.min_count ? 1 : 0;
-  s_sum[tid] = n;
-  __syncthreads();
-  for (int d = kMapThreads / 2; d > 0; d >>= 1) {
-    if (tid < d) s_sum[tid] += s_sum[tid + d];
-    __syncthreads();
-  }
-  if (tid == 0) e.tile_count[blockIdx.x] = s_sum[0];
+  const int all = map_block_sum(s_sum, n);
+  if (tid == 0) e.tile_count[blockIdx.x] = all;
 }
 
 // exclusive scan of the tile counts (one workgroup); tile_prefix[nT] = the sum
@@ -206,17 +169,10 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_scan(const int* __restrict
   const int a = (int)min((long long)nT, (long long)tid * seg), b = (int)min((long long)nT, (long long)a + seg);
   long long sum = 0;
   for (int i = a; i < b; i++) sum += tile_count[i];
-  s_sum[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < kMapThreads; d <<= 1) {
-    const long long v = tid >= d ? s_sum[tid - d] : 0;
-    __syncthreads();
-    s_sum[tid] += v;
-    __syncthreads();
-  }
-  long long run = s_sum[tid] - sum;
+  const long long upto = map_block_scan(s_sum, sum);
+  long long run = upto - sum;
   for (int i = a; i < b; i++) { tile_prefix[i] = run; run += tile_count[i]; }
-  if (tid == kMapThreads - 1) tile_prefix[nT] = s_sum[tid];
+  if (tid == kMapThreads - 1) tile_prefix[nT] = upto;
 }
 
 // emitted cells before the first cell of landmark L (one workgroup per row of plane_base): the prefix of its tile plus the tile's cells before it
@@ -227,13 +183,8 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_plane_off(GridEmitArgs e, 
   const long long T = c1 / cpw, c0 = T * cpw;
   int n = 0;
   for (long long c = c0 + tid; c < c1; c += kMapThreads) n += e.cnt[c] >= e.min_count ? 1 : 0;
-  s_sum[tid] = n;
-  __syncthreads();
-  for (int d = kMapThreads / 2; d > 0; d >>= 1) {
-    if (tid < d) s_sum[tid] += s_sum[tid + d];
-    __syncthreads();
-  }
-  if (tid == 0) e.plane_off[blockIdx.x] = e.tile_prefix[T] + s_sum[0];
+  const int before = map_block_sum(s_sum, n);
+  if (tid == 0) e.plane_off[blockIdx.x] = e.tile_prefix[T] + before;
 }
 
 __global__ __launch_bounds__(kMapThreads) void k_grid_emit(GridSelArgs a, MapMotionTable mt, GridEmitArgs e, long long cpw) {
@@ -253,21 +204,12 @@ __global__ __launch_bounds__(kMapThreads) void k_grid_emit(GridSelArgs a, MapMot
     for (int k = 0; k < kMapWaves; k++) { const int v = s_wave[k]; all += v; if (k < wv) before += v; }
     __syncthreads();
     if (keep) {
-      const long long pos = run + before + grid_lanes_below(m);
-      int lo = 0, hi = a.n_planes;                               // plane_base[lo] <= c < plane_base[hi]
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (e.plane_base[mid] <= c) lo = mid; else hi = mid;
-      }
-      const GridPlaneDev& pl = a.planes[lo];
+      const long long pos = run + before + map_lanes_below(m);
+      const GridPlaneDev& pl = a.planes[map_find(e.plane_base, a.n_planes, c)];
       const long long rel = c - pl.base;
       const long long dj = rel / pl.ni, di = rel - dj * pl.ni;
       const long long idx = grid_key_index(e.key[c], e.oldest);
-      lo = 0; hi = a.n_sel;                                      // out_off[lo] <= idx < out_off[hi]
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.out_off[mid] <= idx) lo = mid; else hi = mid;
-      }
+      const int lo = map_find(a.out_off, a.n_sel, idx);
       MapPt pt = {0.f, 0.f, 0.f, 0u};
       if (idx >= 0 && idx < a.n_out) {                           // (always: the key of a counted cell is a point's)
         pt = a.store[a.src_off[lo] + (idx - a.out_off[lo])];

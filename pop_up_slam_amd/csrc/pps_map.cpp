@@ -1,5 +1,6 @@
-// pps_map.cpp -- host side of the dense map (include/pps.h: pps_map_*): the chunk table, the thinning of main_3d.cpp:544-562, and the calls
-// that drive the kernels of pps_map.hip.
+// pps_map.cpp -- host side of the dense map (include/pps.h: pps_map_*): the chunk table, the thinning of main_3d.cpp:544-562, the
+// selection record both builds and both grids start from (MapSelection, pps_map_host.h), and the calls that drive the kernels of
+// pps_map.hip.
 //
 // Streams.  A pop-up context runs on its own stream, the map's kernels on the stream of the graph it belongs to.  pps_map_add_frame first
 // waits -- on the host -- for the run of the pop-up context (popup_last_run), so the cloud and the plane-id map are complete before the
@@ -36,25 +37,64 @@ void select_chunks(const pps_map_chunk* c, int n, const pps_map_select* s, int32
   }
 }
 
-int table_copy(const std::vector<pps_map_chunk>& t, int cap, pps_map_chunk* out, int* n) {
-  if (!n || cap < 0 || (cap > 0 && !out)) return PPS_EINVAL;
-  *n = (int)t.size();
-  const size_t k = std::min<size_t>((size_t)cap, t.size());
-  if (k) memcpy(out, t.data(), k * sizeof(pps_map_chunk));
-  return PPS_OK;
-}
-
-int map_events(pps_map* m) {
-  for (hipEvent_t& e : m->ev)
-    if (!e) MAP_TRY(m, hipEventCreate(&e));
-  return PPS_OK;
-}
-
 }  // namespace
 
 namespace pps_impl {
 bool map_select_valid(const pps_map_select* s) { return select_valid(s); }
-void map_select_chunks(const pps_map_chunk* c, int n, const pps_map_select* s, int32_t* keep) { select_chunks(c, n, s, keep); }
+
+int map_use_device(pps_map* m) {
+  MAP_TRY(m, hipSetDevice(m->g->props.device));
+  m->on_device = true;
+  return PPS_OK;
+}
+
+void MapSelection::select(const pps_map* m, const pps_map_select* sel) {
+  const int nc = (int)m->chunks.size();
+  keep.resize((size_t)nc);
+  select_chunks(m->chunks.data(), nc, sel, keep.data());
+  src.clear(); total = 0;
+  for (int i = 0; i < nc; i++) {
+    if (!keep[i]) continue;
+    if (m->chunks[i].count > 0) src.push_back(i);
+    total += m->chunks[i].count;
+  }
+}
+
+int MapSelection::upload(pps_map* m, bool posed, const std::map<int, int>* row_of, MapBuf<char>* buf, size_t over, MapSpan* span) {
+  const pps_graph* g = m->g;
+  const size_t ns = src.size();
+  if (posed) map_motion_plan(m, src, &plan);
+  at.src_off = (ns + 1) * sizeof(long long);
+  at.slot = at.src_off + ns * sizeof(long long);
+  at.lm = at.slot + ns * sizeof(int);
+  at.fidx = at.lm + (row_of ? ns * sizeof(int) : 0);
+  at.recs = (at.fidx + ns * sizeof(int) + 7) / 8 * 8;
+  at.bytes = posed ? at.recs + plan.recs.size() * sizeof(MapFrameDev) : at.fidx;
+  host.assign(at.bytes, 0);
+  long long* h_out = reinterpret_cast<long long*>(host.data());
+  long long* h_src = reinterpret_cast<long long*>(host.data() + at.src_off);
+  int* h_slot = reinterpret_cast<int*>(host.data() + at.slot);
+  int* h_lm = reinterpret_cast<int*>(host.data() + at.lm);
+  long long o = 0;
+  for (size_t j = 0; j < ns; j++) {
+    const pps_map_chunk& c = m->chunks[src[j]];
+    h_out[j] = o; o += c.count;
+    h_src[j] = c.offset;
+    const bool live = live_node(g, c.plane_id, NODE_PLANE);
+    h_slot[j] = live ? g->nodes[c.plane_id].slot : -1;
+    if (row_of) h_lm[j] = live ? row_of->at(c.plane_id) : -1;
+  }
+  h_out[ns] = o;
+  if (posed) {
+    memcpy(host.data() + at.fidx, plan.fidx.data(), ns * sizeof(int));
+    memcpy(host.data() + at.recs, plan.recs.data(), plan.recs.size() * sizeof(MapFrameDev));
+  }
+  MAP_TRY(m, buf->reserve(at.bytes, g->stream, over));
+  if (span) MAP_TRY(m, span->begin(g->stream));
+  MAP_TRY(m, hipMemcpyAsync(buf->p, host.data(), at.bytes, hipMemcpyHostToDevice, g->stream));
+  dev = buf->p;
+  return PPS_OK;
+}
 
 void map_motion_plan(const pps_map* m, const std::vector<int>& src, MapMotionPlan* p) {
   const pps_graph* g = m->g;
@@ -74,34 +114,21 @@ void map_motion_plan(const pps_map* m, const std::vector<int>& src, MapMotionPla
   }
 }
 
-int map_motion_launch(pps_map* m, const MapMotionPlan& p, const MapFrameDev* d_recs, const int* d_fidx, MapMotionTable* t) {
+int map_motion_launch(pps_map* m, const MapSelection& s, MapMotionTable* t) {
   pps_graph* g = m->g;
-  const size_t nf = p.recs.size(), bytes = nf * (12 * sizeof(double) + sizeof(int));
-  for (hipEvent_t& e : m->ev_posed)
-    if (!e) MAP_TRY(m, hipEventCreate(&e));
-  if (bytes > m->motion_cap) {
-    MAP_TRY(m, hipStreamSynchronize(g->stream));
-    (void)hipFree(m->d_motion); m->d_motion = nullptr; m->motion_cap = 0;
-    MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_motion), 2 * bytes));
-    m->motion_cap = 2 * bytes;
-  }
+  const size_t nf = s.plan.recs.size();
+  MAP_TRY(m, m->d_motion.reserve(nf * (12 * sizeof(double) + sizeof(int)), g->stream, 2));
   MapMotionArgs a{};
-  a.n_frames = (int)nf; a.recs = d_recs;
+  a.n_frames = (int)nf; a.recs = s.recs();
   a.pose_est = g->dev.pose_est; a.pose_ld = g->dev.pose_ld;
-  a.motion = reinterpret_cast<double*>(m->d_motion);
-  a.moved = reinterpret_cast<int*>(m->d_motion + nf * 12 * sizeof(double));
-  MAP_TRY(m, hipEventRecord(m->ev_posed[0], g->stream));
+  a.motion = reinterpret_cast<double*>(m->d_motion.p);
+  a.moved = reinterpret_cast<int*>(m->d_motion.p + nf * 12 * sizeof(double));
+  MAP_TRY(m, m->t_motion.begin(g->stream));
   MAP_TRY(m, launch_map_motion(a, g->stream));
-  MAP_TRY(m, hipEventRecord(m->ev_posed[1], g->stream));
-  m->n_motion = (int)nf; m->n_unposed = p.n_unposed;
-  t->fidx = d_fidx; t->motion = a.motion; t->moved = a.moved;
+  MAP_TRY(m, m->t_motion.end(g->stream));
+  m->n_motion = (int)nf; m->n_unposed = s.plan.n_unposed;
+  t->fidx = s.fidx(); t->motion = a.motion; t->moved = a.moved;
   return PPS_OK;
-}
-
-void map_motion_done(pps_map* m) {
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, m->ev_posed[0], m->ev_posed[1]);
-  m->posed_sec[0] = 1e-3 * ms;
 }
 }  // namespace pps_impl
 
@@ -127,20 +154,14 @@ int pps_map_create(pps_graph* g, int64_t capacity_points, pps_map** out) {
 
 int pps_map_destroy(pps_map* m) {
   if (!m) return PPS_EINVAL;
-  if (m->d_store || m->d_built || m->d_table || m->h_totals || m->d_sel || m->d_dbg_cloud || m->d_dbg_pid || m->ev[0]) {
+  if (m->on_device) {
     (void)hipSetDevice(m->g->props.device);
     if (m->g->stream) (void)hipStreamSynchronize(m->g->stream);
-    (void)hipFree(m->d_store); (void)hipFree(m->d_built); (void)hipFree(m->d_table); (void)hipFree(m->d_sel);
-    (void)hipFree(m->d_dbg_cloud); (void)hipFree(m->d_dbg_pid);
-    if (m->h_totals) (void)hipHostFree(m->h_totals);
-    for (hipEvent_t e : m->ev) if (e) (void)hipEventDestroy(e);
   }
-  if (m->d_motion || m->ev_posed[0]) {
-    (void)hipSetDevice(m->g->props.device);
-    if (m->g->stream) (void)hipStreamSynchronize(m->g->stream);
-    (void)hipFree(m->d_motion);
-    for (hipEvent_t e : m->ev_posed) if (e) (void)hipEventDestroy(e);
-  }
+  m->d_store.release(); m->d_built.release(); m->d_table.release(); m->d_sel.release(); m->d_dbg_cloud.release(); m->d_dbg_pid.release();
+  m->d_motion.release();
+  if (m->h_totals) (void)hipHostFree(m->h_totals);
+  for (MapSpan* t : {&m->t_count, &m->t_scatter, &m->t_build, &m->t_motion, &m->t_posed}) t->release();
   map_grid_release(m);
   delete m;
   return PPS_OK;
@@ -174,39 +195,30 @@ int add_points(pps_map* m, const char* who, const MapPt* cloud, const int* plane
   if (nplanes > 0) {
     int rc = ensure_device(g);
     if (rc != PPS_OK) return mfail(m, rc, g->err);
-    MAP_TRY(m, hipSetDevice(g->props.device));
-    rc = map_events(m);
+    rc = map_use_device(m);
     if (rc != PPS_OK) return rc;
     const MapTiling t = map_tiling(npx);
-    const size_t need = (size_t)kMapPlanes * t.nT + kMapPlanes;
-    if (need > m->table_cap) {
-      MAP_TRY(m, hipStreamSynchronize(g->stream));
-      (void)hipFree(m->d_table); m->d_table = nullptr; m->table_cap = 0;
-      MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_table), need * sizeof(int)));
-      m->table_cap = need;
-    }
+    MAP_TRY(m, m->d_table.reserve((size_t)kMapPlanes * t.nT + kMapPlanes, g->stream));
     if (!m->h_totals) MAP_TRY(m, hipHostMalloc(reinterpret_cast<void**>(&m->h_totals), kMapPlanes * sizeof(int), hipHostMallocDefault));
-    if (!m->d_store && m->cap > 0) MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_store), (size_t)m->cap * sizeof(MapPt)));
-    int* d_totals = m->d_table + (size_t)kMapPlanes * t.nT;
-    MAP_TRY(m, hipEventRecord(m->ev[0], g->stream));
-    MAP_TRY(m, launch_map_count(cloud, plane_id, npx, nplanes, m->d_table, d_totals, g->stream));
-    MAP_TRY(m, hipEventRecord(m->ev[1], g->stream));
+    MAP_TRY(m, m->d_store.reserve((size_t)m->cap, g->stream));
+    int* d_totals = m->d_table.p + (size_t)kMapPlanes * t.nT;
+    MAP_TRY(m, m->t_count.begin(g->stream));
+    MAP_TRY(m, launch_map_count(cloud, plane_id, npx, nplanes, m->d_table.p, d_totals, g->stream));
+    MAP_TRY(m, m->t_count.end(g->stream));
     MAP_TRY(m, hipMemcpyAsync(m->h_totals, d_totals, (size_t)nplanes * sizeof(int), hipMemcpyDeviceToHost, g->stream));
     MAP_TRY(m, hipStreamSynchronize(g->stream));
     for (int k = 0; k < nplanes; k++)
       if (plane_node_ids[k] >= 0) { cnt[k] = m->h_totals[k]; base.base[k] = m->used + kept; kept += cnt[k]; }
     if (kept > m->cap - m->used)
       return mfail(m, PPS_ENOMEM, std::string(who) + ": the frame keeps " + std::to_string(kept) + " points, the store has room for " + std::to_string(m->cap - m->used));
-    float ms0 = 0, ms1 = 0;
-    (void)hipEventElapsedTime(&ms0, m->ev[0], m->ev[1]);
+    m->sec[0] = m->t_count.seconds();
     if (kept > 0) {
-      MAP_TRY(m, hipEventRecord(m->ev[2], g->stream));
-      MAP_TRY(m, launch_map_scatter(cloud, plane_id, npx, nplanes, m->d_table, base, m->d_store, g->stream));
-      MAP_TRY(m, hipEventRecord(m->ev[3], g->stream));
+      MAP_TRY(m, m->t_scatter.begin(g->stream));
+      MAP_TRY(m, launch_map_scatter(cloud, plane_id, npx, nplanes, m->d_table.p, base, m->d_store.p, g->stream));
+      MAP_TRY(m, m->t_scatter.end(g->stream));
       MAP_TRY(m, hipStreamSynchronize(g->stream));
-      (void)hipEventElapsedTime(&ms1, m->ev[2], m->ev[3]);
+      m->sec[0] += m->t_scatter.seconds();
     }
-    m->sec[0] = 1e-3 * ((double)ms0 + (double)ms1);
   }
   for (int k = 0; k < nplanes; k++) {
     if (plane_node_ids[k] < 0) continue;
@@ -248,18 +260,14 @@ int pps_debug_map_add_points(pps_map* m, const pps_point* cloud, const int* plan
     pps_graph* g = m->g;
     rc = ensure_device(g);
     if (rc != PPS_OK) return mfail(m, rc, g->err);
-    MAP_TRY(m, hipSetDevice(g->props.device));
-    if ((size_t)npx > m->dbg_cap) {
-      MAP_TRY(m, hipStreamSynchronize(g->stream));
-      (void)hipFree(m->d_dbg_cloud); (void)hipFree(m->d_dbg_pid); m->d_dbg_cloud = nullptr; m->d_dbg_pid = nullptr; m->dbg_cap = 0;
-      MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_dbg_cloud), (size_t)npx * sizeof(MapPt)));
-      MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_dbg_pid), (size_t)npx * sizeof(int)));
-      m->dbg_cap = (size_t)npx;
-    }
-    MAP_TRY(m, hipMemcpyAsync(m->d_dbg_cloud, cloud, (size_t)npx * sizeof(MapPt), hipMemcpyHostToDevice, g->stream));
-    MAP_TRY(m, hipMemcpyAsync(m->d_dbg_pid, plane_id, (size_t)npx * sizeof(int), hipMemcpyHostToDevice, g->stream));
+    rc = map_use_device(m);
+    if (rc != PPS_OK) return rc;
+    MAP_TRY(m, m->d_dbg_cloud.reserve((size_t)npx, g->stream));
+    MAP_TRY(m, m->d_dbg_pid.reserve((size_t)npx, g->stream));
+    MAP_TRY(m, hipMemcpyAsync(m->d_dbg_cloud.p, cloud, (size_t)npx * sizeof(MapPt), hipMemcpyHostToDevice, g->stream));
+    MAP_TRY(m, hipMemcpyAsync(m->d_dbg_pid.p, plane_id, (size_t)npx * sizeof(int), hipMemcpyHostToDevice, g->stream));
   }
-  return add_points(m, "debug_add_points", m->d_dbg_cloud, m->d_dbg_pid, (int)npx, frame_seq_id, nplanes, plane_node_ids, counts, nullptr);
+  return add_points(m, "debug_add_points", m->d_dbg_cloud.p, m->d_dbg_pid.p, (int)npx, frame_seq_id, nplanes, plane_node_ids, counts, nullptr);
 }
 
 int pps_map_redirect(pps_map* m, int from_plane, int to_plane) {
@@ -280,8 +288,12 @@ int pps_map_info(const pps_map* m, pps_map_totals* out) {
   return PPS_OK;
 }
 
-int pps_map_chunks(const pps_map* m, int cap, pps_map_chunk* out, int* n) { return m ? table_copy(m->chunks, cap, out, n) : PPS_EINVAL; }
-int pps_map_built_chunks(const pps_map* m, int cap, pps_map_chunk* out, int* n) { return m ? table_copy(m->built, cap, out, n) : PPS_EINVAL; }
+int pps_map_chunks(const pps_map* m, int cap, pps_map_chunk* out, int* n) {
+  return m ? map_table_copy(m->chunks.data(), m->chunks.size(), cap, out, n) : PPS_EINVAL;
+}
+int pps_map_built_chunks(const pps_map* m, int cap, pps_map_chunk* out, int* n) {
+  return m ? map_table_copy(m->built.data(), m->built.size(), cap, out, n) : PPS_EINVAL;
+}
 
 int pps_map_select_host(const pps_map_chunk* chunks, int n, const pps_map_select* sel, int32_t* keep, int* n_keep) {
   if (n < 0 || (n > 0 && (!chunks || !keep)) || !select_valid(sel)) return PPS_EINVAL;
@@ -290,93 +302,54 @@ int pps_map_select_host(const pps_map_chunk* chunks, int n, const pps_map_select
   return PPS_OK;
 }
 
-// pps_map_build and pps_map_build_posed: the selection, the tables of the device and their one upload are the same; the posed build adds
-// the per-chunk frame rows and the frame records to that upload, runs k_map_motion and the posed sibling of k_map_build.
+// pps_map_build and pps_map_build_posed: the selection and its one upload are the same; the posed build adds the per-chunk frame rows and
+// the frame records to that upload, runs k_map_motion and the posed sibling of k_map_build.
 static int build_common(pps_map* m, const pps_map_select* sel, bool posed, int64_t* n_points, int* n_chunks) {
   if (!m) return PPS_EINVAL;
   const char* who = posed ? "build_posed" : "build";
   if (!select_valid(sel)) return mfail(m, PPS_EINVAL, std::string(who) + ": old_every and new_every must be positive");
   pps_graph* g = m->g;
-  const int n = (int)m->chunks.size();
-  std::vector<int32_t> keep((size_t)n);
-  select_chunks(m->chunks.data(), n, sel, keep.data());
+  MapSelection s;
+  s.select(m, sel);
   std::vector<pps_map_chunk> built;
-  std::vector<int> src;                                  // chunks of the device table: selected and not empty
   int64_t total = 0;
-  for (int i = 0; i < n; i++) {
-    if (!keep[i]) continue;
+  for (size_t i = 0; i < m->chunks.size(); i++) {
+    if (!s.keep[i]) continue;
     pps_map_chunk c = m->chunks[i];
-    if (c.count > 0) src.push_back(i);
     c.offset = total; total += c.count;
     built.push_back(c);
   }
-  if (posed) { m->posed_sec[0] = m->posed_sec[1] = 0; m->n_motion = 0; m->n_unposed = 0; m->posed_launches = 0; }
+  if (posed) map_posed_reset(m);
   else m->sec[1] = 0;
   if (total > 0) {
     int rc = prepare_solve(g);
     if (rc != PPS_OK) return mfail(m, rc, g->err);
-    MAP_TRY(m, hipSetDevice(g->props.device));
-    rc = map_events(m);
+    rc = map_use_device(m);
     if (rc != PPS_OK) return rc;
-    if (!m->d_built) MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_built), (size_t)m->cap * sizeof(MapPt)));
-    const size_t ns = src.size();
-    MapMotionPlan plan;
-    if (posed) map_motion_plan(m, src, &plan);
-    const size_t nf = plan.recs.size();
-    const size_t off_src = (ns + 1) * sizeof(long long), off_slot = off_src + ns * sizeof(long long), plain = off_slot + ns * sizeof(int);
-    const size_t off_fidx = plain, off_recs = (off_fidx + ns * sizeof(int) + 7) / 8 * 8;
-    const size_t bytes = posed ? off_recs + nf * sizeof(MapFrameDev) : plain;
-    std::vector<char> host(bytes);
-    long long* out_off = reinterpret_cast<long long*>(host.data());
-    long long* src_off = reinterpret_cast<long long*>(host.data() + off_src);
-    int* slot = reinterpret_cast<int*>(host.data() + off_slot);
-    long long o = 0;
-    for (size_t j = 0; j < ns; j++) {
-      const pps_map_chunk& c = m->chunks[src[j]];
-      out_off[j] = o; o += c.count;
-      src_off[j] = c.offset;
-      slot[j] = live_node(g, c.plane_id, NODE_PLANE) ? g->nodes[c.plane_id].slot : -1;
-    }
-    out_off[ns] = o;
-    if (posed) {
-      memcpy(host.data() + off_fidx, plan.fidx.data(), ns * sizeof(int));
-      memcpy(host.data() + off_recs, plan.recs.data(), nf * sizeof(MapFrameDev));
-    }
-    if (bytes > m->sel_cap) {
-      MAP_TRY(m, hipStreamSynchronize(g->stream));
-      (void)hipFree(m->d_sel); m->d_sel = nullptr; m->sel_cap = 0;
-      MAP_TRY(m, hipMalloc(reinterpret_cast<void**>(&m->d_sel), 2 * bytes));
-      m->sel_cap = 2 * bytes;
-    }
-    MAP_TRY(m, hipMemcpyAsync(m->d_sel, host.data(), bytes, hipMemcpyHostToDevice, g->stream));
+    MAP_TRY(m, m->d_built.reserve((size_t)m->cap, g->stream));
+    rc = s.upload(m, posed, nullptr, &m->d_sel, 2);
+    if (rc != PPS_OK) return rc;
     MapBuildArgs a{};
-    a.n_out = total; a.n_sel = (int)ns;
-    a.out_off = reinterpret_cast<const long long*>(m->d_sel);
-    a.src_off = reinterpret_cast<const long long*>(m->d_sel + off_src);
-    a.slot = reinterpret_cast<const int*>(m->d_sel + off_slot);
+    a.n_out = total; a.n_sel = s.n();
+    a.out_off = s.out_off(); a.src_off = s.src_off(); a.slot = s.slot();
     a.plane_est = g->dev.plane_est; a.plane_ld = g->dev.plane_ld;
-    a.store = m->d_store; a.built = m->d_built;
+    a.store = m->d_store.p; a.built = m->d_built.p;
     if (posed) {
       MapMotionTable t{};
-      rc = map_motion_launch(m, plan, reinterpret_cast<const MapFrameDev*>(m->d_sel + off_recs), reinterpret_cast<const int*>(m->d_sel + off_fidx), &t);
+      rc = map_motion_launch(m, s, &t);
       if (rc != PPS_OK) return rc;
-      MAP_TRY(m, hipEventRecord(m->ev_posed[2], g->stream));
+      MAP_TRY(m, m->t_posed.begin(g->stream));
       MAP_TRY(m, launch_map_build_posed(a, t, g->stream));
-      MAP_TRY(m, hipEventRecord(m->ev_posed[3], g->stream));
+      MAP_TRY(m, m->t_posed.end(g->stream));
       MAP_TRY(m, hipStreamSynchronize(g->stream));
-      map_motion_done(m);
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, m->ev_posed[2], m->ev_posed[3]);
-      m->posed_sec[1] = 1e-3 * ms;
+      m->posed_sec[0] = m->t_motion.seconds(); m->posed_sec[1] = m->t_posed.seconds();
       m->posed_launches = 2;
     } else {
-      MAP_TRY(m, hipEventRecord(m->ev[0], g->stream));
+      MAP_TRY(m, m->t_build.begin(g->stream));
       MAP_TRY(m, launch_map_build(a, g->stream));
-      MAP_TRY(m, hipEventRecord(m->ev[4], g->stream));
-      MAP_TRY(m, hipStreamSynchronize(g->stream));            // (`host` leaves scope; the result is complete on return)
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, m->ev[0], m->ev[4]);
-      m->sec[1] = 1e-3 * ms;
+      MAP_TRY(m, m->t_build.end(g->stream));
+      MAP_TRY(m, hipStreamSynchronize(g->stream));            // (the selection leaves scope; the result is complete on return)
+      m->sec[1] = m->t_build.seconds();
     }
   }
   m->built.swap(built);
@@ -404,7 +377,7 @@ int pps_map_set_frame_pose(pps_map* m, int frame, int pose_node_id, const float 
 }
 
 int pps_map_frames(const pps_map* m, int cap, pps_map_frame* out, int* n) {
-  if (!m || !n || cap < 0 || (cap > 0 && !out)) return PPS_EINVAL;
+  if (!m || !map_table_args(cap, out, n)) return PPS_EINVAL;
   *n = (int)m->frames.size();
   const size_t k = std::min<size_t>((size_t)cap, m->frames.size());
   for (size_t f = 0; f < k; f++) {
@@ -422,8 +395,8 @@ int pps_map_frame_motions(pps_map* m, int cap, double* D, int32_t* moved, int* n
   if (k == 0 || (!D && !moved)) return PPS_OK;
   MAP_TRY(m, hipSetDevice(m->g->props.device));
   static_assert(sizeof(int32_t) == sizeof(int), "moved flags are int32");
-  if (D) MAP_TRY(m, hipMemcpyAsync(D, m->d_motion, k * 12 * sizeof(double), hipMemcpyDeviceToHost, m->g->stream));
-  if (moved) MAP_TRY(m, hipMemcpyAsync(moved, m->d_motion + (size_t)m->n_motion * 12 * sizeof(double), k * sizeof(int), hipMemcpyDeviceToHost, m->g->stream));
+  if (D) MAP_TRY(m, hipMemcpyAsync(D, m->d_motion.p, k * 12 * sizeof(double), hipMemcpyDeviceToHost, m->g->stream));
+  if (moved) MAP_TRY(m, hipMemcpyAsync(moved, m->d_motion.p + (size_t)m->n_motion * 12 * sizeof(double), k * sizeof(int), hipMemcpyDeviceToHost, m->g->stream));
   MAP_TRY(m, hipStreamSynchronize(m->g->stream));
   return PPS_OK;
 }
@@ -456,7 +429,7 @@ int pps_map_download(pps_map* m, int which, int64_t first, int64_t n, pps_point*
   if (first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !out)) return mfail(m, PPS_EINVAL, "download: range outside the buffer");
   if (n == 0) return PPS_OK;
   MAP_TRY(m, hipSetDevice(m->g->props.device));
-  const MapPt* src = (which == 0 ? m->d_store : m->d_built) + first;
+  const MapPt* src = (which == 0 ? m->d_store.p : m->d_built.p) + first;
   MAP_TRY(m, hipMemcpyAsync(out, src, (size_t)n * sizeof(MapPt), hipMemcpyDeviceToHost, m->g->stream));
   MAP_TRY(m, hipStreamSynchronize(m->g->stream));
   return PPS_OK;

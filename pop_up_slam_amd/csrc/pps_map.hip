@@ -17,11 +17,13 @@
 //
 // The posed build (pps_map_build_posed) moves every point rigidly with the correction of its frame's pose before it is projected:
 // k_map_motion computes one motion per frame of the selection from pose_est in place (pps_map_move.h: the text the host entry points are
-// compiled from), k_map_build_posed is k_map_build with the motion of the point's frame applied.
+// compiled from), k_map_build_posed is k_map_build with the motion of the point's frame applied.  Both find a point's chunk in the
+// workgroup's chunk window (pps_map_window.h), which the grid kernels (pps_grid.hip) share with them.
 #include <hip/hip_runtime.h>
 
 #include "pps_map.h"
 #include "pps_map_move.h"
+#include "pps_map_window.h"
 #include "pps_project.h"
 
 namespace pps {
@@ -29,10 +31,6 @@ namespace {
 
 // plane of pixel i if its point is kept: valid bit set and a plane index of this frame
 __device__ __forceinline__ int map_key(unsigned int rgba, int p, int nplanes) { return (((rgba >> 24) & 1u) && p >= 0 && p < nplanes) ? p : -1; }
-
-__device__ __forceinline__ int lanes_below(unsigned long long m) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u));
-}
 
 __global__ __launch_bounds__(kMapThreads) void k_map_count(const MapPt* __restrict__ cloud, const int* __restrict__ plane_id, int npx, int nplanes,
                                                            int wt, int nT, int* __restrict__ table) {
@@ -70,17 +68,10 @@ __global__ __launch_bounds__(kMapThreads) void k_map_scan(int* __restrict__ tabl
   const int a = min(nT, tid * seg), b = min(nT, a + seg);
   int sum = 0;
   for (int i = a; i < b; i++) sum += row[i];
-  s_sum[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < kMapThreads; d <<= 1) {
-    const int v = tid >= d ? s_sum[tid - d] : 0;
-    __syncthreads();
-    s_sum[tid] += v;
-    __syncthreads();
-  }
-  int run = s_sum[tid] - sum;
+  const int upto = map_block_scan(s_sum, sum);
+  int run = upto - sum;
   for (int i = a; i < b; i++) { const int c = row[i]; row[i] = run; run += c; }
-  if (tid == kMapThreads - 1) totals[blockIdx.x] = s_sum[tid];
+  if (tid == kMapThreads - 1) totals[blockIdx.x] = upto;
 }
 
 __global__ __launch_bounds__(kMapThreads) void k_map_scatter(const MapPt* __restrict__ cloud, const int* __restrict__ plane_id, int npx, int nplanes,
@@ -106,7 +97,7 @@ __global__ __launch_bounds__(kMapThreads) void k_map_scatter(const MapPt* __rest
       const unsigned long long m = __ballot(key == kk);
       const int c = cur[kk];                                     // (every lane reads before the leader moves the cursor)
       const long long cb = base.base[kk];
-      if (key == kk && cb >= 0) store[cb + c + lanes_below(m)] = pt;
+      if (key == kk && cb >= 0) store[cb + c + map_lanes_below(m)] = pt;
       __builtin_amdgcn_wave_barrier();
       if (lane == leader) cur[kk] = c + __popcll(m);
       rem &= ~m;
@@ -114,37 +105,16 @@ __global__ __launch_bounds__(kMapThreads) void k_map_scatter(const MapPt* __rest
   }
 }
 
-// One thread per point of the built map.  The workgroup looks up the chunk of its first point in the offset table (thread 0, binary search
-// in global memory) and stages the offsets of the next 256 chunks in LDS: chunks in the table are non-empty, so the 256 points of the
-// workgroup end inside that window; each thread then searches the window.  16 B in, 16 B out.
+// One thread per point of the built map; the workgroup's chunk window (pps_map_window.h) tells a point its chunk.  16 B in, 16 B out.
 __global__ __launch_bounds__(kMapThreads) void k_map_build(MapBuildArgs a) {
-  __shared__ long long s_off[kMapThreads + 1], s_src[kMapThreads];
-  __shared__ int s_slot[kMapThreads];
-  __shared__ int s_c0;
-  const int tid = threadIdx.x;
+  __shared__ MapWindow<false> w;
   const long long first = (long long)blockIdx.x * kMapThreads;
-  if (tid == 0) {
-    int lo = 0, hi = a.n_sel;                                    // out_off[lo] <= first < out_off[hi]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (a.out_off[mid] <= first) lo = mid; else hi = mid;
-    }
-    s_c0 = lo;
-  }
-  __syncthreads();
-  const int c0 = s_c0;
-  for (int j = tid; j <= kMapThreads; j += kMapThreads) s_off[j] = c0 + j <= a.n_sel ? a.out_off[c0 + j] : 0x7fffffffffffffffLL;
-  if (c0 + tid < a.n_sel) { s_src[tid] = a.src_off[c0 + tid]; s_slot[tid] = a.slot[c0 + tid]; }
-  __syncthreads();
-  const long long i = first + tid;
+  map_stage_window(w, a.out_off, a.src_off, a.slot, nullptr, a.n_sel, first);
+  const long long i = first + threadIdx.x;
   if (i >= a.n_out) return;
-  int lo = 0, hi = kMapThreads;                                  // s_off[lo] <= i < s_off[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (s_off[mid] <= i) lo = mid; else hi = mid;
-  }
-  MapPt pt = a.store[s_src[lo] + (i - s_off[lo])];
-  const int sl = s_slot[lo];
+  const int lo = map_window_find(w, i);
+  MapPt pt = a.store[w.src[lo] + (i - w.off[lo])];
+  const int sl = w.slot[lo];
   if (sl >= 0) {                                                 // (a landmark that is gone and was not redirected: untouched, like k_reproject)
     double p[4];
     for (int k = 0; k < 4; k++) p[k] = a.plane_est[(size_t)k * a.plane_ld + sl];
@@ -170,42 +140,23 @@ __global__ __launch_bounds__(kMapThreads) void k_map_motion(MapMotionArgs a) {
   a.moved[f] = mv;
 }
 
-// k_map_build with the motion of the point's frame: the window in LDS also holds the row of every chunk's frame in the motion table.
+// k_map_build with the motion of the point's frame: the window's fourth row is the row of every chunk's frame in the motion table.
 // The 256 points of a workgroup belong to few frames (a chunk is one plane of one frame), so a motion is not loaded per point: the lanes
 // of a wave that share a frame find each other with a ballot, the 96 bytes of that frame's motion are read at a wave-uniform address
 // (scalar loads, one turn per distinct frame of the wave), and the lanes of that frame move their point.  16 B in, 16 B out.
 __global__ __launch_bounds__(kMapThreads) void k_map_build_posed(MapBuildArgs a, const int* __restrict__ fidx, const double* __restrict__ motion,
                                                                  const int* __restrict__ moved) {
-  __shared__ long long s_off[kMapThreads + 1], s_src[kMapThreads];
-  __shared__ int s_slot[kMapThreads], s_fidx[kMapThreads];
-  __shared__ int s_c0;
-  const int tid = threadIdx.x;
+  __shared__ MapWindow<true> w;
   const long long first = (long long)blockIdx.x * kMapThreads;
-  if (tid == 0) {
-    int lo = 0, hi = a.n_sel;                                    // out_off[lo] <= first < out_off[hi]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (a.out_off[mid] <= first) lo = mid; else hi = mid;
-    }
-    s_c0 = lo;
-  }
-  __syncthreads();
-  const int c0 = s_c0;
-  for (int j = tid; j <= kMapThreads; j += kMapThreads) s_off[j] = c0 + j <= a.n_sel ? a.out_off[c0 + j] : 0x7fffffffffffffffLL;
-  if (c0 + tid < a.n_sel) { s_src[tid] = a.src_off[c0 + tid]; s_slot[tid] = a.slot[c0 + tid]; s_fidx[tid] = fidx[c0 + tid]; }
-  __syncthreads();
-  const long long i = first + tid;
+  map_stage_window(w, a.out_off, a.src_off, a.slot, fidx, a.n_sel, first);
+  const long long i = first + threadIdx.x;
   const bool in = i < a.n_out;                                   // (no early return: the ballots below are the whole wave's)
   MapPt pt = {0.f, 0.f, 0.f, 0u};
   int sl = -1, f = -1;
   if (in) {
-    int lo = 0, hi = kMapThreads;                                // s_off[lo] <= i < s_off[hi]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_off[mid] <= i) lo = mid; else hi = mid;
-    }
-    pt = a.store[s_src[lo] + (i - s_off[lo])];
-    sl = s_slot[lo]; f = s_fidx[lo];
+    const int lo = map_window_find(w, i);
+    pt = a.store[w.src[lo] + (i - w.off[lo])];
+    sl = w.slot[lo]; f = w.aux[lo];
   }
   double p[4] = {0.0, 0.0, 1.0, 0.0};
   if (sl >= 0)
@@ -218,12 +169,7 @@ __global__ __launch_bounds__(kMapThreads) void k_map_build_posed(MapBuildArgs a,
     if (moved[F]) {
       double D[12];
       for (int k = 0; k < 12; k++) D[k] = motion[12 * (size_t)F + k];
-      if (f == F) {
-        double x = (double)pt.x, y = (double)pt.y, z = (double)pt.z;
-        map_move_xyz(D, &x, &y, &z);
-        if (sl >= 0) project_to_plane_f64(p, x, y, z, &pt.x, &pt.y, &pt.z);
-        else { pt.x = (float)x; pt.y = (float)y; pt.z = (float)z; }          // (the landmark is gone: moved, not projected)
-      }
+      if (f == F) map_moved_point(D, p, sl >= 0, &pt.x, &pt.y, &pt.z);       // (gone landmark: moved, not projected)
     } else if (f == F && sl >= 0) {                              // a frame without motion: k_map_build's point
       project_to_plane_f32(p, pt.x, pt.y, pt.z, &pt.x, &pt.y, &pt.z);
     }

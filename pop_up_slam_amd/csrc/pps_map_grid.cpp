@@ -1,5 +1,6 @@
-// pps_map_grid.cpp -- host side of the grid map (include/pps.h: pps_map_build_grid and the pps_map_grid_* calls): the selection and the
-// plane table, the frames, the layout of the cell arrays between the passes, and the calls that drive the kernels of pps_grid.hip.
+// pps_map_grid.cpp -- host side of the grid map (include/pps.h: pps_map_build_grid and the pps_map_grid_* calls): the plane table of the
+// selection (MapSelection, pps_map_host.h), the frames, the layout of the cell arrays between the passes, and the calls that drive the
+// kernels of pps_grid.hip.
 //
 // One call synchronises the graph's stream three times, each time for a small table the host has to read: after the extent pass (the boxes
 // decide the size of the cell arrays and the max_cells refusal), after the count / scan (the emitted cells decide the size of the output),
@@ -11,25 +12,11 @@
 
 #include <climits>
 #include <cstdlib>
-#include <map>
 
 using namespace pps;
 using namespace pps_impl;
 
 namespace pps_impl {
-
-template <class T>
-struct GridBuf {
-  T* p = nullptr; size_t cap = 0;                     // elements
-  hipError_t reserve(size_t n) {                      // (the caller has drained the stream)
-    if (n <= cap) return hipSuccess;
-    (void)hipFree(p); p = nullptr; cap = 0;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-    if (e == hipSuccess) cap = n; else p = nullptr;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 
 struct MapGrid {
   // the last grid (valid: the last call succeeded)
@@ -37,29 +24,26 @@ struct MapGrid {
   std::vector<pps_map_grid_plane> planes;
   pps_map_grid_totals tot{};
   // device
-  GridBuf<char> sel;                                  // [out_off | src_off | slot | lm] of the selection
-  GridBuf<GridPlaneDev> d_planes;
-  GridBuf<char> small;                                // GridExtent per landmark, then the dropped counter
-  GridBuf<long long> plane_tab;                       // plane_base[n + 1], plane_off[n + 1]
-  GridBuf<unsigned long long> key;
-  GridBuf<unsigned int> cnt;
-  GridBuf<int> tile_count;
-  GridBuf<long long> tile_prefix;
-  GridBuf<MapPt> out_pts; GridBuf<unsigned int> out_cnt; GridBuf<int> out_ij; GridBuf<long long> out_src;
-  hipEvent_t ev[10] = {};
-  bool any_device() const { return sel.p || d_planes.p || small.p || plane_tab.p || key.p || cnt.p || tile_count.p || tile_prefix.p || out_pts.p || ev[0]; }
+  MapBuf<char> sel;                                   // tables of the selection, with the lm column (MapSelection)
+  MapBuf<GridPlaneDev> d_planes;
+  MapBuf<char> small;                                 // GridExtent per landmark, then the dropped counter
+  MapBuf<long long> plane_tab;                        // plane_base[n + 1], plane_off[n + 1]
+  MapBuf<unsigned long long> key;
+  MapBuf<unsigned int> cnt;
+  MapBuf<int> tile_count;
+  MapBuf<long long> tile_prefix;
+  MapBuf<MapPt> out_pts; MapBuf<unsigned int> out_cnt; MapBuf<int> out_ij; MapBuf<long long> out_src;
+  // tot.sec: [0] the extent pass, [1] zeroing and votes, [2] count + scan + plane_off and the emission, [3] first upload to last kernel
+  MapSpan t_extent, t_vote, t_count, t_emit, t_call;
+  void clear() { valid = false; planes.clear(); tot = pps_map_grid_totals{}; }      // a call that fails leaves no grid
 };
 
 void map_grid_release(pps_map* m) {
   MapGrid* gr = m ? m->grid : nullptr;
   if (!gr) return;
-  if (gr->any_device()) {
-    (void)hipSetDevice(m->g->props.device);
-    if (m->g->stream) (void)hipStreamSynchronize(m->g->stream);
-    gr->sel.release(); gr->d_planes.release(); gr->small.release(); gr->plane_tab.release(); gr->key.release(); gr->cnt.release();
-    gr->tile_count.release(); gr->tile_prefix.release(); gr->out_pts.release(); gr->out_cnt.release(); gr->out_ij.release(); gr->out_src.release();
-    for (hipEvent_t e : gr->ev) if (e) (void)hipEventDestroy(e);
-  }
+  gr->sel.release(); gr->d_planes.release(); gr->small.release(); gr->plane_tab.release(); gr->key.release(); gr->cnt.release();
+  gr->tile_count.release(); gr->tile_prefix.release(); gr->out_pts.release(); gr->out_cnt.release(); gr->out_ij.release(); gr->out_src.release();
+  for (MapSpan* t : {&gr->t_extent, &gr->t_vote, &gr->t_count, &gr->t_emit, &gr->t_call}) t->release();
   delete gr;
   m->grid = nullptr;
 }
@@ -79,28 +63,27 @@ bool vote_combines() {
 int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params& prm, bool posed, int64_t* n_points, int* n_planes) {
   pps_graph* g = m->g;
   MapGrid& G = *m->grid;
+  hipStream_t st = g->stream;
   const double inv_cell = 1.0 / prm.cell;
   // ---- the selection: B's chunks, the plane table
+  MapSelection s;
+  s.select(m, sel);
   const int n = (int)m->chunks.size();
-  std::vector<int32_t> keep((size_t)n);
-  map_select_chunks(m->chunks.data(), n, sel, keep.data());
   std::map<int, int> row_of;                            // live plane node id -> row (ascending ids)
   for (int i = 0; i < n; i++)
-    if (keep[i] && live_node(g, m->chunks[i].plane_id, NODE_PLANE)) row_of[m->chunks[i].plane_id] = 0;
+    if (s.keep[i] && live_node(g, m->chunks[i].plane_id, NODE_PLANE)) row_of[m->chunks[i].plane_id] = 0;
   std::vector<pps_map_grid_plane> planes(row_of.size());
   {
     int r = 0;
     for (auto& kv : row_of) { kv.second = r; planes[r] = pps_map_grid_plane{}; planes[r].plane_id = kv.first; r++; }
   }
-  std::vector<int> src;                                 // chunks of the device table: selected and not empty
-  int64_t total = 0, through = 0;
+  const int64_t total = s.total;
+  int64_t through = 0;
   for (int i = 0; i < n; i++) {
-    if (!keep[i]) continue;
+    if (!s.keep[i]) continue;
     const pps_map_chunk& c = m->chunks[i];
     const auto it = live_node(g, c.plane_id, NODE_PLANE) ? row_of.find(c.plane_id) : row_of.end();
     if (it != row_of.end()) planes[it->second].n_chunks++; else through += c.count;
-    if (c.count > 0) src.push_back(i);
-    total += c.count;
   }
   const int nL = (int)planes.size();
   pps_map_grid_totals tot{};
@@ -118,36 +101,8 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
         return mfail(m, PPS_EINVAL, "build_grid: plane node " + std::to_string(p.plane_id) + " has no normal");
   }
   if (device) {
-    MAP_TRY(m, hipSetDevice(g->props.device));
-    for (hipEvent_t& e : G.ev)
-      if (!e) MAP_TRY(m, hipEventCreate(&e));
-    // ---- tables of the selection
-    const size_t ns = src.size();
-    MapMotionPlan plan;                                              // posed: the frame rows and records ride in the same upload
-    if (posed) map_motion_plan(m, src, &plan);
-    const size_t nf = plan.recs.size();
-    const size_t off_src = (ns + 1) * sizeof(long long), off_slot = off_src + ns * sizeof(long long), off_lm = off_slot + ns * sizeof(int),
-                 off_fidx = off_lm + ns * sizeof(int), off_recs = (off_fidx + ns * sizeof(int) + 7) / 8 * 8,
-                 bytes = posed ? off_recs + nf * sizeof(MapFrameDev) : off_fidx;
-    std::vector<char> host(bytes);
-    long long* out_off = reinterpret_cast<long long*>(host.data());
-    long long* src_off = reinterpret_cast<long long*>(host.data() + off_src);
-    int* slot = reinterpret_cast<int*>(host.data() + off_slot);
-    int* lm = reinterpret_cast<int*>(host.data() + off_lm);
-    long long o = 0;
-    for (size_t j = 0; j < ns; j++) {
-      const pps_map_chunk& c = m->chunks[src[j]];
-      out_off[j] = o; o += c.count;
-      src_off[j] = c.offset;
-      const bool live = live_node(g, c.plane_id, NODE_PLANE);
-      slot[j] = live ? g->nodes[c.plane_id].slot : -1;
-      lm[j] = live ? row_of[c.plane_id] : -1;
-    }
-    out_off[ns] = o;
-    if (posed) {
-      memcpy(host.data() + off_fidx, plan.fidx.data(), ns * sizeof(int));
-      memcpy(host.data() + off_recs, plan.recs.data(), nf * sizeof(MapFrameDev));
-    }
+    int rc = map_use_device(m);
+    if (rc != PPS_OK) return rc;
     std::vector<GridPlaneDev> pd((size_t)nL);
     for (int L = 0; L < nL; L++) {
       pd[L] = GridPlaneDev{};
@@ -157,41 +112,38 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
     std::vector<char> small(small_bytes, 0);
     GridExtent* ext = reinterpret_cast<GridExtent*>(small.data());
     for (int L = 0; L < nL; L++) ext[L] = GridExtent{INT_MAX, INT_MIN, INT_MAX, INT_MIN, 0ull};
-    MAP_TRY(m, hipStreamSynchronize(g->stream));                       // (buffers may grow)
-    MAP_TRY(m, G.sel.reserve(bytes));
-    MAP_TRY(m, G.d_planes.reserve((size_t)nL));
-    MAP_TRY(m, G.small.reserve(small_bytes));
-    MAP_TRY(m, G.plane_tab.reserve(2 * ((size_t)nL + 1)));
-    MAP_TRY(m, hipEventRecord(G.ev[0], g->stream));
-    MAP_TRY(m, hipMemcpyAsync(G.sel.p, host.data(), bytes, hipMemcpyHostToDevice, g->stream));
-    MAP_TRY(m, hipMemcpyAsync(G.d_planes.p, pd.data(), (size_t)nL * sizeof(GridPlaneDev), hipMemcpyHostToDevice, g->stream));
-    MAP_TRY(m, hipMemcpyAsync(G.small.p, small.data(), small_bytes, hipMemcpyHostToDevice, g->stream));
+    MAP_TRY(m, hipStreamSynchronize(st));
+    MAP_TRY(m, G.d_planes.reserve((size_t)nL, st));
+    MAP_TRY(m, G.small.reserve(small_bytes, st));
+    MAP_TRY(m, G.plane_tab.reserve(2 * ((size_t)nL + 1), st));
+    // ---- tables of the selection (posed: the frame rows and records ride in the same upload)
+    rc = s.upload(m, posed, &row_of, &G.sel, 1, &G.t_call);
+    if (rc != PPS_OK) return rc;
+    MAP_TRY(m, hipMemcpyAsync(G.d_planes.p, pd.data(), (size_t)nL * sizeof(GridPlaneDev), hipMemcpyHostToDevice, st));
+    MAP_TRY(m, hipMemcpyAsync(G.small.p, small.data(), small_bytes, hipMemcpyHostToDevice, st));
     GridSelArgs a{};
-    a.n_out = total; a.n_sel = (int)ns;
-    a.out_off = reinterpret_cast<const long long*>(G.sel.p);
-    a.src_off = reinterpret_cast<const long long*>(G.sel.p + off_src);
-    a.slot = reinterpret_cast<const int*>(G.sel.p + off_slot);
-    a.lm = reinterpret_cast<const int*>(G.sel.p + off_lm);
+    a.n_out = total; a.n_sel = s.n();
+    a.out_off = s.out_off(); a.src_off = s.src_off(); a.slot = s.slot(); a.lm = s.lm();
     a.plane_est = g->dev.plane_est; a.plane_ld = g->dev.plane_ld;
-    a.store = m->d_store;
+    a.store = m->d_store.p;
     a.planes = G.d_planes.p; a.n_planes = nL;
     a.inv_cell = inv_cell;
     MapMotionTable mt{};                                             // (all null: B is pps_map_build's)
     if (posed) {
-      const int rc = map_motion_launch(m, plan, reinterpret_cast<const MapFrameDev*>(G.sel.p + off_recs), reinterpret_cast<const int*>(G.sel.p + off_fidx), &mt);
+      rc = map_motion_launch(m, s, &mt);
       if (rc != PPS_OK) return rc;
     }
     // ---- pass 1: extents
     GridExtent* d_ext = reinterpret_cast<GridExtent*>(G.small.p);
     unsigned long long* d_dropped = reinterpret_cast<unsigned long long*>(G.small.p + (size_t)nL * sizeof(GridExtent));
-    MAP_TRY(m, hipEventRecord(G.ev[1], g->stream));
-    MAP_TRY(m, launch_grid_extent(a, d_ext, d_dropped, g->stream, mt));
-    MAP_TRY(m, hipEventRecord(G.ev[2], g->stream));
-    MAP_TRY(m, hipMemcpyAsync(small.data(), G.small.p, small_bytes, hipMemcpyDeviceToHost, g->stream));
-    MAP_TRY(m, hipStreamSynchronize(g->stream));
+    MAP_TRY(m, G.t_extent.begin(st));
+    MAP_TRY(m, launch_grid_extent(a, d_ext, d_dropped, st, mt));
+    MAP_TRY(m, G.t_extent.end(st));
+    MAP_TRY(m, hipMemcpyAsync(small.data(), G.small.p, small_bytes, hipMemcpyDeviceToHost, st));
+    MAP_TRY(m, hipStreamSynchronize(st));
     tot.launches = 1;
-    if (posed) { map_motion_done(m); m->posed_launches = 1; }        // (k_map_motion: counted by pps_map_posed_last)
-    ext = reinterpret_cast<GridExtent*>(small.data());
+    tot.sec[0] = G.t_extent.seconds();
+    if (posed) { m->posed_sec[0] = m->t_motion.seconds(); m->posed_launches = 1; }        // (k_map_motion: counted by pps_map_posed_last)
     tot.n_dropped = (int64_t) * reinterpret_cast<unsigned long long*>(small.data() + (size_t)nL * sizeof(GridExtent));
     // ---- the boxes and the layout of the cell arrays
     int64_t all = 0, largest = -1;
@@ -218,56 +170,47 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
     }
     if (all > 0) {
       const GridTiling t = grid_tiling(all);
-      MAP_TRY(m, G.key.reserve((size_t)all));
-      MAP_TRY(m, G.cnt.reserve((size_t)all));
-      MAP_TRY(m, G.tile_count.reserve((size_t)t.nT));
-      MAP_TRY(m, G.tile_prefix.reserve((size_t)t.nT + 1));
-      MAP_TRY(m, hipMemcpyAsync(G.d_planes.p, pd.data(), (size_t)nL * sizeof(GridPlaneDev), hipMemcpyHostToDevice, g->stream));
-      MAP_TRY(m, hipMemcpyAsync(G.plane_tab.p, ptab.data(), ((size_t)nL + 1) * sizeof(long long), hipMemcpyHostToDevice, g->stream));
+      MAP_TRY(m, G.key.reserve((size_t)all, st));
+      MAP_TRY(m, G.cnt.reserve((size_t)all, st));
+      MAP_TRY(m, G.tile_count.reserve((size_t)t.nT, st));
+      MAP_TRY(m, G.tile_prefix.reserve((size_t)t.nT + 1, st));
+      MAP_TRY(m, hipMemcpyAsync(G.d_planes.p, pd.data(), (size_t)nL * sizeof(GridPlaneDev), hipMemcpyHostToDevice, st));
+      MAP_TRY(m, hipMemcpyAsync(G.plane_tab.p, ptab.data(), ((size_t)nL + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
       // ---- pass 2: votes
-      MAP_TRY(m, hipEventRecord(G.ev[3], g->stream));
-      MAP_TRY(m, hipMemsetAsync(G.key.p, 0, (size_t)all * sizeof(unsigned long long), g->stream));
-      MAP_TRY(m, hipMemsetAsync(G.cnt.p, 0, (size_t)all * sizeof(unsigned int), g->stream));
-      MAP_TRY(m, launch_grid_vote(a, prm.rule == PPS_GRID_OLDEST, vote_combines(), G.key.p, G.cnt.p, g->stream, mt));
-      MAP_TRY(m, hipEventRecord(G.ev[4], g->stream));
+      MAP_TRY(m, G.t_vote.begin(st));
+      MAP_TRY(m, hipMemsetAsync(G.key.p, 0, (size_t)all * sizeof(unsigned long long), st));
+      MAP_TRY(m, hipMemsetAsync(G.cnt.p, 0, (size_t)all * sizeof(unsigned int), st));
+      MAP_TRY(m, launch_grid_vote(a, prm.rule == PPS_GRID_OLDEST, vote_combines(), G.key.p, G.cnt.p, st, mt));
+      MAP_TRY(m, G.t_vote.end(st));
       // ---- pass 3: emission
       GridEmitArgs e{};
       e.n_cells_all = all; e.min_count = (unsigned int)prm.min_count; e.oldest = prm.rule == PPS_GRID_OLDEST;
       e.key = G.key.p; e.cnt = G.cnt.p; e.tile_count = G.tile_count.p; e.tile_prefix = G.tile_prefix.p;
       e.plane_base = G.plane_tab.p; e.plane_off = G.plane_tab.p + (nL + 1);
-      MAP_TRY(m, launch_grid_count(e, nL, g->stream));
-      MAP_TRY(m, hipEventRecord(G.ev[5], g->stream));
-      MAP_TRY(m, hipMemcpyAsync(ptab.data() + (nL + 1), e.plane_off, ((size_t)nL + 1) * sizeof(long long), hipMemcpyDeviceToHost, g->stream));
-      MAP_TRY(m, hipStreamSynchronize(g->stream));
+      MAP_TRY(m, G.t_count.begin(st));
+      MAP_TRY(m, launch_grid_count(e, nL, st));
+      MAP_TRY(m, G.t_count.end(st));
+      MAP_TRY(m, hipMemcpyAsync(ptab.data() + (nL + 1), e.plane_off, ((size_t)nL + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+      MAP_TRY(m, hipStreamSynchronize(st));
       tot.launches += 4;
       const long long* poff = ptab.data() + (nL + 1);
       tot.n_cells = poff[nL];
       for (int L = 0; L < nL; L++) { planes[L].offset = poff[L]; planes[L].count = poff[L + 1] - poff[L]; }
-      float ms_emit = 0;
+      tot.sec[1] = G.t_vote.seconds(); tot.sec[2] = G.t_count.seconds();
       if (tot.n_cells > 0) {
         const size_t nc = (size_t)tot.n_cells;
-        MAP_TRY(m, G.out_pts.reserve(nc)); MAP_TRY(m, G.out_cnt.reserve(nc)); MAP_TRY(m, G.out_ij.reserve(2 * nc)); MAP_TRY(m, G.out_src.reserve(nc));
+        MAP_TRY(m, G.out_pts.reserve(nc, st)); MAP_TRY(m, G.out_cnt.reserve(nc, st)); MAP_TRY(m, G.out_ij.reserve(2 * nc, st)); MAP_TRY(m, G.out_src.reserve(nc, st));
         e.pts = G.out_pts.p; e.counts = G.out_cnt.p; e.ij = G.out_ij.p; e.src = G.out_src.p;
-        MAP_TRY(m, hipEventRecord(G.ev[6], g->stream));
-        MAP_TRY(m, launch_grid_emit(a, e, g->stream, mt));
-        MAP_TRY(m, hipEventRecord(G.ev[7], g->stream));
+        MAP_TRY(m, G.t_emit.begin(st));
+        MAP_TRY(m, launch_grid_emit(a, e, st, mt));
+        MAP_TRY(m, G.t_emit.end(st));
         tot.launches += 1;
       }
-      MAP_TRY(m, hipEventRecord(G.ev[8], g->stream));
-      MAP_TRY(m, hipStreamSynchronize(g->stream));
-      float ms = 0;
-      if (tot.n_cells > 0) (void)hipEventElapsedTime(&ms_emit, G.ev[6], G.ev[7]);
-      (void)hipEventElapsedTime(&ms, G.ev[3], G.ev[4]); tot.sec[1] = 1e-3 * ms;
-      (void)hipEventElapsedTime(&ms, G.ev[4], G.ev[5]); tot.sec[2] = 1e-3 * ((double)ms + (double)ms_emit);
-      (void)hipEventElapsedTime(&ms, G.ev[0], G.ev[8]); tot.sec[3] = 1e-3 * ms;
-    } else {
-      MAP_TRY(m, hipEventRecord(G.ev[8], g->stream));
-      MAP_TRY(m, hipStreamSynchronize(g->stream));
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, G.ev[0], G.ev[8]); tot.sec[3] = 1e-3 * ms;
     }
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, G.ev[1], G.ev[2]); tot.sec[0] = 1e-3 * ms;
+    MAP_TRY(m, G.t_call.end(st));
+    MAP_TRY(m, hipStreamSynchronize(st));
+    if (tot.n_cells > 0) tot.sec[2] += G.t_emit.seconds();
+    tot.sec[3] = G.t_call.seconds();
   }
   G.planes.swap(planes);
   G.tot = tot;
@@ -288,8 +231,8 @@ void pps_map_grid_default_params(pps_map_grid_params* p) {
 
 static int build_grid_checked(pps_map* m, const pps_map_select* sel, const pps_map_grid_params* prm, bool posed, int64_t* n_points, int* n_planes) {
   if (!m) return PPS_EINVAL;
-  if (posed) { m->posed_sec[0] = m->posed_sec[1] = 0; m->n_motion = 0; m->n_unposed = 0; m->posed_launches = 0; }
-  if (m->grid) { m->grid->valid = false; m->grid->planes.clear(); m->grid->tot = pps_map_grid_totals{}; }      // a call that fails leaves no grid
+  if (posed) map_posed_reset(m);
+  if (m->grid) m->grid->clear();
   pps_map_grid_params p;
   pps_map_grid_default_params(&p);
   if (prm) p = *prm;
@@ -303,7 +246,7 @@ static int build_grid_checked(pps_map* m, const pps_map_select* sel, const pps_m
     if (!m->grid) return mfail(m, PPS_ENOMEM, "build_grid: out of host memory");
   }
   const int rc = build_grid(m, sel, p, posed, n_points, n_planes);
-  if (rc != PPS_OK) { m->grid->valid = false; m->grid->planes.clear(); m->grid->tot = pps_map_grid_totals{}; }
+  if (rc != PPS_OK) m->grid->clear();
   return rc;
 }
 
@@ -315,13 +258,10 @@ int pps_map_build_grid_posed(pps_map* m, const pps_map_select* sel, const pps_ma
 }
 
 int pps_map_grid_planes(const pps_map* m, int cap, pps_map_grid_plane* out, int* n) {
-  if (!m || !n || cap < 0 || (cap > 0 && !out)) return PPS_EINVAL;
+  if (!m) return PPS_EINVAL;
   const MapGrid* G = m->grid;
-  const size_t have = G && G->valid ? G->planes.size() : 0;
-  *n = (int)have;
-  const size_t k = std::min<size_t>((size_t)cap, have);
-  if (k) memcpy(out, G->planes.data(), k * sizeof(pps_map_grid_plane));
-  return PPS_OK;
+  const bool have = G && G->valid;
+  return map_table_copy(have ? G->planes.data() : nullptr, have ? G->planes.size() : 0, cap, out, n);
 }
 
 int pps_map_grid_info(const pps_map* m, pps_map_grid_totals* out) {

@@ -52,18 +52,21 @@ PPS_HD void map_move_xyz(const double D[12], double* x, double* y, double* z) {
   *x = mx; *y = my; *z = mz;
 }
 
+// a point of a frame that has a motion, in place: moved by D, then projected onto p, or only moved when the landmark is gone (`project`
+// false: p is not read); cast once.  What the kernels call for such a point (k_map_build_posed, grid_b_point).
+PPS_HD void map_moved_point(const double D[12], const double* p, bool project, float* px, float* py, float* pz) {
+  double x = (double)*px, y = (double)*py, z = (double)*pz;
+  map_move_xyz(D, &x, &y, &z);
+  if (project) project_to_plane_f64(p, x, y, z, px, py, pz);
+  else { *px = (float)x; *py = (float)y; *pz = (float)z; }
+}
+
 // the point of the posed map: moved by D (NULL: the frame has no motion), then projected onto p (NULL: the landmark is gone), cast once.
-// With D == NULL this is project_to_plane_f32 (p given) or the stored point itself.  (The kernels call the two steps themselves.)
+// With D == NULL this is project_to_plane_f32 (p given) or the stored point itself.
 PPS_HD void map_move_point(const double* D, const double* p, float xf, float yf, float zf, float* ox, float* oy, float* oz) {
-  double x = (double)xf, y = (double)yf, z = (double)zf;
-  if (D) {
-    map_move_xyz(D, &x, &y, &z);
-  } else if (!p) {
-    *ox = xf; *oy = yf; *oz = zf;
-    return;
-  }
-  if (p) project_to_plane_f64(p, x, y, z, ox, oy, oz);
-  else { *ox = (float)x; *oy = (float)y; *oz = (float)z; }
+  *ox = xf; *oy = yf; *oz = zf;
+  if (D) map_moved_point(D, p, p != nullptr, ox, oy, oz);
+  else if (p) project_to_plane_f64(p, (double)xf, (double)yf, (double)zf, ox, oy, oz);
 }
 
 }  // namespace pps

@@ -93,7 +93,7 @@ DESIGN_KERNELS = [
     ("k_linearize_repop_robust<2>", "... Factor2 edges, pseudo-Huber"), ("k_chi2_robust<2>", "robust chi2 at the stored state"), ("k_chi2_trial_robust<2>", "... of the one-step loop's trial"),
     ("k_linearize_repop_robust<3>", "... Factor2 edges, Cauchy"), ("k_chi2_robust<3>", "robust chi2 at the stored state"), ("k_chi2_trial_robust<3>", "... of the one-step loop's trial"),
     ("k_loop_gate", "pps_loop_gate: a wave per candidate loop closure, DESIGN.md section 5h"),
-    # the dense map's builds (pps_map.hip): the plain one as the yardstick of its posed sibling
+    # the dense map's builds (pps_map.hip on the chunk window of pps_map_window.h): the plain one as the yardstick of its posed sibling
     ("k_map_build", "pps_map_build: 16 B in, 16 B out per point"), ("k_map_build_posed", "pps_map_build_posed: ... with the frame's motion from scalar loads"),
     ("k_map_motion", "one thread per frame of the selection"),
 ]
