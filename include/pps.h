@@ -896,6 +896,66 @@ int pps_map_grid_download(pps_map* m, int64_t first, int64_t n, pps_point* pts, 
 int pps_map_grid_frame_host(const double abcd[4], double n[3], double e1[3], double e2[3]);
 int pps_map_grid_cell_host(const double e[3], double inv_cell, const float xyz[3], int64_t* cell, int* dropped);
 
+/* ---- rendered view: the grid map seen from a camera pose ---------------------------------------------------------------
+ * pps_map_render casts the ray of every pixel of a pinhole camera onto every landmark plane of the LAST GRID and keeps the nearest hit
+ * whose lattice cell was emitted: the inverse of the pop-up kernel.  It leaves four images on the device, in the shapes of
+ * pps_popup_download: the cloud, the depth, the plane id, and the index of the grid cell that answered.  The view is of the grid as it was
+ * built: the plane equations are the ones grid_frame was given (pps_map_grid_plane_eq), not the graph's current estimate.
+ *
+ * All arithmetic is fp64 in the order written; every product and sum is rounded once, nothing is fused.
+ *   ray           of pixel (col, row): x = col, y = row as doubles, iK and T the floats of the view converted to double.
+ *                 ds[k] = (iK[3k]*x + iK[3k+1]*y) + iK[3k+2];  dw[k] = (T[4k]*ds[0] + T[4k+1]*ds[1]) + T[4k+2]*ds[2];  o[k] = T[4k+3].
+ *   landmark      rows of pps_map_grid_planes in their order (ascending plane id); rows with ni * nj = 0 are skipped.  With p the row's four
+ *                 doubles and l, n, e1, e2 exactly as the grid's frame computes them: dn = p[3] / l,
+ *                 den = (n0*dw0 + n1*dw1) + n2*dw2,  h = ((n0*o0 + n1*o1) + n2*o2) + dn.  No hit if den is 0 or not finite.
+ *                 t = (-h) / den; no hit unless t > 0.  z = t * ds[2]; no hit unless z_near <= z <= z_far (a NaN fails).
+ *                 X[k] = o[k] + t*dw[k], Xf = (float)X; no hit if a component is not finite.  (i, j) = the grid's cell of Xf along e1 and
+ *                 e2 with the grid's inv_cell; no hit if either axis drops the point.  A plane is seen from both sides.
+ *   cell          for ring k = 0 .. reach: for dj = -k .. k ascending, for di = -k .. k ascending, only pairs with max(|di|, |dj|) = k:
+ *                 the first (i + di, j + dj) inside the row's box that is an emitted cell (its count >= the grid's min_count) answers.
+ *                 If none answers there is no hit on this landmark.
+ *   pixel         the hit with the smallest z wins, among equal z the earlier row.  depth = (float)z, plane_id = the landmark's node id,
+ *                 cell = the index of the answering cell in the grid map (what pps_map_grid_download indexes), cloud = (Xf, the rgba of
+ *                 that grid point).  Without a hit: cloud all zero bits, depth 0, plane_id -1, cell -1.  n_hit = the pixels with a hit.
+ * Not offered: anti-aliasing, a back-face rule, a view at the current estimate without a new grid.
+ * The render changes nothing else: the store, the built map, the grid and its download calls, the chunk tables and the graph.  A grid call
+ * of either kind, whether it succeeds or fails, ends the rendered view.  Found by symbol lookup, like pps_map_create; PPS_VERSION was not bumped. */
+typedef struct pps_map_view {
+  int32_t width, height;        /* 1 .. 4096 each */
+  int32_t reach;                /* 0 .. 4: how many rings of neighbouring cells may answer for an empty cell */
+  int32_t reserved;             /* 0 */
+  float   invK[9];              /* row-major, as pps_popup_create takes it */
+  float   T_wc[16];             /* row-major 4x4, sensor -> world; rigid by the rule of pps_map_set_frame_pose */
+  double  z_near, z_far;        /* 0 <= z_near < z_far; z_far may be +inf */
+} pps_map_view;
+typedef struct pps_map_render_totals {
+  int32_t width, height;
+  int32_t n_planes;             /* landmarks cast: the rows of the plane table that have a box */
+  int32_t launches;             /* kernels of the call: 1, 2 on the first render after a grid (the slot table), 0 without a device */
+  int64_t n_hit;
+  double  sec;                  /* device seconds (HIP events) of the render kernels */
+} pps_map_render_totals;
+void pps_map_default_view(pps_map_view* v, int width, int height, const float invK[9], const float T_wc[16]);  /* reach 1, z_near 0, z_far +inf */
+/* n_hit may be NULL.
+ *   PPS_EINVAL  answered on the host before any device work, nothing changed: NULL m or v, a size outside 1 .. 4096, reach outside 0 .. 4,
+ *               reserved != 0, a non-finite invK entry, a T_wc that is not rigid, z_near not finite or < 0, z_far NaN or <= z_near
+ *   PPS_ESTATE  there is no grid: no grid call has succeeded yet, or the last one failed
+ *   PPS_ENOMEM  the device has no room for the images or for the slot table (one int per box cell, made by the first render after a
+ *               grid and kept until the next grid call); the grid stays valid
+ * A grid with zero cells renders PPS_OK with every pixel empty and needs no device. */
+int  pps_map_render(pps_map* m, const pps_map_view* v, int64_t* n_hit);
+/* the images of the last render, width * height records each in raster order; any may be NULL.  PPS_ESTATE: no render present. */
+int  pps_map_render_download(pps_map* m, pps_point* cloud, float* depth, int32_t* plane_id, int64_t* cell);
+int  pps_map_render_info(const pps_map* m, pps_map_render_totals* out);                                       /* PPS_ESTATE: no render present */
+/* the plane equation the last grid was built with: row r of pps_map_grid_planes -> abcd[4 r .. 4 r + 3] (the four doubles the frame was
+ * computed from); *n = rows in all, the first min(cap, *n) are copied */
+int  pps_map_grid_plane_eq(const pps_map* m, int cap, double* abcd, int* n);
+/* host only, no device: ONE pixel against ONE landmark as stated above, compiled from the header the kernel includes.  hit: returns 1 for
+ * a hit (z, xyz = Xf, ij = the cell of Xf, before any ring), 0 for none (outputs zeroed), -1 for a NULL pointer or a plane without a normal. */
+int  pps_map_render_ray_host(const pps_map_view* v, int col, int row, double o[3], double ds[3], double dw[3]);
+int  pps_map_render_hit_host(const double o[3], const double ds[3], const double dw[3], const double abcd[4], double inv_cell,
+                             double z_near, double z_far, double* z, float xyz[3], int64_t ij[2]);
+
 /* ---- posed map: stored points follow their frame's pose estimate -----------------------------------------------------
  * The store holds every frame's points in world coordinates, made with the T_wc its pop-up run was given -- the pose predicted from
  * odometry (main_3d.cpp:426-431).  pps_map_build repairs a point along the normal of its landmark only; when the optimiser moves the

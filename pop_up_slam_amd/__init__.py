@@ -139,6 +139,17 @@ GRID_PLANE_DTYPE = np.dtype([("plane_id", "<i4"), ("n_chunks", "<i4"), ("i0", "<
                              ("offset", "<i8"), ("count", "<i8"), ("n_in", "<i8"), ("n", "<f8", 3), ("e1", "<f8", 3), ("e2", "<f8", 3)])
 
 
+class PpsMapView(C.Structure):
+    """pps_map_view (include/pps.h): the camera of pps_map_render; defaults via pps_map_default_view."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("reach", C.c_int32), ("reserved", C.c_int32),
+                ("invK", C.c_float * 9), ("T_wc", C.c_float * 16), ("z_near", C.c_double), ("z_far", C.c_double)]
+
+
+class PpsMapRenderTotals(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_planes", C.c_int32), ("launches", C.c_int32),
+                ("n_hit", C.c_int64), ("sec", C.c_double)]
+
+
 SYMBOLS = [
     "pps_default_props", "pps_version", "pps_last_error", "pps_graph_create", "pps_graph_destroy",
     "pps_get_props", "pps_set_props", "pps_add_pose", "pps_add_plane", "pps_add_pose_prior",
@@ -169,6 +180,8 @@ SYMBOLS = [
     "pps_map_last_times", "pps_debug_map_add_points",
     "pps_map_grid_default_params", "pps_map_build_grid", "pps_map_grid_planes", "pps_map_grid_info", "pps_map_grid_download",
     "pps_map_grid_frame_host", "pps_map_grid_cell_host",
+    "pps_map_default_view", "pps_map_render", "pps_map_render_download", "pps_map_render_info", "pps_map_grid_plane_eq",
+    "pps_map_render_ray_host", "pps_map_render_hit_host",
     "pps_map_set_frame_pose", "pps_map_frames", "pps_map_build_posed", "pps_map_build_grid_posed", "pps_map_frame_motions",
     "pps_map_posed_last", "pps_map_motion_host", "pps_map_move_point_host",
     "pps_set_cost_function", "pps_get_cost_function",
@@ -335,6 +348,13 @@ def lib():
         L.pps_map_grid_download.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pps_map_grid_frame_host.argtypes = [_dp, _dp, _dp, _dp]
         L.pps_map_grid_cell_host.argtypes = [_dp, C.c_double, _fp, _i64p, _ip]
+        L.pps_map_default_view.argtypes = [C.POINTER(PpsMapView), C.c_int, C.c_int, _fp, _fp]; L.pps_map_default_view.restype = None
+        L.pps_map_render.argtypes = [C.c_void_p, C.POINTER(PpsMapView), _i64p]
+        L.pps_map_render_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pps_map_render_info.argtypes = [C.c_void_p, C.POINTER(PpsMapRenderTotals)]
+        L.pps_map_grid_plane_eq.argtypes = [C.c_void_p, C.c_int, _dp, _ip]
+        L.pps_map_render_ray_host.argtypes = [C.POINTER(PpsMapView), C.c_int, C.c_int, _dp, _dp, _dp]
+        L.pps_map_render_hit_host.argtypes = [_dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, _fp, _i64p]
         L.pps_map_set_frame_pose.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp]
         L.pps_map_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
         L.pps_map_build_posed.argtypes = [C.c_void_p, C.POINTER(PpsMapSelect), _i64p, _ip]
@@ -1203,6 +1223,68 @@ class Map:
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
         self._ck(self.L.pps_map_grid_download(self.h, int(first), int(n), vp(pts), vp(cnt), vp(ij), vp(src)))
         return pts, cnt, ij, src
+
+    def grid_plane_eq(self):
+        """pps_map_grid_plane_eq: (rows of grid_planes, 4) doubles, the plane equations the last grid was built with"""
+        n = C.c_int(); self._ck(self.L.pps_map_grid_plane_eq(self.h, 0, None, C.byref(n)))
+        out = np.zeros((n.value, 4))
+        if n.value:
+            self._ck(self.L.pps_map_grid_plane_eq(self.h, n.value, out.ctypes.data_as(_dp), C.byref(n)))
+        return out
+
+    def render(self, width, height, invK, T_wc, reach=1, z_near=0.0, z_far=float("inf")):
+        """pps_map_render: the last grid seen by a pinhole camera at T_wc (4x4 fp32, sensor -> world) -> dict(cloud POINT_DTYPE, depth
+        float32, plane_id int32, cell int64: (height, width) each; n_hit; totals: pps_map_render_totals as a dict)"""
+        v = map_view(width, height, invK, T_wc, reach, z_near, z_far)
+        n_hit = C.c_int64()
+        self._ck(self.L.pps_map_render(self.h, C.byref(v), C.byref(n_hit)))
+        out = self.render_download()
+        out["n_hit"] = n_hit.value
+        out["totals"] = self.render_info()
+        return out
+
+    def render_download(self):
+        """the four images of the last render as a dict"""
+        t = self.render_info()
+        shape = (t["height"], t["width"])
+        out = dict(cloud=np.zeros(shape, dtype=POINT_DTYPE), depth=np.zeros(shape, dtype=np.float32), plane_id=np.zeros(shape, dtype=np.int32),
+                   cell=np.zeros(shape, dtype=np.int64))
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._ck(self.L.pps_map_render_download(self.h, vp(out["cloud"]), vp(out["depth"]), vp(out["plane_id"]), vp(out["cell"])))
+        return out
+
+    def render_info(self):
+        """pps_map_render_totals of the last render as a dict"""
+        t = PpsMapRenderTotals(); self._ck(self.L.pps_map_render_info(self.h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_}
+
+
+def map_view(width, height, invK, T_wc, reach=1, z_near=0.0, z_far=float("inf")):
+    """a PpsMapView: pps_map_default_view, then the three optional fields"""
+    iK = np.ascontiguousarray(invK, dtype=np.float32).reshape(9); T = np.ascontiguousarray(T_wc, dtype=np.float32).reshape(16)
+    v = PpsMapView(); lib().pps_map_default_view(C.byref(v), int(width), int(height), iK.ctypes.data_as(_fp), T.ctypes.data_as(_fp))
+    v.reach, v.z_near, v.z_far = int(reach), float(z_near), float(z_far)
+    return v
+
+
+def map_render_ray_host(view, col, row):
+    """pps_map_render_ray_host: (o, ds, dw) of pixel (col, row) of a PpsMapView.  No device needed."""
+    o, ds, dw = np.zeros(3), np.zeros(3), np.zeros(3)
+    rc = lib().pps_map_render_ray_host(C.byref(view), int(col), int(row), o.ctypes.data_as(_dp), ds.ctypes.data_as(_dp), dw.ctypes.data_as(_dp))
+    if rc != PPS_OK:
+        raise PpsError(rc, "pps_map_render_ray_host")
+    return o, ds, dw
+
+
+def map_render_hit_host(o, ds, dw, abcd, inv_cell, z_near=0.0, z_far=float("inf")):
+    """pps_map_render_hit_host: one ray against one landmark plane -> (hit, z, xyz float32 (3,), (i, j)).  No device needed."""
+    a = [np.ascontiguousarray(x, dtype=np.float64).reshape(n) for x, n in ((o, 3), (ds, 3), (dw, 3), (abcd, 4))]
+    z = C.c_double(); xyz = np.zeros(3, dtype=np.float32); ij = np.zeros(2, dtype=np.int64)
+    rc = lib().pps_map_render_hit_host(*[x.ctypes.data_as(_dp) for x in a], float(inv_cell), float(z_near), float(z_far), C.byref(z),
+                                       xyz.ctypes.data_as(_fp), ij.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc < 0:
+        raise PpsError(PPS_EINVAL, "pps_map_render_hit_host")
+    return bool(rc), z.value, xyz, (int(ij[0]), int(ij[1]))
 
 
 def map_grid_frame_host(abcd):

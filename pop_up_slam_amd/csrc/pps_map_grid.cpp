@@ -1,6 +1,7 @@
 // pps_map_grid.cpp -- host side of the grid map (include/pps.h: pps_map_build_grid and the pps_map_grid_* calls): the plane table of the
 // selection (MapSelection, pps_map_host.h), the frames, the layout of the cell arrays between the passes, and the calls that drive the
-// kernels of pps_grid.hip.
+// kernels of pps_grid.hip.  The record of the last grid (MapGrid) lives in pps_map_grid_host.h: pps_map_render.cpp reads it, and every
+// grid call ends the view rendered from the grid before (MapGrid::clear).
 //
 // One call synchronises the graph's stream three times, each time for a small table the host has to read: after the extent pass (the boxes
 // decide the size of the cell arrays and the max_cells refusal), after the count / scan (the emitted cells decide the size of the output),
@@ -8,7 +9,7 @@
 // copy of the same doubles (download_state brings it home when the device holds the newer estimate).
 #include "pps_grid.h"
 #include "pps_grid_cell.h"
-#include "pps_map_host.h"
+#include "pps_map_grid_host.h"
 
 #include <climits>
 #include <cstdlib>
@@ -18,32 +19,13 @@ using namespace pps_impl;
 
 namespace pps_impl {
 
-struct MapGrid {
-  // the last grid (valid: the last call succeeded)
-  bool valid = false;
-  std::vector<pps_map_grid_plane> planes;
-  pps_map_grid_totals tot{};
-  // device
-  MapBuf<char> sel;                                   // tables of the selection, with the lm column (MapSelection)
-  MapBuf<GridPlaneDev> d_planes;
-  MapBuf<char> small;                                 // GridExtent per landmark, then the dropped counter
-  MapBuf<long long> plane_tab;                        // plane_base[n + 1], plane_off[n + 1]
-  MapBuf<unsigned long long> key;
-  MapBuf<unsigned int> cnt;
-  MapBuf<int> tile_count;
-  MapBuf<long long> tile_prefix;
-  MapBuf<MapPt> out_pts; MapBuf<unsigned int> out_cnt; MapBuf<int> out_ij; MapBuf<long long> out_src;
-  // tot.sec: [0] the extent pass, [1] zeroing and votes, [2] count + scan + plane_off and the emission, [3] first upload to last kernel
-  MapSpan t_extent, t_vote, t_count, t_emit, t_call;
-  void clear() { valid = false; planes.clear(); tot = pps_map_grid_totals{}; }      // a call that fails leaves no grid
-};
-
 void map_grid_release(pps_map* m) {
   MapGrid* gr = m ? m->grid : nullptr;
   if (!gr) return;
   gr->sel.release(); gr->d_planes.release(); gr->small.release(); gr->plane_tab.release(); gr->key.release(); gr->cnt.release();
   gr->tile_count.release(); gr->tile_prefix.release(); gr->out_pts.release(); gr->out_cnt.release(); gr->out_ij.release(); gr->out_src.release();
   for (MapSpan* t : {&gr->t_extent, &gr->t_vote, &gr->t_count, &gr->t_emit, &gr->t_call}) t->release();
+  gr->render.release();
   delete gr;
   m->grid = nullptr;
 }
@@ -89,6 +71,8 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
   pps_map_grid_totals tot{};
   tot.n_points = total; tot.n_passed_through = through; tot.n_planes = nL; tot.cell = prm.cell; tot.inv_cell = inv_cell;
   const bool device = total - through > 0;
+  std::vector<double> plane_eq;
+  int64_t n_box_cells = 0;
   if (device) {
     const int rc = prepare_solve(g);
     if (rc != PPS_OK) return mfail(m, rc, g->err);
@@ -96,9 +80,11 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
   if (nL > 0) {                                         // the frames, from the doubles the device projects with
     const int rc = download_state(g);
     if (rc != PPS_OK) return mfail(m, rc, g->err);
-    for (pps_map_grid_plane& p : planes)
+    for (pps_map_grid_plane& p : planes) {
       if (!grid_frame(g->nodes[p.plane_id].v, p.n, p.e1, p.e2))
         return mfail(m, PPS_EINVAL, "build_grid: plane node " + std::to_string(p.plane_id) + " has no normal");
+      plane_eq.insert(plane_eq.end(), g->nodes[p.plane_id].v, g->nodes[p.plane_id].v + 4);       // kept with the grid (pps_map_grid_plane_eq)
+    }
   }
   if (device) {
     int rc = map_use_device(m);
@@ -168,6 +154,7 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
                                       std::to_string(p.ni) + " x " + std::to_string(p.nj) + " cells of " + std::to_string(prm.cell) + " m from (" + std::to_string(p.i0) + ", " +
                                       std::to_string(p.j0) + ") for " + std::to_string(p.n_in) + " points (a far outlier makes such a box)");
     }
+    n_box_cells = all;
     if (all > 0) {
       const GridTiling t = grid_tiling(all);
       MAP_TRY(m, G.key.reserve((size_t)all, st));
@@ -213,7 +200,9 @@ int build_grid(pps_map* m, const pps_map_select* sel, const pps_map_grid_params&
     tot.sec[3] = G.t_call.seconds();
   }
   G.planes.swap(planes);
+  G.plane_eq.swap(plane_eq);
   G.tot = tot;
+  G.n_box_cells = n_box_cells; G.min_count = prm.min_count;
   G.valid = true;
   if (n_points) *n_points = tot.n_cells;
   if (n_planes) *n_planes = nL;

@@ -97,7 +97,7 @@ struct pps_map {
   int n_motion = 0, n_unposed = 0, posed_launches = 0;
   pps_impl::MapSpan t_motion, t_posed;                // posed_sec[0]: k_map_motion; posed_sec[1]: k_map_build_posed
   double posed_sec[2] = {0, 0};
-  pps_impl::MapGrid* grid = nullptr;                  // the last grid map and its buffers (pps_map_grid.cpp), made by the first pps_map_build_grid
+  pps_impl::MapGrid* grid = nullptr;                  // the last grid map, its buffers and its rendered view (pps_map_grid_host.h), made by the first pps_map_build_grid
 };
 
 namespace pps_impl {

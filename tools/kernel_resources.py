@@ -96,14 +96,17 @@ DESIGN_KERNELS = [
     # the dense map's builds (pps_map.hip on the chunk window of pps_map_window.h): the plain one as the yardstick of its posed sibling
     ("k_map_build", "pps_map_build: 16 B in, 16 B out per point"), ("k_map_build_posed", "pps_map_build_posed: ... with the frame's motion from scalar loads"),
     ("k_map_motion", "one thread per frame of the selection"),
+    # the rendered view of the grid map (pps_render.hip); neither uses scratch
+    ("k_render", "pps_map_render: one thread per pixel, 26 640 B of LDS for a slice of 256 landmark rows"),
+    ("k_render_slots", "the slot table, once per grid"),
 ]
 TABLE_BEGIN, TABLE_END = "<!-- kernel-table:begin (tools/kernel_resources.py --update-design) -->", "<!-- kernel-table:end -->"
 
 
 def built_table():
-    """{name: dict} of every kernel of the solver objects (and of pps_loop.hip, pps_map.hip) the Makefile built"""
+    """{name: dict} of every kernel of the solver objects (and of pps_loop.hip, pps_map.hip, pps_render.hip) the Makefile built"""
     out = {}
-    for f in ("pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip", "pps_robust.hip", "pps_loop.hip", "pps_map.hip"):
+    for f in ("pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip", "pps_robust.hip", "pps_loop.hip", "pps_map.hip", "pps_render.hip"):
         for r in resources(os.path.join(CSRC, f), [], built=True):
             v = int(r["vgpr_count"])
             out[short_name(r["name"])] = {"vgpr": v, "agpr": int(r["agpr_count"]), "waves": min(8, 512 // max(8, (v + 7) // 8 * 8)),
