@@ -10,7 +10,8 @@
 // leaves memory unspecified, and compares the blocks of S with np.linalg.inv.
 //
 // With -DCOV_DENSE_EMU_MAIN the file is a stand-alone program (for -fsanitize=address,undefined): a chain of fronts with random panels in
-// shapes that are no multiples of 16 or 64, against a sequential restatement of the recursion.  Exit code 0: all within 1e-10 of the largest
+// shapes that are no multiples of 16 or 64 -- and chains at the tile edges no graph reaches (p = 64 with b = 256 and 257, p around 16 and 32 with
+// b around 32 and 64, p = 1 with b = 1) --, against a sequential restatement of the recursion.  Exit code 0: all within 1e-10 of the largest
 // entry, status word zero, and the three refusals (collapsed pivot, corrupted child map, short update-matrix array) raise what they should.
 #include <algorithm>
 #include <cmath>
@@ -221,6 +222,16 @@ int main() {
   int bad = 0;
   bad += run_chain("band shapes", {15, 9, 17, 6, 30, 8}, {33, 30, 27, 25, 8, 0}, 1);
   bad += run_chain("wide fronts", {12, 64, 33, 63, 64, 64, 64, 30}, {300, 257, 230, 170, 108, 46, 29, 0}, 2);
+  // the tile edges no graph reaches (every shape of a graph is a multiple of 3): four full column tiles at the end of the first and one row
+  // into the second 256-row slab of G; p one below / at / one beyond a tile against b around the 32-row k-slab and the 64-row strip (b = 65 and
+  // 80: the last strip leaves waves 1 .. 3 without a row); a front of one pivot and one row
+  bad += run_chain("p 64, b 257 and 256", {64, 64, 64, 64, 64, 64}, {257, 256, 192, 128, 64, 0}, 3);
+  for (int p : {16, 17, 32, 33}) {
+    char label[64];
+    snprintf(label, sizeof label, "p %d, b 80 65 64 33 32 31", p);
+    bad += run_chain(label, {p, p, p, p, p, p, 40}, {80, 65, 64, 33, 32, 31, 0}, 4 + (unsigned)p);
+  }
+  bad += run_chain("p 1, b 1", {1, 3, 4}, {1, 3, 0}, 5);
   return bad ? 1 : 0;
 }
 #endif

@@ -4,9 +4,10 @@ Reference of every comparison: H = J'J assembled in numpy from pps_eval_factor (
 inverted on the CPU.  Per block e = |S_dev - S_ref|_F / |S_ref|_F; the yardstick is the disagreement d between two CPU inverses of
 the same H that share no code path (np.linalg.inv and scipy cho_solve), per graph, maximum over the same blocks: e <= max(16 d, 1e-12).
 
-The figures e and d are printed per graph (run with -s; PPS_COV_TABLE=<file> collects them as JSON lines).  None is quoted here: no device
-run of this file had completed when it was written -- the CPU suite checks the same recursion, and the kernel source
-compiled for the host, against the dense inverse (tests/test_host_cov.py).
+The figures e and d are printed per graph (run with -s; PPS_COV_TABLE=<file> collects them as JSON lines).  The measured tables of the
+covariance calls on an MI355X are in DESIGN.md, section 5b (COVSEL, COVSHAPE: tests/test_gpu_cov_shapes.py pins the level pass at every
+front shape and pattern entry) -- the CPU suite checks the same recursion, and the kernel source compiled for the host, against the dense
+inverse (tests/test_host_cov.py, tests/test_host_cov_shapes.py).
 """
 import json
 import os
