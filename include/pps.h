@@ -1010,6 +1010,73 @@ int pps_map_posed_last(const pps_map* m, double sec[2], int* launches, int* n_un
 int pps_map_motion_host(const float T_wc[16], const double tq[7], double D[12]);
 int pps_map_move_point_host(const double* D, const double* abcd, const float xyz[3], float out[3]);
 
+/* ---- compared views: a pop-up frame against the rendered map view ----------------------------------------------------
+ * pps_map_compare compares the last run of a pop-up context with the LAST RENDER of the map: pixel for pixel, at the same raster index, it
+ * fills a table of integer counters on the device.  It changes neither of them.  Everything is integer except one fp64 expression per
+ * pixel, evaluated in the order written, every product and sum rounded once, nothing fused.
+ *   inputs        the render's images (width x height); the plane table of the grid it was rendered from (the rows of pps_map_grid_planes,
+ *                 n_rows of them, ascending node id) with the grid's own plane equations (pps_map_grid_plane_eq), not the graph's current
+ *                 estimate; the run's cloud and plane-id map (a run in flight is waited for); nplanes (1 .. 65 frame planes, 0 = ground);
+ *                 tol (metres, finite, >= 0).
+ *   frame side    k = the run's plane id of the pixel.  0 <= k < nplanes and the valid bit (bit 24 of rgba) set: valid with frame plane k.
+ *                 k = -1 or the valid bit clear: none.  Any other k (k < -1 or k >= nplanes): none as well, and counted in n_bad_id,
+ *                 whatever its valid bit says.
+ *   view side     the render's plane id is -1: none.  Otherwise r = the row of the plane table whose plane_id equals it.
+ *   classes       every pixel adds 1 to exactly one of: n[k][r] (both sides present), n_new[k] (a frame and no view), n_unseen[r] (a view
+ *                 and no frame), n_neither.
+ *   pair          both sides present.  p = the row's four doubles; l, n exactly as the grid's frame computes them, dn = p[3] / l as the
+ *                 render computes it; x, y, z the fp32 coordinates of the POP-UP point converted to double.
+ *                 e = ((n[0]*x + n[1]*y) + n[2]*z) + dn: the signed distance of the frame's point from the map's plane (a distance to the
+ *                 plane, not a depth difference: the ceiling clamp of the pop-up moves a point along a vertical wall, not off it).
+ *                 agree = fabs(e) <= tol (a NaN fails).  s = e * 4096.0 (exact).  s NaN or s >= 524288: q = 524288; s <= -524288:
+ *                 q = -524288; else q = (long long)rint(s), ties to even.  The pair accumulates n += 1, n_agree += agree, sum_q += q,
+ *                 sum_q2 += q*q, all int64 (width, height <= 4096: sum_q2 <= 2^38 * 2^24).  Mean and rms distance in metres:
+ *                 sum_q / (4096 n) and sqrt(sum_q2 / n) / 4096, to a quantum of 0.24 mm.
+ *   best landmark of frame plane k: the row with the greatest n_agree; among equal rows the greater n, among those the earlier row;
+ *                 best_row = best_plane_id = -1 if no row has n_agree >= 1.
+ *   pair list     the entries with n >= 1, by k ascending, then r ascending.
+ * Every accumulator is an integer: the result does not depend on the order waves run in, two calls on the same state give the same bytes.
+ * The views are compared index by index: nothing asks that the render's T_wc is the run's; render at the pose the frame is to be tested at.
+ * Not offered: a comparison against the graph's current estimate, depth-along-the-ray statistics, a per-pixel output image.
+ * A comparison ends with whatever ends the render (any grid call, a new render) and with the next comparison.  It holds device buffers of
+ * its own, freed with the map.  Found by symbol lookup, like pps_map_create; PPS_VERSION was not bumped. */
+typedef struct pps_map_compare_plane {   /* one per frame plane k */
+  int64_t n_valid, n_new;                /* valid pixels of k; of those, pixels without a view */
+  int32_t best_row, best_plane_id;       /* -1, -1: none */
+  int64_t best_n, best_agree;
+} pps_map_compare_plane;
+typedef struct pps_map_compare_row { int64_t n_view, n_unseen; } pps_map_compare_row;   /* one per row of the plane table */
+typedef struct pps_map_compare_pair {
+  int32_t frame_plane, row, plane_id, reserved;
+  int64_t n, n_agree, sum_q, sum_q2;
+} pps_map_compare_pair;
+typedef struct pps_map_compare_totals {
+  int32_t width, height, nplanes, n_rows;
+  int64_t n_both, n_frame_only, n_view_only, n_neither, n_bad_id, n_pairs;
+  int32_t launches, reserved;            /* kernels of the call */
+  double  tol, sec;                      /* device seconds (HIP events) of the compare kernels */
+} pps_map_compare_totals;
+/* planes ([nplanes], may be NULL): the per-plane records.
+ *   PPS_EINVAL  answered on the host before any device work; the map, the view and an earlier comparison stay as they were: NULL m or p,
+ *               nplanes outside 1 .. 65, tol NaN, infinite or negative, a context on another device, a run whose width x height is not the
+ *               render's
+ *   PPS_ESTATE  no render present; no run yet, or a run with the plane-id output off
+ *   PPS_ENOMEM  the device has no room for the table or the scratch images; the render stays valid */
+int pps_map_compare(pps_map* m, pps_popup* p, int nplanes, double tol, pps_map_compare_plane* planes);
+/* pps_map_compare fed host arrays (npx = width * height records each, raster order: what pps_popup_download returns) in place of a run:
+ * they are copied to scratch buffers of the map, from there on it IS pps_map_compare.  PPS_EINVAL also for NULL cloud or plane_id and
+ * for npx != width * height of the render. */
+int pps_debug_map_compare_points(pps_map* m, const pps_point* cloud, const int* plane_id, int64_t npx, int nplanes, double tol,
+                                 pps_map_compare_plane* planes);
+/* of the last comparison; PPS_ESTATE: no comparison present.  rows: *n = rows in all, the first min(cap, *n) are copied.  pairs: entries
+ * [first, first + count) of the pair list; PPS_EINVAL for a range outside [0, n_pairs]. */
+int pps_map_compare_info(const pps_map* m, pps_map_compare_totals* out);
+int pps_map_compare_rows(pps_map* m, int cap, pps_map_compare_row* out, int* n);
+int pps_map_compare_pairs(pps_map* m, int64_t first, int64_t count, pps_map_compare_pair* out);
+/* host only, no device, compiled from the header the kernel includes: ONE point against ONE plane.  Returns agree (0 / 1), -1 for a NULL
+ * pointer or a plane without a normal. */
+int pps_map_compare_point_host(const double abcd[4], const float xyz[3], double tol, double* e, int64_t* q);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,20 @@ class PpsMapRenderTotals(C.Structure):
                 ("n_hit", C.c_int64), ("sec", C.c_double)]
 
 
+class PpsMapCompareTotals(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("nplanes", C.c_int32), ("n_rows", C.c_int32),
+                ("n_both", C.c_int64), ("n_frame_only", C.c_int64), ("n_view_only", C.c_int64), ("n_neither", C.c_int64),
+                ("n_bad_id", C.c_int64), ("n_pairs", C.c_int64), ("launches", C.c_int32), ("reserved", C.c_int32),
+                ("tol", C.c_double), ("sec", C.c_double)]
+
+
+MAP_COMPARE_PLANE_DTYPE = np.dtype([("n_valid", "<i8"), ("n_new", "<i8"), ("best_row", "<i4"), ("best_plane_id", "<i4"),
+                                    ("best_n", "<i8"), ("best_agree", "<i8")])                                    # pps_map_compare_plane
+MAP_COMPARE_ROW_DTYPE = np.dtype([("n_view", "<i8"), ("n_unseen", "<i8")])                                         # pps_map_compare_row
+MAP_COMPARE_PAIR_DTYPE = np.dtype([("frame_plane", "<i4"), ("row", "<i4"), ("plane_id", "<i4"), ("reserved", "<i4"),
+                                   ("n", "<i8"), ("n_agree", "<i8"), ("sum_q", "<i8"), ("sum_q2", "<i8")])        # pps_map_compare_pair
+
+
 SYMBOLS = [
     "pps_default_props", "pps_version", "pps_last_error", "pps_graph_create", "pps_graph_destroy",
     "pps_get_props", "pps_set_props", "pps_add_pose", "pps_add_plane", "pps_add_pose_prior",
@@ -182,6 +196,8 @@ SYMBOLS = [
     "pps_map_grid_frame_host", "pps_map_grid_cell_host",
     "pps_map_default_view", "pps_map_render", "pps_map_render_download", "pps_map_render_info", "pps_map_grid_plane_eq",
     "pps_map_render_ray_host", "pps_map_render_hit_host",
+    "pps_map_compare", "pps_debug_map_compare_points", "pps_map_compare_info", "pps_map_compare_rows", "pps_map_compare_pairs",
+    "pps_map_compare_point_host",
     "pps_map_set_frame_pose", "pps_map_frames", "pps_map_build_posed", "pps_map_build_grid_posed", "pps_map_frame_motions",
     "pps_map_posed_last", "pps_map_motion_host", "pps_map_move_point_host",
     "pps_set_cost_function", "pps_get_cost_function",
@@ -355,6 +371,12 @@ def lib():
         L.pps_map_grid_plane_eq.argtypes = [C.c_void_p, C.c_int, _dp, _ip]
         L.pps_map_render_ray_host.argtypes = [C.POINTER(PpsMapView), C.c_int, C.c_int, _dp, _dp, _dp]
         L.pps_map_render_hit_host.argtypes = [_dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, _fp, _i64p]
+        L.pps_map_compare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+        L.pps_debug_map_compare_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_void_p]
+        L.pps_map_compare_info.argtypes = [C.c_void_p, C.POINTER(PpsMapCompareTotals)]
+        L.pps_map_compare_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
+        L.pps_map_compare_pairs.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        L.pps_map_compare_point_host.argtypes = [_dp, _fp, C.c_double, _dp, _i64p]
         L.pps_map_set_frame_pose.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp]
         L.pps_map_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _ip]
         L.pps_map_build_posed.argtypes = [C.c_void_p, C.POINTER(PpsMapSelect), _i64p, _ip]
@@ -1257,6 +1279,59 @@ class Map:
         """pps_map_render_totals of the last render as a dict"""
         t = PpsMapRenderTotals(); self._ck(self.L.pps_map_render_info(self.h, C.byref(t)))
         return {k: getattr(t, k) for k, _ in t._fields_}
+
+
+    def compare(self, popup, nplanes, tol=0.05):
+        """pps_map_compare: the last run of `popup` against the last render, pixel for pixel -> MAP_COMPARE_PLANE_DTYPE (nplanes,): per
+        frame plane its valid pixels, those without a view, and the landmark most of its pixels agree with (-1: none)"""
+        out = np.zeros(max(int(nplanes), 0), dtype=MAP_COMPARE_PLANE_DTYPE)
+        self._ck(self.L.pps_map_compare(self.h, popup.h if popup is not None else None, int(nplanes), float(tol), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def debug_compare(self, cloud, plane_id, nplanes, tol=0.05):
+        """pps_debug_map_compare_points: compare fed host arrays (cloud: POINT_DTYPE, plane_id: int32, one record per pixel of the
+        rendered view in raster order -- what Popup.download returns) in place of a pop-up run"""
+        cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE).reshape(-1)
+        pid = np.ascontiguousarray(plane_id, dtype=np.int32).reshape(-1)
+        if len(cloud) != len(pid):
+            raise ValueError("debug_compare: cloud and plane_id differ in length")
+        out = np.zeros(max(int(nplanes), 0), dtype=MAP_COMPARE_PLANE_DTYPE)
+        self._ck(self.L.pps_debug_map_compare_points(self.h, cloud.ctypes.data_as(C.c_void_p), pid.ctypes.data_as(C.c_void_p), len(cloud),
+                                                     int(nplanes), float(tol), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def compare_info(self):
+        """pps_map_compare_totals of the last comparison as a dict"""
+        t = PpsMapCompareTotals(); self._ck(self.L.pps_map_compare_info(self.h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in t._fields_ if k != "reserved"}
+
+    def compare_rows(self):
+        """per row of the grid's plane table (MAP_COMPARE_ROW_DTYPE): the pixels of the view that show it, and those without a frame point"""
+        n = C.c_int(); self._ck(self.L.pps_map_compare_rows(self.h, 0, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=MAP_COMPARE_ROW_DTYPE)
+        if n.value:
+            self._ck(self.L.pps_map_compare_rows(self.h, n.value, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out
+
+    def compare_pairs(self, first=0, n=None):
+        """entries [first, first + n) of the pair list (MAP_COMPARE_PAIR_DTYPE; by frame plane, then row): n, n_agree, sum_q, sum_q2 of
+        every (frame plane, landmark) that shares a pixel"""
+        if n is None:
+            n = self.compare_info()["n_pairs"] - first
+        out = np.zeros(max(int(n), 0), dtype=MAP_COMPARE_PAIR_DTYPE)
+        self._ck(self.L.pps_map_compare_pairs(self.h, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+
+def map_compare_point_host(abcd, xyz, tol):
+    """pps_map_compare_point_host: one fp32 point against one plane -> (agree, e: signed distance in metres, q: e in 1/4096 m, rounded
+    and saturated).  No device needed."""
+    p = np.ascontiguousarray(abcd, dtype=np.float64).reshape(4); x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(3)
+    e = C.c_double(); q = C.c_int64()
+    rc = lib().pps_map_compare_point_host(p.ctypes.data_as(_dp), x.ctypes.data_as(_fp), float(tol), C.byref(e), C.byref(q))
+    if rc < 0:
+        raise PpsError(PPS_EINVAL, "pps_map_compare_point_host")
+    return bool(rc), e.value, q.value
 
 
 def map_view(width, height, invK, T_wc, reach=1, z_near=0.0, z_far=float("inf")):

@@ -1,11 +1,26 @@
-// pps_map_grid_host.h -- the record of the last grid map and of the last view rendered from it, shared by pps_map_grid.cpp (which builds
-// the grid) and pps_map_render.cpp (which only reads it).
+// pps_map_grid_host.h -- the record of the last grid map, of the last view rendered from it and of the last comparison with that view,
+// shared by pps_map_grid.cpp (which builds the grid), pps_map_render.cpp and pps_map_compare.cpp (which only read it).
 #pragma once
+#include "pps_compare.h"
 #include "pps_grid.h"
 #include "pps_map_host.h"
 #include "pps_render.h"
 
 namespace pps_impl {
+
+// The last pps_map_compare, of THIS view: whatever ends the view ends it (MapRender::clear, a new render).  tables: the plane rows and
+// their ids are on the device for this grid.
+struct MapCompare {
+  bool valid = false, tables = false;
+  pps_map_compare_totals tot{};
+  MapBuf<unsigned long long> table;
+  MapBuf<pps::ComparePlane> planes; MapBuf<int> ids;
+  MapBuf<pps::CompareBlock> block;
+  MapBuf<pps_map_compare_row> rows; MapBuf<pps_map_compare_pair> pairs;
+  MapSpan t_kernels;
+  void clear() { valid = tables = false; tot = pps_map_compare_totals{}; }
+  void release() { table.release(); planes.release(); ids.release(); block.release(); rows.release(); pairs.release(); t_kernels.release(); }
+};
 
 // The last pps_map_render.  tables: the slot table, the landmark rows and their ids are on the device for THIS grid (made by the first
 // render after a grid call, kept until the next one).  on_host: the grid had no cell, the view is empty and no buffer holds it.
@@ -18,10 +33,11 @@ struct MapRender {
   MapBuf<pps::MapPt> cloud; MapBuf<float> depth; MapBuf<int> plane_id; MapBuf<long long> cell;
   MapBuf<unsigned long long> n_hit;
   MapSpan t_kernels;
-  void clear() { valid = tables = on_host = false; tot = pps_map_render_totals{}; n_rows = 0; }
+  MapCompare compare;
+  void clear() { valid = tables = on_host = false; tot = pps_map_render_totals{}; n_rows = 0; compare.clear(); }
   void release() {
     slot.release(); rows.release(); ids.release(); cloud.release(); depth.release(); plane_id.release(); cell.release(); n_hit.release();
-    t_kernels.release();
+    t_kernels.release(); compare.release();
   }
 };
 

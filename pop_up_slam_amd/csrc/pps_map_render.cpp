@@ -111,6 +111,7 @@ int pps_map_render(pps_map* m, const pps_map_view* v, int64_t* n_hit) {
   MapGrid* G = m->grid;
   if (!G || !G->valid) return mfail(m, PPS_ESTATE, "render: there is no grid (no pps_map_build_grid call has succeeded, or the last one failed)");
   pps_map_render_totals tot{};
+  G->render.compare.valid = false;                                   // a comparison is of the view that goes now
   const int rc = render(m, *G, v, &tot);
   if (rc != PPS_OK) {                                                // the grid stays; the view that was there is gone
     const bool tables = G->render.tables;

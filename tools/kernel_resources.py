@@ -99,14 +99,17 @@ DESIGN_KERNELS = [
     # the rendered view of the grid map (pps_render.hip); neither uses scratch
     ("k_render", "pps_map_render: one thread per pixel, 26 640 B of LDS for a slice of 256 landmark rows"),
     ("k_render_slots", "the slot table, once per grid"),
+    # a frame against the rendered view (pps_compare.hip); none uses scratch
+    ("k_compare", "pps_map_compare: four pixels per thread, a table of 64 entries in LDS per workgroup"),
+    ("k_compare_scan", "per frame plane: best landmark, margins, pairs to come"), ("k_compare_emit", "the pair list in order, row records, totals"),
 ]
 TABLE_BEGIN, TABLE_END = "<!-- kernel-table:begin (tools/kernel_resources.py --update-design) -->", "<!-- kernel-table:end -->"
 
 
 def built_table():
-    """{name: dict} of every kernel of the solver objects (and of pps_loop.hip, pps_map.hip, pps_render.hip) the Makefile built"""
+    """{name: dict} of every kernel of the solver objects (and of pps_loop.hip, pps_map.hip, pps_render.hip, pps_compare.hip) the Makefile built"""
     out = {}
-    for f in ("pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip", "pps_robust.hip", "pps_loop.hip", "pps_map.hip", "pps_render.hip"):
+    for f in ("pps_k1.hip", "pps_k1_lanes.hip", "pps_k2.hip", "pps_k3.hip", "pps_k4.hip", "pps_robust.hip", "pps_loop.hip", "pps_map.hip", "pps_render.hip", "pps_compare.hip"):
         for r in resources(os.path.join(CSRC, f), [], built=True):
             v = int(r["vgpr_count"])
             out[short_name(r["name"])] = {"vgpr": v, "agpr": int(r["agpr_count"]), "waves": min(8, 512 // max(8, (v + 7) // 8 * 8)),
