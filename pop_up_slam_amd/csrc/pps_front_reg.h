@@ -68,7 +68,24 @@ __device__ __forceinline__ void front_reg_eliminate(const G& d, int rec, double*
   // past the front reads row 0 -- finite values in entries that stay dead (an MFMA update of entry (i, j) reads row i and column j
   // only; nothing stores or extracts a dead row or a column right of the diagonal), and 3 selects + an address clamp per element
   // less in front of the first panel.
-  double4_t c[NT * (NT + 1) / 2];
+  // FIRST4 (the register-only 4-column form): the first panel -- columns 0 .. 3 of row `lane` -- and the rhs row are read from the
+  // triangle AHEAD of the tiles, at the addresses the tile load uses for tile column 0 (same row clamp, same entries of the next rows
+  // above the diagonal): what extraction + read-back of the K = 0 step would deliver.  LDS returns in order, so the first pivot block
+  // waits for these reads only and the tile reads drain under it; the first trailing update is their first use.
+  constexpr bool FIRST4 = W == 4 && !STRIP && NT <= 4;
+  double r0[4] = {0.0, 0.0, 0.0, 0.0}, y = 0.0;                // (y, lane f: the rhs . rhs corner, which nothing reads)
+  if constexpr (FIRST4) {
+    const double* Fl = F + tri24(lane < mr ? lane : 0);
+#pragma unroll
+    for (int m = 0; m < 4; m++) r0[m] = Fl[m];
+    const double t = F[lane <= f ? tri24(f) + lane : 0]; y = lane < f ? t : 0.0;
+    __builtin_amdgcn_wave_barrier();                           // (the order of issue: these reads stand in front of the tile reads)
+  }
+  // With FIRST4 the values stay single registers (ct) until the first pivot block is through: what gathers them into the tiles -- register
+  // copies behind paired LDS reads -- would otherwise stand, with its waits, in front of that block (tiles_from_reads, in the K = 0 step).
+  constexpr int kTiles = NT * (NT + 1) / 2;
+  double4_t c[kTiles];
+  double ct[FIRST4 ? kTiles : 1][4];
 #pragma unroll
   for (int ti = 0; ti < NT; ti++)
 #pragma unroll
@@ -76,10 +93,22 @@ __device__ __forceinline__ void front_reg_eliminate(const G& d, int rec, double*
       const int row = 16 * ti + lq + 4 * r;
       const double* Fr = F + (tri24(row < mr ? row : 0) + l16);
 #pragma unroll
-      for (int tj = 0; tj <= ti; tj++) c[tile_id(ti, tj)][r] = Fr[16 * tj];
+      for (int tj = 0; tj <= ti; tj++) {
+        if constexpr (FIRST4) ct[tile_id(ti, tj)][r] = Fr[16 * tj];
+        else c[tile_id(ti, tj)][r] = Fr[16 * tj];
+      }
     }
-  double y = 0.0;                                              // (lane f: the rhs . rhs corner, which nothing reads)
-  if (!STRIP) { const double t = F[lane <= f ? tri24(f) + lane : 0]; y = lane < f ? t : 0.0; }
+  (void)ct;
+  auto tiles_from_reads = [&]() __attribute__((always_inline)) {
+#ifndef PPS_WAVE_EMU
+    __builtin_amdgcn_sched_barrier(0);                         // (nothing of the tiles' gathering moves up into the pivot block)
+#endif
+#pragma unroll
+    for (int t = 0; t < (FIRST4 ? kTiles : 0); t++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) c[t][r] = ct[t][r];
+  };
+  if (!STRIP && !FIRST4) { const double t = F[lane <= f ? tri24(f) + lane : 0]; y = lane < f ? t : 0.0; }
   __builtin_amdgcn_wave_barrier();
   double* __restrict__ Lp = d.L + (((long long)__builtin_amdgcn_readlane(rec, 10) << 32) | (unsigned int)__builtin_amdgcn_readlane(rec, 9));
   long long cyc_panel = 0, cyc_trail = 0;
@@ -229,15 +258,22 @@ __device__ __forceinline__ void front_reg_eliminate(const G& d, int rec, double*
   // loop over its at most four steps, behind kFlat4 of them unrolled with K a literal.
   auto column4 = [&](auto tjc) __attribute__((always_inline)) {
     constexpr int TJ = decltype(tjc)::value;
-    auto step = [&](const int K) __attribute__((always_inline)) {
+    // firstc: the K = 0 step of a front, whose panel rows came straight from the triangle (r0 above) -- no extraction, no read-back
+    auto step = [&](const int K, auto firstc) __attribute__((always_inline)) {
+      constexpr bool FIRST = decltype(firstc)::value;
       const long long tk0 = (TR && d.trace) ? clock64() : 0;
       const int nb = p - K < 4 ? p - K : 4;
-      reg_extract_panel4<TJ, NT>(c, P, K - 16 * TJ, lane);
-      __builtin_amdgcn_wave_barrier();
       // ---- panel: lane = row; the rhs row takes the idle lane f, its entries of columns K .. K+3 sit in lanes K .. K+3 of y ----
       double r[4], x[4];
+      if constexpr (FIRST) {
 #pragma unroll
-      for (int m = 0; m < 4; m++) r[m] = P[lane * kP8Stride + m];
+        for (int m = 0; m < 4; m++) r[m] = r0[m];
+      } else {
+        reg_extract_panel4<TJ, NT>(c, P, K - 16 * TJ, lane);
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int m = 0; m < 4; m++) r[m] = P[lane * kP8Stride + m];
+      }
 #pragma unroll
       for (int m = 0; m < 4; m++) { const double q = readlane_d(y, K + m); r[m] = lane == f ? q : r[m]; }
       const Chol4 c1 = chol4(readlane_d(r[0], K), readlane_d(r[0], K + 1), readlane_d(r[1], K + 1), readlane_d(r[0], K + 2), readlane_d(r[1], K + 2),
@@ -255,6 +291,7 @@ __device__ __forceinline__ void front_reg_eliminate(const G& d, int rec, double*
       }
       __builtin_amdgcn_wave_barrier();
       const long long tk1 = (TR && d.trace) ? clock64() : 0;
+      if constexpr (FIRST) tiles_from_reads();
       reg_trailing4<TJ, NT>(c, P, nb, lane);
       __builtin_amdgcn_wave_barrier();
       if (TR && d.trace) { const long long tk2 = clock64(); cyc_panel += tk1 - tk0; cyc_trail += tk2 - tk1; }
@@ -265,12 +302,14 @@ __device__ __forceinline__ void front_reg_eliminate(const G& d, int rec, double*
 #pragma unroll
     for (int q = 0; q < NF; q++) {
       if (16 * TJ + 4 * q >= kend) { more = false; break; }
-      step(16 * TJ + 4 * q);
+      if (TJ == 0 && q == 0) step(0, std::true_type{});        // (p >= 1: every front takes this step)
+      else step(16 * TJ + 4 * q, std::false_type{});
     }
     if (NF < 4 && more)
-      for (int K = 16 * TJ + 4 * NF; K < kend; K += 4) step(K);
+      for (int K = 16 * TJ + 4 * NF; K < kend; K += 4) step(K, std::false_type{});
   };
-  if constexpr (W == 4 && !STRIP && NT <= 4) {
+  if constexpr (FIRST4) {
+    static_assert(kFlat4<0> >= 1, "the K = 0 step, which gathers the tiles, is the first straight-line step of column 0");
     column4(std::integral_constant<int, 0>{});
     column4(std::integral_constant<int, 1>{});
     if constexpr (NT > 2) column4(std::integral_constant<int, 2>{});
